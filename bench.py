@@ -19,6 +19,13 @@ Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (bucket ac
 HBM roofline the north star mandates; `cpu_baseline` is the oracle's CPU restatement timed on the same workload on
 this box's host cores (the only place the oracle is touched here).
 
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: preparation, the library's schedule
+calibration, warm-up, the K timed steps and the JSON line.  `--full` adds everything else this file measures or checks, after
+the timed region: the closed-form check of every proof, telemetry, the schedule A/B, the isolated / single-proof / latency
+readings, the stand-alone MSM / NTT readings, the e2e block and `cpu_baseline`.  `--dump-outputs DIR` writes the proof of the
+last timed step (A, B, C as raw Montgomery bytes, float64) to DIR/proof_{a,b,c}.npy; the r, s of the timed steps come from
+their own seeded generator, so the same arguments give the same outputs on every run and every build.
+
 --dry-run-emul (tests only): the same control flow over the CPU emulator build of the library and gloo, tiny n --
 checks the launcher / rank / JSON plumbing on a machine without GPUs; its numbers are not measurements and say so.
 """
@@ -89,9 +96,18 @@ def parse_args():
     ap.add_argument("--profile-run", action="store_true",
                     help="for rocprofv3: nothing but preparation, warm-up and the timed region (no A/B, isolated, single-proof, "
                          "latency or stand-alone readings), so that every proof of the trace ran under ONE schedule (ARK355_SCHED)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline, after the timed region: closed-form check, telemetry, schedule A/B, "
+                         "isolated / latency / stand-alone readings, e2e, cpu_baseline (the --no-* flags still apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the proof of the last timed step to DIR/proof_{a,b,c}.npy (raw Montgomery bytes as float64)")
     args = ap.parse_args()
-    if args.profile_run:
+    if args.profile_run or not args.full:
         args.no_ab = args.no_micro = args.no_telemetry = args.no_cpu_baseline = args.no_e2e = True
+    if not args.full:
+        args.no_check = True
+    # the readings that take runs of their own (diagnostic kernels, isolated / single-proof / latency runs)
+    args.extras = args.full and not args.profile_run
     if args.dry_run_emul:
         args.inflight = 1                # the emulator is single-threaded
     if args.log_n is None:
@@ -479,9 +495,12 @@ def main():
     trace = [] if os.environ.get("ARK355_BENCH_TRACE") else None
     worker_cpu = [0.0]                   # CPU seconds of the proving threads (they are created and joined per run())
 
-    def run(nsteps, record, per_worker=False, z_host=None):
+    def run(nsteps, record, per_worker=False, z_host=None, tasks=None):
         # per_worker: every context proves `nsteps` times (warm-up must touch each context's scratch and streams)
-        todo = [(rnd.randrange(cv.r), rnd.randrange(cv.r)) for _ in range(nsteps * (len(ctxs) if per_worker else 1))]
+        # tasks: the (r, s) of the steps in the order they are handed out (default: drawn from rnd)
+        if tasks is None:
+            tasks = [(rnd.randrange(cv.r), rnd.randrange(cv.r)) for _ in range(nsteps * (len(ctxs) if per_worker else 1))]
+        todo = list(reversed(tasks))
         quota = {id(c): nsteps for c in ctxs}
         results = []
 
@@ -536,7 +555,7 @@ def main():
             telemetry["error"] = "%s: %s" % (type(e).__name__, str(e)[:160])
     # which of the proving streams share an in-order hardware queue of the runtime (idle device; see ark355_diag_streams)
     stream_map = None
-    if not emul and rank == 0 and not args.profile_run:
+    if not emul and rank == 0 and args.extras:
         try:
             # GPU-side cost of a dispatch in an in-order stream on THIS box (ark355_diag_dispatch): the fingerprint that
             # separates the boxes of the pool -- a few us on most, 50-90 us on some, where everything but the long
@@ -585,7 +604,7 @@ def main():
     # the multiply-add rate of this box, warm, right before (and right after) the timed region -- outside it
     mad_peak = {}
     def read_mad_peak(tag):
-        if emul or rank != 0 or args.profile_run:
+        if emul or rank != 0 or not args.extras:
             return
         try:
             mad_peak[tag] = g.lib.diag_mad_rate(g.ctx, 20.0)["tmad_per_s"]
@@ -595,12 +614,16 @@ def main():
     gpu_clocks = {}
     def read_gpu_clocks(tag):
         # shader-clock cycles and 100 MHz ticks of the GPU's own counters (ark355_diag_clocks), bracketing the timed region
-        if emul or rank != 0 or args.profile_run:
+        if emul or rank != 0 or not args.extras:
             return
         try:
             gpu_clocks[tag] = g.lib.diag_clocks(g.ctx)
         except Exception as e:                                # noqa: BLE001
             gpu_clocks[tag + "_error"] = str(e)[:120]
+    # the (r, s) of the timed steps: their own generator, untouched by how many proofs calibration and warm-up took, so that
+    # the same arguments give the same proofs (--dump-outputs) on every run
+    trng = random.Random(seed + 0x7100)
+    timed_tasks = [(trng.randrange(cv.r), trng.randrange(cv.r)) for _ in range(args.steps)]
     if world > 1:
         dist.barrier()
     dev_sync()
@@ -610,7 +633,7 @@ def main():
     cpu0 = time.process_time()
     wall0 = time.time()
     t0 = time.perf_counter()
-    results = run(args.steps, rec)
+    results = run(args.steps, rec, tasks=timed_tasks)
     dev_sync()
     if world > 1:
         dist.barrier()
@@ -625,6 +648,15 @@ def main():
     host_cpu_s = time.process_time() - cpu0          # CPU time of all threads of this rank over the timed region
     thr1 = thread_cpu_times()
     stage("timed region done: %.2f ms per step" % (dt / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:
+        # the last step handed out (with several proofs in flight, the order of completion varies from run to run)
+        last_rs = timed_tasks[-1]
+        pr = next(p for p, r_, s_ in results if (r_, s_) == last_rs)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, raw in zip("abc", (pr.a, pr.b, pr.c) if hasattr(pr, "a") else tuple(pr)):
+            arr = np.frombuffer(bytes(raw), dtype=np.uint8).astype(np.float64).reshape(2, -1)     # rows: x, y
+            np.save(os.path.join(args.dump_outputs, "proof_%s.npy" % name), arr)
+        stage("proof of the last timed step written to %s" % args.dump_outputs)
     resident = sum(max(0.0, t1_ - thr0.get(key, 0.0)) for key, t1_ in thr1.items())
     # where the cores go: the proving threads (launches, event polling, result copies), the threads that live through the
     # region (main thread, the HIP runtime's own), and what is left: short-lived native threads (the O(1) proof tail)
@@ -666,7 +698,7 @@ def main():
     # are ISOLATED kernel times -- the box-independent check of the kernels themselves ("kernels equal, overlap slower" shows
     # at a glance), and the clean source of the secondary metrics (MSM scalar-mul/s, NTT elements/s).
     isolated = None
-    if not shard and not emul and rank == 0 and not args.profile_run:
+    if not shard and not emul and rank == 0 and args.extras:
         g.lib.ctx_set_policy(g.ctx, "SCHED", 0)
         # (a lone one-stream proof normally runs its witness map and its G2 tails on side streams: not here -- ONE stream)
         side = {k: g.lib.ctx_get_policy(g.ctx, k) for k in ("SIDE_WM", "SIDE_G2_TAILS")}
@@ -698,12 +730,12 @@ def main():
     # schedule choice for the "alone" class has latched, then three for the uncontended launch duration of the dominant
     # kernel (with several proofs in flight its launches share the chip with the other proofs' kernels)
     solo = None
-    if not shard and pkh is not None and not emul and not args.profile_run:
+    if not shard and pkh is not None and not emul and args.extras:
         for _ in range(16):
             if g.lib.sched_info(g.ctx, pkh, False)["latched"] != "auto":
                 break
             prove_on(g.ctx, rnd.randrange(cv.r), rnd.randrange(cv.r))
-    if not shard and len(ctxs) > 1 and not args.profile_run:
+    if not shard and len(ctxs) > 1 and args.extras:
         solo_rec = [0.0, 0, 0]
         wm_side = g.lib.ctx_get_policy(g.ctx, "SIDE_WM")        # the accumulation launches ALONE: no witness map beside the first ones
         g.lib.ctx_set_policy(g.ctx, "SIDE_WM", 0)
@@ -724,7 +756,7 @@ def main():
     latency = None
     # (a sharded proof is a collective: with several ranks rank 0 cannot prove on its own -- there every step already IS a
     # single proof from start to finish, so ms_per_step is the latency)
-    if rank == 0 and not (shard and world > 1) and not args.profile_run and (not emul or os.environ.get('ARK355_BENCH_EMUL_LATENCY')):
+    if rank == 0 and not (shard and world > 1) and args.extras and (not emul or os.environ.get('ARK355_BENCH_EMUL_LATENCY')):
         import ctypes
         ptr = ctypes.c_void_p()
         assert g.lib.dll.ark355_host_alloc(len(zb), ctypes.byref(ptr)) == 0
@@ -850,7 +882,8 @@ def main():
             # box-normalised figures: the same library reads 4-5 % apart on two boxes of the pool (sustained clock under the power
             # cap); these are the headline numbers rescaled to a box that issues MAD_PEAK_REF_T multiply-adds per second, and the
             # time in gfx clock cycles (mean gfxclk of the timed region from the telemetry sampler)
-            "box": box_block(gpu_clocks, dt, args.steps, (1 if shard else world) * n * args.steps / dt, n, telemetry),
+            "box": box_block(gpu_clocks, dt, args.steps, (1 if shard else world) * n * args.steps / dt, n, telemetry)
+                   if args.extras else None,
             # host CPU seconds burnt per second of the timed region by this rank (launch threads, waits, the O(1) proof tail)
             "host_cpu_cores": host_cpu_s / dt if dt > 0 else None,
             "host_cpu_threads": host_cpu_threads,      # cores per thread name over the timed region (top 8)
@@ -912,7 +945,7 @@ def main():
                 out["parity"] = "MISMATCH against oracle/c"
         if sampler is not None:
             telemetry["host_at_end"] = GT.host_counters()
-        if not emul and not args.profile_run:
+        if not emul and args.extras:
             try:
                 telemetry["dispatch_gap_after"] = g.lib.diag_dispatch(g.ctx)
             except Exception as e:                            # noqa: BLE001

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -25,7 +26,7 @@ def _run(*extra, **more_env):
 
 
 def test_bench_gpus_2_spawns_two_replica_ranks():
-    d = _run("--gpus", "2")
+    d = _run("--gpus", "2", "--full")
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["steps"] == 2 and d["warmup"] == 1
     assert d["parity"] == "proof == trapdoor closed form"
     assert "EMULATOR DRY RUN" in d["data"] and "replicas x2" in d["config"]["parallelism"]
@@ -37,10 +38,27 @@ def test_bench_gpus_2_spawns_two_replica_ranks():
 def test_bench_shard_mode_two_ranks(exchange):
     # ARK355_BENCH_EMUL_LATENCY=1 arms the single-proof readings that rank 0 takes alone on a GPU run: in shard mode with
     # several ranks they must be skipped (a sharded proof is a collective; rank 0 proving alone would wait forever)
-    d = _run("--gpus", "2", "--mode", "shard", "--shard-exchange", exchange, "--log-n", "7", ARK355_BENCH_EMUL_LATENCY="1")
+    d = _run("--gpus", "2", "--mode", "shard", "--shard-exchange", exchange, "--log-n", "7", "--full",
+             ARK355_BENCH_EMUL_LATENCY="1")
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["latency"] is None
     assert d["parity"] == "proof == trapdoor closed form"
     assert "msm-shard x2" in d["config"]["parallelism"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_proof(tmp_path):
+    """A plain run does only what the headline needs (no closed-form check, no readings after the timed region); with
+    --dump-outputs it writes the proof of the last timed step.  The --full run of the same arguments computes the same proof
+    and checks every proof it made against the trapdoor closed form."""
+    plain = _run("--steps", "3", "--dump-outputs", str(tmp_path / "plain"))
+    assert plain["steps"] == 3 and plain["parity"] == "skipped" and plain["latency"] is None and plain["box"] is None
+    for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype"):
+        assert key in plain
+    full = _run("--steps", "3", "--full", "--dump-outputs", str(tmp_path / "full"))
+    assert full["parity"] == "proof == trapdoor closed form"
+    for name in "abc":
+        a, b = (np.load(str(tmp_path / d / ("proof_%s.npy" % name))) for d in ("plain", "full"))
+        assert a.dtype == np.float64 and a.shape[0] == 2 and a.any()
+        assert np.array_equal(a, b)
 
 
 def test_bench_refuses_a_world_size_that_contradicts_gpus():
@@ -55,7 +73,7 @@ def test_bench_gpus_8_ranks(mode):
     """The driver's 8-GPU launch shape on CPU: eight ranks (one per GPU), one JSON line from rank 0, whole-job value.
     Replica: eight independent proof streams, no collective on the data path; shard: ONE proof whose MSM term ranges are
     spread over the eight ranks, exchanged through the (emulated) RCCL behind the C ABI."""
-    extra = ["--gpus", "8", "--steps", "1", "--warmup", "1"]
+    extra = ["--gpus", "8", "--steps", "1", "--warmup", "1", "--full"]
     if mode == "shard":
         extra += ["--mode", "shard", "--log-n", "7"]
     d = _run(*extra)
@@ -74,7 +92,7 @@ def test_bench_line_carries_the_8d_latency_and_host_cpu_fields():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run-emul", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert "proofs in flight per GPU, z resident in HBM" in d["metric"]
