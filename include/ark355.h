@@ -75,7 +75,7 @@ int32_t ark355_sizes(int32_t curve, uint32_t what[4]);
  *                 (table rows bit-packed 1 / one word per limb 0 / per curve -1), TABLE_STRIDE, HBM_BUDGET_MB, SHARD_DIST_WM, RCCL_SELF (diagnostic: a rank at world size 1 exchanges with
  *                 itself) -- read when a key or base set is loaded THROUGH this context;
  *   per call      MSM_SEG, ACC_THREADS (workgroup size of the LDS-free accumulation kernels: 64 / 128 / 256; 0 [default]: 64 for a
- *                 proof alone on one stream, else 256), MSM_TWO_LEVEL_MIN, NTT_RMAX, NTT_DIRECT_MAX, NTT_NOFUSE (A/B and test knobs).
+ *                 proof alone on one stream, else 256), NTT_RMAX, NTT_DIRECT_MAX, NTT_NOFUSE (A/B and test knobs).
  *                 CHECK_SATISFIED (default 0: a proof is computed for whatever z is handed in, as ark-groth16's release build does;
  *                 1: ark355_prove / _dev / _batch also compare a_i b_i with c_i on the rows the witness map computes anyway -- the
  *                 check ark-groth16 runs under debug_assert!(cs.is_satisfied()) -- and return ARK355_E_UNSATISFIABLE, with the index

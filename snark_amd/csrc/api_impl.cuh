@@ -65,6 +65,7 @@ struct GenericScratch {
   MsmSort sort;
   MsmBuckets bk;
   DevBuf a, b, c;
+  DevBuf rows;       // the 28-bit rows of a one-shot MSM's bases (msm_host)
 };
 
 template <class Curve>
@@ -165,28 +166,30 @@ struct Api {
     if (res != d_data) ARK_CHECK_HIP(hipMemcpyAsync(d_data, res, bytes, hipMemcpyDeviceToDevice, st));
   }
 
+  // d_rows: 28-bit rows in the format `packed`; tab: the window tables they are, nullptr for the re-encoded bases of a one-shot
+  // MSM (msm_plan without tables: every window its own bucket set)
   template <class F>
-  static void msm_generic(ark355_ctx* ctx, GenericScratch& g, const Affine<F>* d_bases, const void* d_scalars,
+  static void msm_generic(ark355_ctx* ctx, GenericScratch& g, const void* d_rows, bool packed, const void* d_scalars,
                           uint64_t n, int mont, uint8_t* out, bool want_affine, const PrecompTable* tab = nullptr) {
     hipStream_t st = ctx->stream;
     hipEvent_t e0, e1;
     ARK_CHECK_HIP(hipEventCreate(&e0));
     ARK_CHECK_HIP(hipEventCreate(&e1));
     try {
-      const int fmt = tab != nullptr ? tab->fmt() : 0;
       msm_sort<Fr>(ctx, g.sort, d_scalars, n, mont, st, tab);
-      // what the tails leave on the device: one sum (32-bit tails) or c partial sums per bucket set (28-bit tails)
-      const uint32_t parts = msm_parts_count(g.sort.plan, fmt);
+      // what the tails leave on the device: c partial sums per bucket set
+      const uint32_t parts = msm_parts_count(g.sort.plan);
       g.c.ensure((size_t)parts * sizeof(XYZZ<F>));
       XYZZ<F>* d_res = g.c.as<XYZZ<F>>();
-      msm_buckets<F>(ctx, g.sort, g.bk, d_bases, d_res, 0, st, n ? e0 : nullptr, n ? e1 : nullptr, fmt);
-      // The last 2c group operations of the bucket reduction (Horner over the bit sums) and the one inversion of the
-      // normalisation run in the library's host-compiled field code: ~1 us per group operation against ~12 us for a device
-      // lane, tens of microseconds for the inversion against ~1 ms.
+      msm_accumulate_phase<F>(ctx, g.sort, g.bk, d_rows, packed, st, n ? e0 : nullptr, n ? e1 : nullptr);
+      msm_reduce_phase<F>(ctx, g.sort, g.bk, d_res, st);
+      // The last 2c group operations per bucket set (Horner over the bit sums) and the one inversion of the normalisation run
+      // in the library's host-compiled field code: ~1 us per group operation against ~12 us for a device lane, tens of
+      // microseconds for the inversion against ~1 ms.
       std::vector<XYZZ<F>> h_parts(parts);
       ARK_CHECK_HIP(hipMemcpyAsync(h_parts.data(), d_res, (size_t)parts * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, st));
       ARK_CHECK_HIP(hipStreamSynchronize(st));
-      const XYZZ<F> h_res = msm_parts_finish<F>(h_parts.data(), g.sort.plan, fmt);
+      const XYZZ<F> h_res = msm_parts_finish<F>(h_parts.data(), g.sort.plan);
       if (want_affine) {
         const Affine<F> a = xyzz_to_affine(h_res);
         memcpy(out, &a, sizeof(a));
@@ -207,18 +210,28 @@ struct Api {
     (void)hipEventDestroy(e1);
   }
 
+  // One-shot MSM over the caller's bases: uploaded and re-encoded to 28-bit rows in the format a key of this curve gets
+  // (table_pack_default), then the accumulation and tails of the resident keys over the plan without tables.
+  template <class F>
+  static void msm_host_t(ark355_ctx* ctx, GenericScratch& g, const uint8_t* bases, const uint8_t* scalars, uint64_t n,
+                         uint8_t* out) {
+    hipStream_t st = ctx->stream;
+    const bool pack = table_pack_default<Fq>(ctx->policy);
+    g.a.ensure(n * sizeof(Affine<F>));
+    g.b.ensure(n * sizeof(Fr));
+    g.rows.ensure(n * table_row_bytes<F>(pack));
+    if (n) {
+      ARK_CHECK_HIP(hipMemcpyAsync(g.a.p, bases, n * sizeof(Affine<F>), hipMemcpyHostToDevice, st));
+      ARK_CHECK_HIP(hipMemcpyAsync(g.b.p, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, st));
+      rows_to28<F>(g.a.as<Affine<F>>(), g.rows.p, n, pack, st);
+    }
+    msm_generic<F>(ctx, g, g.rows.p, pack, g.b.p, n, 0, out, true);
+  }
+
   static void msm_host(ark355_ctx* ctx, GenericScratch& g, int group, const uint8_t* bases, const uint8_t* scalars,
                        uint64_t n, uint8_t* out) {
-    hipStream_t st = ctx->stream;
-    const size_t psz = group == 1 ? sizeof(Affine<Fq>) : sizeof(Affine<Fq2>);
-    g.a.ensure(n * psz);
-    g.b.ensure(n * sizeof(Fr));
-    if (n) {
-      ARK_CHECK_HIP(hipMemcpyAsync(g.a.p, bases, n * psz, hipMemcpyHostToDevice, st));
-      ARK_CHECK_HIP(hipMemcpyAsync(g.b.p, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, st));
-    }
-    if (group == 1) msm_generic<Fq>(ctx, g, g.a.as<Affine<Fq>>(), g.b.p, n, 0, out, true);
-    else msm_generic<Fq2>(ctx, g, g.a.as<Affine<Fq2>>(), g.b.p, n, 0, out, true);
+    if (group == 1) msm_host_t<Fq>(ctx, g, bases, scalars, n, out);
+    else msm_host_t<Fq2>(ctx, g, bases, scalars, n, out);
   }
 
   static BasesDev* bases_load(const TunePolicy& pol, int group, const uint8_t* bases, uint64_t n, hipStream_t st) {
@@ -247,8 +260,8 @@ struct Api {
   static void msm_dev(ark355_ctx* ctx, GenericScratch& g, const BasesDev& b, const void* d_scalars, uint64_t n, int mont,
                       uint8_t* out, bool want_affine) {
     ARK_REQUIRE(n <= b.n, ARK355_EINVAL, "more scalars than bases");
-    if (b.group == 1) msm_generic<Fq>(ctx, g, b.tab.table.as<Affine<Fq>>(), d_scalars, n, mont, out, want_affine, &b.tab);
-    else msm_generic<Fq2>(ctx, g, b.tab.table.as<Affine<Fq2>>(), d_scalars, n, mont, out, want_affine, &b.tab);
+    if (b.group == 1) msm_generic<Fq>(ctx, g, b.tab.table.p, b.tab.packed, d_scalars, n, mont, out, want_affine, &b.tab);
+    else msm_generic<Fq2>(ctx, g, b.tab.table.p, b.tab.packed, d_scalars, n, mont, out, want_affine, &b.tab);
   }
 
   template <class F>

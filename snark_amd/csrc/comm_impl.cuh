@@ -45,14 +45,7 @@ struct CommDev {
   }
 };
 
-// dst[i] += src[i] over canonical XYZZ points (buckets of the 32-bit accumulation kernels)
-template <class F>
-__global__ void __launch_bounds__(256)
-xyzz_add_inplace_kernel(XYZZ<F>* __restrict__ dst, const XYZZ<F>* __restrict__ src, uint32_t count) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) dst[i] = xyzz_add(dst[i], src[i]);
-}
-// ... and over 28-bit bucket slots (every MSM over resident tables; a lane pair per G2 slot): tails28_impl.cuh
+// dst[i] += src[i] over 28-bit bucket slots (a lane pair per G2 slot): tails28_impl.cuh
 template <class P, bool G2>
 __global__ void __launch_bounds__(256, ARK_TAIL28_WAVES)
 slot28_add_inplace_kernel(void* __restrict__ dst_, const void* __restrict__ src_, uint32_t count) {
@@ -76,28 +69,22 @@ static inline void ring_chunk(uint32_t total, int world, int c, uint32_t* lo, ui
   *n = (uint32_t)(b - a);
 }
 
-// Ring reduce-scatter of `total` buckets (fmt: the slot format of the bucket array, MsmBuckets::fmt -- canonical XYZZ or
-// 28-bit slots); afterwards rank g's range (g+1) mod G holds the sum over all ranks and every other range is zeroed
-// (= infinity in both formats), so the ordinary bucket reduction over the whole array yields this rank's share of
-// sum_b (b+1) B_b.
+// Ring reduce-scatter of `total` buckets (28-bit slots); afterwards rank g's range (g+1) mod G holds the sum over all ranks and
+// every other range is zeroed (= infinity), so the ordinary bucket reduction over the whole array yields this rank's share
+// of sum_b (b+1) B_b.
 // self_exchange (policy RCCL_SELF, world size 1 only): one ring step of the rank with itself -- the lower half of the
 // array travels through ncclSend / ncclRecv (peer = own rank, grouped) into the staging buffer, is cleared in place and
 // comes back through the same EC-add kernel: 0 + x = x, the array is unchanged.
 template <class F>
-static void ring_reduce_scatter_buckets(CommDev& cm, void* buckets_, uint32_t total, int fmt, hipStream_t stream, bool self_exchange = false) {
+static void ring_reduce_scatter_buckets(CommDev& cm, void* buckets_, uint32_t total, hipStream_t stream, bool self_exchange = false) {
   using P = typename Tail28Of<F>::P;
   constexpr bool G2 = Tail28Of<F>::G2;
-  const size_t slot = msm_slot_bytes<F>(fmt);
+  const size_t slot = msm_slot_bytes<F>();
   uint8_t* buckets = static_cast<uint8_t*>(buckets_);
   auto add_inplace = [&](uint8_t* dst, const uint8_t* src, uint32_t n) {
-    if (fmt) {
-      constexpr uint32_t lpi = Tail28<P, G2>::LPI;
-      ARK_LAUNCH((slot28_add_inplace_kernel<P, G2>), dim3((uint32_t)(((uint64_t)n * lpi + 255) / 256)), dim3(256), 0, stream, (void*)dst,
-                 (const void*)src, n);
-    } else {
-      ARK_LAUNCH((xyzz_add_inplace_kernel<F>), dim3((n + 255) / 256), dim3(256), 0, stream, reinterpret_cast<XYZZ<F>*>(dst),
-                 reinterpret_cast<const XYZZ<F>*>(src), n);
-    }
+    constexpr uint32_t lpi = Tail28<P, G2>::LPI;
+    ARK_LAUNCH((slot28_add_inplace_kernel<P, G2>), dim3((uint32_t)(((uint64_t)n * lpi + 255) / 256)), dim3(256), 0, stream, (void*)dst,
+               (const void*)src, n);
     ARK_CHECK_LAUNCH();
   };
   const int G = cm.world, g = cm.rank;

@@ -380,46 +380,6 @@ struct Fp {
     r.l[N - 1] = (uint32_t)acc;
     return reduce_once(r, (uint32_t)(acc >> 32));
   }
-  // (x1*y1 + x2*y2 + x3*y3 + x4*y4) * R^-1 mod p, one reduction for four products (the fused
-  // Y3 = R*(Q - X3) - Y1*PPP of the lane-split G2 mixed addition).  (4 p^2 + m p)/R < p (1 + 4p/R) < 2p needs
-  // 4p < R, i.e. two spare top bits.
-  template <int K>
-  ARK_D static void m4_col_lo(uint64_t& acc, uint32_t& top, const Fp& x1, const Fp& y1, const Fp& x2, const Fp& y2,
-                              const Fp& x3, const Fp& y3, const Fp& x4, const Fp& y4, uint32_t* m) {
-    if constexpr (K < N) {
-      col_dual<K + 1, 0, K, true>(acc, top, x1, y1, x2, y2);
-      col_dual<K + 1, 0, K>(acc, top, x3, y3, x4, y4);
-      col_red<K, 0, K>(acc, top, m);
-      m[K] = (uint32_t)acc * P::INV;
-      macc_vs(acc, top, m[K], P::mod(0));
-      acc = (acc >> 32) | ((uint64_t)top << 32);
-      m4_col_lo<K + 1>(acc, top, x1, y1, x2, y2, x3, y3, x4, y4, m);
-    }
-  }
-  template <int K>
-  ARK_D static void m4_col_hi(uint64_t& acc, uint32_t& top, const Fp& x1, const Fp& y1, const Fp& x2, const Fp& y2,
-                              const Fp& x3, const Fp& y3, const Fp& x4, const Fp& y4, const uint32_t* m, Fp& r) {
-    if constexpr (K < 2 * N - 1) {
-      col_dual<2 * N - 1 - K, K - N + 1, K, true>(acc, top, x1, y1, x2, y2);
-      col_dual<2 * N - 1 - K, K - N + 1, K>(acc, top, x3, y3, x4, y4);
-      col_red<2 * N - 1 - K, K - N + 1, K>(acc, top, m);
-      r.l[K - N] = (uint32_t)acc;
-      acc = (acc >> 32) | ((uint64_t)top << 32);
-      m4_col_hi<K + 1>(acc, top, x1, y1, x2, y2, x3, y3, x4, y4, m, r);
-    }
-  }
-  ARK_D static Fp mul4sum(const Fp& x1, const Fp& y1, const Fp& x2, const Fp& y2, const Fp& x3, const Fp& y3,
-                          const Fp& x4, const Fp& y4) {
-    static_assert(P::BITS <= 32 * N - 2, "needs two spare top bits");
-    uint32_t m[N];
-    Fp r;
-    uint64_t acc = 0;
-    uint32_t top = 0;
-    m4_col_lo<0>(acc, top, x1, y1, x2, y2, x3, y3, x4, y4, m);
-    m4_col_hi<N>(acc, top, x1, y1, x2, y2, x3, y3, x4, y4, m, r);
-    r.l[N - 1] = (uint32_t)acc;
-    return reduce_once(r, (uint32_t)(acc >> 32));
-  }
 #else
   ARK_HD static Fp mul(const Fp& a, const Fp& b) {
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__SIZEOF_INT128__)
@@ -430,10 +390,6 @@ struct Fp {
   }
   ARK_HD static Fp mul2sum(const Fp& x1, const Fp& y1, const Fp& x2, const Fp& y2) {
     return add(mul_c(x1, y1), mul_c(x2, y2));
-  }
-  ARK_HD static Fp mul4sum(const Fp& x1, const Fp& y1, const Fp& x2, const Fp& y2, const Fp& x3, const Fp& y3,
-                           const Fp& x4, const Fp& y4) {
-    return add(add(mul_c(x1, y1), mul_c(x2, y2)), add(mul_c(x3, y3), mul_c(x4, y4)));
   }
 #endif
   // a*b - c*d with ONE Montgomery reduction (the Y3 of the mixed addition)
@@ -528,105 +484,6 @@ struct Fp2 {
     return Fp2{Base::mul_ni(a.c0, ni), Base::neg(Base::mul_ni(a.c1, ni))};
   }
 };
-
-#ifndef ARK_PLAIN_HOST
-// Lane-split Fq2: the two lanes of a pair (lane ^ 1) hold c0 and c1 of the SAME element.  Used by the G2 bucket
-// accumulation so that a G2 mixed addition needs G1-like registers per lane (the whole-element version sits at
-// 256 VGPR + 253 AGPR, one wave per SIMD).  Additions are component-wise; a multiplication exchanges the two
-// operands with the partner lane (DPP) and is ONE fused dual-product Montgomery pass per lane:
-//   lane 0:  c0 = a0*b0 + (-a1)*b1        lane 1:  c1 = a0*b1 + a1*b0
-// Every predicate (is_zero, ==) is pair-wide, so control flow stays uniform inside a pair.
-template <class P>
-struct Fp2L {
-  using Base = Fp<P>;
-  using Params = P;
-  static constexpr int N = Base::N;
-  Base c;     // c0 on even lanes, c1 on odd lanes
-
-  ARK_D static uint32_t parity() { return threadIdx.x & 1u; }
-  ARK_D static Base xchg(const Base& v) {
-    Base r;
-#pragma unroll
-    for (int i = 0; i < N; i++) r.l[i] = ark_pair_xchg(v.l[i]);
-    return r;
-  }
-  ARK_D static Fp2L zero() { return Fp2L{Base::zero()}; }
-  ARK_D static Fp2L one() { return Fp2L{parity() ? Base::zero() : Base::one()}; }
-  ARK_D bool is_zero() const {
-    uint32_t accw = 0;
-#pragma unroll
-    for (int i = 0; i < N; i++) accw |= c.l[i];
-    const uint32_t other = ark_pair_xchg(accw);
-    return (accw | other) == 0;
-  }
-  ARK_D bool operator==(const Fp2L& o) const {
-    uint32_t accw = 0;
-#pragma unroll
-    for (int i = 0; i < N; i++) accw |= (c.l[i] ^ o.c.l[i]);
-    const uint32_t other = ark_pair_xchg(accw);
-    return (accw | other) == 0;
-  }
-  ARK_D bool operator!=(const Fp2L& o) const { return !(*this == o); }
-  ARK_D static Fp2L add(const Fp2L& a, const Fp2L& b) { return Fp2L{Base::add(a.c, b.c)}; }
-  ARK_D static Fp2L sub(const Fp2L& a, const Fp2L& b) { return Fp2L{Base::sub(a.c, b.c)}; }
-  ARK_D static Fp2L neg(const Fp2L& a) { return Fp2L{Base::neg(a.c)}; }
-  ARK_D static Fp2L dbl(const Fp2L& a) { return add(a, a); }
-  ARK_D static Fp2L mul2(const Fp2L& a) { return add(a, a); }
-  ARK_D static Fp2L mul3(const Fp2L& a) { return add(add(a, a), a); }
-  ARK_D static Fp2L mul(const Fp2L& a, const Fp2L& b) {
-    const Base pa = xchg(a.c), pb = xchg(b.c);
-    const Base npa = Base::neg(pa);
-    const bool odd = parity() != 0;
-    Base x1, x2;
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-      x1.l[i] = odd ? pa.l[i] : a.c.l[i];
-      x2.l[i] = odd ? a.c.l[i] : npa.l[i];
-    }
-    return Fp2L{Base::mul2sum(x1, b.c, x2, pb)};
-  }
-  // (a0 + a1 u)^2 = (a0 + a1)(a0 - a1) + 2 a0 a1 u: ONE single-product Montgomery pass per lane
-  //   even lane: (a0 + a1) * (a0 - a1)        odd lane: (a0 + a0) * a1
-  ARK_D static Fp2L sqr(const Fp2L& a) {
-    const Base pa = xchg(a.c);
-    const bool odd = parity() != 0;
-    Base t;
-#pragma unroll
-    for (int i = 0; i < N; i++) t.l[i] = odd ? pa.l[i] : a.c.l[i];
-    const Base u = Base::add(pa, t);                 // even: a1 + a0      odd: a0 + a0
-    const Base d = Base::sub(a.c, pa);               // even: a0 - a1      (odd: unused)
-    Base v;
-#pragma unroll
-    for (int i = 0; i < N; i++) v.l[i] = odd ? a.c.l[i] : d.l[i];
-    return Fp2L{Base::mul(u, v)};
-  }
-  // a*b - c*d: four products, one reduction per lane
-#ifndef ARK_G2L_FUSE_Y3
-#define ARK_G2L_FUSE_Y3 1
-#endif
-  static constexpr bool FUSED_MUL_SUB = ARK_G2L_FUSE_Y3 != 0;
-  ARK_D static Fp2L mul_sub(const Fp2L& a, const Fp2L& b, const Fp2L& c, const Fp2L& d) {
-    const bool odd = parity() != 0;
-    const Base pa = xchg(a.c), pb = xchg(b.c), pc = xchg(c.c), pd = xchg(d.c);
-    const Base npa = Base::neg(pa), nc = Base::neg(c.c);
-    Base x1, x2, x3, x4;
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-      x1.l[i] = odd ? pa.l[i] : a.c.l[i];            // even: a0*b0 - a1*b1        odd: a0*b1 + a1*b0
-      x2.l[i] = odd ? a.c.l[i] : npa.l[i];
-      x4.l[i] = odd ? nc.l[i] : pc.l[i];             // even: -c0*d0 + c1*d1       odd: -c0*d1 - c1*d0
-    }
-    const Base npc = Base::neg(pc);
-#pragma unroll
-    for (int i = 0; i < N; i++) x3.l[i] = odd ? npc.l[i] : nc.l[i];
-    return Fp2L{Base::mul4sum(x1, b.c, x2, pb, x3, d.c, x4, pd)};
-  }
-  ARK_D static Fp2L mul_ni(const Fp2L& a, const Fp2L& b) { return mul(a, b); }
-  ARK_D static Fp2L sqr_ni(const Fp2L& a) { return mul(a, a); }
-  static constexpr bool COLD_INLINE_MUL = true;     // curve.cuh: a lane's half of an Fq2 operation has Fq-like registers
-};
-
-#endif  // ARK_PLAIN_HOST
 
 using BlsFq = Fp<BlsFqParams>;
 using BlsFr = Fp<BlsFrParams>;

@@ -269,14 +269,13 @@ struct ProofParts {
   using Fq = typename Curve::Fq;
   using Fq2 = typename Curve::Fq2;
   MsmPlan plan[5];          // A, B1, L', H, B2
-  int fmt[5] = {0, 0, 0, 0, 0};
   uint32_t count[5] = {0, 0, 0, 0, 0};
   size_t off[5] = {0, 0, 0, 0, 0};          // byte offsets in the results buffer
   size_t bytes = 0;
   void layout() {
     bytes = 0;
     for (int i = 0; i < 5; i++) {
-      count[i] = msm_parts_count(plan[i], fmt[i]);
+      count[i] = msm_parts_count(plan[i]);
       off[i] = bytes;
       bytes += (size_t)count[i] * (i < 4 ? sizeof(XYZZ<Fq>) : sizeof(XYZZ<Fq2>));
     }
@@ -284,9 +283,9 @@ struct ProofParts {
   // host: the five sums from a copy of the results buffer (the four G1 Horner passes beside the G2 one)
   void finish(const uint8_t* land, XYZZ<Fq> g1[4], XYZZ<Fq2>& g2) const {
     auto f_g2 = std::async(std::launch::async, [&] {
-      return msm_parts_finish<Fq2>(reinterpret_cast<const XYZZ<Fq2>*>(land + off[4]), plan[4], fmt[4]);
+      return msm_parts_finish<Fq2>(reinterpret_cast<const XYZZ<Fq2>*>(land + off[4]), plan[4]);
     });
-    for (int i = 0; i < 4; i++) g1[i] = msm_parts_finish<Fq>(reinterpret_cast<const XYZZ<Fq>*>(land + off[i]), plan[i], fmt[i]);
+    for (int i = 0; i < 4; i++) g1[i] = msm_parts_finish<Fq>(reinterpret_cast<const XYZZ<Fq>*>(land + off[i]), plan[i]);
     g2 = f_g2.get();
   }
 };
@@ -639,23 +638,19 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, const PkDev& pk, const
       FillBatch fb(sS);
       msm_sort_plan<Fr>(ctx, sc.sortZ, pk.z_cnt, sS, &pk.a_ext, &fb);
       // bucket sets are sized and cleared here as well (msm_prepare_phase)
-      msm_prepare_phase<Fq2>(pol, sc.sortZ, sc.bkB2, sS, pk.b2_ext.fmt(), &fb);
-      msm_prepare_phase<Fq>(pol, sc.sortZ, sc.bkA, sS, pk.a_ext.fmt(), &fb);
-      msm_prepare_phase<Fq>(pol, sc.sortZ, sc.bkB1, sS, pk.b1_ext.fmt(), &fb);
-      msm_prepare_phase<Fq>(pol, sc.sortZ, sc.bkL, sS, pk.l_ext.fmt(), &fb);
+      msm_prepare_phase<Fq2>(pol, sc.sortZ, sc.bkB2, sS, &fb);
+      msm_prepare_phase<Fq>(pol, sc.sortZ, sc.bkA, sS, &fb);
+      msm_prepare_phase<Fq>(pol, sc.sortZ, sc.bkB1, sS, &fb);
+      msm_prepare_phase<Fq>(pol, sc.sortZ, sc.bkL, sS, &fb);
       msm_sort_plan<Fr>(ctx, sc.sortH, pk.h_cnt, sS, &pk.h_query, &fb);
-      msm_prepare_phase<Fq>(pol, sc.sortH, sc.bkH, sS, pk.h_query.fmt(), &fb);
+      msm_prepare_phase<Fq>(pol, sc.sortH, sc.bkH, sS, &fb);
       fb.flush();
     }
     // what the five MSMs leave for the host (c partial sums per bucket set and MSM: tails28_impl.cuh), A, B1, L', H, then B2
     ProofParts<Curve> parts;
     {
       const MsmSort* so[5] = {&sc.sortZ, &sc.sortZ, &sc.sortZ, &sc.sortH, &sc.sortZ};
-      const PrecompTable* tb[5] = {&pk.a_ext, &pk.b1_ext, &pk.l_ext, &pk.h_query, &pk.b2_ext};
-      for (int i = 0; i < 5; i++) {
-        parts.plan[i] = so[i]->plan;
-        parts.fmt[i] = tb[i]->fmt();
-      }
+      for (int i = 0; i < 5; i++) parts.plan[i] = so[i]->plan;
       parts.layout();
     }
     sc.results.ensure(parts.bytes);
@@ -706,11 +701,9 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, const PkDev& pk, const
       ARK_CHECK_HIP(hipStreamWaitEvent(sA, ev[jb.sort_ev], 0));
       const MsmSort* red_sort = jb.sort;          // what the reduction reads offsets / counts from
       if (jb.g2) {
-        msm_accumulate_phase<Fq2>(ctx, *jb.sort, *jb.bk, jb.tab->table.template as<Affine<Fq2>>(), sA, acc0[j], acc1[j],
-                                  jb.tab->fmt());
+        msm_accumulate_phase<Fq2>(ctx, *jb.sort, *jb.bk, jb.tab->table.p, jb.tab->packed, sA, acc0[j], acc1[j]);
       } else {
-        msm_accumulate_phase<Fq>(ctx, *jb.sort, *jb.bk, jb.tab->table.template as<Affine<Fq>>(), sA, acc0[j], acc1[j],
-                                 jb.tab->fmt());
+        msm_accumulate_phase<Fq>(ctx, *jb.sort, *jb.bk, jb.tab->table.p, jb.tab->packed, sA, acc0[j], acc1[j]);
       }
       ARK_CHECK_HIP(hipEventRecord(ev[E_ACC_DONE0 + j], sA));
       pts += (uint64_t)jb.sort->plan.windows * jb.sort->plan.n;
@@ -726,19 +719,18 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, const PkDev& pk, const
       ARK_CHECK_HIP(hipStreamWaitEvent(sT, ev[E_ACC_DONE0 + j], 0));
       if (ring) {
         // bucket-level exchange: the ranks run their MSMs in the same order, so the ring steps pair up
-        const int bfmt = jb.bk->fmt;
         if (jb.g2)
-          msm_reduce_phase<Fq2>(ctx, *red_sort, *jb.bk, g2res, 0, sT, [&](void* bk, uint32_t nb, hipStream_t st) {
-            ring_reduce_scatter_buckets<Fq2>(*cm, bk, nb, bfmt, st, pol.rccl_self != 0);
+          msm_reduce_phase<Fq2>(ctx, *red_sort, *jb.bk, g2res, sT, [&](void* bk, uint32_t nb, hipStream_t st) {
+            ring_reduce_scatter_buckets<Fq2>(*cm, bk, nb, st, pol.rccl_self != 0);
           });
         else
-          msm_reduce_phase<Fq>(ctx, *red_sort, *jb.bk, g1res[jb.res], 0, sT, [&](void* bk, uint32_t nb, hipStream_t st) {
-            ring_reduce_scatter_buckets<Fq>(*cm, bk, nb, bfmt, st, pol.rccl_self != 0);
+          msm_reduce_phase<Fq>(ctx, *red_sort, *jb.bk, g1res[jb.res], sT, [&](void* bk, uint32_t nb, hipStream_t st) {
+            ring_reduce_scatter_buckets<Fq>(*cm, bk, nb, st, pol.rccl_self != 0);
           });
       } else if (jb.g2) {
-        msm_reduce_phase<Fq2>(ctx, *red_sort, *jb.bk, g2res, 0, sT);
+        msm_reduce_phase<Fq2>(ctx, *red_sort, *jb.bk, g2res, sT);
       } else {
-        msm_reduce_phase<Fq>(ctx, *red_sort, *jb.bk, g1res[jb.res], 0, sT);
+        msm_reduce_phase<Fq>(ctx, *red_sort, *jb.bk, g1res[jb.res], sT);
       }
       if (side_tail) {
         h_tails_aside = true;
@@ -756,10 +748,10 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, const PkDev& pk, const
       if (side_g2) {
         sc.ensure_streams(pol.stream_prio != 0);
         ARK_CHECK_HIP(hipStreamWaitEvent(sc.sR, ev[E_ACC_DONE0 + 0], 0));
-        msm_reduce_phase<Fq2>(ctx, sc.sortZ, sc.bkB2, g2res, 0, sc.sR);
+        msm_reduce_phase<Fq2>(ctx, sc.sortZ, sc.bkB2, g2res, sc.sR);
         ARK_CHECK_HIP(hipEventRecord(ev[E_G2T], sc.sR));
       } else {
-        msm_reduce_phase<Fq2>(ctx, sc.sortZ, sc.bkB2, g2res, 0, sR);
+        msm_reduce_phase<Fq2>(ctx, sc.sortZ, sc.bkB2, g2res, sR);
       }
       const MsmSort* sorts[4] = {&sc.sortZ, &sc.sortZ, &sc.sortZ, &sc.sortH};
       MsmBuckets* bks[4] = {&sc.bkA, &sc.bkB1, &sc.bkL, &sc.bkH};
@@ -772,13 +764,13 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, const PkDev& pk, const
         ARK_CHECK_HIP(hipStreamWaitEvent(sc.sR, ev[E_ACC_DONE0 + 3], 0));
         batched = msm_reduce_phase_batch<Fq>(ctx, 3, sorts, bks, outs, sc.sR);
         if (!batched)
-          for (int i = 0; i < 3; i++) msm_reduce_phase<Fq>(ctx, *sorts[i], *bks[i], outs[i], 0, sc.sR);
+          for (int i = 0; i < 3; i++) msm_reduce_phase<Fq>(ctx, *sorts[i], *bks[i], outs[i], sc.sR);
         ARK_CHECK_HIP(hipEventRecord(ev[E_G2T], sc.sR));        // (re-recorded: now behind the G2 tails AND the batch of three)
-        msm_reduce_phase<Fq>(ctx, *sorts[3], *bks[3], outs[3], 0, sR);
+        msm_reduce_phase<Fq>(ctx, *sorts[3], *bks[3], outs[3], sR);
       } else {
         batched = msm_reduce_phase_batch<Fq>(ctx, 4, sorts, bks, outs, sR);
         if (!batched)
-          for (int i = 0; i < 4; i++) msm_reduce_phase<Fq>(ctx, *sorts[i], *bks[i], outs[i], 0, sR);
+          for (int i = 0; i < 4; i++) msm_reduce_phase<Fq>(ctx, *sorts[i], *bks[i], outs[i], sR);
       }
       if (trace_host)
         fprintf(stderr, "[ark355] G1 tails: %s%s\n", batched ? "one launch per step" : "per MSM", side_g1 ? " (A, B1, L' aside, H at the end)" : " for the four MSMs");

@@ -1,9 +1,8 @@
-// Bucket accumulation over radix-2^28 window tables (field28.cuh): the hot kernel of every resident-key G1 MSM.
+// Bucket accumulation over radix-2^28 rows (field28.cuh): the hot kernels of every MSM, G1 and -- on lane pairs -- G2.
 //
-// Same algorithm, same segment/run/flush protocol and the same outputs as msm_accumulate_kernel (msm_impl.cuh); the
-// mixed addition runs on lazily reduced 28-bit limbs so that a Montgomery product needs no carry instructions.
-// Window tables are converted to Affine28 rows once per key (table_to28_kernel); bucket partials leave the kernel
-// in the canonical 32-bit form every other kernel uses.
+// The segment/run/flush protocol of K4 (msm_impl.cuh); the mixed addition runs on lazily reduced 28-bit limbs so that a
+// Montgomery product needs no carry instructions.  Window tables are converted to Affine28 rows once per key, the bases of a
+// one-shot MSM once per call (table_to28_kernel); bucket partials stay in that form for the tails (tails28_impl.cuh).
 #pragma once
 #include "field28.cuh"
 #include "curve.cuh"
@@ -136,7 +135,7 @@ ARK_HD bool slot28_get(const Slot28<P>* src, Acc28<P>& a) {
   return any == 0;
 }
 
-// Where a finished run goes (same protocol as msm_flush_run, msm_impl.cuh): buckets[key] when it is the bucket's only run,
+// Where a finished run goes (the protocol the merge of tails28_impl.cuh relies on): buckets[key] when it is the bucket's only run,
 // head[seg] when it opened the segment, tail[seg] otherwise.  Three explicit branches, NOT a select among the pointers:
 // hipcc turns such a select into an indexed load from the caller's closure object, which then cannot be scalarised -- and
 // every captured variable, the accumulator included, lives in scratch memory for the whole loop.
@@ -357,8 +356,8 @@ ARK_D void madd28(Acc28<P>& acc, bool& empty, const Fp28<P>& px, const Fp28<P>& 
 // (Round 6, run O: this walk at THREE waves per SIMD -- 168 registers, x / zz / zzz of the accumulator in LDS through ZzLds, no
 // row prefetch, `msm_accumulate28w3_kernel` of commit 2a07047 -- measured 4.7 % slower per launch and 3.7 % per proof in
 // flight, profiles/r06_runO_g1_three_waves.txt: a third wave does not take the slots the relay of two leaves.)
-// Same contract as msm_accumulate_kernel<Fp<P>, false>; `bases` holds UNPACKED rows (Affine28U): the plain segment walk of
-// rounds 2-4 -- the row of the next entry prefetched into registers, a finished run flushed where it ends.
+// `bases` holds UNPACKED rows (Affine28U): the plain segment walk of rounds 2-4 -- the row of the next entry prefetched into
+// registers, a finished run flushed where it ends.
 //
 // What bounds this kernel (round 5; tools/ubench5, tools/acc_trace.py on a tracing build, rocprofv3 --pmc; DESIGN.md
 // section 11): VALU issue.  A lane executes ~4 560 VALU instructions per addition (3 155 multiply-adds); the SIMD
@@ -399,7 +398,7 @@ msm_accumulate28_kernel(const Affine28U<P>* __restrict__ bases, const uint32_t* 
     msm_flush_slot28<P>(buckets, head, tail, head_key, tail_key, true, key, acc, empty, first_run, run_start, run_end, seg, offsets,
                         counts, sizeof(Slot28<P>));
   };
-  // software prefetch of the next row into explicit 16-byte registers (see msm_accumulate_kernel)
+  // software prefetch of the next row into explicit 16-byte registers
   uint4 nx[Q];
   uint32_t v_next = sorted_vals[start];
   {
@@ -449,7 +448,7 @@ msm_accumulate28_kernel(const Affine28U<P>* __restrict__ bases, const uint32_t* 
 
 
 // ---- the segment walk of the kernels over PACKED rows (msm_accumulate28p_kernel, msm_accumulate_g2l28p_kernel) ------------
-// Run / flush protocol as in msm_accumulate_kernel (msm_impl.cuh): a lane walks ONE segment of the sorted entry list; a
+// Run / flush protocol as in the plain walk above: a lane walks ONE segment of the sorted entry list; a
 // maximal stretch of equal keys is a run; a finished run goes to buckets[key] when it is the bucket's only run, to
 // head[seg] when it opened the segment, to tail[seg] otherwise.
 //
@@ -603,9 +602,9 @@ msm_accumulate28p_kernel(const Affine28<P>* __restrict__ bases, const uint32_t* 
 
 // ================================================================================================================
 // G2: lane-split accumulation on 28-bit limbs.  Two lanes per segment (even: c0 components, odd: c1 components of
-// every Fq2 value, as in msm_accumulate_g2l_kernel); a table row is two Affine28 halves, {x.c0, y.c0} then
+// every Fq2 value); a table row is two Affine28 halves, {x.c0, y.c0} then
 // {x.c1, y.c1}, so that each lane gathers one aligned half.
-// Measured on MI355X: 9.2 ms per 2^20-term MSM against 10.8 ms for the 32-bit lane-split kernel (same box, both
+// Measured on MI355X: 9.2 ms per 2^20-term MSM against 10.8 ms for the 32-bit lane-split kernel of rounds 1-5 (same box, both
 // interleaved with the witness map) -- once the accumulator really lived in registers.  The first version of this
 // kernel only tied: its flush picked the destination with a select among captured pointers, hipcc turned that into an
 // indexed load from the lambda's closure object, the closure could not be scalarised, and EVERY captured variable (the

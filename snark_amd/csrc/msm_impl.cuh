@@ -2,29 +2,27 @@
 //
 // Device replacement for ark-ec `VariableBaseMSM::msm_bigint` (un-vendored crate,
 // ark-ec/src/scalar_mul/variable_base/mod.rs) as called five times by the Groth16 prover
-// (SURVEY.md 3.1 HOT LOOP #5).  Same mathematics -- signed c-bit window digits, bucket
-// accumulation, running-sum bucket reduction, window combination -- laid out for the GPU:
+// (SURVEY.md 3.1 HOT LOOP #5).  Same mathematics -- signed c-bit window digits, bucket accumulation,
+// sum_b (b+1) B_b per bucket set, window combination -- laid out for the GPU:
 //
+//   rows           the bases in the radix-2^28 form of field28.cuh (table_to28_kernel, packed or one word per limb).
+//                  A resident key keeps window tables T[w*n + i] = 2^(c*w) * P_i, so that every window shares ONE bucket
+//                  set (or every wstride-th window has a table: wstride sets); a one-shot MSM re-encodes the caller's bases
+//                  and keeps one bucket set per window
 //   K2/K3 sort     signed c-bit digits of every scalar (key = bucket, value = table row | sign) and a two-level
 //                  counting sort of the (key, value) entries: level 1 groups by key >> 8 with per-workgroup LDS
 //                  histograms and private output ranges, level 2 places tiles of 4096 entries with LDS ranks and one
 //                  global atomic per (tile, key)  ("two-level counting sort" below; the one-pass version with
 //                  per-entry global atomics is kept as ARK355_SORT=legacy)
-//   K4 accumulate  THE dominant kernels: the sorted entry list is cut into fixed segments of L
+//   K4 accumulate  THE dominant kernels (msm28_impl.cuh): the sorted entry list is cut into fixed segments of L
 //                  entries, one lane per segment (two lanes for G2), so every lane performs exactly L mixed
 //                  additions (XYZZ += affine) whatever the bucket-size distribution; runs that cover a whole
 //                  bucket are written straight to the bucket array, the at most two partial runs
-//                  per segment go to head/tail slots.  Resident keys: radix-2^28 kernels over window tables
-//                  (msm28_impl.cuh); ad-hoc bases: the 32-bit kernels of this file
-//      merge       one thread per bucket that straddles segments adds its partial runs (a workgroup for heavy ones)
-//   K5 reduce      per window sum_b (b+1) B_b: every lane takes K consecutive buckets (running sum),
-//                  adds (first index)*S via a short double-and-add, then wave-wide butterfly
-//                  reduction with __shfl_xor, one partial per workgroup
-//      combine     lane w sums window w's partials, doubles it c*w times, __shfl_xor tree over windows
-//                  (with window tables there is ONE bucket set and no doubling)
-//   The merge / reduce / combine tails are latency-bound (a few dozen dependent group operations on 32-128 workgroups).
-//   G1: the out-of-line group addition inlines its multiplications (curve.cuh); G2: the *_pair_kernel flavours give every
-//   bucket / chunk to a LANE PAIR (Fp2L: one component of each Fq2 coordinate per lane).
+//                  per segment go to head/tail slots
+//   tails          (tails28_impl.cuh) merge: one lane per bucket that straddles segments adds its partial runs (a
+//                  workgroup for heavy ones); then sum_b (b+1) B_b as PLAIN sums -- the row / column sums of the bucket
+//                  matrix, then c bit sums per bucket set
+//   host           Horner over the bit sums, bucket set j weighted 2^(c*j) (msm_finish_host), and the normalisation
 //
 // Algorithmic bytes per term: 32 B scalar + affine base (G1 96 B / G2 192 B BLS12-381).
 #pragma once
@@ -42,11 +40,7 @@ constexpr uint32_t MSM_INVALID = 0xFFFFFFFFu;
 // entries per accumulate lane: msm_seg_len() below (32 keeps small MSMs wide enough to fill the chip; ~64 halves the
 // partial runs of the 2^24-entry MSMs of a 2^20 proof -- measured on MI355X: 53.7 / 52.6 / 52.3 ms per proof for
 // 32 / 64 / 128)
-constexpr uint32_t MSM_RED_K = 4;         // buckets per reduce lane (latency-bound kernel: short chains, many lanes)
 constexpr uint32_t MSM_THREADS = 256;
-#ifndef ARK_G1_PREFETCH
-#define ARK_G1_PREFETCH 1   // measured neutral on MI355X (7.75 vs 7.79 ms for A+B1); kept for small-n latency
-#endif
 
 struct MsmPlan {
   uint64_t n = 0;
@@ -58,7 +52,7 @@ struct MsmPlan {
   bool precomp = false;
   // Window tables may hold only every wstride-th window (T[q*n + i] = 2^(c*wstride*q) * P_i, q < table_windows): a key
   // whose full tables would not fit HBM trades table rows for bucket sets.  Window w = wstride*q + j then reads table
-  // row q and lands in bucket set j; the sets are combined as sum_j 2^(c*j) S_j (msm_combine_kernel), i.e. c*(wstride-1)
+  // row q and lands in bucket set j; the sets are combined as sum_j 2^(c*j) S_j (msm_finish_host), i.e. c*(wstride-1)
   // doublings per MSM come back.  wstride = 1: one bucket set, no doubling at all (the default whenever it fits);
   // without tables wstride = windows (every window its own set, every value indexes the base vector itself).
   uint32_t wstride = 1, table_windows = 0;
@@ -595,107 +589,11 @@ sort_lo_kernel(const uint2* __restrict__ tmp /* (key, value) pairs grouped by bi
   }
 }
 
-// ---- K4: bucket accumulation -----------------------------------------------------------------------------
-template <class F>
-struct SegPartial {
-  XYZZ<F> pt;
-};
-
-template <class F>
-ARK_D void msm_flush_run(uint32_t key, const XYZZ<F>& acc, bool first_run, uint32_t run_start, uint32_t run_end,
-                         uint32_t seg, const uint32_t* offsets, const uint32_t* counts, XYZZ<F>* buckets,
-                         XYZZ<F>* head, uint32_t* head_key, XYZZ<F>* tail, uint32_t* tail_key) {
-  const uint32_t o = offsets[key], cnt = counts[key];
-  const bool complete = (run_start == o) && (run_end == o + cnt);
-  if (complete) {
-    buckets[key] = acc;
-  } else if (first_run) {
-    head[seg] = acc;
-    head_key[seg] = key;
-  } else {
-    tail[seg] = acc;
-    tail_key[seg] = key;
-  }
-}
-
+// ---- K4: bucket accumulation (msm28_impl.cuh) and the tails (tails28_impl.cuh) ---------------------------------------
 }  // namespace ark355
 #include "tails28_impl.cuh"     // (includes msm28_impl.cuh: the 28-bit accumulation kernels and their bucket slots)
 namespace ark355 {
 
-template <class F, bool NI>
-__global__ void __launch_bounds__(MSM_THREADS)
-msm_accumulate_kernel(const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ sorted_keys,
-                      const uint32_t* __restrict__ sorted_vals, const uint32_t* __restrict__ total_ptr,
-                      const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                      XYZZ<F>* __restrict__ buckets, XYZZ<F>* __restrict__ head, uint32_t* __restrict__ head_key,
-                      XYZZ<F>* __restrict__ tail, uint32_t* __restrict__ tail_key, uint32_t seg_len) {
-  const uint32_t seg = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t total = *total_ptr;
-  const uint32_t MSM_SEG = seg_len;
-  const uint64_t start64 = (uint64_t)seg * seg_len;
-  if (start64 >= total) return;
-  const uint32_t start = (uint32_t)start64;
-  const uint32_t end = (start + MSM_SEG < total) ? start + MSM_SEG : total;
-  uint32_t cur_key = sorted_keys[start];
-  uint32_t run_start = start;
-  bool first_run = true;
-  XYZZ<F> acc = XYZZ<F>::inf();
-  // Software prefetch: the next base (a random 96/192-byte gather from the window tables) is in flight while the
-  // current mixed addition runs.  It is held in explicit 16-byte registers: a struct copy here was lowered by
-  // hipcc to scratch-to-scratch copies with a vmcnt(0) after every load (seen in the round-1 ISA).
-  constexpr int Q = sizeof(Affine<F>) / 16;
-  // G2 lives at the edge of the 512-register file: holding the prefetched point (48 more registers) costs more
-  // in spills than the gather latency it hides (one ~2 us gather per ~60 us mixed addition)
-  constexpr bool PREFETCH = ARK_G1_PREFETCH && sizeof(F) <= 64;
-  uint4 nx[Q];
-  uint32_t v_next = sorted_vals[start];
-  if constexpr (PREFETCH) {
-    const uint4* src = reinterpret_cast<const uint4*>(bases + (v_next & ARK_TBL_MASK));
-#pragma unroll
-    for (int k = 0; k < Q; k++) nx[k] = src[k];
-  }
-  for (uint32_t e = start; e < end; e++) {
-    const uint32_t key = sorted_keys[e];
-    uint32_t v = v_next;
-    Affine<F> p;
-    if constexpr (PREFETCH) {
-      uint32_t* d = reinterpret_cast<uint32_t*>(&p);
-#pragma unroll
-      for (int k = 0; k < Q; k++) {
-        d[4 * k + 0] = nx[k].x;
-        d[4 * k + 1] = nx[k].y;
-        d[4 * k + 2] = nx[k].z;
-        d[4 * k + 3] = nx[k].w;
-      }
-      const uint32_t en = (e + 1 < end) ? e + 1 : e;     // clamp: the last iteration re-reads its own entry
-      v_next = sorted_vals[en];
-      const uint4* src = reinterpret_cast<const uint4*>(bases + (v_next & ARK_TBL_MASK));
-#pragma unroll
-      for (int k = 0; k < Q; k++) nx[k] = src[k];
-    } else {
-      v = sorted_vals[e];
-      p = bases[v & ARK_TBL_MASK];
-    }
-    if (key != cur_key) {
-      msm_flush_run<F>(cur_key, acc, first_run, run_start, e, seg, offsets, counts, buckets, head, head_key, tail,
-                       tail_key);
-      cur_key = key;
-      run_start = e;
-      first_run = false;
-      acc = XYZZ<F>::inf();
-    }
-    if (v >> 31) p.y = F::neg(p.y);
-    if constexpr (NI) xyzz_madd_ni(acc, p);
-    else xyzz_madd(acc, p);
-  }
-  msm_flush_run<F>(cur_key, acc, first_run, run_start, end, seg, offsets, counts, buckets, head, head_key, tail,
-                   tail_key);
-}
-
-// ---- K4 for G2: lane-split accumulation -------------------------------------------------------------------------
-// Two lanes per segment: even lanes carry the c0 components, odd lanes the c1 components of every Fq2 value
-// (field.cuh Fp2L).  Same segment/run logic as msm_accumulate_kernel; loads and stores touch this lane's half
-// of each Fq2 coordinate.
 template <class P>
 struct is_fp2 {
   static constexpr bool value = false;
@@ -705,125 +603,12 @@ struct is_fp2<Fp2<P>> {
   static constexpr bool value = true;
 };
 
-template <class P>
-ARK_D void g2l_store(XYZZ<Fp2<P>>* dst, const XYZZ<Fp2L<P>>& v, uint32_t par) {
-  Fp<P>* d = reinterpret_cast<Fp<P>*>(dst);
-  d[0 + par] = v.x.c;
-  d[2 + par] = v.y.c;
-  d[4 + par] = v.zz.c;
-  d[6 + par] = v.zzz.c;
-}
-
-#ifndef ARK_G2L_PREFETCH
-#define ARK_G2L_PREFETCH 0
-#endif
-// Two waves per SIMD need <= 256 registers per lane.  With the register prefetch of the next base the kernel
-// lands on 251-256, and that build ran at 11.2 ms on some MI355X boxes but 17-24 ms on others (same binary);
-// without it there is head-room below the cliff.
-template <class P>
-__global__ void __launch_bounds__(MSM_THREADS, 2)
-msm_accumulate_g2l_kernel(const Affine<Fp2<P>>* __restrict__ bases, const uint32_t* __restrict__ sorted_keys,
-                          const uint32_t* __restrict__ sorted_vals, const uint32_t* __restrict__ total_ptr,
-                          const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                          XYZZ<Fp2<P>>* __restrict__ buckets, XYZZ<Fp2<P>>* __restrict__ head,
-                          uint32_t* __restrict__ head_key, XYZZ<Fp2<P>>* __restrict__ tail,
-                          uint32_t* __restrict__ tail_key, uint32_t seg_len) {
-  using FL = Fp2L<P>;
-  using Fq = Fp<P>;
-  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t seg = gid >> 1, par = gid & 1u;       // blockDim is even: par == lane parity
-  const uint32_t total = *total_ptr;
-  const uint64_t start64 = (uint64_t)seg * seg_len;
-  if (start64 >= total) return;                        // both lanes of a pair leave together
-  const uint32_t start = (uint32_t)start64;
-  const uint32_t end = (start + seg_len < total) ? start + seg_len : total;
-  uint32_t cur_key = sorted_keys[start];
-  uint32_t run_start = start;
-  bool first_run = true;
-  XYZZ<FL> acc = XYZZ<FL>::inf();
-  auto flush = [&](uint32_t key, uint32_t run_end) {
-    const uint32_t o = offsets[key], cnt = counts[key];
-    const bool complete = (run_start == o) && (run_end == o + cnt);
-    if (complete) {
-      g2l_store<P>(&buckets[key], acc, par);
-    } else if (first_run) {
-      g2l_store<P>(&head[seg], acc, par);
-      if (par == 0) head_key[seg] = key;
-    } else {
-      g2l_store<P>(&tail[seg], acc, par);
-      if (par == 0) tail_key[seg] = key;
-    }
-  };
-  // this lane's halves of a base: x.c[par] and y.c[par], 3 (BLS) / 2 (BN) x 16 B each; optionally prefetched one
-  // iteration ahead into registers
-  constexpr int Q = sizeof(Fq) / 16;
-  constexpr bool PF = ARK_G2L_PREFETCH != 0;
-  uint4 nx[2 * Q];
-  auto fetch = [&](uint32_t v) {
-    const Fq* b = reinterpret_cast<const Fq*>(bases + (v & ARK_TBL_MASK));
-    const uint4* sx = reinterpret_cast<const uint4*>(b + par);
-    const uint4* sy = reinterpret_cast<const uint4*>(b + 2 + par);
-#pragma unroll
-    for (int k = 0; k < Q; k++) {
-      nx[k] = sx[k];
-      nx[Q + k] = sy[k];
-    }
-  };
-  uint32_t v_next = sorted_vals[start];
-  if constexpr (PF) fetch(v_next);
-  for (uint32_t e = start; e < end; e++) {
-    const uint32_t key = sorted_keys[e];
-    uint32_t v = v_next;
-    if constexpr (!PF) {
-      v = sorted_vals[e];
-      fetch(v);
-    }
-    Affine<FL> p;
-    {
-      uint32_t* dx = p.x.c.l;
-      uint32_t* dy = p.y.c.l;
-#pragma unroll
-      for (int k = 0; k < Q; k++) {
-        dx[4 * k + 0] = nx[k].x;
-        dx[4 * k + 1] = nx[k].y;
-        dx[4 * k + 2] = nx[k].z;
-        dx[4 * k + 3] = nx[k].w;
-        dy[4 * k + 0] = nx[Q + k].x;
-        dy[4 * k + 1] = nx[Q + k].y;
-        dy[4 * k + 2] = nx[Q + k].z;
-        dy[4 * k + 3] = nx[Q + k].w;
-      }
-    }
-    if constexpr (PF) {
-      const uint32_t en = (e + 1 < end) ? e + 1 : e;
-      v_next = sorted_vals[en];
-      fetch(v_next);
-    }
-    if (key != cur_key) {
-      flush(cur_key, e);
-      cur_key = key;
-      run_start = e;
-      first_run = false;
-      acc = XYZZ<FL>::inf();
-    }
-    if (v >> 31) p.y = FL::neg(p.y);
-    xyzz_madd(acc, p);
-  }
-  flush(cur_key, end);
-}
-
-// The latency-bound tail kernels (merge, bucket reduction) keep to 256 registers per lane: two waves per SIMD, so that a
-// wave of theirs and a wave of an accumulation kernel of another proof in flight can share a SIMD.  (Left to itself the
-// Fq2 group addition takes 456 registers -- one wave per SIMD -- and the CUs a tail kernel sits on stop accumulating.)
-#ifndef MSM_TAIL_WAVES
-#define MSM_TAIL_WAVES 2
-#endif
-// buckets whose entries straddle segment boundaries: add their partial runs.  Buckets spread over more than
-// heavy_span segments (skewed scalars: boolean witnesses, the all-equal DummyCircuit, a short top window) are
-// only recorded here and summed by a whole workgroup each in msm_merge_heavy_kernel.  heavy_span is MSM_HEAVY_SPAN, or
-// twice the AVERAGE span when that is larger: in a 2^24-term MSM every bucket of a uniform input spans
-// ~130 segments, and sending all 32 768 of them through the 128 workgroups of the heavy kernel took 46 ms where one lane
-// per bucket takes 4 (profiles/r02_msm_microbench.txt).
+// The merge (msm_merge28_kernel, tails28_impl.cuh) adds the partial runs of buckets whose entries straddle segment
+// boundaries.  Buckets spread over more than heavy_span segments (skewed scalars: boolean witnesses, the all-equal
+// DummyCircuit, a short top window) are only recorded there and summed by a whole workgroup each in
+// msm_merge_heavy28_kernel.  heavy_span is MSM_HEAVY_SPAN, or twice the AVERAGE span when that is larger: in a 2^24-term
+// MSM every bucket of a uniform input spans ~130 segments, and sending all 32 768 of them through the 128 workgroups of the
+// heavy kernel took 46 ms where one lane per bucket takes 4 (profiles/r02_msm_microbench.txt).
 #ifndef ARK_MSM_HEAVY_SPAN
 #define ARK_MSM_HEAVY_SPAN 48   // tests shrink it so that tiny cases take the heavy path
 #endif
@@ -834,31 +619,6 @@ constexpr uint32_t MSM_HEAVY_SPAN = ARK_MSM_HEAVY_SPAN;
 // held the reduction stream for ~0.6 ms per MSM (round-2 timeline).
 #define ARK_MSM_HEAVY_GRID 128u
 #endif
-template <class F>
-__global__ void __launch_bounds__(MSM_THREADS, MSM_TAIL_WAVES)
-msm_merge_kernel(uint32_t total_buckets, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                 XYZZ<F>* __restrict__ buckets, const XYZZ<F>* __restrict__ head, const uint32_t* __restrict__ head_key,
-                 const XYZZ<F>* __restrict__ tail, const uint32_t* __restrict__ tail_key,
-                 uint32_t* __restrict__ heavy_count, uint32_t* __restrict__ heavy_list, uint32_t seg_len,
-                 uint32_t heavy_span) {
-  const uint32_t key = blockIdx.x * blockDim.x + threadIdx.x;
-  if (key >= total_buckets) return;
-  const uint32_t cnt = counts[key];
-  if (cnt == 0) return;
-  const uint32_t o = offsets[key];
-  const uint32_t t0 = o / seg_len, t1 = (o + cnt - 1) / seg_len;
-  if (t0 == t1) return;   // the single run was complete and already written
-  if (t1 - t0 > heavy_span) {
-    heavy_list[atomicAdd(heavy_count, 1u)] = key;
-    return;
-  }
-  XYZZ<F> sum = XYZZ<F>::inf();
-  for (uint32_t t = t0; t <= t1; t++) {
-    if (head_key[t] == key) sum = xyzz_add(sum, head[t]);
-    if (tail_key[t] == key) sum = xyzz_add(sum, tail[t]);
-  }
-  buckets[key] = sum;
-}
 
 // ---- wave-level reduction of XYZZ points with __shfl_xor ---------------------------------------------------
 template <class F>
@@ -879,355 +639,6 @@ ARK_D XYZZ<F> wave_reduce_sum(XYZZ<F> v) {
     v = xyzz_add(v, o);
   }
   return v;
-}
-
-// one workgroup per heavy bucket: lanes stride over the bucket's segments, wave butterfly, 4 waves through LDS
-template <class F>
-__global__ void __launch_bounds__(MSM_THREADS, MSM_TAIL_WAVES)
-msm_merge_heavy_kernel(const uint32_t* __restrict__ heavy_count, const uint32_t* __restrict__ heavy_list,
-                       const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                       XYZZ<F>* __restrict__ buckets, const XYZZ<F>* __restrict__ head,
-                       const uint32_t* __restrict__ head_key, const XYZZ<F>* __restrict__ tail,
-                       const uint32_t* __restrict__ tail_key, uint32_t seg_len) {
-  __shared__ uint32_t wave_out[(MSM_THREADS / 64) * (sizeof(XYZZ<F>) / 4)];
-  constexpr int WORDS = sizeof(XYZZ<F>) / 4;
-  const uint32_t nheavy = *heavy_count;
-  for (uint32_t h = blockIdx.x; h < nheavy; h += gridDim.x) {
-    const uint32_t key = heavy_list[h];
-    const uint32_t o = offsets[key], cnt = counts[key];
-    const uint32_t t0 = o / seg_len, t1 = (o + cnt - 1) / seg_len;
-    XYZZ<F> sum = XYZZ<F>::inf();
-    for (uint32_t t = t0 + threadIdx.x; t <= t1; t += blockDim.x) {
-      if (head_key[t] == key) sum = xyzz_add(sum, head[t]);
-      if (tail_key[t] == key) sum = xyzz_add(sum, tail[t]);
-    }
-    sum = wave_reduce_sum(sum);
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-      const uint32_t* src = reinterpret_cast<const uint32_t*>(&sum);
-      for (int i = 0; i < WORDS; i++) wave_out[wave * WORDS + i] = src[i];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      XYZZ<F> tot = XYZZ<F>::inf();
-      for (uint32_t v = 0; v < blockDim.x / 64; v++) {
-        XYZZ<F> t;
-        uint32_t* dst = reinterpret_cast<uint32_t*>(&t);
-        for (int i = 0; i < WORDS; i++) dst[i] = wave_out[v * WORDS + i];
-        tot = xyzz_add(tot, t);
-      }
-      buckets[key] = tot;
-    }
-    __syncthreads();
-  }
-}
-
-// ---- K5: bucket reduction: per window sum_{b} (b+1) * bucket[b] -----------------------------------------------
-// grid.x = blocks per window, grid.y = windows.  Output: partials[window * gridDim.x + blockIdx.x].
-template <class F>
-__global__ void __launch_bounds__(MSM_THREADS, MSM_TAIL_WAVES)
-msm_reduce_kernel(const XYZZ<F>* __restrict__ buckets, uint32_t buckets_per_window, XYZZ<F>* __restrict__ partials) {
-  __shared__ uint32_t wave_out[(MSM_THREADS / 64) * (sizeof(XYZZ<F>) / 4)];
-  const uint32_t w = blockIdx.y;
-  const uint32_t chunk = blockIdx.x * blockDim.x + threadIdx.x;   // chunk index inside the window
-  const uint32_t first = chunk * MSM_RED_K;
-  XYZZ<F> contrib = XYZZ<F>::inf();
-  if (first < buckets_per_window) {
-    const uint32_t last = (first + MSM_RED_K < buckets_per_window) ? first + MSM_RED_K : buckets_per_window;
-    const XYZZ<F>* wb = buckets + (uint64_t)w * buckets_per_window;
-    XYZZ<F> running = XYZZ<F>::inf();
-    XYZZ<F> acc = XYZZ<F>::inf();
-    for (uint32_t b = last; b-- > first;) {
-      running = xyzz_add(running, wb[b]);
-      acc = xyzz_add(acc, running);
-    }
-    // acc = sum (b - first + 1) * bucket[b];  add first * running
-    if (first != 0 && !running.is_inf()) {
-      uint32_t k = first;
-      acc = xyzz_add(acc, xyzz_mul_scalar(running, &k, 1));
-    }
-    contrib = acc;
-  }
-  contrib = wave_reduce_sum(contrib);
-  constexpr int WORDS = sizeof(XYZZ<F>) / 4;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(&contrib);
-    for (int i = 0; i < WORDS; i++) wave_out[wave * WORDS + i] = src[i];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    XYZZ<F> sum = XYZZ<F>::inf();
-    for (uint32_t v = 0; v < blockDim.x / 64; v++) {
-      XYZZ<F> t;
-      uint32_t* dst = reinterpret_cast<uint32_t*>(&t);
-      for (int i = 0; i < WORDS; i++) dst[i] = wave_out[v * WORDS + i];
-      sum = xyzz_add(sum, t);
-    }
-    partials[w * gridDim.x + blockIdx.x] = sum;
-  }
-}
-
-// ---- the same tails for G2 with LANE PAIRS (field.cuh Fp2L) ------------------------------------------------------------
-// Over Fq2 the out-of-line group addition with inlined multiplications needs 456 registers, so the kernels above call a
-// function per field multiplication when F = Fq2 -- 3.9 ms of bucket reduction and 1.2 ms of merge per 2^20-term MSM on a
-// few dozen workgroups.  Here every bucket / chunk belongs to TWO lanes, each holding one component of every coordinate:
-// G1-like registers per lane, multiplications inlined, and each Fq2 product is shared by the pair.  Control flow is
-// uniform inside a pair (keys, counts and the pair-wide predicates of Fp2L).
-#ifndef ARK_PLAIN_HOST
-template <class P>
-ARK_D XYZZ<Fp2L<P>> pair_load(const XYZZ<Fp2<P>>* p) {
-  const Fp<P>* q = reinterpret_cast<const Fp<P>*>(p);
-  const uint32_t par = threadIdx.x & 1u;
-  return XYZZ<Fp2L<P>>{Fp2L<P>{q[0 + par]}, Fp2L<P>{q[2 + par]}, Fp2L<P>{q[4 + par]}, Fp2L<P>{q[6 + par]}};
-}
-template <class P>
-ARK_D void pair_store(XYZZ<Fp2<P>>* p, const XYZZ<Fp2L<P>>& v) {
-  Fp<P>* q = reinterpret_cast<Fp<P>*>(p);
-  const uint32_t par = threadIdx.x & 1u;
-  q[0 + par] = v.x.c;
-  q[2 + par] = v.y.c;
-  q[4 + par] = v.zz.c;
-  q[6 + par] = v.zzz.c;
-}
-// butterfly over the 32 pairs of a wave (the masks keep the lane parity)
-template <class P>
-ARK_D XYZZ<Fp2L<P>> wave_reduce_sum_pairs(XYZZ<Fp2L<P>> v) {
-  for (int mask = 32; mask >= 2; mask >>= 1) {
-    XYZZ<Fp2L<P>> o = xyzz_shfl_xor(v, mask);
-    v = xyzz_add(v, o);
-  }
-  return v;
-}
-
-template <class P>
-__global__ void __launch_bounds__(MSM_THREADS, MSM_TAIL_WAVES)
-msm_merge_pair_kernel(uint32_t total_buckets, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                      XYZZ<Fp2<P>>* __restrict__ buckets, const XYZZ<Fp2<P>>* __restrict__ head,
-                      const uint32_t* __restrict__ head_key, const XYZZ<Fp2<P>>* __restrict__ tail,
-                      const uint32_t* __restrict__ tail_key, uint32_t* __restrict__ heavy_count,
-                      uint32_t* __restrict__ heavy_list, uint32_t seg_len, uint32_t heavy_span) {
-  using L = Fp2L<P>;
-  const uint32_t key = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;
-  if (key >= total_buckets) return;
-  const uint32_t cnt = counts[key];
-  if (cnt == 0) return;
-  const uint32_t o = offsets[key];
-  const uint32_t t0 = o / seg_len, t1 = (o + cnt - 1) / seg_len;
-  if (t0 == t1) return;   // the single run was complete and already written
-  if (t1 - t0 > heavy_span) {
-    if ((threadIdx.x & 1u) == 0) heavy_list[atomicAdd(heavy_count, 1u)] = key;
-    return;
-  }
-  XYZZ<L> sum = XYZZ<L>::inf();
-  for (uint32_t t = t0; t <= t1; t++) {
-    if (head_key[t] == key) sum = xyzz_add(sum, pair_load<P>(&head[t]));
-    if (tail_key[t] == key) sum = xyzz_add(sum, pair_load<P>(&tail[t]));
-  }
-  pair_store<P>(&buckets[key], sum);
-}
-
-// one workgroup per heavy bucket: the 128 pairs stride over the bucket's segments, pair butterfly, 4 waves through LDS
-template <class P>
-__global__ void __launch_bounds__(MSM_THREADS, MSM_TAIL_WAVES)
-msm_merge_heavy_pair_kernel(const uint32_t* __restrict__ heavy_count, const uint32_t* __restrict__ heavy_list,
-                            const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                            XYZZ<Fp2<P>>* __restrict__ buckets, const XYZZ<Fp2<P>>* __restrict__ head,
-                            const uint32_t* __restrict__ head_key, const XYZZ<Fp2<P>>* __restrict__ tail,
-                            const uint32_t* __restrict__ tail_key, uint32_t seg_len) {
-  using L = Fp2L<P>;
-  constexpr int WORDS = sizeof(XYZZ<Fp2<P>>) / 4, HALF = sizeof(Fp<P>) / 4;
-  __shared__ uint32_t wave_out[(MSM_THREADS / 64) * WORDS];
-  const uint32_t nheavy = *heavy_count;
-  for (uint32_t h = blockIdx.x; h < nheavy; h += gridDim.x) {
-    const uint32_t key = heavy_list[h];
-    const uint32_t o = offsets[key], cnt = counts[key];
-    const uint32_t t0 = o / seg_len, t1 = (o + cnt - 1) / seg_len;
-    XYZZ<L> sum = XYZZ<L>::inf();
-    for (uint32_t t = t0 + (threadIdx.x >> 1); t <= t1; t += blockDim.x / 2) {
-      if (head_key[t] == key) sum = xyzz_add(sum, pair_load<P>(&head[t]));
-      if (tail_key[t] == key) sum = xyzz_add(sum, pair_load<P>(&tail[t]));
-    }
-    sum = wave_reduce_sum_pairs<P>(sum);
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane < 2) {
-      const Fp<P>* src[4] = {&sum.x.c, &sum.y.c, &sum.zz.c, &sum.zzz.c};
-      for (int k = 0; k < 4; k++)
-        for (int i = 0; i < HALF; i++) wave_out[wave * WORDS + (2 * k + lane) * HALF + i] = src[k]->l[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-      XYZZ<L> tot = XYZZ<L>::inf();
-      for (uint32_t v = 0; v < blockDim.x / 64; v++)
-        tot = xyzz_add(tot, pair_load<P>(reinterpret_cast<const XYZZ<Fp2<P>>*>(&wave_out[v * WORDS])));
-      pair_store<P>(&buckets[key], tot);
-    }
-    __syncthreads();
-  }
-}
-
-// grid.x = blocks per window (MSM_THREADS / 2 chunks each), grid.y = windows
-template <class P>
-__global__ void __launch_bounds__(MSM_THREADS, MSM_TAIL_WAVES)
-msm_reduce_pair_kernel(const XYZZ<Fp2<P>>* __restrict__ buckets, uint32_t buckets_per_window,
-                       XYZZ<Fp2<P>>* __restrict__ partials) {
-  using L = Fp2L<P>;
-  constexpr int WORDS = sizeof(XYZZ<Fp2<P>>) / 4, HALF = sizeof(Fp<P>) / 4;
-  __shared__ uint32_t wave_out[(MSM_THREADS / 64) * WORDS];
-  const uint32_t w = blockIdx.y;
-  const uint32_t chunk = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;
-  const uint32_t first = chunk * MSM_RED_K;
-  XYZZ<L> contrib = XYZZ<L>::inf();
-  if (first < buckets_per_window) {
-    const uint32_t last = (first + MSM_RED_K < buckets_per_window) ? first + MSM_RED_K : buckets_per_window;
-    const XYZZ<Fp2<P>>* wb = buckets + (uint64_t)w * buckets_per_window;
-    XYZZ<L> running = XYZZ<L>::inf();
-    XYZZ<L> acc = XYZZ<L>::inf();
-    for (uint32_t b = last; b-- > first;) {
-      running = xyzz_add(running, pair_load<P>(&wb[b]));
-      acc = xyzz_add(acc, running);
-    }
-    if (first != 0 && !running.is_inf()) {
-      uint32_t k = first;
-      acc = xyzz_add(acc, xyzz_mul_scalar(running, &k, 1));
-    }
-    contrib = acc;
-  }
-  contrib = wave_reduce_sum_pairs<P>(contrib);
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane < 2) {          // the first pair of the wave: component `lane` of each coordinate
-    const Fp<P>* src[4] = {&contrib.x.c, &contrib.y.c, &contrib.zz.c, &contrib.zzz.c};
-    for (int k = 0; k < 4; k++)
-      for (int i = 0; i < HALF; i++) wave_out[wave * WORDS + (2 * k + lane) * HALF + i] = src[k]->l[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    XYZZ<L> sum = XYZZ<L>::inf();
-    for (uint32_t v = 0; v < blockDim.x / 64; v++)
-      sum = xyzz_add(sum, pair_load<P>(reinterpret_cast<const XYZZ<Fp2<P>>*>(&wave_out[v * WORDS])));
-    pair_store<P>(&partials[w * gridDim.x + blockIdx.x], sum);
-  }
-}
-
-// one wave = 32 pairs; window tables only (ONE bucket set: the pairs share its partials)
-template <class P>
-__global__ void __launch_bounds__(64)
-msm_combine_pair_kernel(const XYZZ<Fp2<P>>* __restrict__ partials, uint32_t count, XYZZ<Fp2<P>>* __restrict__ out,
-                        int accumulate) {
-  using L = Fp2L<P>;
-  const uint32_t pr = threadIdx.x >> 1;
-  XYZZ<L> v = XYZZ<L>::inf();
-  for (uint32_t i = pr; i < count; i += 32) v = xyzz_add(v, pair_load<P>(&partials[i]));
-  v = wave_reduce_sum_pairs<P>(v);
-  if (threadIdx.x < 2) {
-    if (accumulate) v = xyzz_add(v, pair_load<P>(out));
-    pair_store<P>(out, v);
-  }
-}
-#endif  // ARK_PLAIN_HOST
-
-// ---- two-level bucket reduction for large bucket sets (window sizes c >= 18 over window tables) ---------------------
-// sum_b (b+1) B_b with b = K j + i:  sum_j [ W_j + K j T_j ],  T_j = sum_i B_{Kj+i},  W_j = sum_i (i+1) B_{Kj+i}.
-// Level 1 gives every lane K consecutive buckets (two additions per bucket, no scalar multiplication at all); level 2
-// is the weighted sum of the T_j -- the same shape as msm_reduce_kernel, 1/K of its size -- plus the plain sum of the
-// W_j.  The one-level kernel pays a double-and-add by the chunk's first index (~28 group operations per 4 buckets); at
-// 2^19 buckets that alone was 40 % of the accumulation work (round-1 measurement: c = 20 saved 5 % of the accumulation
-// and lost 14 ms in the reduction), which is what kept the window size at 16.
-constexpr uint32_t MSM_RED_L1 = 16;       // buckets per level-1 lane (power of two: K T is log2 K doublings)
-constexpr uint32_t MSM_RED_L1_LOG = 4;
-template <class F>
-__global__ void __launch_bounds__(MSM_THREADS, MSM_TAIL_WAVES)
-msm_reduce_l1_kernel(const XYZZ<F>* __restrict__ buckets, uint32_t nbuckets, XYZZ<F>* __restrict__ T,
-                     XYZZ<F>* __restrict__ W) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t first = (uint64_t)j * MSM_RED_L1;
-  if (first >= nbuckets) return;
-  const uint32_t last = (first + MSM_RED_L1 < nbuckets) ? (uint32_t)first + MSM_RED_L1 : nbuckets;
-  XYZZ<F> running = XYZZ<F>::inf(), acc = XYZZ<F>::inf();
-  for (uint32_t b = last; b-- > (uint32_t)first;) {
-    running = xyzz_add(running, buckets[b]);
-    acc = xyzz_add(acc, running);
-  }
-  T[j] = running;
-  W[j] = acc;
-}
-
-// Output: partials[blockIdx.x] = sum over this workgroup's lanes of  sum_j W_j + K * sum_j j T_j
-template <class F>
-__global__ void __launch_bounds__(MSM_THREADS, MSM_TAIL_WAVES)
-msm_reduce_l2_kernel(const XYZZ<F>* __restrict__ T, const XYZZ<F>* __restrict__ W, uint32_t items,
-                     XYZZ<F>* __restrict__ partials) {
-  __shared__ uint32_t wave_out[(MSM_THREADS / 64) * (sizeof(XYZZ<F>) / 4)];
-  const uint32_t chunk = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t first = (uint64_t)chunk * MSM_RED_K;
-  XYZZ<F> contrib = XYZZ<F>::inf();
-  if (first < items) {
-    const uint32_t last = (first + MSM_RED_K < items) ? (uint32_t)first + MSM_RED_K : items;
-    XYZZ<F> running = XYZZ<F>::inf(), acc = XYZZ<F>::inf(), wsum = XYZZ<F>::inf();
-    for (uint32_t j = last; j-- > (uint32_t)first;) {
-      acc = xyzz_add(acc, running);             // acc = sum (j - first) T_j
-      running = xyzz_add(running, T[j]);
-      wsum = xyzz_add(wsum, W[j]);
-    }
-    if (first != 0 && !running.is_inf()) {
-      uint32_t k = (uint32_t)first;
-      acc = xyzz_add(acc, xyzz_mul_scalar(running, &k, 1));
-    }
-    if (!acc.is_inf())
-      for (uint32_t d = 0; d < MSM_RED_L1_LOG; d++) acc = xyzz_dbl(acc);
-    contrib = xyzz_add(wsum, acc);
-  }
-  contrib = wave_reduce_sum(contrib);
-  constexpr int WORDS = sizeof(XYZZ<F>) / 4;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(&contrib);
-    for (int i = 0; i < WORDS; i++) wave_out[wave * WORDS + i] = src[i];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    XYZZ<F> sum = XYZZ<F>::inf();
-    for (uint32_t v = 0; v < blockDim.x / 64; v++) {
-      XYZZ<F> t;
-      uint32_t* dst = reinterpret_cast<uint32_t*>(&t);
-      for (int i = 0; i < WORDS; i++) dst[i] = wave_out[v * WORDS + i];
-      sum = xyzz_add(sum, t);
-    }
-    partials[blockIdx.x] = sum;
-  }
-}
-
-// one wave.  Several bucket sets (no window tables): lane w -> 2^(c*w) * (sum of window w's partials), butterfly
-// over lanes.  One bucket set (window tables): the lanes share the partials of the single set.  Lane 0
-// writes / accumulates into *out.
-template <class F>
-__global__ void __launch_bounds__(64)
-msm_combine_kernel(const XYZZ<F>* __restrict__ partials, uint32_t per_window, uint32_t windows, uint32_t c,
-                   XYZZ<F>* __restrict__ out, int accumulate) {
-  const uint32_t w = threadIdx.x;
-  XYZZ<F> v = XYZZ<F>::inf();
-  if (windows == 1) {
-    for (uint32_t i = w; i < per_window; i += 64) v = xyzz_add(v, partials[i]);
-  } else if (w < windows) {
-    for (uint32_t i = 0; i < per_window; i++) v = xyzz_add(v, partials[w * per_window + i]);
-    if (!v.is_inf()) {
-      const uint32_t dbl = c * w;
-      for (uint32_t i = 0; i < dbl; i++) v = xyzz_dbl(v);
-    }
-  }
-  v = wave_reduce_sum(v);
-  if (threadIdx.x == 0) {
-    if (accumulate) v = xyzz_add(v, *out);
-    *out = v;
-  }
-}
-
-// XYZZ -> affine for `count` points (one lane each)
-template <class F>
-__global__ void __launch_bounds__(64)
-xyzz_to_affine_kernel(const XYZZ<F>* __restrict__ in, Affine<F>* __restrict__ out, uint32_t count) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) out[i] = xyzz_to_affine(in[i]);
 }
 
 // sum of `count` XYZZ points -> out[0] (single wave; the cross-GPU combine of SURVEY 8e)
@@ -1288,11 +699,9 @@ batch_to_affine_kernel(const XYZZ<F>* __restrict__ in, Affine<F>* __restrict__ o
 // Window tables of a base vector: T[w*n + i] = 2^(c*w) * P_i, affine, for the plan the MSM of this length uses.
 struct PrecompTable {
   MsmPlan plan;
-  DevBuf table;          // windows * n rows: Affine<F>, or Affine28 rows when limb28 is set
+  DevBuf table;          // windows * n rows in the radix-2^28 form of field28.cuh (msm28_impl.cuh)
   uint64_t n = 0;
-  bool limb28 = false;   // rows are stored in the radix-2^28 form of field28.cuh (msm28_impl.cuh)
-  bool packed = false;   // ... bit-packed (Affine28: 96 / 64 B per G1 row) instead of one word per limb (Affine28U: 128 / 80 B)
-  int fmt() const { return limb28 ? (packed ? 2 : 1) : 0; }       // what msm_accumulate_phase is told
+  bool packed = false;   // rows bit-packed (Affine28: 96 / 64 B per G1 row) instead of one word per limb (Affine28U: 128 / 80 B)
 };
 
 // ---- HBM footprint of window tables -------------------------------------------------------------------------------------
@@ -1301,8 +710,7 @@ struct PrecompTable {
 // below pick the smallest window stride (MsmPlan::wstride) whose tables fit the budget, so that such a key still loads
 // -- with every second (third, ...) window's table and that many bucket sets -- instead of failing in hipMalloc.
 template <class F>
-static inline size_t table_row_bytes(bool limb28, bool packed = false) {
-  if (!limb28) return sizeof(Affine<F>);
+static inline size_t table_row_bytes(bool packed) {
   if constexpr (is_fp2<F>::value) {
     using P = typename F::Base::Params;
     return packed ? sizeof(Affine28G2<P, true>) : sizeof(Affine28G2<P, false>);
@@ -1369,7 +777,7 @@ static inline uint32_t table_stride_plan(const TunePolicy& pol, const TableNeed*
       const MsmPlan p = msm_plan(need[i].n, Fr::Params::BITS, true,
                                  need[i].plan_n ? (int)msm_plan(need[i].plan_n, Fr::Params::BITS, true, 0, 0, pc).c : 0, s, pc);
       if (p.windows > max_windows) max_windows = p.windows;
-      const size_t row = need[i].g2 ? table_row_bytes<Fq2>(true, pk) : table_row_bytes<Fq>(true, pk);
+      const size_t row = need[i].g2 ? table_row_bytes<Fq2>(pk) : table_row_bytes<Fq>(pk);
       const size_t aff = need[i].g2 ? sizeof(Affine<Fq2>) : sizeof(Affine<Fq>);
       const size_t xyzz = need[i].g2 ? sizeof(XYZZ<Fq2>) : sizeof(XYZZ<Fq>);
       resident += (size_t)p.table_windows * need[i].n * row;
@@ -1384,6 +792,25 @@ static inline uint32_t table_stride_plan(const TunePolicy& pol, const TableNeed*
       return 0;
     }
   }
+}
+
+// Canonical affine rows -> the 28-bit rows of msm28_impl.cuh (packed or one word per limb): the blocks of a window table, the
+// bases of a one-shot MSM
+template <class F>
+static void rows_to28(const Affine<F>* src, void* dst, uint64_t n, bool pack, hipStream_t stream) {
+  const dim3 grid((uint32_t)((n + 255) / 256));
+  if constexpr (is_fp2<F>::value) {
+    using P = typename F::Base::Params;
+    if (pack)
+      ARK_LAUNCH((table_to28_g2_kernel<P, true>), grid, dim3(256), 0, stream, src, static_cast<Affine28G2<P, true>*>(dst), n);
+    else
+      ARK_LAUNCH((table_to28_g2_kernel<P, false>), grid, dim3(256), 0, stream, src, static_cast<Affine28G2<P, false>*>(dst), n);
+  } else {
+    using P = typename F::Params;
+    if (pack) ARK_LAUNCH((table_to28_kernel<P, true>), grid, dim3(256), 0, stream, src, static_cast<Affine28<P>*>(dst), n);
+    else ARK_LAUNCH((table_to28_kernel<P, false>), grid, dim3(256), 0, stream, src, static_cast<Affine28U<P>*>(dst), n);
+  }
+  ARK_CHECK_LAUNCH();
 }
 
 // plan_n: the length the window size is chosen for (0 = n).  The shards of one key pass the LARGEST shard length so
@@ -1414,34 +841,14 @@ static void precomp_build(const TunePolicy& pol, PrecompTable& t, const void* d_
   bool pack;
   if constexpr (is_fp2<F>::value) pack = packed >= 0 ? packed != 0 : table_pack_default<typename F::Base>(pol);
   else pack = packed >= 0 ? packed != 0 : table_pack_default<F>(pol);
-  const size_t row = table_row_bytes<F>(true, pack);
+  const size_t row = table_row_bytes<F>(pack);
   t.table.alloc((size_t)TW * (n ? n : 1) * row);
-  t.limb28 = true;
   t.packed = pack;
   if (n == 0) return;
   DevBuf stage[2] = {DevBuf(n * sizeof(Affine<F>)), DevBuf(n * sizeof(Affine<F>))};
   DevBuf tmp(n * sizeof(XYZZ<F>));
-  const dim3 grid28((uint32_t)((n + 255) / 256));
   auto encode = [&](const DevBuf& src, uint32_t w) {
-    uint8_t* dst = t.table.as<uint8_t>() + (size_t)w * n * row;
-    if constexpr (is_fp2<F>::value) {
-      using P = typename F::Base::Params;
-      if (pack)
-        ARK_LAUNCH((table_to28_g2_kernel<P, true>), grid28, dim3(256), 0, stream, (const Affine<F>*)src.as<Affine<F>>(),
-                   reinterpret_cast<Affine28G2<P, true>*>(dst), n);
-      else
-        ARK_LAUNCH((table_to28_g2_kernel<P, false>), grid28, dim3(256), 0, stream, (const Affine<F>*)src.as<Affine<F>>(),
-                   reinterpret_cast<Affine28G2<P, false>*>(dst), n);
-    } else {
-      using P = typename F::Params;
-      if (pack)
-        ARK_LAUNCH((table_to28_kernel<P, true>), grid28, dim3(256), 0, stream, (const Affine<F>*)src.as<Affine<F>>(),
-                   reinterpret_cast<Affine28<P>*>(dst), n);
-      else
-        ARK_LAUNCH((table_to28_kernel<P, false>), grid28, dim3(256), 0, stream, (const Affine<F>*)src.as<Affine<F>>(),
-                   reinterpret_cast<Affine28U<P>*>(dst), n);
-    }
-    ARK_CHECK_LAUNCH();
+    rows_to28<F>(src.as<Affine<F>>(), t.table.as<uint8_t>() + (size_t)w * n * row, n, pack, stream);
   };
   ARK_CHECK_HIP(hipMemcpyAsync(stage[0].p, d_bases, n * sizeof(Affine<F>), hipMemcpyDeviceToDevice, stream));
   encode(stage[0], 0);
@@ -1625,12 +1032,11 @@ static void msm_sort(ark355_ctx* ctx, MsmSort& s, const void* d_scalars, uint64_
   msm_sort_run<Fr>(ctx, s, d_scalars, n, mont, stream, tab);
 }
 
-// Scratch for the bucket phase of one group type.
+// Scratch for the bucket phase of one group type.  buckets / head / tail hold 28-bit slots (Tail28<P, G2>::Slot).
 struct MsmBuckets {
-  DevBuf buckets, head, tail, head_key, tail_key, partials, heavy_count, heavy_list, lvl_t, lvl_w;
+  DevBuf buckets, head, tail, head_key, tail_key, heavy_count, heavy_list;
   DevBuf rc;                            // row / column sums of the bucket matrix (tails28_impl.cuh, stage A)
   uint32_t seg_len = 32, segs = 0;      // of the last accumulation over this bucket set (G1 and G2 differ)
-  int fmt = 0;                          // slot format of buckets / head / tail: 0 canonical XYZZ<F>, else Slot28 / Slot28G2
   bool prepared = false;                // msm_prepare_phase ran for the coming accumulation
   bool heavy_cleared = false;           // msm_prepare_phase already cleared heavy_count for the coming merge
 };
@@ -1647,15 +1053,15 @@ struct Tail28Of<Fp2<P_>> {
   static constexpr bool G2 = true;
 };
 template <class F>
-static inline size_t msm_slot_bytes(int fmt) {
-  return fmt ? sizeof(typename Tail28<typename Tail28Of<F>::P, Tail28Of<F>::G2>::Slot) : sizeof(XYZZ<F>);
+static inline size_t msm_slot_bytes() {
+  return sizeof(typename Tail28<typename Tail28Of<F>::P, Tail28Of<F>::G2>::Slot);
 }
-// What an MSM leaves on the device for the host: ONE XYZZ sum from the 32-bit tails (one-shot MSMs over caller's bases), c
-// partial sums per bucket set from the 28-bit tails (resident tables); msm_parts_finish turns either into the sum.
-static inline uint32_t msm_parts_count(const MsmPlan& p, int fmt) { return fmt ? p.key_windows * p.c : 1u; }
+// What an MSM leaves on the device for the host: c partial sums per bucket set (the bit sums of tails28_impl.cuh);
+// msm_parts_finish turns them into the sum.
+static inline uint32_t msm_parts_count(const MsmPlan& p) { return p.key_windows * p.c; }
 template <class F>
-static XYZZ<F> msm_parts_finish(const XYZZ<F>* parts, const MsmPlan& p, int fmt) {
-  return fmt ? msm_finish_host<F>(parts, p.key_windows, p.c) : parts[0];
+static XYZZ<F> msm_parts_finish(const XYZZ<F>* parts, const MsmPlan& p) {
+  return msm_finish_host<F>(parts, p.key_windows, p.c);
 }
 
 // Phase 1 of the bucket method over an existing sort: bucket accumulation (the chip-filling kernel).
@@ -1664,14 +1070,12 @@ static XYZZ<F> msm_parts_finish(const XYZZ<F>* parts, const MsmPlan& p, int fmt)
 // fill kernels in front of every accumulation launch sat behind the other proofs' workgroups and opened a gap between
 // consecutive accumulations (31 fills per proof, 2.5 ms of stream time with four proofs in flight).
 template <class F>
-static void msm_prepare_phase(const TunePolicy& pol, const MsmSort& s, MsmBuckets& b, hipStream_t stream, int fmt = 0,
-                              FillBatch* fb = nullptr) {
+static void msm_prepare_phase(const TunePolicy& pol, const MsmSort& s, MsmBuckets& b, hipStream_t stream, FillBatch* fb = nullptr) {
   const MsmPlan& p = s.plan;
   b.prepared = true;
   b.heavy_cleared = false;
-  b.fmt = fmt;
   if (p.n == 0) return;
-  const size_t slot = msm_slot_bytes<F>(fmt);
+  const size_t slot = msm_slot_bytes<F>();
   const uint64_t entries = (uint64_t)p.windows * p.n;
   b.seg_len = msm_seg_len(entries, is_fp2<F>::value, pol.msm_seg);
   b.segs = (uint32_t)((entries + b.seg_len - 1) / b.seg_len);
@@ -1684,7 +1088,7 @@ static void msm_prepare_phase(const TunePolicy& pol, const MsmSort& s, MsmBucket
   fill_bytes(fb, b.buckets.p, 0, (size_t)p.total_buckets * slot, stream);
   fill_bytes(fb, b.head_key.p, 0xFF, (size_t)segs * 4, stream);
   fill_bytes(fb, b.tail_key.p, 0xFF, (size_t)segs * 4, stream);
-  // the heavy-bucket counter of the merge that follows the accumulation (msm_reduce_phase clears it itself otherwise)
+  // the heavy-bucket counter of the merge that follows the accumulation (msm_tails28_launch clears it itself otherwise)
   b.heavy_count.ensure(16);
   fill_bytes(fb, b.heavy_count.p, 0, 4, stream);
   b.heavy_cleared = true;
@@ -1692,23 +1096,20 @@ static void msm_prepare_phase(const TunePolicy& pol, const MsmSort& s, MsmBucket
 
 // destination arrays of the 28-bit accumulation kernels: which = 0 buckets, 1 head, 2 tail
 template <class P, int COORDS>
-static Msm28Slot<P, COORDS>* msm_slots28(MsmBuckets& b, uint32_t total_buckets, int which) {
-  (void)total_buckets;
+static Msm28Slot<P, COORDS>* msm_slots28(MsmBuckets& b, int which) {
   return (which == 0 ? b.buckets : (which == 1 ? b.head : b.tail)).as<Msm28Slot<P, COORDS>>();
 }
 
+// d_rows: 28-bit rows -- a window table (PrecompTable::table) or the re-encoded bases of a one-shot MSM; packed: their
+// format (PrecompTable::packed), which picks the accumulation kernel
 template <class F>
-static void msm_accumulate_phase(ark355_ctx* ctx, const MsmSort& s, MsmBuckets& b, const Affine<F>* d_bases,
-                                 hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
-                                 int fmt = 0) {
-  // fmt: PrecompTable::fmt() of the table d_bases points to -- 0 canonical Affine<F> rows, 1 unpacked, 2 packed 28-bit rows
+static void msm_accumulate_phase(ark355_ctx* ctx, const MsmSort& s, MsmBuckets& b, const void* d_rows, bool packed,
+                                 hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
   const MsmPlan& p = s.plan;
-  if (!b.prepared) msm_prepare_phase<F>(ctx->policy, s, b, stream, fmt);      // stand-alone MSMs: same stream
-  ARK_REQUIRE(b.fmt == fmt, ARK355_EINVAL, "bucket set was prepared for another slot format");
+  if (!b.prepared) msm_prepare_phase<F>(ctx->policy, s, b, stream);      // stand-alone MSMs: same stream
   b.prepared = false;
   if (p.n == 0) return;
   const uint32_t segs = b.segs;
-  const uint32_t grid_s = (segs + MSM_THREADS - 1) / MSM_THREADS;
   // Workgroup size of the two kernels without LDS (unpacked 28-bit rows).  A 256-lane workgroup needs a free register slot on
   // four SIMDs at once and gives its slots back only when its slowest wave is done; with 64 lanes every SIMD refills by itself.
   // Measured, same box, interleaved (runs T, V): a LONE one-stream 2^20 proof 24.4-24.6 -> 23.8 ms device-resident with 64; four
@@ -1718,50 +1119,37 @@ static void msm_accumulate_phase(ark355_ctx* ctx, const MsmSort& s, MsmBuckets& 
   // 256 overrides it (0, the default: the hint, else 256).
   const int acc_want = ctx->policy.acc_threads ? ctx->policy.acc_threads : ctx->acc_threads_hint;
   const uint32_t acc_t = (acc_want == 64 || acc_want == 128) ? (uint32_t)acc_want : MSM_THREADS;
+  const uint32_t* keys = s.sorted_keys.as<uint32_t>();
+  const uint32_t* vals = s.sorted_vals.as<uint32_t>();
   if (ev0) ARK_CHECK_HIP(hipEventRecord(ev0, stream));
   if constexpr (is_fp2<F>::value) {
     // G2: lane-split kernels (two lanes per segment; the whole-element kernels of round 1 lost to them by 2x and are gone)
     using P = typename F::Base::Params;
-    const uint32_t grid_l = (2 * segs + MSM_THREADS - 1) / MSM_THREADS;
-    if (fmt == 2) {
-      ARK_LAUNCH((msm_accumulate_g2l28p_kernel<P>), dim3(grid_l), dim3(MSM_THREADS), 0, stream,
-                 reinterpret_cast<const Affine28G2<P, true>*>(d_bases), s.sorted_keys.as<uint32_t>(),
-                 s.sorted_vals.as<uint32_t>(), s.total.as<uint32_t>(), s.offsets.as<uint32_t>(),
-                 s.counts.as<uint32_t>(), msm_slots28<P, 8>(b, p.total_buckets, 0), msm_slots28<P, 8>(b, p.total_buckets, 1),
-                 b.head_key.as<uint32_t>(), msm_slots28<P, 8>(b, p.total_buckets, 2), b.tail_key.as<uint32_t>(), b.seg_len);
-    } else if (fmt == 1) {
+    if (packed) {
+      ARK_LAUNCH((msm_accumulate_g2l28p_kernel<P>), dim3((2 * segs + MSM_THREADS - 1) / MSM_THREADS), dim3(MSM_THREADS), 0, stream,
+                 static_cast<const Affine28G2<P, true>*>(d_rows), keys, vals, s.total.as<uint32_t>(), s.offsets.as<uint32_t>(),
+                 s.counts.as<uint32_t>(), msm_slots28<P, 8>(b, 0), msm_slots28<P, 8>(b, 1), b.head_key.as<uint32_t>(),
+                 msm_slots28<P, 8>(b, 2), b.tail_key.as<uint32_t>(), b.seg_len);
+    } else {
       constexpr bool ZL = g2l28_zz_in_lds<P>();
       ARK_LAUNCH((msm_accumulate_g2l28_kernel<P, ZL>), dim3((2 * segs + acc_t - 1) / acc_t), dim3(acc_t),
-                 ZL ? ZzLds<P>::bytes(acc_t) : (size_t)0, stream,
-                 reinterpret_cast<const Affine28G2<P, false>*>(d_bases), s.sorted_keys.as<uint32_t>(),
-                 s.sorted_vals.as<uint32_t>(), s.total.as<uint32_t>(), s.offsets.as<uint32_t>(),
-                 s.counts.as<uint32_t>(), msm_slots28<P, 8>(b, p.total_buckets, 0), msm_slots28<P, 8>(b, p.total_buckets, 1),
-                 b.head_key.as<uint32_t>(), msm_slots28<P, 8>(b, p.total_buckets, 2), b.tail_key.as<uint32_t>(), b.seg_len);
-    } else {
-      ARK_LAUNCH((msm_accumulate_g2l_kernel<P>), dim3(grid_l), dim3(MSM_THREADS), 0, stream, d_bases,
-                 s.sorted_keys.as<uint32_t>(), s.sorted_vals.as<uint32_t>(), s.total.as<uint32_t>(),
-                 s.offsets.as<uint32_t>(), s.counts.as<uint32_t>(), b.buckets.as<XYZZ<F>>(), b.head.as<XYZZ<F>>(),
-                 b.head_key.as<uint32_t>(), b.tail.as<XYZZ<F>>(), b.tail_key.as<uint32_t>(), b.seg_len);
+                 ZL ? ZzLds<P>::bytes(acc_t) : (size_t)0, stream, static_cast<const Affine28G2<P, false>*>(d_rows), keys, vals,
+                 s.total.as<uint32_t>(), s.offsets.as<uint32_t>(), s.counts.as<uint32_t>(), msm_slots28<P, 8>(b, 0),
+                 msm_slots28<P, 8>(b, 1), b.head_key.as<uint32_t>(), msm_slots28<P, 8>(b, 2), b.tail_key.as<uint32_t>(), b.seg_len);
     }
-  } else if (fmt == 2) {
-    using P = typename F::Params;
-    ARK_LAUNCH((msm_accumulate28p_kernel<P>), dim3(grid_s), dim3(MSM_THREADS), 0, stream,
-               reinterpret_cast<const Affine28<P>*>(d_bases), s.sorted_keys.as<uint32_t>(),
-               s.sorted_vals.as<uint32_t>(), s.total.as<uint32_t>(), s.offsets.as<uint32_t>(),
-               s.counts.as<uint32_t>(), msm_slots28<P, 4>(b, p.total_buckets, 0), msm_slots28<P, 4>(b, p.total_buckets, 1),
-               b.head_key.as<uint32_t>(), msm_slots28<P, 4>(b, p.total_buckets, 2), b.tail_key.as<uint32_t>(), b.seg_len);
-  } else if (fmt == 1) {
-    using P = typename F::Params;
-    ARK_LAUNCH((msm_accumulate28_kernel<P>), dim3((segs + acc_t - 1) / acc_t), dim3(acc_t), 0, stream,
-               reinterpret_cast<const Affine28U<P>*>(d_bases), s.sorted_keys.as<uint32_t>(),
-               s.sorted_vals.as<uint32_t>(), s.total.as<uint32_t>(), s.offsets.as<uint32_t>(),
-               s.counts.as<uint32_t>(), msm_slots28<P, 4>(b, p.total_buckets, 0), msm_slots28<P, 4>(b, p.total_buckets, 1),
-               b.head_key.as<uint32_t>(), msm_slots28<P, 4>(b, p.total_buckets, 2), b.tail_key.as<uint32_t>(), b.seg_len);
   } else {
-    ARK_LAUNCH((msm_accumulate_kernel<F, false>), dim3(grid_s), dim3(MSM_THREADS), 0, stream, d_bases,
-               s.sorted_keys.as<uint32_t>(), s.sorted_vals.as<uint32_t>(), s.total.as<uint32_t>(),
-               s.offsets.as<uint32_t>(), s.counts.as<uint32_t>(), b.buckets.as<XYZZ<F>>(), b.head.as<XYZZ<F>>(),
-               b.head_key.as<uint32_t>(), b.tail.as<XYZZ<F>>(), b.tail_key.as<uint32_t>(), b.seg_len);
+    using P = typename F::Params;
+    if (packed) {
+      ARK_LAUNCH((msm_accumulate28p_kernel<P>), dim3((segs + MSM_THREADS - 1) / MSM_THREADS), dim3(MSM_THREADS), 0, stream,
+                 static_cast<const Affine28<P>*>(d_rows), keys, vals, s.total.as<uint32_t>(), s.offsets.as<uint32_t>(),
+                 s.counts.as<uint32_t>(), msm_slots28<P, 4>(b, 0), msm_slots28<P, 4>(b, 1), b.head_key.as<uint32_t>(),
+                 msm_slots28<P, 4>(b, 2), b.tail_key.as<uint32_t>(), b.seg_len);
+    } else {
+      ARK_LAUNCH((msm_accumulate28_kernel<P>), dim3((segs + acc_t - 1) / acc_t), dim3(acc_t), 0, stream,
+                 static_cast<const Affine28U<P>*>(d_rows), keys, vals, s.total.as<uint32_t>(), s.offsets.as<uint32_t>(),
+                 s.counts.as<uint32_t>(), msm_slots28<P, 4>(b, 0), msm_slots28<P, 4>(b, 1), b.head_key.as<uint32_t>(),
+                 msm_slots28<P, 4>(b, 2), b.tail_key.as<uint32_t>(), b.seg_len);
+    }
   }
   ARK_CHECK_LAUNCH();
   if (ev1) ARK_CHECK_HIP(hipEventRecord(ev1, stream));
@@ -1770,8 +1158,8 @@ static void msm_accumulate_phase(ark355_ctx* ctx, const MsmSort& s, MsmBuckets& 
 // Phase 2 of `count` (<= TAIL28_MAX) MSMs over 28-bit slots whose accumulations have been queued on `stream`, as ONE launch
 // per step (tails28_impl.cuh: merge, heavy merge, row / column sums, bit sums; blockIdx.z = MSM) -- a one-stream proof runs
 // the tails of its four G1 MSMs side by side.  outs[i] receives msm_parts_count() partial sums (msm_parts_finish on the host).
-// Returns false -- nothing queued -- when the MSMs cannot share launches (different bucket layouts, an empty one, 32-bit
-// slots): the caller then runs msm_reduce_phase per MSM.
+// Returns false -- nothing queued -- when the MSMs cannot share launches (different bucket layouts, an empty one): the caller
+// then runs msm_reduce_phase per MSM.
 // after_merge (optional, count == 1): called with the complete local bucket array (slots) between the merge and the
 // reduction -- the bucket-level cross-GPU exchange of comm_impl.cuh.
 template <class F, class Hook = std::nullptr_t>
@@ -1789,7 +1177,7 @@ static bool msm_tails28_launch(ark355_ctx* ctx, int count, const MsmSort* const*
   const bool empty_with_hook = HOOK && count == 1 && p0.n == 0;
   for (int i = 0; i < count; i++) {
     const MsmPlan& p = sorts[i]->plan;
-    if ((p.n == 0 && !empty_with_hook) || !bks[i]->fmt) return false;
+    if (p.n == 0 && !empty_with_hook) return false;
     if (p.total_buckets != p0.total_buckets || p.buckets_per_window != p0.buckets_per_window || p.key_windows != p0.key_windows ||
         p.c != p0.c)
       return false;
@@ -1854,148 +1242,23 @@ static bool msm_tails28_launch(ark355_ctx* ctx, int count, const MsmSort* const*
   return true;
 }
 
-// G2 tails run on lane pairs (round 2; the one-lane-per-bucket kernels with out-of-line Fq2 arithmetic they replaced took
-// 2.5x as long and are gone -- profiles/r02_g2_pair_tails_ab.txt)
-static inline bool msm_g2_pair_tails(const ark355_ctx*) { return true; }
-
-// Phase 2: straddling-run merge, weighted bucket reduction, window combination; writes/accumulates the XYZZ
-// result into d_out.  Only a handful of workgroups and latency-bound, so the prover runs it on its own stream
-// underneath the next MSM's accumulation.
-// after_merge (optional): called with the complete local bucket array between the merge and the weighted reduction
-// (the bucket-level cross-GPU exchange of comm_impl.cuh).
+// Phase 2 of one MSM: the tails above on their own; d_out receives msm_parts_count() partial sums.  Only a handful of
+// workgroups and latency-bound, so the prover runs it on its own stream underneath the next MSM's accumulation.
+// after_merge (optional): called with the complete local bucket array between the merge and the sums (the bucket-level
+// cross-GPU exchange of comm_impl.cuh).
 template <class F, class Hook = std::nullptr_t>
-static void msm_reduce_phase(ark355_ctx* ctx, const MsmSort& s, MsmBuckets& b, XYZZ<F>* d_out, int accumulate,
-                             hipStream_t stream, Hook after_merge = nullptr) {
+static void msm_reduce_phase(ark355_ctx* ctx, const MsmSort& s, MsmBuckets& b, XYZZ<F>* d_out, hipStream_t stream,
+                             Hook after_merge = nullptr) {
   const MsmPlan& p = s.plan;
-  constexpr bool HOOK = !std::is_same<Hook, std::nullptr_t>::value;
-  if (b.fmt) {
-    // buckets in 28-bit slots (every MSM over resident window tables): the round-6 tails; d_out receives msm_parts_count()
-    // partial sums
-    ARK_REQUIRE(!accumulate, ARK355_EINVAL, "the 28-bit tails do not accumulate into a previous result");
-    if (p.n == 0 && !HOOK) {
-      ARK_CHECK_HIP(hipMemsetAsync(d_out, 0, (size_t)msm_parts_count(p, b.fmt) * sizeof(XYZZ<F>), stream));
-      return;
-    }
-    const MsmSort* sorts[1] = {&s};
-    MsmBuckets* bks[1] = {&b};
-    XYZZ<F>* outs[1] = {d_out};
-    const bool ok = msm_tails28_launch<F, Hook>(ctx, 1, sorts, bks, outs, stream, after_merge);
-    ARK_REQUIRE(ok, ARK355_EINVAL, "28-bit tails refused a bucket set");
+  if (p.n == 0 && std::is_same<Hook, std::nullptr_t>::value) {
+    ARK_CHECK_HIP(hipMemsetAsync(d_out, 0, (size_t)msm_parts_count(p) * sizeof(XYZZ<F>), stream));
     return;
   }
-  if (p.n == 0) {
-    if constexpr (HOOK) {
-      // an empty shard still takes part in the exchange: all-infinity bucket array
-      b.buckets.ensure((size_t)p.total_buckets * sizeof(XYZZ<F>));
-      ARK_CHECK_HIP(hipMemsetAsync(b.buckets.p, 0, (size_t)p.total_buckets * sizeof(XYZZ<F>), stream));
-    } else {
-      if (!accumulate) ARK_CHECK_HIP(hipMemsetAsync(d_out, 0, sizeof(XYZZ<F>), stream));
-      return;
-    }
-  } else {
-    const uint32_t segs = b.segs;
-    const uint32_t grid_b = (p.total_buckets + MSM_THREADS - 1) / MSM_THREADS;
-    // at most entries / (MSM_HEAVY_SPAN * segment length) buckets can be heavy
-    const uint32_t max_heavy = segs / MSM_HEAVY_SPAN + 1;
-    // "heavy" is relative: twice the average span of a bucket once that exceeds the fixed threshold
-    const uint32_t avg_span = (uint32_t)(((uint64_t)segs + p.total_buckets - 1) / p.total_buckets);
-    const uint32_t heavy_span = (2 * avg_span > MSM_HEAVY_SPAN) ? 2 * avg_span : MSM_HEAVY_SPAN;
-    b.heavy_count.ensure(16);
-    b.heavy_list.ensure((size_t)max_heavy * 4);
-    if (!b.heavy_cleared) ARK_CHECK_HIP(hipMemsetAsync(b.heavy_count.p, 0, 4, stream));
-    b.heavy_cleared = false;
-    if constexpr (is_fp2<F>::value) {
-      if (msm_g2_pair_tails(ctx)) {
-        using P = typename F::Base::Params;
-        ARK_LAUNCH((msm_merge_pair_kernel<P>), dim3(2 * grid_b), dim3(MSM_THREADS), 0, stream, p.total_buckets,
-                   s.offsets.as<uint32_t>(), s.counts.as<uint32_t>(), b.buckets.as<XYZZ<F>>(), b.head.as<XYZZ<F>>(),
-                   b.head_key.as<uint32_t>(), b.tail.as<XYZZ<F>>(), b.tail_key.as<uint32_t>(),
-                   b.heavy_count.as<uint32_t>(), b.heavy_list.as<uint32_t>(), b.seg_len, heavy_span);
-      } else {
-        ARK_LAUNCH((msm_merge_kernel<F>), dim3(grid_b), dim3(MSM_THREADS), 0, stream, p.total_buckets,
-                   s.offsets.as<uint32_t>(), s.counts.as<uint32_t>(), b.buckets.as<XYZZ<F>>(), b.head.as<XYZZ<F>>(),
-                   b.head_key.as<uint32_t>(), b.tail.as<XYZZ<F>>(), b.tail_key.as<uint32_t>(),
-                   b.heavy_count.as<uint32_t>(), b.heavy_list.as<uint32_t>(), b.seg_len, heavy_span);
-      }
-    } else {
-      ARK_LAUNCH((msm_merge_kernel<F>), dim3(grid_b), dim3(MSM_THREADS), 0, stream, p.total_buckets,
-                 s.offsets.as<uint32_t>(), s.counts.as<uint32_t>(), b.buckets.as<XYZZ<F>>(), b.head.as<XYZZ<F>>(),
-                 b.head_key.as<uint32_t>(), b.tail.as<XYZZ<F>>(), b.tail_key.as<uint32_t>(),
-                 b.heavy_count.as<uint32_t>(), b.heavy_list.as<uint32_t>(), b.seg_len, heavy_span);
-    }
-    ARK_CHECK_LAUNCH();
-    const uint32_t grid_h = max_heavy < ARK_MSM_HEAVY_GRID ? max_heavy : ARK_MSM_HEAVY_GRID;
-    bool heavy_done = false;
-    if constexpr (is_fp2<F>::value) {
-      if (msm_g2_pair_tails(ctx)) {
-        using P = typename F::Base::Params;
-        ARK_LAUNCH((msm_merge_heavy_pair_kernel<P>), dim3(grid_h), dim3(MSM_THREADS), 0, stream, b.heavy_count.as<uint32_t>(),
-                   b.heavy_list.as<uint32_t>(), s.offsets.as<uint32_t>(), s.counts.as<uint32_t>(), b.buckets.as<XYZZ<F>>(),
-                   b.head.as<XYZZ<F>>(), b.head_key.as<uint32_t>(), b.tail.as<XYZZ<F>>(), b.tail_key.as<uint32_t>(), b.seg_len);
-        heavy_done = true;
-      }
-    }
-    if (!heavy_done)
-      ARK_LAUNCH((msm_merge_heavy_kernel<F>), dim3(grid_h), dim3(MSM_THREADS), 0, stream, b.heavy_count.as<uint32_t>(),
-                 b.heavy_list.as<uint32_t>(), s.offsets.as<uint32_t>(), s.counts.as<uint32_t>(), b.buckets.as<XYZZ<F>>(),
-                 b.head.as<XYZZ<F>>(), b.head_key.as<uint32_t>(), b.tail.as<XYZZ<F>>(), b.tail_key.as<uint32_t>(), b.seg_len);
-    ARK_CHECK_LAUNCH();
-  }
-  if constexpr (HOOK) after_merge(b.buckets.p, p.total_buckets, stream);
-
-#ifndef ARK_MSM_TWO_LEVEL_MIN
-#define ARK_MSM_TWO_LEVEL_MIN (1u << 17)        // bucket count from which the two-level reduction is used (tests: small)
-#endif
-  const uint32_t two_level_min = ctx->policy.msm_two_level_min >= 0 ? (uint32_t)ctx->policy.msm_two_level_min
-                                                                     : (uint32_t)ARK_MSM_TWO_LEVEL_MIN;       // A/B knob
-  if (p.key_windows == 1 && p.total_buckets >= two_level_min) {
-    const uint32_t items = (p.total_buckets + MSM_RED_L1 - 1) / MSM_RED_L1;
-    b.lvl_t.ensure((size_t)items * sizeof(XYZZ<F>));
-    b.lvl_w.ensure((size_t)items * sizeof(XYZZ<F>));
-    ARK_LAUNCH((msm_reduce_l1_kernel<F>), dim3((items + MSM_THREADS - 1) / MSM_THREADS), dim3(MSM_THREADS), 0, stream,
-               (const XYZZ<F>*)b.buckets.as<XYZZ<F>>(), p.total_buckets, b.lvl_t.as<XYZZ<F>>(), b.lvl_w.as<XYZZ<F>>());
-    ARK_CHECK_LAUNCH();
-    const uint32_t chunks2 = (items + MSM_RED_K - 1) / MSM_RED_K;
-    const uint32_t blocks2 = (chunks2 + MSM_THREADS - 1) / MSM_THREADS;
-    b.partials.ensure((size_t)blocks2 * sizeof(XYZZ<F>));
-    ARK_LAUNCH((msm_reduce_l2_kernel<F>), dim3(blocks2), dim3(MSM_THREADS), 0, stream, (const XYZZ<F>*)b.lvl_t.as<XYZZ<F>>(),
-               (const XYZZ<F>*)b.lvl_w.as<XYZZ<F>>(), items, b.partials.as<XYZZ<F>>());
-    ARK_CHECK_LAUNCH();
-    ARK_LAUNCH((msm_combine_kernel<F>), dim3(1), dim3(64), 0, stream, b.partials.as<XYZZ<F>>(), blocks2, 1u, p.c, d_out,
-               accumulate);
-    ARK_CHECK_LAUNCH();
-    return;
-  }
-  const uint32_t chunks = (p.buckets_per_window + MSM_RED_K - 1) / MSM_RED_K;
-  if constexpr (is_fp2<F>::value) {
-    if (msm_g2_pair_tails(ctx)) {
-      using P = typename F::Base::Params;
-      const uint32_t blocks_pw = (chunks + MSM_THREADS / 2 - 1) / (MSM_THREADS / 2);       // a lane pair per chunk
-      b.partials.ensure((size_t)blocks_pw * p.key_windows * sizeof(XYZZ<F>));
-      ARK_LAUNCH((msm_reduce_pair_kernel<P>), dim3(blocks_pw, p.key_windows), dim3(MSM_THREADS), 0, stream,
-                 (const XYZZ<F>*)b.buckets.as<XYZZ<F>>(), p.buckets_per_window, b.partials.as<XYZZ<F>>());
-      ARK_CHECK_LAUNCH();
-      if (p.key_windows == 1) {
-        ARK_LAUNCH((msm_combine_pair_kernel<P>), dim3(1), dim3(64), 0, stream, (const XYZZ<F>*)b.partials.as<XYZZ<F>>(),
-                   blocks_pw, d_out, accumulate);
-      } else {
-        ARK_REQUIRE(p.key_windows <= 64, ARK355_EINVAL, "window count exceeds one wave");
-        ARK_LAUNCH((msm_combine_kernel<F>), dim3(1), dim3(64), 0, stream, b.partials.as<XYZZ<F>>(), blocks_pw,
-                   p.key_windows, p.c, d_out, accumulate);
-      }
-      ARK_CHECK_LAUNCH();
-      return;
-    }
-  }
-  const uint32_t blocks_per_window = (chunks + MSM_THREADS - 1) / MSM_THREADS;
-  b.partials.ensure((size_t)blocks_per_window * p.key_windows * sizeof(XYZZ<F>));
-  ARK_LAUNCH((msm_reduce_kernel<F>), dim3(blocks_per_window, p.key_windows), dim3(MSM_THREADS), 0, stream,
-             b.buckets.as<XYZZ<F>>(), p.buckets_per_window, b.partials.as<XYZZ<F>>());
-  ARK_CHECK_LAUNCH();
-  ARK_REQUIRE(p.key_windows <= 64, ARK355_EINVAL, "window count exceeds one wave");
-  ARK_LAUNCH((msm_combine_kernel<F>), dim3(1), dim3(64), 0, stream, b.partials.as<XYZZ<F>>(), blocks_per_window,
-             p.key_windows, p.c, d_out, accumulate);
-  ARK_CHECK_LAUNCH();
+  const MsmSort* sorts[1] = {&s};
+  MsmBuckets* bks[1] = {&b};
+  XYZZ<F>* outs[1] = {d_out};
+  const bool ok = msm_tails28_launch<F, Hook>(ctx, 1, sorts, bks, outs, stream, after_merge);
+  ARK_REQUIRE(ok, ARK355_EINVAL, "28-bit tails refused a bucket set");
 }
 
 template <class F>
@@ -2003,15 +1266,6 @@ static bool msm_reduce_phase_batch(ark355_ctx* ctx, int count, const MsmSort* co
                                    XYZZ<F>* const* outs, hipStream_t stream) {
   if (count < 2) return false;
   return msm_tails28_launch<F>(ctx, count, sorts, bks, outs, stream);
-}
-
-// Both phases on one stream.
-template <class F>
-static void msm_buckets(ark355_ctx* ctx, const MsmSort& s, MsmBuckets& b, const Affine<F>* d_bases, XYZZ<F>* d_out,
-                        int accumulate, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
-                        int fmt = 0) {
-  msm_accumulate_phase<F>(ctx, s, b, d_bases, stream, ev0, ev1, fmt);
-  msm_reduce_phase<F>(ctx, s, b, d_out, accumulate, stream);
 }
 
 }  // namespace ark355

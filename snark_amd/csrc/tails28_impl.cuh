@@ -231,7 +231,7 @@ struct TailBatch28 {
 #endif
 
 // Merge: the lane (pair) of a bucket whose entries straddle segment boundaries adds its partial runs.  Which slots those
-// are follows from the flush protocol of the accumulation (msm_flush_run): segment t0 holds the bucket's first run in
+// are follows from the flush protocol of the accumulation (msm28_impl.cuh): segment t0 holds the bucket's first run in
 // head[t0] when the bucket starts the segment and in tail[t0] otherwise; every later segment t0 < t <= t1 STARTS inside the
 // bucket, so its first run -- head[t] -- is the bucket's.  One addition per loop iteration for every lane of the wave
 // (the rounds-1-5 kernel tested head and tail of every segment in turn: two divergent additions per iteration).  Buckets
@@ -328,7 +328,7 @@ msm_merge_heavy28_kernel(TailBatch28 tb) {
 // with the TOP bit clear (so that outputs c - 2 and c - 1 add up to the plain total); written in the canonical 32-bit form
 // to out[set][k] for the host (msm_finish_host).
 // An output's items are dealt to the wave's lanes (lane pairs) round-robin: ceil(count / 64) - 1 sequential additions per
-// lane, then the butterfly (6 steps; 5 on pairs).
+// lane, then the butterfly (6 steps; 5 on pairs; fewer when the output has fewer than 64 items).
 template <class P, bool G2, int STAGE>
 __global__ void __launch_bounds__(64, ARK_TAIL28_WAVES)
 msm_selsum28_kernel(TailBatch28 tb, uint32_t lb, uint32_t hb) {
@@ -386,7 +386,13 @@ msm_selsum28_kernel(TailBatch28 tb, uint32_t lb, uint32_t hb) {
     T::load(&src[idx], p, pe);
     T::add(sum, empty, p, pe);
   }
-  T::wave_sum(sum, empty);
+  // The butterfly of T::wave_sum, without the steps whose partner lanes all hold infinity (count is wave-uniform): an output of
+  // fewer than 64 items (32 on pairs) -- the short one-shot MSMs, 64 bucket sets of 1-4 items each at c = 4 -- runs ceil(log2 count)
+  // steps instead of all six (five), and lane / pair 0 still ends with the sum.
+  int top = 32;
+  while (top >= T::LPI && (uint32_t)top >= count * T::LPI) top >>= 1;
+#pragma unroll 1
+  for (int mask = top; mask >= T::LPI; mask >>= 1) T::add_xor(sum, empty, mask);
   if (threadIdx.x < (uint32_t)T::LPI) {
     if constexpr (STAGE == 0) {
       T::store(static_cast<Slot*>(J.rc) + (size_t)set * (H + L) + o, sum, empty);

@@ -10,6 +10,8 @@ Bases: P_i = k_i * G made on the device for the first min(n, 2^20) rows, tiled b
 bases does not change Pippenger's cost; byte-exactness at 2^20 / 2^22 is tests/test_gpu_o3_large.py's job).  Every
 result up to 2^20 is checked against (sum k_i s_i) * G.  The time is the latency of one ark355_msm_dev call: digit
 sort, bucket accumulation, bucket reduction, normalisation and the D2H of the result.
+--one-shot times ark355_msm_g1 / _g2 instead (bases from host memory, nothing resident: upload, re-encoding, sort,
+accumulation, tails).  ARK355_LIB picks the library build.
 Prints one line per (group, size, distribution) and, with --json, a JSON list.  Dev tool; run on an MI355X."""
 import argparse
 import json
@@ -59,6 +61,7 @@ def main():
     ap.add_argument("--groups", default="1,2")
     ap.add_argument("--dists", default="uniform,equal,boolean")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--one-shot", action="store_true", help="time lib.msm (host bases) instead of bases_load + msm_dev")
     ap.add_argument("--no-check", action="store_true", help="timing experiments with libraries that compute wrong sums on purpose")
     args = ap.parse_args()
     cv = params.CURVES[args.curve]
@@ -77,13 +80,18 @@ def main():
         for lg in range(args.min_log, args.max_log + 1, args.step):
             n = 1 << lg
             bases = distinct[:n] if n <= nd else np.tile(distinct, (n // nd, 1))
-            h = L.bases_load(ctx, cv.curve_id, group, np.ascontiguousarray(bases).reshape(-1), n)
+            if args.one_shot:
+                hb = np.ascontiguousarray(bases).reshape(-1)
+                run = lambda ks, kd: L.msm(ctx, cv.curve_id, group, hb, ks, n, psz)             # noqa: E731
+            else:
+                h = L.bases_load(ctx, cv.curve_id, group, np.ascontiguousarray(bases).reshape(-1), n)
+                run = lambda ks, kd: L.msm_dev(ctx, h, kd.data_ptr(), n, 0, psz)              # noqa: E731
             del bases
             for dist in args.dists.split(","):
                 ks = scalars(cv, n, dist, rnd)
                 kd = torch.from_numpy(ks.view(np.uint8).reshape(-1).copy()).cuda()
                 torch.cuda.synchronize()
-                out = L.msm_dev(ctx, h, kd.data_ptr(), n, 0, psz)                 # warm-up (+ correctness)
+                out = run(ks, kd)                                                  # warm-up (+ correctness)
                 checked = ""
                 if n <= nd and not args.no_check:
                     ki = to_ints(ks)
@@ -94,7 +102,7 @@ def main():
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(args.reps):
-                    L.msm_dev(ctx, h, kd.data_ptr(), n, 0, psz)
+                    run(ks, kd)
                 torch.cuda.synchronize()
                 ms = (time.perf_counter() - t0) / args.reps * 1e3
                 acc = L.kernel_stats(ctx)["accumulate_ms"]
@@ -103,7 +111,8 @@ def main():
                 rows.append({"curve": args.curve, "group": group, "log_n": lg, "dist": dist, "ms": ms,
                              "accumulate_ms": acc, "mscalar_mul_per_s": n / ms / 1e3, "checked": bool(checked)})
                 del kd
-            L.dll.ark355_bases_free(h)
+            if not args.one_shot:
+                L.dll.ark355_bases_free(h)
     L.ctx_destroy(ctx)
     if args.json:
         with open(args.json, "w") as f:

@@ -4,8 +4,8 @@
 usage: pmc_summary.py [--json OUT.json] [--workload TEXT] [--recorded TEXT]
 Reads <dir>/prof_fetch and <dir>/prof_write (two separate passes: FETCH_SIZE, WRITE_SIZE; --dir, default gpurun_out).
 With --merge the record is added to the "workloads" map of an existing JSON (one record per workload; bench.py's pmc_traffic).
-Counter unit: KiB.  With --json also writes the per-launch figures of the dominant kernel
-(msm_accumulate_kernel) that bench.py reports as `roofline.traffic`."""
+Counter unit: KiB.  With --json also writes the per-launch figures of the dominant kernels (msm_accumulate*; the record
+key is the one bench.py reads for `roofline.traffic`)."""
 import collections
 import csv
 import glob

@@ -92,24 +92,6 @@ static int check_mul(const char* name) {
   return hb != 0;
 }
 
-template <class P>
-__global__ void __launch_bounds__(256, 2) k_madd_g2l(XYZZ<Fp2<P>>* out, const Affine<Fp2<P>>* in, int iters) {
-  using FL = Fp2L<P>;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int seg = t >> 1, par = t & 1;
-  XYZZ<FL> acc = XYZZ<FL>::inf();
-  for (int it = 0; it < iters; it++) {
-    const Fp<P>* b = reinterpret_cast<const Fp<P>*>(in + ((seg * 7 + it * 13) & 511));
-    Affine<FL> p;
-    p.x.c = b[par];
-    p.y.c = b[2 + par];
-    xyzz_madd(acc, p);
-  }
-  Fp<P>* d = reinterpret_cast<Fp<P>*>(out + seg);
-  d[par] = acc.x.c; d[2 + par] = acc.y.c; d[4 + par] = acc.zz.c; d[6 + par] = acc.zzz.c;
-}
-template <class P> static void l_madd_g2l(void* c);
-
 static float time_it(void (*launch)(void*), void* ctx, int reps) {
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   launch(ctx); hipDeviceSynchronize();
@@ -126,7 +108,6 @@ template <class F, bool NI> static void l_fmul(void* c) { Ctx* x = (Ctx*)c; hipL
 template <class F> static void l_fmul28(void* c) { Ctx* x = (Ctx*)c; hipLaunchKernelGGL((k_fmul28<F>), dim3(x->blocks), dim3(256), 0, 0, (F*)x->out, (const F*)x->in, x->iters); }
 template <class F, bool NI> static void l_madd(void* c) { Ctx* x = (Ctx*)c; hipLaunchKernelGGL((k_madd<F, NI>), dim3(x->blocks), dim3(256), 0, 0, (XYZZ<F>*)x->out, (const Affine<F>*)x->in, x->iters); }
 
-template <class P> static void l_madd_g2l(void* c) { Ctx* x = (Ctx*)c; hipLaunchKernelGGL((k_madd_g2l<P>), dim3(x->blocks), dim3(256), 0, 0, (XYZZ<Fp2<P>>*)x->out, (const Affine<Fp2<P>>*)x->in, x->iters); }
 
 int main() {
   hipDeviceProp_t prop; CHECK(hipGetDeviceProperties(&prop, 0));
@@ -161,8 +142,7 @@ int main() {
   struct { const char* n; void (*l)(void*); } md[] = {
     {"G1 BLS madd inline", l_madd<BlsFq, false>}, {"G1 BLS madd noinline", l_madd<BlsFq, true>},
     {"G2 BLS madd inline", l_madd<BlsFq2, false>}, {"G2 BLS madd noinline", l_madd<BlsFq2, true>},
-    {"G1 BN madd inline", l_madd<BnFq, false>}, {"G2 BN madd noinline", l_madd<BnFq2, true>},
-    {"G2 BLS madd lane-split (x2 lanes)", l_madd_g2l<BlsFqParams>}, {"G2 BN madd lane-split (x2 lanes)", l_madd_g2l<BnFqParams>}};
+    {"G1 BN madd inline", l_madd<BnFq, false>}, {"G2 BN madd noinline", l_madd<BnFq2, true>}};
   for (auto& f : md) {
     float ms = time_it(f.l, &c, 3);
     double ops = (double)c.blocks * 256 * c.iters;
