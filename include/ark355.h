@@ -35,6 +35,7 @@ extern "C" {
 typedef struct ark355_ctx ark355_ctx;
 typedef struct ark355_pk ark355_pk;
 typedef struct ark355_r1cs ark355_r1cs;
+typedef struct ark355_gr1cs ark355_gr1cs;
 
 enum { ARK355_BLS12_381 = 0, ARK355_BN254 = 1 };
 
@@ -299,6 +300,63 @@ int32_t ark355_is_satisfied(ark355_ctx* ctx, const ark355_r1cs* r1cs, const uint
 /* A z, B z, C z (n Fr each, Montgomery): mat_vec_mul, utils/matrix.rs:26-36 */
 int32_t ark355_r1cs_mat_vec(ark355_ctx* ctx, const ark355_r1cs* r1cs, const uint8_t* z, uint64_t z_len,
                             uint8_t* az, uint8_t* bz, uint8_t* cz);
+
+/* ---- GR1CS: every predicate of a constraint system, not only "R1CS" ------------------------------------------------
+ * ark-relations keeps a BTreeMap<Label, PredicateConstraintSystem> (constraint_system.rs:44-97): every predicate is a sparse
+ * multivariate polynomial of some arity t over t matrices (predicate/polynomial_constraint.rs), "R1CS" (x0 x1 - x2) merely the
+ * one registered by default, and to_matrices returns one list of matrices PER LABEL.  A handle holds all of them on the device,
+ * with one coefficient pool; the satisfaction check is one fused kernel per predicate (one lane per row: the t inner products,
+ * the polynomial, a 64-bit atomic minimum) and one 8-byte copy back for the whole system (snark_amd/csrc/gr1cs_impl.cuh).
+ * Limits, checked at load (ARK355_EINVAL beyond them; exponents may be any uint32_t): */
+#define ARK355_GR1CS_MAX_ARITY 16
+#define ARK355_GR1CS_MAX_TERMS 256
+#define ARK355_GR1CS_MAX_FACTORS 1024
+#define ARK355_GR1CS_MAX_PREDICATES 1024
+#define ARK355_GR1CS_MAX_ROWS 4294967295
+typedef struct {
+  const char* label;              /* NUL-terminated UTF-8, unique within one load                                        */
+  uint32_t arity;                 /* t in 1 .. ARK355_GR1CS_MAX_ARITY                                                    */
+  uint64_t n_constraints;         /* rows of each of the t matrices (<= ARK355_GR1CS_MAX_ROWS, as is every matrix's number
+                                     of entries); 0 is legal: the default "R1CS" predicate of a circuit without R1CS rows */
+  uint32_t n_terms;               /* polynomial = sum_k term_coeff[k] * prod_{j in [term_ptr[k], term_ptr[k+1])} x_{term_var[j]} ^ term_exp[j];
+                                     <= ARK355_GR1CS_MAX_TERMS terms, <= ARK355_GR1CS_MAX_FACTORS factors in all; a term without
+                                     factors is the constant term, a repeated variable multiplies, exponent 0 contributes 1 */
+  const uint8_t* term_coeff;      /* n_terms Fr, Montgomery                                                              */
+  const uint32_t* term_ptr;       /* n_terms + 1, non-decreasing from 0                                                  */
+  const uint32_t* term_var;       /* each < arity                                                                        */
+  const uint32_t* term_exp;
+  const uint64_t* const* row_ptr; /* arity CSR matrices (row_ptr: n_constraints + 1 each), the column convention and       */
+  const uint32_t* const* col;     /* semantics of ark355_r1cs_load: repeated columns of a row are summed, an empty row is  */
+  const uint8_t* const* coeff;    /* the zero linear combination                                                          */
+} ark355_predicate_desc;
+/* to_matrices for all labels plus get_predicate (constraint_system.rs:768-774, predicate/mod.rs): preds[0 .. n_preds) in any
+ * order, n_preds <= ARK355_GR1CS_MAX_PREDICATES.  ARK355_EINVAL (with a message, never a fault) for arity 0, a variable >= arity,
+ * a column >= num_instance + num_witness, a row_ptr that decreases, duplicate labels, a NULL where a count is nonzero and
+ * anything beyond the limits above. */
+int32_t ark355_gr1cs_load(ark355_ctx* ctx, int32_t curve, uint64_t num_instance, uint64_t num_witness,
+                          const ark355_predicate_desc* preds, uint32_t n_preds, ark355_gr1cs** out);
+void ark355_gr1cs_free(ark355_gr1cs* g);
+/* sum of the predicates' rows (constraint_system.rs:210-215) */
+uint64_t ark355_gr1cs_num_constraints(const ark355_gr1cs* g);
+/* which_is_unsatisfied (constraint_system.rs:652-687): the labels are visited in byte-wise lexicographic order (the BTreeMap's),
+ * rows ascending; *predicate = the CALLER's index (into preds of the load) of the first failing predicate in that order,
+ * *constraint = its first failing row -- the reference's "<label> - <row>" -- and (-1, -1) when every row is satisfied.
+ * ARK355_E_ASSIGNMENT_MISSING if z_len < num_instance + num_witness. */
+int32_t ark355_gr1cs_which_is_unsatisfied(ark355_ctx* ctx, const ark355_gr1cs* g, const uint8_t* z, uint64_t z_len,
+                                          int64_t* predicate, int64_t* constraint);
+/* mat_vec_mul (utils/matrix.rs:26-36) for each of the t matrices of predicate `predicate` (caller's index): out = t x n Fr,
+ * matrix-major, Montgomery */
+int32_t ark355_gr1cs_mat_vec(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t* z, uint64_t z_len,
+                             uint8_t* out);
+/* PolynomialPredicate::eval on every row (predicate/polynomial_constraint.rs:33-48): out[i] = P(M_0 z, .., M_{t-1} z)_i, n Fr,
+ * Montgomery; zero exactly where row i is satisfied */
+int32_t ark355_gr1cs_eval(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t* z, uint64_t z_len,
+                          uint8_t* out);
+/* An ordinary ark355_r1cs handle, for ark355_prove* and freed with ark355_r1cs_free, from the predicate labelled "R1CS", built on the
+ * device from the resident matrices.  Groth16 proves R1CS only: ARK355_EINVAL when any OTHER predicate carries a constraint
+ * (ark355_last_error names its label) -- a proof that drops constraints is not obtainable through this path -- and when the
+ * label "R1CS" is absent or not the polynomial x0 x1 - x2 of arity 3. */
+int32_t ark355_gr1cs_r1cs(ark355_ctx* ctx, const ark355_gr1cs* g, ark355_r1cs** out);
 
 /* in-place radix-2 NTT over Fr, natural order in and out (ark-poly Radix2EvaluationDomain
  * fft / ifft / coset_fft / coset_ifft).  Errors with ARK355_E_POLY_DEGREE_TOO_LARGE past the

@@ -17,6 +17,10 @@ pub struct ark355_r1cs {
     _p: [u8; 0],
 }
 #[repr(C)]
+pub struct ark355_gr1cs {
+    _p: [u8; 0],
+}
+#[repr(C)]
 pub struct ark355_comm {
     _p: [u8; 0],
 }
@@ -45,6 +49,12 @@ pub const ARK355_SHARD_BUCKET_RING: i32 = 1;
 pub const ARK355_VALIDATE_NONE: i32 = 0;
 pub const ARK355_VALIDATE_FULL: i32 = 1;
 pub const ARK355_VALIDATE_CURVE: i32 = 2;
+/// limits of `ark355_gr1cs_load` (ARK355_EINVAL beyond them)
+pub const ARK355_GR1CS_MAX_ARITY: u32 = 16;
+pub const ARK355_GR1CS_MAX_TERMS: u32 = 256;
+pub const ARK355_GR1CS_MAX_FACTORS: u32 = 1024;
+pub const ARK355_GR1CS_MAX_PREDICATES: u32 = 1024;
+pub const ARK355_GR1CS_MAX_ROWS: u64 = 4294967295;
 
 #[repr(C)]
 pub struct ark355_pk_desc {
@@ -61,6 +71,23 @@ pub struct ark355_pk_desc {
     pub delta_g1: *const u8,
     pub beta_g2: *const u8,
     pub delta_g2: *const u8,
+}
+
+/// One predicate of `ark355_gr1cs_load`: the polynomial (sum_k term_coeff[k] * prod_{j in [term_ptr[k], term_ptr[k+1])}
+/// x_{term_var[j]} ^ term_exp[j]) and its `arity` matrices in CSR.
+#[repr(C)]
+pub struct ark355_predicate_desc {
+    pub label: *const c_char,
+    pub arity: u32,
+    pub n_constraints: u64,
+    pub n_terms: u32,
+    pub term_coeff: *const u8,
+    pub term_ptr: *const u32,
+    pub term_var: *const u32,
+    pub term_exp: *const u32,
+    pub row_ptr: *const *const u64,
+    pub col: *const *const u32,
+    pub coeff: *const *const u8,
 }
 
 #[repr(C)]
@@ -283,6 +310,29 @@ extern "C" {
         bz: *mut u8,
         cz: *mut u8,
     ) -> i32;
+
+    pub fn ark355_gr1cs_load(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        num_instance: u64,
+        num_witness: u64,
+        preds: *const ark355_predicate_desc,
+        n_preds: u32,
+        out: *mut *mut ark355_gr1cs,
+    ) -> i32;
+    pub fn ark355_gr1cs_free(g: *mut ark355_gr1cs);
+    pub fn ark355_gr1cs_num_constraints(g: *const ark355_gr1cs) -> u64;
+    pub fn ark355_gr1cs_which_is_unsatisfied(
+        ctx: *mut ark355_ctx,
+        g: *const ark355_gr1cs,
+        z: *const u8,
+        z_len: u64,
+        predicate: *mut i64,
+        constraint: *mut i64,
+    ) -> i32;
+    pub fn ark355_gr1cs_mat_vec(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, predicate: u32, z: *const u8, z_len: u64, out: *mut u8) -> i32;
+    pub fn ark355_gr1cs_eval(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, predicate: u32, z: *const u8, z_len: u64, out: *mut u8) -> i32;
+    pub fn ark355_gr1cs_r1cs(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, out: *mut *mut ark355_r1cs) -> i32;
 
     pub fn ark355_ntt_fr(ctx: *mut ark355_ctx, curve: i32, data: *mut u8, log_n: u32, inverse: i32, coset: i32) -> i32;
     pub fn ark355_ntt_fr_dev(

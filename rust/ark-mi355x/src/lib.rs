@@ -7,6 +7,7 @@
 mod cache;
 mod error;
 pub mod ffi;
+pub mod gr1cs;
 mod marshal;
 mod pool;
 
@@ -24,6 +25,7 @@ use ark_std::rand::{CryptoRng, RngCore};
 
 pub use cache::{evict, lookup, matrices_hash, set_device, trust_cache, Resident};
 pub use error::Mi355xError;
+pub use gr1cs::DeviceGr1cs;
 pub use marshal::{layout_self_test, Mi355xCurve};
 pub use pool::{PinnedAssignment, ProverPool, Ticket};
 
@@ -101,6 +103,9 @@ where
             }
         }
         let syn = synthesize(circuit, false)?;
+        // Groth16 proves R1CS only: a constraint under any other predicate is an error here, not dropped.  (The witness-only
+        // fast path above records no constraints and cannot count them; only types that passed this check reach it.)
+        gr1cs::require_r1cs_only(&syn.cs)?;
         let mats = syn.cs.to_matrices()?; // constraint_system.rs:768
         let r1cs = mats.get(R1CS_PREDICATE_LABEL).ok_or(Mi355xError::Synthesis(SynthesisError::PredicateNotFound))?;
         let mh = cache::matrices_hash(r1cs, syn.cs.num_constraints());
@@ -340,6 +345,7 @@ pub mod sharded {
             circuit: C,
         ) -> Result<Self, Mi355xError> {
             let syn = synthesize(circuit, false)?;
+            gr1cs::require_r1cs_only(&syn.cs)?;
             let mats = syn.cs.to_matrices()?;
             let r1cs = mats.get(R1CS_PREDICATE_LABEL).ok_or(Mi355xError::Synthesis(SynthesisError::PredicateNotFound))?;
             let flat = marshal::flatten_key::<E, P1, P2>(pk)?;
@@ -445,7 +451,14 @@ where
         circuit: C,
         rng: &mut R,
     ) -> Result<(Self::ProvingKey, Self::VerifyingKey), Self::Error> {
-        Groth16::<E>::circuit_specific_setup(circuit, rng).map_err(Mi355xError::from)
+        // Groth16 proves R1CS only: a circuit with a constraint under any other predicate gets no key here (upstream would
+        // build one for the R1CS rows alone, and every proof under it would prove a weaker statement)
+        let refused = core::cell::RefCell::new(None);
+        let res = Groth16::<E>::circuit_specific_setup(gr1cs::R1csOnly { circuit, refused: &refused }, rng);
+        if let Some(e) = refused.into_inner() {
+            return Err(e);
+        }
+        res.map_err(Mi355xError::from)
     }
 
     /// snark/src/lib.rs:50-54 -- the accelerated path.

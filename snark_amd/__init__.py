@@ -32,3 +32,5 @@ def lib() -> Lib:
 
 
 CURVE_IDS = {"bls12_381": BLS12_381, "bn254": BN254}
+
+from .gr1cs import GR1CS  # noqa: E402,F401 -- every predicate of a constraint system on the device (snark_amd/gr1cs.py)

@@ -26,6 +26,11 @@ E_POLY_DEGREE_TOO_LARGE = -18
 COMM_ID_BYTES = 128
 SHARD_WINDOW = 0
 SHARD_BUCKET_RING = 1
+GR1CS_MAX_ARITY = 16
+GR1CS_MAX_TERMS = 256
+GR1CS_MAX_FACTORS = 1024
+GR1CS_MAX_PREDICATES = 1024
+GR1CS_MAX_ROWS = 4294967295
 
 _ERR_NAMES = {
     EINVAL: "EINVAL", ENOMEM: "ENOMEM", EHIP: "EHIP", ERCCL: "ERCCL", ENODEV: "ENODEV",
@@ -39,7 +44,9 @@ SYMBOLS = [
     "ark355_host_alloc", "ark355_host_free",
     "ark355_pk_load", "ark355_pk_free", "ark355_r1cs_load", "ark355_r1cs_free",
     "ark355_r1cs_domain_size", "ark355_prove", "ark355_prove_dev", "ark355_witness_map", "ark355_witness_map_dist_sim",
-    "ark355_is_satisfied", "ark355_r1cs_mat_vec", "ark355_ntt_fr", "ark355_ntt_fr_dev",
+    "ark355_is_satisfied", "ark355_r1cs_mat_vec",
+    "ark355_gr1cs_load", "ark355_gr1cs_free", "ark355_gr1cs_num_constraints", "ark355_gr1cs_which_is_unsatisfied",
+    "ark355_gr1cs_mat_vec", "ark355_gr1cs_eval", "ark355_gr1cs_r1cs", "ark355_ntt_fr", "ark355_ntt_fr_dev",
     "ark355_msm_g1", "ark355_msm_g2", "ark355_bases_load", "ark355_bases_free", "ark355_msm_dev",
     "ark355_msm_dev_partial", "ark355_xyzz_sum", "ark355_fixed_base_mul", "ark355_get_timings",
     "ark355_get_kernel_stats", "ark355_pk_load_shard", "ark355_partial_size", "ark355_prove_shard",
@@ -74,6 +81,12 @@ class PkDesc(C.Structure):
 class VkDesc(C.Structure):
     _fields_ = [("num_instance", C.c_uint64), ("alpha_g1", C.c_void_p), ("beta_g2", C.c_void_p), ("gamma_g2", C.c_void_p),
                 ("delta_g2", C.c_void_p), ("gamma_abc_g1", C.c_void_p)]
+
+
+class PredicateDesc(C.Structure):
+    _fields_ = [("label", C.c_char_p), ("arity", C.c_uint32), ("n_constraints", C.c_uint64), ("n_terms", C.c_uint32),
+                ("term_coeff", C.c_void_p), ("term_ptr", C.c_void_p), ("term_var", C.c_void_p), ("term_exp", C.c_void_p),
+                ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("coeff", C.c_void_p)]
 
 
 class ProofRaw(C.Structure):
@@ -138,6 +151,15 @@ class Lib:
         d.ark355_witness_map_dist_sim.argtypes = [vp, vp, vp, u64, C.c_uint32, vp]
         d.ark355_is_satisfied.argtypes = [vp, vp, vp, u64, P(i64)]
         d.ark355_r1cs_mat_vec.argtypes = [vp, vp, vp, u64, vp, vp, vp]
+        d.ark355_gr1cs_load.argtypes = [vp, i32, u64, u64, P(PredicateDesc), u32, P(vp)]
+        d.ark355_gr1cs_free.argtypes = [vp]
+        d.ark355_gr1cs_free.restype = None
+        d.ark355_gr1cs_num_constraints.argtypes = [vp]
+        d.ark355_gr1cs_num_constraints.restype = u64
+        d.ark355_gr1cs_which_is_unsatisfied.argtypes = [vp, vp, vp, u64, P(i64), P(i64)]
+        d.ark355_gr1cs_mat_vec.argtypes = [vp, vp, u32, vp, u64, vp]
+        d.ark355_gr1cs_eval.argtypes = [vp, vp, u32, vp, u64, vp]
+        d.ark355_gr1cs_r1cs.argtypes = [vp, vp, P(vp)]
         d.ark355_ntt_fr.argtypes = [vp, i32, vp, u32, i32, i32]
         d.ark355_ntt_fr_dev.argtypes = [vp, i32, vp, vp, u32, i32, i32, vp]
         d.ark355_msm_g1.argtypes = [vp, i32, vp, vp, u64, vp]
@@ -478,6 +500,76 @@ class Lib:
         zb, k = _buf(z)
         self.check(ctx, self.dll.ark355_r1cs_mat_vec(ctx, r1cs, zb, z_len, *[o.ctypes.data_as(C.c_void_p) for o in outs]))
         return [o.tobytes()[:n * fr_size] for o in outs]
+
+    # ---- GR1CS: every predicate of a constraint system (include/ark355.h "GR1CS") ---------------------------------
+    def gr1cs_load(self, ctx, curve, ell, w, preds):
+        """preds: a list of (label str, arity, n_constraints, term_coeff bytes, term_ptr u32[n_terms + 1], term_var u32[],
+        term_exp u32[], mats) with mats = arity (row_ptr u64[n + 1], col u32[nnz], coeff bytes) tuples; an entry of a
+        tuple may be None to hand the library a NULL pointer."""
+        keep = []
+
+        def ptr(a, dtype):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.size == 0:
+                a = np.zeros(1, dtype)               # a valid pointer for an empty array (never read)
+            keep.append(a)
+            return a.ctypes.data
+
+        descs = (PredicateDesc * max(1, len(preds)))()
+        for d, (label, arity, n, term_coeff, term_ptr, term_var, term_exp, mats) in zip(descs, preds):
+            d.label = label.encode("utf-8") if label is not None else None
+            d.arity, d.n_constraints = arity, n
+            d.n_terms = (len(term_ptr) - 1) if term_ptr is not None else (len(term_coeff) // 32 if term_coeff is not None else 0)
+            d.term_coeff = ptr(np.frombuffer(term_coeff, dtype=np.uint8), np.uint8) if term_coeff is not None else None
+            d.term_ptr, d.term_var, d.term_exp = ptr(term_ptr, np.uint32), ptr(term_var, np.uint32), ptr(term_exp, np.uint32)
+            if mats is not None:
+                k = max(1, len(mats))
+                rp, cl, cf = (C.c_void_p * k)(), (C.c_void_p * k)(), (C.c_void_p * k)()
+                for i, (row_ptr, col, coeff) in enumerate(mats):
+                    rp[i] = ptr(row_ptr, np.uint64)
+                    cl[i] = ptr(col, np.uint32)
+                    cf[i] = ptr(np.frombuffer(coeff, dtype=np.uint8), np.uint8) if coeff is not None else None
+                keep += [rp, cl, cf]
+                d.row_ptr, d.col, d.coeff = C.addressof(rp), C.addressof(cl), C.addressof(cf)
+        h = C.c_void_p()
+        self.check(ctx, self.dll.ark355_gr1cs_load(ctx, curve, ell, w, descs, len(preds), C.byref(h)))
+        return h
+
+    def gr1cs_free(self, g):
+        self.dll.ark355_gr1cs_free(g)
+
+    def gr1cs_num_constraints(self, g):
+        return self.dll.ark355_gr1cs_num_constraints(g)
+
+    def gr1cs_which_is_unsatisfied(self, ctx, g, z, z_len):
+        """(caller's predicate index, row) of the first unsatisfied constraint in label order, or None"""
+        pred, row = C.c_int64(0), C.c_int64(0)
+        zb, k = _buf(z)
+        self.check(ctx, self.dll.ark355_gr1cs_which_is_unsatisfied(ctx, g, zb, z_len, C.byref(pred), C.byref(row)))
+        return None if pred.value < 0 else (pred.value, row.value)
+
+    def gr1cs_mat_vec(self, ctx, g, predicate, z, z_len, arity, n, fr_size):
+        """the arity vectors M_k z of one predicate (n Fr each, Montgomery)"""
+        out = np.zeros(max(1, arity * n * fr_size), dtype=np.uint8)
+        zb, k = _buf(z)
+        self.check(ctx, self.dll.ark355_gr1cs_mat_vec(ctx, g, predicate, zb, z_len, out.ctypes.data_as(C.c_void_p)))
+        b = out.tobytes()
+        return [b[i * n * fr_size:(i + 1) * n * fr_size] for i in range(arity)]
+
+    def gr1cs_eval(self, ctx, g, predicate, z, z_len, n, fr_size):
+        """the residual of every row of one predicate (n Fr, Montgomery; zero where the row is satisfied)"""
+        out = np.zeros(max(1, n * fr_size), dtype=np.uint8)
+        zb, k = _buf(z)
+        self.check(ctx, self.dll.ark355_gr1cs_eval(ctx, g, predicate, zb, z_len, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:n * fr_size]
+
+    def gr1cs_r1cs(self, ctx, g):
+        """an ark355_r1cs handle from the predicate labelled "R1CS" (refused when another predicate has a row)"""
+        h = C.c_void_p()
+        self.check(ctx, self.dll.ark355_gr1cs_r1cs(ctx, g, C.byref(h)))
+        return h
 
     def ntt(self, ctx, curve, data: bytes, log_n, inverse=False, coset=False):
         a = np.frombuffer(bytearray(data), dtype=np.uint8)

@@ -4,6 +4,7 @@
 #include <thread>
 #include "common.h"
 #include "groth16_impl.cuh"
+#include "gr1cs_impl.cuh"
 #include "wire_impl.cuh"
 #include "pairing_host.hpp"
 
@@ -147,6 +148,48 @@ struct Api {
     }
     ARK_CHECK_HIP(hipStreamSynchronize(st));
   }
+
+  // ---- GR1CS (gr1cs_impl.cuh) ------------------------------------------------------------------------------------
+  static Gr1csDev* gr1cs_load(uint64_t ell, uint64_t w, const ark355_predicate_desc* preds, uint32_t n_preds) {
+    return gr1cs_upload<Curve>(ell, w, preds, n_preds);
+  }
+  static void* gr1cs_stage_z(ark355_ctx* ctx, ProverScratch& sc, const Gr1csDev& g, const uint8_t* z) {
+    sc.zx.ensure((g.m + 4) * sizeof(Fr));
+    ARK_CHECK_HIP(hipMemcpyAsync(sc.zx.p, z, g.m * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    return sc.zx.p;
+  }
+  // *predicate = the caller's index of the first failing predicate in label order, *constraint = its first failing row
+  static void gr1cs_check(ark355_ctx* ctx, ProverScratch& sc, const Gr1csDev& g, const uint8_t* z, int64_t* predicate,
+                          int64_t* constraint) {
+    hipStream_t st = ctx->stream;
+    void* d_z = gr1cs_stage_z(ctx, sc, g, z);
+    sc.ws.first_bad.ensure(8);
+    gr1cs_check_run<Curve>(g, d_z, sc.ws.first_bad.as<unsigned long long>(), st);
+    unsigned long long key = 0;
+    ARK_CHECK_HIP(hipMemcpyAsync(&key, sc.ws.first_bad.p, 8, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+    *predicate = -1;
+    *constraint = -1;
+    if (key == ~0ull) return;
+    const uint32_t rank = (uint32_t)(key >> GR1CS_ROW_BITS);
+    for (size_t p = 0; p < g.preds.size(); p++)
+      if (g.preds[p].rank == rank) *predicate = (int64_t)p;
+    *constraint = (int64_t)(key & ((1ull << GR1CS_ROW_BITS) - 1));
+  }
+  static void gr1cs_mat_vec(ark355_ctx* ctx, ProverScratch& sc, GenericScratch& gs, const Gr1csDev& g, uint32_t p,
+                            const uint8_t* z, uint8_t* out, bool eval) {
+    hipStream_t st = ctx->stream;
+    const Gr1csPred& P = g.preds[p];
+    if (!P.n) return;
+    void* d_z = gr1cs_stage_z(ctx, sc, g, z);
+    const size_t bytes = (size_t)(eval ? 1 : P.arity) * P.n * sizeof(Fr);
+    gs.a.ensure(bytes);
+    if (eval) gr1cs_eval_run<Curve>(g, P, d_z, gs.a.p, st);
+    else gr1cs_spmv_run<Curve>(g, P, d_z, gs.a.p, st);
+    ARK_CHECK_HIP(hipMemcpyAsync(out, gs.a.p, bytes, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+  static R1csDev* gr1cs_r1cs(ark355_ctx* ctx, const Gr1csDev& g) { return gr1cs_to_r1cs<Curve>(g, ctx->stream); }
 
   static void ntt_host(ark355_ctx* ctx, GenericScratch& g, uint8_t* data, uint32_t log_n, bool inverse, bool coset) {
     hipStream_t st = ctx->stream;

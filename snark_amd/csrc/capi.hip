@@ -21,6 +21,9 @@ struct ark355_pk {
 struct ark355_r1cs {
   R1csDev* d;
 };
+struct ark355_gr1cs {
+  Gr1csDev* d;
+};
 struct ark355_bases {
   BasesDev* d;
 };
@@ -532,6 +535,72 @@ int32_t ark355_r1cs_mat_vec(ark355_ctx* ctx, const ark355_r1cs* r1, const uint8_
   return guarded(ctx, [&] {
     CtxExtra& ex = extra(ctx);
     CURVE_DISPATCH(r1->d->curve, A::mat_vec(ctx, ex.prover, *r1->d, z, az, bz, cz, nullptr));
+  });
+}
+
+int32_t ark355_gr1cs_load(ark355_ctx* ctx, int32_t curve, uint64_t ell, uint64_t w, const ark355_predicate_desc* preds,
+                          uint32_t n_preds, ark355_gr1cs** out) {
+  if (!ctx || !out) return ARK355_EINVAL;
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    Gr1csDev* d = nullptr;
+    CURVE_DISPATCH(curve, d = A::gr1cs_load(ell, w, preds, n_preds));
+    *out = new ark355_gr1cs{d};
+  });
+}
+void ark355_gr1cs_free(ark355_gr1cs* g) {
+  if (!g) return;
+  delete g->d;
+  delete g;
+}
+uint64_t ark355_gr1cs_num_constraints(const ark355_gr1cs* g) { return g ? g->d->total : 0; }
+
+int32_t ark355_gr1cs_which_is_unsatisfied(ark355_ctx* ctx, const ark355_gr1cs* g, const uint8_t* z, uint64_t z_len,
+                                          int64_t* predicate, int64_t* constraint) {
+  if (!ctx || !g || !z || !predicate || !constraint) return ARK355_EINVAL;
+  if (z_len < g->d->m) {
+    ctx->last_error = "assignment shorter than num_instance + num_witness";
+    return ARK355_E_ASSIGNMENT_MISSING;
+  }
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(g->d->curve, A::gr1cs_check(ctx, ex.prover, *g->d, z, predicate, constraint));
+  });
+}
+
+static int32_t gr1cs_vec_common(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t* z, uint64_t z_len,
+                                uint8_t* out, bool eval) {
+  if (!ctx || !g || !z) return ARK355_EINVAL;
+  if (predicate >= g->d->preds.size()) {
+    ctx->last_error = "predicate index out of range";
+    return ARK355_EINVAL;
+  }
+  if (!out && g->d->preds[predicate].n) return ARK355_EINVAL;
+  if (z_len < g->d->m) {
+    ctx->last_error = "assignment shorter than num_instance + num_witness";
+    return ARK355_E_ASSIGNMENT_MISSING;
+  }
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(g->d->curve, A::gr1cs_mat_vec(ctx, ex.prover, ex.generic, *g->d, predicate, z, out, eval));
+  });
+}
+int32_t ark355_gr1cs_mat_vec(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t* z, uint64_t z_len,
+                             uint8_t* out) {
+  return gr1cs_vec_common(ctx, g, predicate, z, z_len, out, false);
+}
+int32_t ark355_gr1cs_eval(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t* z, uint64_t z_len,
+                          uint8_t* out) {
+  return gr1cs_vec_common(ctx, g, predicate, z, z_len, out, true);
+}
+
+int32_t ark355_gr1cs_r1cs(ark355_ctx* ctx, const ark355_gr1cs* g, ark355_r1cs** out) {
+  if (!ctx || !g || !out) return ARK355_EINVAL;
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    R1csDev* d = nullptr;
+    CURVE_DISPATCH(g->d->curve, d = A::gr1cs_r1cs(ctx, *g->d));
+    *out = new ark355_r1cs{d};
   });
 }
 

@@ -96,47 +96,83 @@ qap_quotient_kernel(Fr* __restrict__ raw, const Fr* __restrict__ c, uint64_t N, 
   raw[i] = Fr::sub(Fr::mul(raw[i], pow_lookup<Fr>(gi_lo, gz_hi, lo_bits, i)), Fr::mul(c[i], *cf));
 }
 
+// interned coefficients (elems[0] = one): mirrors the idea of field_interner.rs:24-57
+template <class Fr>
+struct FrInterner {
+  struct Key {
+    uint32_t l[Fr::N];
+    bool operator==(const Key& o) const { return memcmp(l, o.l, sizeof(l)) == 0; }
+  };
+  struct KeyHash {
+    size_t operator()(const Key& k) const {
+      uint64_t h = 1469598103934665603ull;
+      for (int i = 0; i < Fr::N; i++) h = (h ^ k.l[i]) * 1099511628211ull;
+      return (size_t)h;
+    }
+  };
+  std::unordered_map<Key, uint32_t, KeyHash> index;
+  std::vector<Fr> elems;
+  FrInterner() {
+    elems.push_back(Fr::one());
+    Key k;
+    memcpy(k.l, elems[0].l, sizeof(k.l));
+    index.emplace(k, 0u);
+  }
+  // image: sizeof(Fr) bytes, Montgomery
+  uint32_t intern(const uint8_t* image) {
+    Key key;
+    memcpy(key.l, image, sizeof(key.l));
+    auto it = index.find(key);
+    if (it == index.end()) {
+      Fr f;
+      memcpy(f.l, key.l, sizeof(key.l));
+      it = index.emplace(key, (uint32_t)elems.size()).first;
+      elems.push_back(f);
+    }
+    return it->second;
+  }
+};
+
+// dimensions and evaluation domain of an instance (shared by the host upload below and the device-side build of
+// gr1cs_impl.cuh)
+template <class Curve>
+static void r1cs_set_dims(R1csDev* r, uint64_t n, uint64_t ell, uint64_t w) {
+  using P = typename Curve::Fr::Params;
+  r->curve = Curve::ID;
+  r->n = n;
+  r->ell = ell;
+  r->w = w;
+  r->m = ell + w;
+  ARK_REQUIRE(ell >= 1, ARK355_EINVAL, "num_instance must include the constant One");
+  ARK_REQUIRE(r->m < (1ull << 31), ARK355_EINVAL, "too many variables");
+  uint64_t need = n + ell;
+  uint32_t lg = 0;
+  while ((1ull << lg) < need) lg++;
+  ARK_REQUIRE(lg <= (uint32_t)P::TWO_ADICITY, ARK355_E_POLY_DEGREE_TOO_LARGE,
+              "n + ell exceeds the largest radix-2 domain of Fr");
+  r->log_n = lg;
+  r->N = 1ull << lg;
+}
+// (g^N - 1)^-1
+template <class Curve>
+static void r1cs_upload_zinv(R1csDev* r) {
+  using Fr = typename Curve::Fr;
+  using P = typename Fr::Params;
+  Fr g = fr_from_params<Fr>(&P::gen);
+  Fr gn = fr_pow2k(g, r->log_n);
+  Fr zinv = Fr::inv(Fr::sub(gn, Fr::one()));
+  r->zinv.alloc(sizeof(Fr));
+  ARK_CHECK_HIP(hipMemcpy(r->zinv.p, &zinv, sizeof(Fr), hipMemcpyHostToDevice));
+}
+
 template <class Curve>
 static R1csDev* r1cs_upload(uint64_t n, uint64_t ell, uint64_t w, const uint64_t* const row_ptr[3],
                             const uint32_t* const col[3], const uint8_t* const coeff[3]) {
   using Fr = typename Curve::Fr;
-  using P = typename Fr::Params;
   auto* r = new R1csDev();
   try {
-    r->curve = Curve::ID;
-    r->n = n;
-    r->ell = ell;
-    r->w = w;
-    r->m = ell + w;
-    ARK_REQUIRE(ell >= 1, ARK355_EINVAL, "num_instance must include the constant One");
-    ARK_REQUIRE(r->m < (1ull << 31), ARK355_EINVAL, "too many variables");
-    uint64_t need = n + ell;
-    uint32_t lg = 0;
-    while ((1ull << lg) < need) lg++;
-    ARK_REQUIRE(lg <= (uint32_t)P::TWO_ADICITY, ARK355_E_POLY_DEGREE_TOO_LARGE,
-                "n + ell exceeds the largest radix-2 domain of Fr");
-    r->log_n = lg;
-    r->N = 1ull << lg;
-    // intern coefficients (pool[0] = one): mirrors the idea of field_interner.rs:24-57
-    struct Key {
-      uint32_t l[Fr::N];
-      bool operator==(const Key& o) const { return memcmp(l, o.l, sizeof(l)) == 0; }
-    };
-    struct KeyHash {
-      size_t operator()(const Key& k) const {
-        uint64_t h = 1469598103934665603ull;
-        for (int i = 0; i < Fr::N; i++) h = (h ^ k.l[i]) * 1099511628211ull;
-        return (size_t)h;
-      }
-    };
-    std::unordered_map<Key, uint32_t, KeyHash> interner;
-    std::vector<Fr> pool;
-    pool.push_back(Fr::one());
-    {
-      Key k;
-      memcpy(k.l, pool[0].l, sizeof(k.l));
-      interner.emplace(k, 0u);
-    }
+    r1cs_set_dims<Curve>(r, n, ell, w);
+    FrInterner<Fr> pool;
     for (int mtx = 0; mtx < 3; mtx++) {
       const uint64_t nnz = row_ptr[mtx][n];
       ARK_REQUIRE(nnz < (1ull << 32), ARK355_EINVAL, "nnz must be < 2^32");
@@ -149,16 +185,7 @@ static R1csDev* r1cs_upload(uint64_t n, uint64_t ell, uint64_t w, const uint64_t
       }
       for (uint64_t k = 0; k < nnz; k++) {
         ARK_REQUIRE(col[mtx][k] < r->m, ARK355_EINVAL, "column index out of range");
-        Key key;
-        memcpy(key.l, coeff[mtx] + k * sizeof(Fr), sizeof(key.l));
-        auto it = interner.find(key);
-        if (it == interner.end()) {
-          Fr f;
-          memcpy(f.l, key.l, sizeof(key.l));
-          it = interner.emplace(key, (uint32_t)pool.size()).first;
-          pool.push_back(f);
-        }
-        ci[k] = it->second;
+        ci[k] = pool.intern(coeff[mtx] + k * sizeof(Fr));
       }
       r->row_ptr[mtx].alloc((n + 1) * 4);
       r->col[mtx].alloc(nnz * 4);
@@ -169,14 +196,9 @@ static R1csDev* r1cs_upload(uint64_t n, uint64_t ell, uint64_t w, const uint64_t
         ARK_CHECK_HIP(hipMemcpy(r->cidx[mtx].p, ci.data(), nnz * 4, hipMemcpyHostToDevice));
       }
     }
-    r->pool.alloc(pool.size() * sizeof(Fr));
-    ARK_CHECK_HIP(hipMemcpy(r->pool.p, pool.data(), pool.size() * sizeof(Fr), hipMemcpyHostToDevice));
-    // (g^N - 1)^-1
-    Fr g = fr_from_params<Fr>(&P::gen);
-    Fr gn = fr_pow2k(g, lg);
-    Fr zinv = Fr::inv(Fr::sub(gn, Fr::one()));
-    r->zinv.alloc(sizeof(Fr));
-    ARK_CHECK_HIP(hipMemcpy(r->zinv.p, &zinv, sizeof(Fr), hipMemcpyHostToDevice));
+    r->pool.alloc(pool.elems.size() * sizeof(Fr));
+    ARK_CHECK_HIP(hipMemcpy(r->pool.p, pool.elems.data(), pool.elems.size() * sizeof(Fr), hipMemcpyHostToDevice));
+    r1cs_upload_zinv<Curve>(r);
   } catch (...) {
     delete r;
     throw;

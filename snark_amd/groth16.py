@@ -16,6 +16,12 @@ Inputs come from the unchanged ``ark-relations`` constraint system on the host:
 (/root/reference/relations/src/gr1cs/constraint_system.rs:768-774; ``Matrix<F> = Vec<Vec<(F, usize)>>``,
 utils/matrix.rs:4) and ``z`` is ``instance_assignment || witness_assignment``
 (constraint_system.rs:193-206).  Error behaviour follows ``SynthesisError`` (utils/error.rs:5-21).
+
+``R1CS`` only ever sees those three matrices.  ``to_matrices()`` returns one list of matrices PER predicate label, and a
+host that takes ``["R1CS"]`` out of a system whose other predicates carry constraints proves a weaker statement than its
+circuit states, in silence.  Such a host goes through ``snark_amd.GR1CS`` (snark_amd/gr1cs.py) instead: it loads every
+predicate, checks all of them on the device, and its ``r1cs_handle()`` refuses to hand the prover an R1CS while another
+predicate has a row.
 """
 from __future__ import annotations
 
