@@ -576,6 +576,12 @@ class Lib:
         self.check(ctx, self.dll.ark355_ntt_fr(ctx, curve, a.ctypes.data_as(C.c_void_p), log_n, int(inverse), int(coset)))
         return a.tobytes()
 
+    def ntt_dev(self, ctx, curve, d_data, d_scratch, log_n, inverse=False, coset=False, stream=None):
+        """in place on DEVICE pointers (2^log_n Fr each; the content of d_scratch afterwards is unspecified), queued on `stream`
+        (a hipStream_t as an integer; None = the context's own) and NOT synchronised: the caller waits for that stream"""
+        self.check(ctx, self.dll.ark355_ntt_fr_dev(ctx, curve, C.c_void_p(d_data), C.c_void_p(d_scratch), log_n, int(inverse),
+                                                   int(coset), C.c_void_p(stream) if stream else None))
+
     def msm(self, ctx, curve, group, bases: bytes, scalars: bytes, n, out_size):
         out = np.zeros(out_size, dtype=np.uint8)
         bb, k1 = _buf(bases if n else None)

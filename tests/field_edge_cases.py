@@ -1,0 +1,169 @@
+"""Operands that uniform sampling never produces, shared by the CPU-emulator tier and the GPU tier.
+
+The Montgomery multiplier of csrc/field.cuh is an inline-assembly carry chain on the device and portable C++ everywhere else
+(emulator, host): only a GPU run executes the former.  What enters the multiplier is the Montgomery IMAGE x R mod p of a
+value, so the operands here are chosen by their image: all-zero / all-one limbs, single carries across every limb, the
+neighbourhood of the modulus.  Every expected value is computed in Python integers."""
+from __future__ import annotations
+
+import itertools
+import random
+
+from helpers import fr_vec_from_mont, r1cs_load_from_rows, z_bytes
+from oracle import serialize as Z
+from oracle.curves import g1
+
+
+def montgomery_images(p, nbytes):
+    """The limb patterns (32-bit limbs, R = 2^(8 nbytes)), every one below p."""
+    W = 8 * nbytes
+    Rm = 1 << W
+    nl = W // 32
+    low = (1 << (W - 32)) - 1                            # all limbs but the top one
+    top = p >> (W - 32)
+    ones = 0xFFFFFFFF
+    even = sum(ones << (64 * i) for i in range(nl // 2))                      # limbs 0, 2, 4, ..: the top limb is zero
+    odd = sum(ones << (64 * i + 32) for i in range(nl // 2 - 1)) | ((top - 1) << (W - 32))   # limbs 1, 3, ..; top limb just below p's
+    images = [0, 1, p - 1, p - 2, (p - 1) // 2, (p + 1) // 2, Rm % p, Rm * Rm % p, (1 << 32) - 1, 1 << 32, low,
+              ((top - 1) << (W - 32)) | low,               # the largest value below p whose lower limbs are all ones
+              (1 << (p.bit_length() - 1)) - 1,             # all ones below p's top bit
+              even, odd, p - (1 << 32), p - (1 << (W - 32))]
+    assert all(0 <= v < p for v in images) and len(set(images)) == len(images)
+    return images
+
+
+def pattern_values(C):
+    """Fr elements whose Montgomery images are montgomery_images(r): x = image R^-1 mod r"""
+    r = C.r
+    images = montgomery_images(r, C.fr_bytes)
+    rinv = pow(1 << (8 * C.fr_bytes), -1, r)
+    vals = [v * rinv % r for v in images]
+    for v, im in zip(vals, images):
+        assert int.from_bytes(Z.fr_mont(C, v), "little") == im
+    return vals
+
+
+def diagonal_pairs_case(lib, ctx, C, gr1cs=True):
+    """All ordered pairs (a, b) of the pattern values through ONE multiplication each: A = diag(a_i) and B = diag(b_i) over
+    z = (1, b_0, b_1, ..) make ark355_r1cs_mat_vec return a_i b_i and b_i b_i.  With C_i = (a_i b_i)(b_i b_i) on the constant
+    column the system is satisfied (the check multiplies the two products); one coefficient off by one is reported at its row."""
+    r = C.r
+    vals = pattern_values(C)
+    pairs = list(itertools.product(vals, vals))
+    n = len(pairs)
+    A = [[(a, 1 + i)] for i, (a, b) in enumerate(pairs)]
+    B = [[(b, 1 + i)] for i, (a, b) in enumerate(pairs)]
+    ab = [a * b % r for a, b in pairs]
+    bb = [b * b % r for a, b in pairs]
+    cc = [x * y % r for x, y in zip(ab, bb)]
+    Cm = [[(c, 0)] for c in cc]
+    z = [1] + [b for a, b in pairs]
+    zb = z_bytes(C, z)
+    rh = r1cs_load_from_rows(lib, ctx, C, A, B, Cm, 1, n)
+    try:
+        az, bz, cz = lib.mat_vec(ctx, rh, zb, len(z), n, 32)
+        assert fr_vec_from_mont(C, az) == ab, (C.name, "a_i b_i")
+        assert fr_vec_from_mont(C, bz) == bb, (C.name, "b_i b_i")
+        assert fr_vec_from_mont(C, cz) == cc, (C.name, "c_i 1")
+        assert lib.is_satisfied(ctx, rh, zb, len(z)) == -1
+    finally:
+        lib.dll.ark355_r1cs_free(rh)
+    minus1 = montgomery_images(r, C.fr_bytes).index(r - 1)             # the pair whose two images are r - 1
+    for k in (0, minus1 * len(vals) + minus1, n // 2 + 3, n - 1):
+        bad = list(Cm)
+        bad[k] = [((cc[k] + 1) % r, 0)]
+        rh = r1cs_load_from_rows(lib, ctx, C, A, B, bad, 1, n)
+        try:
+            assert lib.is_satisfied(ctx, rh, zb, len(z)) == k, (C.name, k)
+        finally:
+            lib.dll.ark355_r1cs_free(rh)
+    if not gr1cs:
+        return
+    # the same pairs through a degree-2 predicate (x0 x1 - x2) of ark355_gr1cs_eval: with C_i = 1 the residual is
+    # (a_i b_i)(b_i b_i) - 1, a product of two products and a subtraction on every row
+    from snark_amd import GR1CS
+    spec = {"R1CS": (3, [(1, [(0, 1), (1, 1)]), (r - 1, [(2, 1)])], [A, B, [[(1, 0)] for _ in pairs]])}
+    g = GR1CS.from_matrices(C.curve_id, 1, n, spec).load(lib, ctx)
+    try:
+        assert fr_vec_from_mont(C, g.eval("R1CS", zb)) == [(c - 1) % r for c in cc], (C.name, "gr1cs_eval")
+        first = next((i for i, c in enumerate(cc) if c != 1), None)
+        got = g.which_is_unsatisfied(zb)
+        assert got == (None if first is None else ("R1CS", first))
+    finally:
+        g.free()
+    spec = {"R1CS": (3, [(1, [(0, 1), (1, 1)]), (r - 1, [(2, 1)])], [A, B, Cm])}
+    g = GR1CS.from_matrices(C.curve_id, 1, n, spec).load(lib, ctx)
+    try:
+        assert fr_vec_from_mont(C, g.eval("R1CS", zb)) == [0] * n
+        assert g.which_is_unsatisfied(zb) is None
+    finally:
+        g.free()
+
+
+# ---- the base field, through points -------------------------------------------------------------------------------------------
+def pattern_points_g1(C):
+    """Points of y^2 = x^3 + b whose x has a Montgomery image at (or a few steps from) each pattern, both signs of y.  Only for
+    a G1 of cofactor 1 (BN254): there every curve point is in the prime-order subgroup, which every MSM path assumes."""
+    q = C.q
+    G1 = g1(C)
+    assert q % 4 == 3, "square roots as a^((q + 1) / 4)"
+    gx, gy = C.g1_gen
+    b = (gy * gy - gx * gx * gx) % q
+    rinv = pow(1 << (8 * C.fq_bytes), -1, q)
+    pts = []
+    for im in montgomery_images(q, C.fq_bytes):
+        for t in itertools.chain.from_iterable((t, -t) for t in range(0, 200)):
+            if not 0 <= im + t < q:
+                continue
+            x = (im + t) * rinv % q
+            rhs = (x * x * x + b) % q
+            y = pow(rhs, (q + 1) // 4, q)
+            if y * y % q == rhs and y != 0:
+                break
+        else:
+            raise AssertionError("no curve point near image %x" % im)
+        for P in ((x, y), (x, q - y)):
+            assert G1.is_on_curve(P)
+            pts.append(P)
+    return pts
+
+
+def pattern_points_case(lib, ctx, C, to_dev, seed=77):
+    """The pattern points through every G1 path that computes in Fq: the one-shot MSM, resident tables + ark355_msm_dev, the
+    fixed-base table with each of them as the base, both wire formats -- against the Python group law and encoders."""
+    G1 = g1(C)
+    rnd = random.Random(seed)
+    pts = pattern_points_g1(C)
+    n = len(pts)
+    assert n >= 32
+    psz = lib.sizes(C.curve_id)["g1"]
+    raws = b"".join(Z.g1_raw(C, P) for P in pts)
+    half = (C.r - 1) // 2
+    special = [1, C.r - 1, 2, half, half + 1, 0, (1 << 32) - 1, 1 << 128]
+    ks = [special[i] if i < len(special) else rnd.randrange(C.r) for i in range(n)]
+    kb = b"".join(Z.fr_canon(C, k) for k in ks)
+    expect = G1.msm(pts, ks)
+    assert Z.g1_from_raw(C, lib.msm(ctx, C.curve_id, 1, raws, kb, n, psz)) == expect, (C.name, "msm_g1")
+    # all scalars one: the plain sum, every addition between two pattern points (P and -P are neighbours: it is the infinity)
+    ones = b"".join(Z.fr_canon(C, 1) for _ in range(n))
+    assert Z.g1_from_raw(C, lib.msm(ctx, C.curve_id, 1, raws, ones, n, psz)) is None
+    odd = [1 if i % 2 == 0 else 2 for i in range(n)]        # P_i - 2 P_i: sum of -P over the patterns
+    assert Z.g1_from_raw(C, lib.msm(ctx, C.curve_id, 1, raws, b"".join(Z.fr_canon(C, k) for k in odd), n, psz)) == G1.msm(pts, odd)
+    h = lib.bases_load(ctx, C.curve_id, 1, raws, n)
+    try:
+        ptr, keep = to_dev(kb)
+        assert Z.g1_from_raw(C, lib.msm_dev(ctx, h, ptr, n, 0, psz)) == expect, (C.name, "bases_load + msm_dev")
+        ptr, keep = to_dev(b"".join(Z.fr_mont(C, k) for k in ks))
+        assert Z.g1_from_raw(C, lib.msm_dev(ctx, h, ptr, n, 1, psz)) == expect, (C.name, "msm_dev, Montgomery scalars")
+    finally:
+        lib.dll.ark355_bases_free(h)
+    fks = [1, 2, 3, C.r - 1, rnd.randrange(C.r), (1 << 253) - 1]
+    fkb = b"".join(Z.fr_canon(C, k) for k in fks)
+    for i, P in enumerate(pts):
+        out = lib.fixed_base_mul(ctx, C.curve_id, 1, Z.g1_raw(C, P), fkb, len(fks), psz)
+        got = [Z.g1_from_raw(C, out[j * psz:(j + 1) * psz]) for j in range(len(fks))]
+        assert got == [G1.mul(P, k) for k in fks], (C.name, "fixed_base_mul, base", i)
+    for comp, enc in ((True, Z.g1_compressed), (False, Z.g1_uncompressed)):
+        wire = b"".join(enc(C, P) for P in pts)
+        assert lib.points_encode(ctx, C.curve_id, 1, raws, n, comp) == wire, (C.name, "encode", comp)
+        assert lib.points_decode(ctx, C.curve_id, 1, wire, n, comp, True, psz) == raws, (C.name, "decode", comp)

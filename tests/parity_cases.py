@@ -375,5 +375,76 @@ def resident_known_dlog_case(lib, ctx, C, group, n, to_dev, seed=21):
         out = lib.msm_dev(ctx, h, ptr, n, 0, psz)
         expect = G_.mul(G_.gen, sum(k * s for k, s in zip(ks, ss)) % C.r)
         assert fromraw(C, out) == expect, (C.name, group, n)
+        # scalars_mont = 1: the same scalars as Montgomery images, converted on the device
+        ptr_m, keep_m = to_dev(b"".join(Z.fr_mont(C, k) for k in ks))
+        out_m = lib.msm_dev(ctx, h, ptr_m, n, 1, psz)
+        assert fromraw(C, out_m) == expect, (C.name, group, n, "scalars_mont")
+        assert out_m == out
     finally:
         lib.dll.ark355_bases_free(h)
+
+
+def resident_partial_and_sum_case(lib, ctx, C, group, to_dev, cuts=(0, 20, 50), prefix=7, seed=9, zero_partial=None):
+    """ark355_bases_load (window tables) + msm over a PREFIX of the rows + XYZZ partial / ark355_xyzz_sum: the pieces the
+    multi-GPU sharded MSM is made of (SURVEY 8e).  cuts: the row ranges [cuts[i], cuts[i + 1]) of the partials;
+    zero_partial: the index of a partial whose scalars are all zero (it is the point at infinity)."""
+    G_ = g1(C) if group == 1 else g2(C)
+    raw = Z.g1_raw if group == 1 else Z.g2_raw
+    fromraw = Z.g1_from_raw if group == 1 else Z.g2_from_raw
+    rnd = random.Random(seed)
+    n = cuts[-1]
+    pts = G_.fixed_base_muls(G_.gen, [rnd.randrange(C.r) for _ in range(n)])
+    ks = [rnd.randrange(C.r) for _ in range(n)]
+    sz = lib.sizes(C.curve_id)
+    psz = sz["g1"] if group == 1 else sz["g2"]
+    if zero_partial is not None:
+        for i in range(cuts[zero_partial], cuts[zero_partial + 1]):
+            ks[i] = 0
+    parts = []
+    for j, (lo, hi) in enumerate(zip(cuts[:-1], cuts[1:])):
+        bh = lib.bases_load(ctx, C.curve_id, group, b"".join(raw(C, p) for p in pts[lo:hi]), hi - lo)
+        try:
+            ptr, keep = to_dev(b"".join(Z.fr_canon(C, k) for k in ks[lo:hi]))
+            parts.append(lib.msm_dev(ctx, bh, ptr, hi - lo, 0, 2 * psz, partial=True))
+            if j == zero_partial:
+                assert fromraw(C, lib.xyzz_sum(ctx, C.curve_id, group, parts[-1], 1, psz)) is None
+            if lo == 0 and prefix:   # prefix of the rows with the same handle
+                pre = lib.msm_dev(ctx, bh, ptr, prefix, 0, psz)
+                assert fromraw(C, pre) == G_.msm(pts[:prefix], ks[:prefix])
+        finally:
+            lib.dll.ark355_bases_free(bh)
+    out = lib.xyzz_sum(ctx, C.curve_id, group, b"".join(parts), len(parts), psz)
+    assert fromraw(C, out) == G_.msm(pts, ks), (C.name, group, cuts)
+
+
+def resident_count_zero_and_one_case(lib, ctx, C, group, to_dev, seed=10):
+    """count = 0 and count = 1 of ark355_msm_dev / ark355_msm_dev_partial / ark355_xyzz_sum: the empty sum is the point at
+    infinity, one term is k P, the sum of one partial is that partial."""
+    G_ = g1(C) if group == 1 else g2(C)
+    raw = Z.g1_raw if group == 1 else Z.g2_raw
+    fromraw = Z.g1_from_raw if group == 1 else Z.g2_from_raw
+    rnd = random.Random(seed + group)
+    sz = lib.sizes(C.curve_id)
+    psz = sz["g1"] if group == 1 else sz["g2"]
+    pts = G_.fixed_base_muls(G_.gen, [rnd.randrange(C.r) for _ in range(3)])
+    ks = [rnd.randrange(C.r) for _ in range(3)]
+    assert fromraw(C, lib.xyzz_sum(ctx, C.curve_id, group, b"", 0, psz)) is None
+    bh = lib.bases_load(ctx, C.curve_id, group, b"".join(raw(C, p) for p in pts), 3)
+    try:
+        ptr, keep = to_dev(b"".join(Z.fr_canon(C, k) for k in ks))
+        assert fromraw(C, lib.msm_dev(ctx, bh, ptr, 0, 0, psz)) is None
+        assert fromraw(C, lib.msm_dev(ctx, bh, ptr, 1, 0, psz)) == G_.mul(pts[0], ks[0])
+        empty = lib.msm_dev(ctx, bh, ptr, 0, 0, 2 * psz, partial=True)
+        one = lib.msm_dev(ctx, bh, ptr, 1, 0, 2 * psz, partial=True)
+        assert fromraw(C, lib.xyzz_sum(ctx, C.curve_id, group, empty, 1, psz)) is None
+        assert fromraw(C, lib.xyzz_sum(ctx, C.curve_id, group, one, 1, psz)) == G_.mul(pts[0], ks[0])
+        assert fromraw(C, lib.xyzz_sum(ctx, C.curve_id, group, empty + one + empty, 3, psz)) == G_.mul(pts[0], ks[0])
+    finally:
+        lib.dll.ark355_bases_free(bh)
+    # a base set of ONE row
+    bh = lib.bases_load(ctx, C.curve_id, group, raw(C, pts[1]), 1)
+    try:
+        ptr, keep = to_dev(Z.fr_canon(C, ks[1]))
+        assert fromraw(C, lib.msm_dev(ctx, bh, ptr, 1, 0, psz)) == G_.mul(pts[1], ks[1])
+    finally:
+        lib.dll.ark355_bases_free(bh)
