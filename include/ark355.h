@@ -81,6 +81,8 @@ int32_t ark355_sizes(int32_t curve, uint32_t what[4]);
  *                 1: ark355_prove / _dev / _batch also compare a_i b_i with c_i on the rows the witness map computes anyway -- the
  *                 check ark-groth16 runs under debug_assert!(cs.is_satisfied()) -- and return ARK355_E_UNSATISFIABLE, with the index
  *                 of the first unsatisfied constraint in ark355_last_error, instead of a proof that cannot verify).
+ *                 PAIRING_DEVICE (0 host threads, 1 device, -1 [default] device from PAIRING_DEVICE_MIN pairs on) and
+ *                 PAIRING_DEVICE_MIN: where the Miller loops of ark355_multi_pairing and ark355_verify_batch run.
  * ARK355_EINVAL for an unknown name.  ark355_prove_batch runs its worker contexts under the caller's policy.
  * (No counterpart in the reference: ark-groth16 has no runtime knobs; rayon's thread count is its only one.) */
 int32_t ark355_ctx_set_policy(ark355_ctx* ctx, const char* name, int64_t value);
@@ -397,7 +399,8 @@ int32_t ark355_fixed_base_mul(ark355_ctx* ctx, int32_t curve, int32_t group, con
  * Checks `count` proofs of ONE verifying key at once with the random-linear-combination test
  *   prod_j e(rho_j A_j, B_j) = e((sum rho_j) alpha, beta) e(sum_i (sum_j rho_j x_ji) gamma_abc_i, gamma) e(sum rho_j C_j, delta):
  * count + 3 Miller loops and ONE final exponentiation instead of 4 count pairings.  The two multi-scalar sums run on
- * the device; the Miller loops and the final exponentiation on host threads.  public_inputs: count x (num_instance - 1)
+ * the device; the final exponentiation on the host; the curve checks, rho_j A_j and the Miller loops on host threads or on
+ * the device (policy PAIRING_DEVICE, below).  public_inputs: count x (num_instance - 1)
  * Fr (Montgomery; the leading One is implicit, as in SNARK::verify); rho: count x 32 B canonical, non-zero, drawn by
  * the caller from its rng (soundness error ~ 1/|rho|); NULL is allowed for count == 1 (plain verification).
  * *ok = 1 iff every proof verifies (with overwhelming probability over rho). */
@@ -411,6 +414,22 @@ typedef struct {
 } ark355_vk_desc;
 int32_t ark355_verify_batch(ark355_ctx* ctx, int32_t curve, const ark355_vk_desc* vk, const ark355_proof_raw* proofs,
                             const uint8_t* public_inputs, const uint8_t* rho, uint64_t count, int32_t* ok);
+
+/* ark-ec Pairing::multi_pairing: GT = final_exponentiation(prod_i miller_loop(P_i, Q_i)).
+ * g1: n raw affine G1 images, g2: n raw affine G2 images (Montgomery, as everywhere in this header); a pair with either
+ * point at infinity contributes one, n == 0 gives one.  out_gt: 12 Fq, Montgomery, in ark-ff's Fp12 memory order
+ *   c0.c0.c0, c0.c0.c1, c0.c1.c0, c0.c1.c1, c0.c2.c0, c0.c2.c1, c1.c0.c0, ..., c1.c2.c1
+ * over the tower Fq2 = Fq[u]/(u^2 + 1), Fq6 = Fq2[v]/(v^3 - xi), Fq12 = Fq6[w]/(w^2 - v), xi = 1 + u (BLS12-381) or
+ * 9 + u (BN254).  *is_one = 1 iff GT is the identity (the pairing-product check).
+ * Every point is checked against its curve equation first: one that fails gives ARK355_EINVAL and ark355_last_error
+ * names the argument and the index.  Subgroup membership is NOT checked (that is ark355_points_decode's
+ * ARK355_VALIDATE_FULL, as for ark355_verify_batch); a point on its curve but outside the r-torsion returns cleanly with
+ * an unspecified value.
+ * Policy PAIRING_DEVICE (this call and ark355_verify_batch): 0 Miller loops on host threads, 1 on the device, -1 (default)
+ * on the device when the call has at least PAIRING_DEVICE_MIN pairs (count + 3 for ark355_verify_batch).  The final
+ * exponentiation runs on the host, once per call. */
+int32_t ark355_multi_pairing(ark355_ctx* ctx, int32_t curve, const uint8_t* g1, const uint8_t* g2, uint64_t n,
+                             uint8_t* out_gt /* may be NULL */, int32_t* is_one /* may be NULL */);
 
 /* The scalars of the Groth16 generator (circuit_specific_setup, snark/src/lib.rs:43-46; upstream
  * generate_parameters_with_qap) from the R1CS matrices in CSR and the five trapdoor elements tau, alpha, beta, gamma,

@@ -390,6 +390,17 @@ extern "C" {
         ok: *mut i32,
     ) -> i32;
 
+    /// `Pairing::multi_pairing` over raw affine images; `out_gt` (12 Fq, ark-ff `Fp12` memory order) and `is_one` may be null.
+    pub fn ark355_multi_pairing(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        g1: *const u8,
+        g2: *const u8,
+        n: u64,
+        out_gt: *mut u8,
+        is_one: *mut i32,
+    ) -> i32;
+
     pub fn ark355_setup_scalars(
         curve: i32,
         n_constraints: u64,

@@ -54,7 +54,7 @@ SYMBOLS = [
     "ark355_prove_sharded", "ark355_prove_sharded_dev", "ark355_point_size", "ark355_pk_load_bytes", "ark355_pk_dims",
     "ark355_pk_table_info",
     "ark355_points_decode", "ark355_points_encode", "ark355_proof_to_bytes", "ark355_proof_from_bytes",
-    "ark355_setup_scalars", "ark355_verify_batch",
+    "ark355_setup_scalars", "ark355_verify_batch", "ark355_multi_pairing",
     "ark355_ctx_set_policy", "ark355_ctx_get_policy", "ark355_sched_info", "ark355_sched_reset", "ark355_diag_streams", "ark355_diag_dispatch",
     "ark355_diag_mad_rate", "ark355_diag_clocks",
 ]
@@ -194,6 +194,7 @@ class Lib:
         d.ark355_proof_from_bytes.argtypes = [i32, vp, u64, i32, i32, P(ProofRaw)]
         d.ark355_setup_scalars.argtypes = [i32, u64, u64, u64, P(vp * 3), P(vp * 3), P(vp * 3), vp, vp, vp, vp, vp, vp, vp]
         d.ark355_verify_batch.argtypes = [vp, i32, P(VkDesc), vp, vp, vp, u64, P(i32)]
+        d.ark355_multi_pairing.argtypes = [vp, i32, vp, vp, u64, vp, P(i32)]
         d.ark355_ctx_set_policy.argtypes = [vp, C.c_char_p, i64]
         d.ark355_ctx_get_policy.argtypes = [vp, C.c_char_p, P(i64)]
         d.ark355_sched_info.argtypes = [vp, vp, i32, P(SchedReport)]
@@ -664,6 +665,18 @@ class Lib:
         ok = C.c_int32(0)
         self.check(ctx, self.dll.ark355_verify_batch(ctx, curve, C.byref(d), arr, ib, rb, len(proofs), C.byref(ok)))
         return bool(ok.value)
+
+    def multi_pairing(self, ctx, curve, g1: bytes, g2: bytes, n, want_gt=True):
+        """ark355_multi_pairing over n raw affine pairs.  Returns (gt, is_one): gt = 12 Fq (Montgomery, ark-ff Fp12 order) as
+        bytes, or None with want_gt=False."""
+        fq = self.sizes(curve)["fq"]
+        out = np.zeros(12 * fq, dtype=np.uint8)
+        b1, k1 = _buf(g1 if g1 else None)
+        b2, k2 = _buf(g2 if g2 else None)
+        one = C.c_int32(0)
+        self.check(ctx, self.dll.ark355_multi_pairing(ctx, curve, b1, b2, n, out.ctypes.data_as(C.c_void_p) if want_gt else None,
+                                                      C.byref(one)))
+        return (out.tobytes() if want_gt else None), bool(one.value)
 
     def timings(self, ctx):
         t = Timings()

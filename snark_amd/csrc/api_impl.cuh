@@ -1,5 +1,6 @@
 // Per-curve implementation of the C ABI (explicitly instantiated in ark355_bls.hip / ark355_bn.hip).
 #pragma once
+#include <chrono>
 #include <functional>
 #include <thread>
 #include "common.h"
@@ -7,6 +8,7 @@
 #include "gr1cs_impl.cuh"
 #include "wire_impl.cuh"
 #include "pairing_host.hpp"
+#include "pairing_impl.cuh"
 
 namespace ark355 {
 
@@ -67,6 +69,7 @@ struct GenericScratch {
   MsmBuckets bk;
   DevBuf a, b, c;
   DevBuf rows;       // the 28-bit rows of a one-shot MSM's bases (msm_host)
+  DevBuf pg1, pg2, plines, ppart, pout, psc;      // device pairing (pairing_impl.cuh): points, lines, partial products, scalars
 };
 
 template <class Curve>
@@ -492,6 +495,149 @@ struct Api {
     });
   }
 
+  // ---- pairing (pairing_impl.cuh on the device, pairing_host.hpp on host threads) ------------------------------------
+  using PH = PairingHost<Curve>;
+  using PD = PairingDev<Curve>;
+  using Gt = typename PH::Fq12;
+
+  // policy PAIRING_DEVICE: 0 host threads, 1 device, -1 device from PAIRING_DEVICE_MIN pairs on
+  static bool pairing_on_device(const TunePolicy& pol, uint64_t pairs) {
+    if (pol.pairing_device == 0) return false;
+    if (pol.pairing_device > 0) return true;
+    return pairs >= (uint64_t)std::max<int64_t>(pol.pairing_device_min, 0);
+  }
+  static unsigned host_threads() {
+    unsigned nt = std::thread::hardware_concurrency();
+    if (nt == 0) nt = 4;
+    return nt > 16 ? 16 : nt;
+  }
+  static double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  }
+
+  // prod_i miller_loop(P_i, Q_i) on host threads (the loop of PairingHost::product_is_one, value kept)
+  static Gt miller_product_host(const std::vector<Affine<Fq>>& Ps, const std::vector<Affine<Fq2>>& Qs) {
+    const size_t n = Ps.size();
+    const unsigned threads = (unsigned)std::min<size_t>(host_threads(), n);
+    std::vector<Gt> part(threads ? threads : 1, Gt::one());
+    (void)PH::consts();
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < threads; t++)
+      th.emplace_back([&, t] {
+        Gt acc = Gt::one();
+        for (size_t i = t; i < n; i += threads) acc = Gt::mul(acc, PH::miller_loop(Ps[i], Qs[i]));
+        part[t] = acc;
+      });
+    for (auto& x : th) x.join();
+    Gt f = Gt::one();
+    for (const auto& p : part) f = Gt::mul(f, p);
+    return f;
+  }
+
+  // y^2 = x^3 + b on the device for n1 + n2 resident points; returns the kernel's word (0: all on their curves)
+  static unsigned long long on_curve_dev(GenericScratch& g, const void* d_g1, uint64_t n1, const void* d_g2, uint64_t n2,
+                                         hipStream_t st) {
+    if (n1 + n2 == 0) return 0;
+    g.c.ensure(8);
+    ARK_CHECK_HIP(hipMemsetAsync(g.c.p, 0, 8, st));
+    ARK_LAUNCH((on_curve_kernel<Curve>), dim3((uint32_t)((n1 + n2 + 127) / 128)), dim3(128), 0, st,
+               reinterpret_cast<const Affine<Fq>*>(d_g1), n1, reinterpret_cast<const Affine<Fq2>*>(d_g2), n2,
+               g.c.as<unsigned long long>());
+    ARK_CHECK_LAUNCH();
+    unsigned long long e = 0;
+    ARK_CHECK_HIP(hipMemcpyAsync(&e, g.c.p, 8, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+    return e;
+  }
+
+  // prod_i miller_loop(P_i, Q_i) for n resident pairs (g.pg1 / g.pg2), every point on its curve.  At most PAIR_CHUNK pairs
+  // have their lines in HBM at a time (about 20 KB per pair); the partial products of all chunks meet in one last launch.
+  static constexpr uint64_t PAIR_CHUNK = 1u << 15;
+  static Gt multi_miller_dev(GenericScratch& g, const Affine<Fq>* d1, const Affine<Fq2>* d2, uint64_t n, hipStream_t st) {
+    if (n == 0) return Gt::one();
+    typename PD::Consts k{};
+    PD::schedule(&k);
+    k.two_inv = Fq::inv(Fq::add(Fq::one(), Fq::one()));
+    k.frob_x = PH::consts().frob_x;
+    k.frob_y = PH::consts().frob_y;
+    const uint64_t blocks_total = (n + PAIR_LANES - 1) / PAIR_LANES;
+    const uint64_t cap = std::min<uint64_t>(n, PAIR_CHUNK);
+    const uint32_t stride = (uint32_t)((cap + PAIR_LANES - 1) / PAIR_LANES * PAIR_LANES);
+    g.plines.ensure((size_t)k.steps * 3 * PD::W2 * stride * sizeof(uint32_t));
+    g.ppart.ensure(blocks_total * PD::W12 * sizeof(uint32_t));
+    g.pout.ensure(PD::W12 * sizeof(uint32_t));
+    for (uint64_t off = 0; off < n; off += PAIR_CHUNK) {
+      const uint32_t m = (uint32_t)std::min<uint64_t>(PAIR_CHUNK, n - off);
+      const dim3 grid((m + PAIR_LANES - 1) / PAIR_LANES);
+      ARK_LAUNCH((pairing_lines_kernel<Curve>), grid, dim3(PAIR_LANES), 0, st, d1 + off, d2 + off, m, stride, k,
+                 g.plines.template as<uint32_t>());
+      ARK_CHECK_LAUNCH();
+      ARK_LAUNCH((pairing_accumulate_kernel<Curve>), grid, dim3(PAIR_LANES), 0, st, d1 + off, d2 + off, m, stride, k,
+                 (const uint32_t*)g.plines.template as<uint32_t>(), g.ppart.template as<uint32_t>() + (off / PAIR_LANES) * PD::W12);
+      ARK_CHECK_LAUNCH();
+    }
+    ARK_LAUNCH((pairing_product_kernel<Curve>), dim3(1), dim3(PAIR_LANES), 0, st, (const uint32_t*)g.ppart.template as<uint32_t>(),
+               (uint32_t)blocks_total, g.pout.template as<uint32_t>());
+    ARK_CHECK_LAUNCH();
+    Fq2 c[6];
+    ARK_CHECK_HIP(hipMemcpyAsync(c, g.pout.p, sizeof(c), hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+    // coefficients of w^0 .. w^5 -> the tower of pairing_host.hpp (v = w^2)
+    Gt f{{c[0], c[2], c[4]}, {c[1], c[3], c[5]}};
+    return BN ? f : Gt::conj(f);      // BLS12-381: x < 0
+  }
+  static constexpr bool BN = Curve::ID == ARK355_BN254;
+
+  static Gt final_exp(const Gt& f) {
+    ARK_REQUIRE(!PH::consts().final_exp.l.empty(), ARK355_EINVAL, "the final exponent could not be formed");
+    return PH::final_exponentiation(f);
+  }
+  static void trace_pairing(const ark355_ctx* ctx, const char* what, int device, uint64_t n, double check_ms, double mul_ms,
+                            double miller_ms, double fe_ms) {
+    if (ctx->policy.trace_host)
+      fprintf(stderr, "[ark355] %s route=%s pairs=%llu check_ms=%.3f scalar_mul_ms=%.3f miller_ms=%.3f final_exp_ms=%.3f\n", what,
+              device ? "device" : "host", (unsigned long long)n, check_ms, mul_ms, miller_ms, fe_ms);
+  }
+
+  // ark-ec Pairing::multi_pairing over raw affine images
+  static void multi_pairing(ark355_ctx* ctx, GenericScratch& g, const uint8_t* g1, const uint8_t* g2, uint64_t n, uint8_t* out_gt,
+                            int32_t* is_one) {
+    hipStream_t st = ctx->stream;
+    const bool dev = n > 0 && pairing_on_device(ctx->policy, n);
+    const double t0 = now_ms();
+    double t1 = t0;
+    Gt f = Gt::one();
+    auto refuse = [](int group, uint64_t idx) {
+      throw HipError{ARK355_EINVAL, std::string(group == 1 ? "g1[" : "g2[") + std::to_string(idx) + "]: point not on curve"};
+    };
+    if (dev) {
+      g.pg1.ensure(n * sizeof(Affine<Fq>));
+      g.pg2.ensure(n * sizeof(Affine<Fq2>));
+      ARK_CHECK_HIP(hipMemcpyAsync(g.pg1.p, g1, n * sizeof(Affine<Fq>), hipMemcpyHostToDevice, st));
+      ARK_CHECK_HIP(hipMemcpyAsync(g.pg2.p, g2, n * sizeof(Affine<Fq2>), hipMemcpyHostToDevice, st));
+      const unsigned long long e = on_curve_dev(g, g.pg1.p, n, g.pg2.p, n, st);
+      if (e) refuse((int)(e & 15), (e >> 4) - 1);
+      t1 = now_ms();
+      f = multi_miller_dev(g, g.pg1.template as<Affine<Fq>>(), g.pg2.template as<Affine<Fq2>>(), n, st);
+    } else if (n > 0) {
+      std::vector<Affine<Fq>> Ps(n);
+      std::vector<Affine<Fq2>> Qs(n);
+      memcpy(Ps.data(), g1, n * sizeof(Affine<Fq>));
+      memcpy(Qs.data(), g2, n * sizeof(Affine<Fq2>));
+      for (uint64_t i = 0; i < n; i++) {
+        if (!Ps[i].is_inf() && !(Fq::sqr_ni(Ps[i].y) == W::curve_rhs(Ps[i].x))) refuse(1, i);
+        if (!Qs[i].is_inf() && !(Fq2::sqr_ni(Qs[i].y) == W::curve_rhs(Qs[i].x))) refuse(2, i);
+      }
+      t1 = now_ms();
+      f = miller_product_host(Ps, Qs);
+    }
+    const double t2 = now_ms();
+    const Gt gt = final_exp(f);
+    trace_pairing(ctx, "multi_pairing", dev, n, t1 - t0, 0.0, t2 - t1, now_ms() - t2);
+    if (out_gt) memcpy(out_gt, &gt, sizeof(gt));
+    if (is_one) *is_one = gt == Gt::one() ? 1 : 0;
+  }
+
   // ---- batch verification (pairing_host.hpp) --------------------------------------------------------------------------
   // sum_j rho_j [ e(A_j, B_j) = e(alpha, beta) e(acc_j, gamma) e(C_j, delta) ]  <=>
   //   prod_j e(rho_j A_j, B_j) * e(-(sum rho_j) alpha, beta) * e(-sum_i (sum_j rho_j x_ji) gamma_abc_i, gamma)
@@ -517,6 +663,25 @@ struct Api {
     // affine Miller loop (its line functions never use the curve constant, (0, y) / y = 0 cases would divide by zero
     // silently).  Three curve equations per proof on the host; subgroup membership is ark355_proof_from_bytes' job
     // (ARK355_VALIDATE_FULL), as upstream splits it between deserialization and verification.
+    // Device route (policy PAIRING_DEVICE): the same three equations, rho_j A_j and the count + 3 Miller loops as kernels of
+    // pairing_impl.cuh; g.pg1 = A_0 .. A_{count-1}, C_0 .. C_{count-1}, then room for the count + 3 first arguments of the loops.
+    const bool dev = pairing_on_device(ctx->policy, count + 3);
+    hipStream_t st = ctx->stream;
+    const double t0 = now_ms();
+    if (dev) {
+      std::vector<Affine<Fq>> ac(2 * count);
+      std::vector<Affine<Fq2>> bs(count);
+      for (uint64_t j = 0; j < count; j++) {
+        ac[j] = g1_of(proofs[j].a);
+        ac[count + j] = g1_of(proofs[j].c);
+        bs[j] = g2_of(proofs[j].b);
+      }
+      g.pg1.ensure((3 * count + 3) * sizeof(Affine<Fq>));
+      g.pg2.ensure((count + 3) * sizeof(Affine<Fq2>));
+      ARK_CHECK_HIP(hipMemcpyAsync(g.pg1.p, ac.data(), 2 * count * sizeof(Affine<Fq>), hipMemcpyHostToDevice, st));
+      ARK_CHECK_HIP(hipMemcpyAsync(g.pg2.p, bs.data(), count * sizeof(Affine<Fq2>), hipMemcpyHostToDevice, st));
+      if (on_curve_dev(g, g.pg1.p, 2 * count, g.pg2.p, count, st) != 0) return false;
+    } else
     for (uint64_t j = 0; j < count; j++) {
       const Affine<Fq> a = g1_of(proofs[j].a), c = g1_of(proofs[j].c);
       const Affine<Fq2> b = g2_of(proofs[j].b);
@@ -524,6 +689,7 @@ struct Api {
       if (!c.is_inf() && !(Fq::sqr_ni(c.y) == W::curve_rhs(c.x))) return false;
       if (!b.is_inf() && !(Fq2::sqr_ni(b.y) == W::curve_rhs(b.x))) return false;
     }
+    const double t1 = now_ms();
     std::vector<Fr> r(count), coef(ell, Fr::zero());
     for (uint64_t j = 0; j < count; j++) {
       if (rho) {
@@ -560,6 +726,20 @@ struct Api {
     unsigned nt = std::thread::hardware_concurrency();
     if (nt == 0) nt = 4;
     if (nt > 16) nt = 16;
+    const double t2 = now_ms();
+    if (dev) {
+      // rho_j A_j: one lane per proof, canonical rho_j (sc holds them since the second sum), into the slots after the C_j
+      Affine<Fq>* dP = g.pg1.template as<Affine<Fq>>() + 2 * count;
+      if (rho) {
+        g.psc.ensure(count * sizeof(Fr));
+        ARK_CHECK_HIP(hipMemcpyAsync(g.psc.p, sc.data(), count * sizeof(Fr), hipMemcpyHostToDevice, st));
+        ARK_LAUNCH((g1_scalar_mul_kernel<Curve>), dim3((uint32_t)((count + 127) / 128)), dim3(128), 0, st,
+                   (const Affine<Fq>*)g.pg1.template as<Affine<Fq>>(), (const Fr*)g.psc.template as<Fr>(), count, dP);
+        ARK_CHECK_LAUNCH();
+      } else {
+        ARK_CHECK_HIP(hipMemcpyAsync(dP, g.pg1.p, count * sizeof(Affine<Fq>), hipMemcpyDeviceToDevice, st));
+      }
+    } else
     {
       // rho_j A_j on host threads (one 255-bit scalar multiplication each)
       std::vector<std::thread> th;
@@ -583,6 +763,25 @@ struct Api {
     Qs[count + 1] = g2_of(vk->gamma_g2);
     Ps[count + 2] = csum.is_inf() ? csum : Affine<Fq>::neg(csum);
     Qs[count + 2] = g2_of(vk->delta_g2);
+    if (dev) {
+      ARK_CHECK_HIP(hipMemcpyAsync(g.pg1.template as<Affine<Fq>>() + 3 * count, Ps.data() + count, 3 * sizeof(Affine<Fq>),
+                                   hipMemcpyHostToDevice, st));
+      ARK_CHECK_HIP(hipMemcpyAsync(g.pg2.template as<Affine<Fq2>>() + count, Qs.data() + count, 3 * sizeof(Affine<Fq2>),
+                                   hipMemcpyHostToDevice, st));
+      ARK_CHECK_HIP(hipStreamSynchronize(st));
+      const double t3 = now_ms();
+      const Gt f = multi_miller_dev(g, g.pg1.template as<Affine<Fq>>() + 2 * count, g.pg2.template as<Affine<Fq2>>(), count + 3, st);
+      const double t4 = now_ms();
+      const bool good = final_exp(f) == Gt::one();
+      trace_pairing(ctx, "verify_batch", 1, count + 3, t1 - t0, t3 - t2, t4 - t3, now_ms() - t4);
+      return good;
+    }
+    if (ctx->policy.trace_host) {
+      // the same phases for the host route (timing only: the verdict below is PairingHost::product_is_one's)
+      const double t3 = now_ms();
+      fprintf(stderr, "[ark355] verify_batch route=host pairs=%llu check_ms=%.3f scalar_mul_ms=%.3f\n",
+              (unsigned long long)(count + 3), t1 - t0, t3 - t2);
+    }
     return PH::product_is_one(Ps, Qs, nt);
   }
 

@@ -776,6 +776,16 @@ int32_t ark355_verify_batch(ark355_ctx* ctx, int32_t curve, const ark355_vk_desc
   });
 }
 
+int32_t ark355_multi_pairing(ark355_ctx* ctx, int32_t curve, const uint8_t* g1, const uint8_t* g2, uint64_t n, uint8_t* out_gt,
+                             int32_t* is_one) {
+  if (!ctx || (n && (!g1 || !g2))) return ARK355_EINVAL;
+  if (is_one) *is_one = 0;
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(curve, A::multi_pairing(ctx, ex.generic, g1, g2, n, out_gt, is_one));
+  });
+}
+
 int32_t ark355_setup_scalars(int32_t curve, uint64_t n, uint64_t ell, uint64_t w, const uint64_t* const row_ptr[3],
                              const uint32_t* const col[3], const uint8_t* const coeff[3], const uint8_t* trapdoor,
                              uint8_t* out_u, uint8_t* out_v, uint8_t* out_w, uint8_t* out_l, uint8_t* out_gamma_abc,

@@ -2,10 +2,12 @@
 // `SNARK::verify_with_processed_vk`, /root/reference/snark/src/lib.rs:76-80; upstream ark-groth16 verifier.rs).
 //
 // What runs where: the random linear combination of a batch is group arithmetic in G1 -- the two multi-scalar sums go
-// through the device MSM like every other MSM of this library -- while the k + 3 Miller loops and the ONE final
-// exponentiation of a batch of k proofs are sequential tower-field arithmetic with no width to fill a GPU; they run on host
-// threads in the library's own host-compiled field code.  Verification is not on the hot path of the prover; this exists
-// so that a host that proves on the device can also check what it produced without leaving the C ABI.
+// through the device MSM like every other MSM of this library.  ONE Miller loop is a sequential chain of tower-field
+// arithmetic with no width to fill a GPU, and that is what this file computes, on host threads in the library's own
+// host-compiled field code; a BATCH of k + 3 loops is k + 3 independent chains, which pairing_impl.cuh runs one lane each
+// on the device from PAIRING_DEVICE_MIN pairs on (policy.h; ark355_verify_batch and ark355_multi_pairing).  The ONE final
+// exponentiation of a call stays here on both routes.  This file is also the checker the device route is pinned to: both
+// routes give the same GT byte for byte (tests/pairing_cases.py, routes_agree_case).
 //
 // Construction (textbook, kept simple): F_q2 = F_q[u]/(u^2 + 1), F_q6 = F_q2[v]/(v^3 - xi), F_q12 = F_q6[w]/(w^2 - v)
 // with xi = 1 + u (BLS12-381, M-type twist) or 9 + u (BN254, D-type twist); affine Miller loop over the twist with the

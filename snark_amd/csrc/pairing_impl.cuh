@@ -1,0 +1,375 @@
+// Device pairing: multi-Miller loop, elementwise G1 scalar multiplication and the on-curve check of batch verification.
+//
+// One Miller loop is a sequential chain of tower-field arithmetic; a BATCH of n loops is n independent chains, one lane each.
+// The work is split the way ark-ec splits it (G2Prepared / multi_miller_loop):
+//
+//   pass A  pairing_lines_kernel       one lane per pair walks T = [k]Q on the twist in homogeneous projective coordinates
+//                                      (no inversion: doubling and mixed addition of Costello-Lange-Naehrig as ark-ec has
+//                                      them), evaluates each line at P and writes its three F_q2 coefficients to HBM.
+//   pass B  pairing_accumulate_kernel  one lane per pair squares f and multiplies it by the sparse lines.  f does not fit a
+//                                      lane's registers (144 dwords for BLS12-381), so every lane keeps f and one product
+//                                      buffer in LDS (2 x 576 B x 64 lanes = 72 KiB per workgroup, two workgroups per CU) and
+//                                      the register-level unit is ONE F_q2 product whose operands are read from LDS by a
+//                                      run-time coefficient index: the loops over coefficients stay rolled, so the kernel
+//                                      holds a handful of inlined F_q2 multiplications instead of ~40 and nothing spills.
+//                                      The workgroup then multiplies its 64 values with a product tree in LDS.
+//   pass C  pairing_product_kernel     one workgroup multiplies the per-workgroup partial products (second launch).
+//
+// F_q12 is held as F_q2[w] / (w^6 - xi), six F_q2 coefficients c_k of w^k.  That is the tower of pairing_host.hpp read
+// differently (v = w^2: c0.c0, c1.c0, c0.c1, c1.c1, c0.c2, c1.c2 are the coefficients of w^0 .. w^5), and it makes every
+// product one double loop: out_k = sum_{i+j=k} a_i b_j + xi sum_{i+j=k+6} a_i b_j.  A line has three non-zero coefficients,
+// at w^0, w^2, w^3 (BLS12-381, M-type twist) or w^0, w^1, w^3 (BN254, D-type twist), as in pairing_host.hpp.  The lines
+// differ from the host's affine ones by a factor in F_q2, which the final exponentiation removes.
+//
+// Memory layout: everything a lane touches repeatedly is stored dword-transposed, element [dword][lane], so that the 64
+// lanes of a wave read 64 consecutive dwords (one 256 B line of HBM, 64 distinct banks of LDS).
+#pragma once
+#include "common.h"
+#include "wire_impl.cuh"
+
+namespace ark355 {
+
+constexpr uint32_t PAIR_LANES = 64;          // lanes per workgroup of the Miller-loop kernels (one wave)
+
+template <class Curve>
+struct PairingDev {
+  using Fq = typename Curve::Fq;
+  using Fq2 = typename Curve::Fq2;
+  using Fr = typename Curve::Fr;
+  using W = Wire<Curve>;
+  static constexpr bool BN = Curve::ID == ARK355_BN254;
+  static constexpr uint32_t W2 = 2 * Fq::N;              // dwords of one F_q2
+  static constexpr uint32_t W12 = 6 * W2;                // dwords of one F_q12
+  // loop count: |x| (BLS12-381) or 6x + 2 = 2^64 + LOOP_LO (BN254); most significant bit first, top bit skipped
+  static constexpr uint64_t LOOP_LO = BN ? 0x9D797039BE763BA8ull : 0xd201000000010000ull;
+  static constexpr int LOOP_TOP = BN ? 64 : 63;
+  // w-powers of the second and third line coefficient (the first sits at w^0)
+  static constexpr int LP1 = BN ? 1 : 2, LP2 = 3;
+
+  struct Consts {
+    Fq two_inv;               // 1/2
+    Fq2 frob_x, frob_y;       // BN254: xi^((q-1)/3), xi^((q-1)/2)
+    uint64_t sqr_mask[2];     // bit s: line s belongs to a doubling step (f is squared before it is multiplied in)
+    uint32_t steps;           // lines per pair
+  };
+
+  // the schedule both passes follow, one bit per line
+  static void schedule(Consts* k) {
+    uint32_t s = 0;
+    k->sqr_mask[0] = k->sqr_mask[1] = 0;
+    for (int i = LOOP_TOP - 1; i >= 0; i--) {
+      k->sqr_mask[s >> 6] |= 1ull << (s & 63);
+      s++;
+      if ((LOOP_LO >> i) & 1ull) s++;
+    }
+    if (BN) s += 2;
+    k->steps = s;
+  }
+
+  ARK_HD static Fq2 mul_fq(const Fq2& a, const Fq& k) { return Fq2{Fq::mul(a.c0, k), Fq::mul(a.c1, k)}; }
+  ARK_HD static Fq2 mul_xi(const Fq2& a) {
+    if (BN) {
+      const Fq a0_8 = Fq::dbl(Fq::dbl(Fq::dbl(a.c0))), a1_8 = Fq::dbl(Fq::dbl(Fq::dbl(a.c1)));
+      return Fq2{Fq::sub(Fq::add(a0_8, a.c0), a.c1), Fq::add(Fq::add(a1_8, a.c1), a.c0)};
+    }
+    return Fq2{Fq::sub(a.c0, a.c1), Fq::add(a.c0, a.c1)};
+  }
+
+  // ---- dword-transposed F_q2: dword d of the element at p[d * st] ---------------------------------------------------
+  ARK_D static Fq2 ld(const uint32_t* p, size_t st) {
+    Fq2 r;
+#pragma unroll
+    for (int i = 0; i < Fq::N; i++) {
+      r.c0.l[i] = p[(size_t)i * st];
+      r.c1.l[i] = p[(size_t)(Fq::N + i) * st];
+    }
+    return r;
+  }
+  ARK_D static void st(uint32_t* p, size_t stride, const Fq2& v) {
+#pragma unroll
+    for (int i = 0; i < Fq::N; i++) {
+      p[(size_t)i * stride] = v.c0.l[i];
+      p[(size_t)(Fq::N + i) * stride] = v.c1.l[i];
+    }
+  }
+
+  // ---- F_q12 in a lane's LDS column: coefficient k at f + k * W2 * PAIR_LANES, dword stride PAIR_LANES ----------------
+  static constexpr uint32_t CK = W2 * PAIR_LANES;
+  ARK_D static Fq2 ldc(const uint32_t* f, int k) { return ld(f + (uint32_t)k * CK, PAIR_LANES); }
+  ARK_D static void stc(uint32_t* f, int k, const Fq2& v) { st(f + (uint32_t)k * CK, PAIR_LANES, v); }
+  ARK_D static void set_one(uint32_t* f) {
+    stc(f, 0, Fq2::one());
+    for (int k = 1; k < 6; k++) stc(f, k, Fq2::zero());
+  }
+  ARK_D static void copy12(uint32_t* o, const uint32_t* a) {
+    for (uint32_t d = 0; d < W12; d++) o[d * PAIR_LANES] = a[d * PAIR_LANES];
+  }
+
+  // o = a^2 (o and a distinct): 21 products, one multiplication site
+  ARK_D static void sqr12(uint32_t* o, const uint32_t* a) {
+#pragma unroll 1
+    for (int k = 0; k < 6; k++) {
+      Fq2 lo = Fq2::zero(), hi = Fq2::zero();
+#pragma unroll 1
+      for (int i = 0; i < 6; i++) {
+        int j = k - i;
+        const bool wrap = j < 0;
+        if (wrap) j += 6;
+        if (i > j) continue;
+        Fq2 p = Fq2::mul(ldc(a, i), ldc(a, j));
+        if (i < j) p = Fq2::dbl(p);
+        if (wrap) hi = Fq2::add(hi, p);
+        else lo = Fq2::add(lo, p);
+      }
+      stc(o, k, Fq2::add(lo, mul_xi(hi)));
+    }
+  }
+
+  // o = a * b (o distinct from both); b is any dword-transposed F_q12: coefficient stride cb, dword stride sb
+  ARK_D static void mul12(uint32_t* o, const uint32_t* a, const uint32_t* b, size_t cb, size_t sb) {
+#pragma unroll 1
+    for (int k = 0; k < 6; k++) {
+      Fq2 lo = Fq2::zero(), hi = Fq2::zero();
+#pragma unroll 1
+      for (int i = 0; i < 6; i++) {
+        int j = k - i;
+        const bool wrap = j < 0;
+        if (wrap) j += 6;
+        const Fq2 p = Fq2::mul(ldc(a, i), ld(b + (size_t)j * cb, sb));
+        if (wrap) hi = Fq2::add(hi, p);
+        else lo = Fq2::add(lo, p);
+      }
+      stc(o, k, Fq2::add(lo, mul_xi(hi)));
+    }
+  }
+
+  // o = a * (l0 + l1 w^LP1 + l2 w^LP2): 18 products
+  ARK_D static void mul12_sparse(uint32_t* o, const uint32_t* a, const Fq2& l0, const Fq2& l1, const Fq2& l2) {
+#pragma unroll 1
+    for (int k = 0; k < 6; k++) {
+      Fq2 lo = Fq2::mul(l0, ldc(a, k)), hi = Fq2::zero();
+      {
+        int j = k - LP1;
+        const bool wrap = j < 0;
+        if (wrap) j += 6;
+        const Fq2 p = Fq2::mul(l1, ldc(a, j));
+        if (wrap) hi = p;
+        else lo = Fq2::add(lo, p);
+      }
+      {
+        int j = k - LP2;
+        const bool wrap = j < 0;
+        if (wrap) j += 6;
+        const Fq2 p = Fq2::mul(l2, ldc(a, j));
+        if (wrap) hi = Fq2::add(hi, p);
+        else lo = Fq2::add(lo, p);
+      }
+      stc(o, k, Fq2::add(lo, mul_xi(hi)));
+    }
+  }
+
+  // product of the workgroup's 64 values (each lane's at f, scratch at g) -> lane 0's f
+  ARK_D static void block_product(uint32_t* f, uint32_t* g, uint32_t lane) {
+#pragma unroll 1
+    for (uint32_t s = PAIR_LANES / 2; s >= 1; s >>= 1) {
+      __syncthreads();
+      if (lane < s) mul12(g, f, f + s, CK, PAIR_LANES);
+      __syncthreads();
+      if (lane < s) copy12(f, g);
+    }
+  }
+
+  // ---- pass A: the lines ---------------------------------------------------------------------------------------------
+  struct Proj {
+    Fq2 x, y, z;
+  };
+  // line s of this lane: three F_q2, coefficient c at out + (3 s + c) * W2 * stride
+  ARK_D static void put_line(uint32_t* out, size_t stride, uint32_t s, const Fq2& l0, const Fq2& l1, const Fq2& l2) {
+    uint32_t* p = out + (size_t)(3 * s) * W2 * stride;
+    st(p, stride, l0);
+    st(p + (size_t)W2 * stride, stride, l1);
+    st(p + (size_t)2 * W2 * stride, stride, l2);
+  }
+  // T <- 2T, tangent at T evaluated at P
+  ARK_D static void dbl_step(Proj& T, const Fq& xp, const Fq& yp, const Fq& two_inv, uint32_t* out, size_t stride, uint32_t s) {
+    const Fq2 a = mul_fq(Fq2::mul(T.x, T.y), two_inv);
+    const Fq2 b = Fq2::sqr(T.y);
+    const Fq2 c = Fq2::sqr(T.z);
+    const Fq2 e = Fq2::mul(W::g2_b(), Fq2::mul3(c));
+    const Fq2 f = Fq2::mul3(e);
+    const Fq2 g = mul_fq(Fq2::add(b, f), two_inv);
+    const Fq2 h = Fq2::sub(Fq2::sqr(Fq2::add(T.y, T.z)), Fq2::add(b, c));
+    const Fq2 i = Fq2::sub(e, b);
+    const Fq2 j3 = mul_fq(Fq2::mul3(Fq2::sqr(T.x)), xp);
+    const Fq2 hy = Fq2::neg(mul_fq(h, yp));
+    if (BN) put_line(out, stride, s, hy, j3, i);
+    else put_line(out, stride, s, i, j3, hy);
+    const Fq2 e2 = Fq2::sqr(e);
+    T.x = Fq2::mul(a, Fq2::sub(b, f));
+    T.y = Fq2::sub(Fq2::sqr(g), Fq2::mul3(e2));
+    T.z = Fq2::mul(b, h);
+  }
+  // T <- T + Q (Q affine), line through T and Q evaluated at P
+  ARK_D static void add_step(Proj& T, const Fq2& qx, const Fq2& qy, const Fq& xp, const Fq& yp, uint32_t* out, size_t stride,
+                             uint32_t s) {
+    const Fq2 theta = Fq2::sub(T.y, Fq2::mul(qy, T.z));
+    const Fq2 lambda = Fq2::sub(T.x, Fq2::mul(qx, T.z));
+    {
+      const Fq2 j = Fq2::sub(Fq2::mul(theta, qx), Fq2::mul(lambda, qy));
+      const Fq2 tx = Fq2::neg(mul_fq(theta, xp));
+      const Fq2 ly = mul_fq(lambda, yp);
+      if (BN) put_line(out, stride, s, ly, tx, j);
+      else put_line(out, stride, s, j, tx, ly);
+    }
+    const Fq2 c = Fq2::sqr(theta);
+    const Fq2 d = Fq2::sqr(lambda);
+    const Fq2 e = Fq2::mul(lambda, d);
+    const Fq2 f = Fq2::mul(T.z, c);
+    const Fq2 g = Fq2::mul(T.x, d);
+    const Fq2 h = Fq2::sub(Fq2::add(e, f), Fq2::dbl(g));
+    T.x = Fq2::mul(lambda, h);
+    T.y = Fq2::sub(Fq2::mul(theta, Fq2::sub(g, h)), Fq2::mul(e, T.y));
+    T.z = Fq2::mul(T.z, e);
+  }
+};
+
+// A pair with either point at infinity contributes 1: it writes no lines and pass B leaves its f at one.
+template <class Curve>
+__global__ void __launch_bounds__(PAIR_LANES)
+pairing_lines_kernel(const Affine<typename Curve::Fq>* __restrict__ g1, const Affine<typename Curve::Fq2>* __restrict__ g2,
+                     uint32_t n, uint32_t stride, typename PairingDev<Curve>::Consts k, uint32_t* __restrict__ lines) {
+  using D = PairingDev<Curve>;
+  using Fq = typename Curve::Fq;
+  using Fq2 = typename Curve::Fq2;
+  const uint32_t i = blockIdx.x * PAIR_LANES + threadIdx.x;
+  if (i >= n) return;
+  const Affine<Fq> P = g1[i];
+  const Affine<Fq2> Q = g2[i];
+  if (P.is_inf() || Q.is_inf()) return;
+  typename D::Proj T{Q.x, Q.y, Fq2::one()};
+  uint32_t* out = lines + i;
+  uint32_t s = 0;
+#pragma unroll 1
+  for (int b = D::LOOP_TOP - 1; b >= 0; b--) {
+    D::dbl_step(T, P.x, P.y, k.two_inv, out, stride, s++);
+    if ((D::LOOP_LO >> b) & 1ull) D::add_step(T, Q.x, Q.y, P.x, P.y, out, stride, s++);
+  }
+  if (D::BN) {
+    // Q1 = pi(Q), Q2 = -pi^2(Q)
+    Fq2 x = Q.x, y = Q.y;
+#pragma unroll 1
+    for (int r = 0; r < 2; r++) {
+      x = Fq2::mul(Fq2{x.c0, Fq::neg(x.c1)}, k.frob_x);
+      y = Fq2::mul(Fq2{y.c0, Fq::neg(y.c1)}, k.frob_y);
+      D::add_step(T, x, r ? Fq2::neg(y) : y, P.x, P.y, out, stride, s++);
+    }
+  }
+}
+
+// f_i = prod over the lines of pair i (squaring before every doubling line); partial[block] = prod of the block's f_i,
+// W12 plain dwords each.
+template <class Curve>
+__global__ void __launch_bounds__(PAIR_LANES)
+pairing_accumulate_kernel(const Affine<typename Curve::Fq>* __restrict__ g1, const Affine<typename Curve::Fq2>* __restrict__ g2,
+                          uint32_t n, uint32_t stride, typename PairingDev<Curve>::Consts k,
+                          const uint32_t* __restrict__ lines, uint32_t* __restrict__ partial) {
+  using D = PairingDev<Curve>;
+  __shared__ uint32_t lds[2 * D::W12 * PAIR_LANES];
+  const uint32_t lane = threadIdx.x, i = blockIdx.x * PAIR_LANES + lane;
+  uint32_t* f = lds + lane;
+  uint32_t* g = lds + D::W12 * PAIR_LANES + lane;
+  D::set_one(f);
+  bool live = i < n;
+  if (live) live = !g1[i].is_inf() && !g2[i].is_inf();
+  if (live) {
+    const uint32_t* in = lines + i;
+#pragma unroll 1
+    for (uint32_t s = 0; s < k.steps; s++) {
+      if ((k.sqr_mask[s >> 6] >> (s & 63)) & 1ull) {
+        D::sqr12(g, f);
+        uint32_t* t = f;
+        f = g;
+        g = t;
+      }
+      const uint32_t* p = in + (size_t)(3 * s) * D::W2 * stride;
+      const auto l0 = D::ld(p, stride), l1 = D::ld(p + (size_t)D::W2 * stride, stride),
+                 l2 = D::ld(p + (size_t)2 * D::W2 * stride, stride);
+      D::mul12_sparse(g, f, l0, l1, l2);
+      uint32_t* t = f;
+      f = g;
+      g = t;
+    }
+    if (f != lds + lane) {
+      D::copy12(g, f);
+      f = lds + lane;
+      g = lds + D::W12 * PAIR_LANES + lane;
+    }
+  }
+  D::block_product(f, g, lane);
+  if (lane == 0)
+    for (uint32_t d = 0; d < D::W12; d++) partial[(size_t)blockIdx.x * D::W12 + d] = f[d * PAIR_LANES];
+}
+
+// out (W12 plain dwords) = prod of `count` partial products; one workgroup
+template <class Curve>
+__global__ void __launch_bounds__(PAIR_LANES)
+pairing_product_kernel(const uint32_t* __restrict__ partial, uint32_t count, uint32_t* __restrict__ out) {
+  using D = PairingDev<Curve>;
+  __shared__ uint32_t lds[2 * D::W12 * PAIR_LANES];
+  const uint32_t lane = threadIdx.x;
+  uint32_t* f = lds + lane;
+  uint32_t* g = lds + D::W12 * PAIR_LANES + lane;
+  D::set_one(f);
+#pragma unroll 1
+  for (uint32_t j = lane; j < count; j += PAIR_LANES) {
+    D::mul12(g, f, partial + (size_t)j * D::W12, D::W2, 1);
+    D::copy12(f, g);
+  }
+  D::block_product(f, g, lane);
+  if (lane == 0)
+    for (uint32_t d = 0; d < D::W12; d++) out[d] = f[d * PAIR_LANES];
+}
+
+// out[j] = s[j] * P[j] in G1 (canonical scalars), affine: the rho_j A_j of batch verification
+template <class Curve>
+__global__ void __launch_bounds__(128)
+g1_scalar_mul_kernel(const Affine<typename Curve::Fq>* __restrict__ p, const typename Curve::Fr* __restrict__ s, uint64_t n,
+                     Affine<typename Curve::Fq>* __restrict__ out) {
+  using Fq = typename Curve::Fq;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const typename Curve::Fr k = s[i];
+  out[i] = xyzz_to_affine(xyzz_mul_scalar(XYZZ<Fq>::from_affine(p[i]), k.l, Curve::Fr::N));
+}
+
+// y^2 = x^3 + b for n1 points of G1 and n2 points of G2 (infinity passes), one lane per point; *err receives the smallest
+// (index + 1) << 4 | group of a failing point (0 = all good), the word wire_decode_kernel reports with
+template <class Curve>
+__global__ void __launch_bounds__(128)
+on_curve_kernel(const Affine<typename Curve::Fq>* __restrict__ g1, uint64_t n1, const Affine<typename Curve::Fq2>* __restrict__ g2,
+                uint64_t n2, unsigned long long* __restrict__ err) {
+  using W = Wire<Curve>;
+  using Fq = typename Curve::Fq;
+  using Fq2 = typename Curve::Fq2;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n1 + n2) return;
+  bool good;
+  if (i < n1) {
+    const Affine<Fq> a = g1[i];
+    good = a.is_inf() || Fq::sqr_ni(a.y) == W::curve_rhs(a.x);
+  } else {
+    const Affine<Fq2> a = g2[i - n1];
+    good = a.is_inf() || Fq2::sqr_ni(a.y) == W::curve_rhs(a.x);
+  }
+  if (!good) {
+    const unsigned long long code = i < n1 ? (((i + 1) << 4) | 1ull) : (((i - n1 + 1) << 4) | 2ull);
+    unsigned long long cur = *err;
+    while (cur == 0 || code < cur) {
+      const unsigned long long prev = atomicCAS(err, cur, code);
+      if (prev == cur) break;
+      cur = prev;
+    }
+  }
+}
+
+}  // namespace ark355

@@ -329,6 +329,23 @@ class Groth16:
 
     verify_with_processed_vk = verify
 
+    # ---- ark-ec Pairing::multi_pairing ----------------------------------------------------------------------------------
+    def multi_pairing(self, g1_points: Sequence[bytes], g2_points: Sequence[bytes]) -> bytes:
+        """`ark355_multi_pairing`: final_exponentiation(prod_i miller_loop(P_i, Q_i)) over raw affine images -> GT as 12 Fq
+        (Montgomery) in ark-ff's `Fp12` memory order.  Points off their curves raise; subgroup membership is not checked."""
+        if len(g1_points) != len(g2_points):
+            raise ValueError("multi_pairing needs as many G1 as G2 points")
+        try:
+            gt, _ = self.lib.multi_pairing(self.ctx, self.curve.curve_id, b"".join(g1_points), b"".join(g2_points),
+                                           len(g1_points))
+        except Ark355Error as e:
+            raise SynthesisError(str(e)) from e
+        return gt
+
+    def alpha_g1_beta_g2(self, vk: VerifyingKey) -> bytes:
+        """The `alpha_g1_beta_g2` of ark-groth16's `PreparedVerifyingKey`: e(alpha_g1, beta_g2) in GT."""
+        return self.multi_pairing([vk.alpha_g1], [vk.beta_g2])
+
     def verify_batch(self, vk: VerifyingKey, public_inputs, proofs, rng=None) -> bool:
         """`ark355_verify_batch`: all proofs of ONE verifying key checked with a random linear combination (count + 3
         Miller loops, one final exponentiation).  `rng` yields the 128-bit coefficients; required for more than one proof."""

@@ -35,6 +35,12 @@ KERNELS = [
     (r"ntt_pass_kernelINS_2FpINS_11BlsFrParamsEEELi9E", "bls12_381.ntt_pass9"),
     (r"ntt_pass_kernelINS_2FpINS_11BlsFrParamsEEELi6E", "bls12_381.ntt_pass6"),
     (r"ntt_seam_kernelINS_2FpINS_11BlsFrParamsEEELi6E", "bls12_381.ntt_seam6"),
+    (r"pairing_lines_kernelINS_8BlsCurve", "bls12_381.pairing_lines"),
+    (r"pairing_accumulate_kernelINS_8BlsCurve", "bls12_381.pairing_accumulate"),
+    (r"pairing_product_kernelINS_8BlsCurve", "bls12_381.pairing_product"),
+    (r"pairing_lines_kernelINS_7BnCurve", "bn254.pairing_lines"),
+    (r"pairing_accumulate_kernelINS_7BnCurve", "bn254.pairing_accumulate"),
+    (r"pairing_product_kernelINS_7BnCurve", "bn254.pairing_product"),
 ]
 
 

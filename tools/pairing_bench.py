@@ -1,0 +1,182 @@
+#!/usr/bin/env python3
+"""Pairing micro-benchmark: `ark355_multi_pairing` and `ark355_verify_batch`, host route (PAIRING_DEVICE=0: Miller loops,
+curve checks and rho_j A_j on at most 16 host threads) against device route (PAIRING_DEVICE=1: the kernels of
+snark_amd/csrc/pairing_impl.cuh), both curves, 1 .. 16384 pairs.
+
+The four readings of a size (multi_pairing host / device, verify_batch host / device) are interleaved in one process, after
+one warm-up of each; every figure is the median of --reps runs of a synchronous call on the host clock, inputs in pageable
+host memory (uploads included, as a caller sees them).  `verify_batch` of n proofs runs n + 3 Miller loops.  The library
+reports its phases on stderr under policy TRACE_HOST (curve checks, scalar multiplications, Miller loops, final
+exponentiation); the child reads them back, so the final exponentiation -- host code on both routes, once per call -- and
+the rho_j A_j step are listed on their own.  The pairs are a_i G1, b_i G2 with random a_i, b_i; the proofs are eight
+oracle-made proofs of one key, cycled, each with its own 128-bit rho.
+
+The last lines give, per curve and entry, the smallest size from which the device route is at least 10 % faster at that size
+and at every larger one: policy.h's PAIRING_DEVICE_MIN is that figure for the slower curve.
+
+One child process per curve, each under its own `timeout`.  Dev tool; run on an MI355X:
+  python tools/pairing_bench.py [--reps 5] [--out profiles/pairing_bench.txt]
+  rocprofv3 --kernel-trace --stats --output-format csv -- python tools/pairing_bench.py --one-verify 4096
+                                      (one BLS12-381 verify_batch under the default policy, for profiles/pairing_kernel_stats.csv)"""
+import argparse
+import os
+import random
+import re
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+SIZES = [1, 4, 16, 64, 256, 1024, 4096, 16384]
+PHASE = re.compile(r"\[ark355\] (\w+) route=(\w+) pairs=(\d+) check_ms=([\d.]+) scalar_mul_ms=([\d.]+)"
+                   r"(?: miller_ms=([\d.]+) final_exp_ms=([\d.]+))?")
+
+
+def child(curve_name, reps, sizes):
+    import snark_amd
+    import pairing_cases as P
+    from oracle import serialize as Z
+    from oracle.fields import BLS12_381, BN254
+    C = {"bls12_381": BLS12_381, "bn254": BN254}[curve_name]
+    lib = snark_amd.lib()
+    ctx = lib.ctx_create(0)
+    lib.ctx_set_policy(ctx, "TRACE_HOST", 1)
+    sz = lib.sizes(C.curve_id)
+    rnd = random.Random(71)
+    nmax = max(sizes)
+    a = [rnd.randrange(1, C.r) for _ in range(nmax)]
+    b = [rnd.randrange(1, C.r) for _ in range(nmax)]
+    g1, g2 = P.points_with_dlogs(lib, ctx, C, a, b, cross_check=1)
+    vk, proofs, inputs, _, _ = P.oracle_batch(C, 8)
+    rho = [Z.fr_canon(C, rnd.randrange(1, 1 << 128)) for _ in range(nmax)]
+
+    # the library's phase lines arrive on fd 2: point it at a file for the length of the measurement
+    trace = tempfile.TemporaryFile(mode="w+")
+    saved = os.dup(2)
+    os.dup2(trace.fileno(), 2)
+    rows = []
+    try:
+        for n in sizes:
+            p1, p2 = g1[:n * sz["g1"]], g2[:n * sz["g2"]]
+            ps = [proofs[j % 8] for j in range(n)]
+            xs = b"".join(inputs[j % 8] for j in range(n))
+            rh = rho[:n] if n > 1 else None
+
+            def mp(route):
+                lib.ctx_set_policy(ctx, "PAIRING_DEVICE", route)
+                return lib.multi_pairing(ctx, C.curve_id, p1, p2, n)
+
+            def vb(route):
+                lib.ctx_set_policy(ctx, "PAIRING_DEVICE", route)
+                assert lib.verify_batch(ctx, C.curve_id, vk, ps, xs, rh)
+
+            calls = [("mp_host", lambda: mp(0)), ("mp_dev", lambda: mp(1)), ("vb_host", lambda: vb(0)), ("vb_dev", lambda: vb(1))]
+            assert mp(0) == mp(1)                      # warm-up of both routes, and they agree byte for byte
+            vb(0)
+            vb(1)
+            t = {k: [] for k, _ in calls}
+            ph = {k: [] for k, _ in calls}
+            for _ in range(reps):
+                for k, f in calls:
+                    trace.seek(0, os.SEEK_END)
+                    pos = trace.tell()
+                    t0 = time.perf_counter()
+                    f()
+                    t[k].append((time.perf_counter() - t0) * 1e3)
+                    trace.seek(pos)
+                    m = [PHASE.search(l) for l in trace.read().splitlines()]
+                    m = [x for x in m if x]
+                    if m:
+                        ph[k].append([float(v) if v else float("nan") for v in m[-1].groups()[3:]])
+            med = {k: statistics.median(v) for k, v in t.items()}
+
+            def phase(k, i):
+                v = [x[i] for x in ph[k] if x[i] == x[i]]
+                return statistics.median(v) if v else float("nan")
+
+            rows.append((n, med, {k: [phase(k, i) for i in range(4)] for k in t}))
+    finally:
+        os.dup2(saved, 2)
+        os.close(saved)
+    lib.ctx_destroy(ctx)
+    print("curve %s: ms per call, median of %d interleaved runs (host clock); speed-up = host / device" % (C.name, reps))
+    print("%7s | %11s %11s %8s | %11s %11s %8s | %9s | %13s %13s | %11s %11s"
+          % ("pairs", "mp host", "mp device", "speed-up", "vb host", "vb device", "speed-up", "final exp",
+             "rho*A host", "rho*A device", "miller host", "miller dev"))
+    for n, med, ph in rows:
+        print("%7d | %11.3f %11.3f %8.2f | %11.3f %11.3f %8.2f | %9.3f | %13.3f %13.3f | %11.3f %11.3f"
+              % (n, med["mp_host"], med["mp_dev"], med["mp_host"] / med["mp_dev"], med["vb_host"], med["vb_dev"],
+                 med["vb_host"] / med["vb_dev"], ph["mp_dev"][3], ph["vb_host"][1], ph["vb_dev"][1], ph["mp_host"][2], ph["mp_dev"][2]))
+    for entry, h, d in (("multi_pairing", "mp_host", "mp_dev"), ("verify_batch", "vb_host", "vb_dev")):
+        cross = None
+        for i in range(len(rows) - 1, -1, -1):
+            if rows[i][1][d] * 1.10 <= rows[i][1][h]:
+                cross = rows[i][0]
+            else:
+                break
+        print("crossover %s %s: device route at least 10 %% faster from %s pairs on" % (C.name, entry, cross))
+    print("", flush=True)
+
+
+def one_verify(count):
+    """one ark355_verify_batch of `count` BLS12-381 proofs under the default policy, in this process (for a kernel trace)"""
+    import snark_amd
+    import pairing_cases as P
+    from oracle import serialize as Z
+    from oracle.fields import BLS12_381 as C
+    lib = snark_amd.lib()
+    ctx = lib.ctx_create(0)
+    vk, proofs, inputs, _, _ = P.oracle_batch(C, 8)
+    rnd = random.Random(73)
+    ps = [proofs[j % 8] for j in range(count)]
+    xs = b"".join(inputs[j % 8] for j in range(count))
+    rho = [Z.fr_canon(C, rnd.randrange(1, 1 << 128)) for _ in range(count)]
+    ok = lib.verify_batch(ctx, C.curve_id, vk, ps, xs, rho if count > 1 else None)
+    lib.ctx_destroy(ctx)
+    print("verify_batch of %d proofs: %s" % (count, "accepted" if ok else "REJECTED"))
+    return 0 if ok else 1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sizes", default=",".join(str(s) for s in SIZES))
+    ap.add_argument("--curves", default="bls12_381,bn254")
+    ap.add_argument("--timeout", type=int, default=420, help="seconds per curve")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", default=None)
+    ap.add_argument("--one-verify", type=int, default=0, metavar="COUNT")
+    a = ap.parse_args()
+    if a.one_verify:
+        return one_verify(a.one_verify)
+    sizes = [int(s) for s in a.sizes.split(",")]
+    if a.child:
+        child(a.child, a.reps, sizes)
+        return 0
+    text = []
+    rc = 0
+    for curve in a.curves.split(","):
+        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", curve,
+               "--reps", str(a.reps), "--sizes", a.sizes]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        print(r.stdout, end="", flush=True)
+        text.append(r.stdout)
+        if r.returncode != 0:            # a fault, an abort or the time limit: nothing more is started on the device
+            print("child for %s ended with status %d\n%s" % (curve, r.returncode, r.stderr[-2000:]), flush=True)
+            rc = r.returncode
+            break
+    if a.out and rc == 0:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("pairing_bench: host route (PAIRING_DEVICE=0) against device route (PAIRING_DEVICE=1), one process per curve\n\n")
+            f.write("".join(text))
+    return rc
+
+
+if __name__ == "__main__":
+    sys.exit(main())
