@@ -901,7 +901,6 @@ struct Api {
     };
     const Span alpha = single(1), beta2 = single(2), gamma2 = single(2), delta2 = single(2), gabc = vec(1);
     const Span beta1 = single(1), delta1 = single(1), aq = vec(1), b1q = vec(1), b2q = vec(2), hq = vec(1), lq = vec(1);
-    (void)gamma2;
     ARK_REQUIRE(off == len, ARK355_EINVAL, "trailing bytes in proving key");
     const uint64_t ell = gabc.n, m = aq.n, w = lq.n, N = hq.n + 1;
     ARK_REQUIRE(ell >= 1 && m == ell + w && b1q.n == m && b2q.n == m && (N & (N - 1)) == 0, ARK355_EINVAL,
@@ -913,13 +912,19 @@ struct Api {
       decode_dev(sp.group, d_bytes.as<uint8_t>() + sp.off, sp.n, compressed, validate, out.p, d_err, st, what);
     };
     DevBuf d_a, d_b1, d_b2, d_h, d_l;
+    {
+      // the verifying key's gamma_abc_g1 and gamma_g2 are no part of the resident key: decoded for the verdict only, so
+      // that a bad point anywhere in the stream is refused as upstream's deserialiser refuses it
+      DevBuf d_gabc;
+      decode_vec(gabc, d_gabc, "gamma_abc_g1");
+    }
     decode_vec(aq, d_a, "a_query");
     decode_vec(b1q, d_b1, "b_g1_query");
     decode_vec(b2q, d_b2, "b_g2_query");
     decode_vec(hq, d_h, "h_query");
     decode_vec(lq, d_l, "l_query");
     Affine<Fq> h_alpha, h_beta1, h_delta1;
-    Affine<Fq2> h_beta2, h_delta2;
+    Affine<Fq2> h_beta2, h_gamma2, h_delta2;
     auto dec1 = [&](const Span& sp, Affine<Fq>* o, const char* what) {
       const int e = W::g1_decode(bytes + sp.off, compressed, validate, o);
       if (e != WIRE_OK) throw HipError{ARK355_EINVAL, std::string(what) + ": " + wire_status_name(e)};
@@ -932,6 +937,7 @@ struct Api {
     dec1(beta1, &h_beta1, "beta_g1");
     dec1(delta1, &h_delta1, "delta_g1");
     dec2(beta2, &h_beta2, "beta_g2");
+    dec2(gamma2, &h_gamma2, "gamma_g2");
     dec2(delta2, &h_delta2, "delta_g2");
     ark355_pk_desc d{};
     d.num_instance = ell;

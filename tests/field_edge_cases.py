@@ -9,9 +9,11 @@ from __future__ import annotations
 import itertools
 import random
 
+import pytest
+
 from helpers import fr_vec_from_mont, r1cs_load_from_rows, z_bytes
 from oracle import serialize as Z
-from oracle.curves import g1
+from oracle.curves import g1, g2
 
 
 def montgomery_images(p, nbytes):
@@ -102,8 +104,9 @@ def diagonal_pairs_case(lib, ctx, C, gr1cs=True):
 
 # ---- the base field, through points -------------------------------------------------------------------------------------------
 def pattern_points_g1(C):
-    """Points of y^2 = x^3 + b whose x has a Montgomery image at (or a few steps from) each pattern, both signs of y.  Only for
-    a G1 of cofactor 1 (BN254): there every curve point is in the prime-order subgroup, which every MSM path assumes."""
+    """Points of y^2 = x^3 + b whose x has a Montgomery image at (or a few steps from) each pattern, both signs of y.  On
+    BN254 (cofactor 1) they are in the prime-order subgroup; on BLS12-381 they are on the curve and outside it, which
+    pattern_points_group_case takes into account (pattern_points_case does not: it is for BN254)."""
     q = C.q
     G1 = g1(C)
     assert q % 4 == 3, "square roots as a^((q + 1) / 4)"
@@ -167,3 +170,170 @@ def pattern_points_case(lib, ctx, C, to_dev, seed=77):
         wire = b"".join(enc(C, P) for P in pts)
         assert lib.points_encode(ctx, C.curve_id, 1, raws, n, comp) == wire, (C.name, "encode", comp)
         assert lib.points_decode(ctx, C.curve_id, 1, wire, n, comp, True, psz) == raws, (C.name, "decode", comp)
+
+
+def pattern_points_g2(C):
+    """Points of the twist y^2 = x^3 + b' whose x.c0 and x.c1 have Montgomery images at the patterns -- every pattern with itself
+    and with its successor in the list -- x.c0 stepped both ways (image p - 1 has no room upward) until x^3 + b' has a root in
+    Fq2; both signs of y.  All of them are on the twist and outside the r-torsion."""
+    q = C.q
+    G2 = g2(C)
+    F = G2.F
+    rinv = pow(1 << (8 * C.fq_bytes), -1, q)
+    images = montgomery_images(q, C.fq_bytes)
+    pts = []
+    for k, im0 in enumerate(images):
+        for im1 in (im0, images[(k + 1) % len(images)]):
+            for t in itertools.chain.from_iterable((t, -t) for t in range(0, 200)):
+                if not 0 <= im0 + t < q:
+                    continue
+                x = ((im0 + t) * rinv % q, im1 * rinv % q)
+                y = Z.fq2_sqrt(C, F.add(F.mul(F.sqr(x), x), G2.b))
+                if y is not None and y != (0, 0):
+                    break
+            else:
+                raise AssertionError("no point of the twist near images %x, %x" % (im0, im1))
+            for P in ((x, y), (x, F.neg(y))):
+                assert G2.is_on_curve(P)
+                pts.append(P)
+    return pts
+
+
+_PATTERN_POINTS = {}
+
+
+def pattern_points(C, group):
+    """(points, True where they are in the prime-order subgroup), made once per session"""
+    key = (C.name, group)
+    if key not in _PATTERN_POINTS:
+        Gp = g1(C) if group == 1 else g2(C)
+        pts = pattern_points_g1(C) if group == 1 else pattern_points_g2(C)
+        member = [Z.has_order_dividing_r(Gp, P, C.r) for P in pts[::2]]
+        cofactor_one = C.bn_like and group == 1
+        assert all(member) if cofactor_one else not any(member), "outside the r-torsion unless the cofactor is 1"
+        _PATTERN_POINTS[key] = (pts, cofactor_one)
+    return _PATTERN_POINTS[key]
+
+
+def _codec(C, group):
+    if group == 1:
+        return g1(C), Z.g1_raw, Z.g1_from_raw, "g1"
+    return g2(C), Z.g2_raw, Z.g2_from_raw, "g2"
+
+
+def pattern_wire_case(lib, ctx, C, group):
+    """Both wire forms of the pattern points: encode, decode under VALIDATE_CURVE and VALIDATE_NONE against the oracle's codecs;
+    VALIDATE_FULL answers "subgroup" at index 0 (it returns the points where the cofactor is 1)."""
+    pts, in_subgroup = pattern_points(C, group)
+    Gp, raw, from_raw, key = _codec(C, group)
+    n = len(pts)
+    rsz = lib.sizes(C.curve_id)[key]
+    raws = b"".join(raw(C, P) for P in pts)
+    for comp, enc, dec in ((True, Z.g1_compressed if group == 1 else Z.g2_compressed, Z.g1_decode if group == 1 else Z.g2_decode),
+                           (False, Z.g1_uncompressed if group == 1 else Z.g2_uncompressed, Z.g1_decode if group == 1 else Z.g2_decode)):
+        wire = b"".join(enc(C, P) for P in pts)
+        psz = len(wire) // n
+        assert [dec(C, wire[i * psz:(i + 1) * psz], comp, Z.VALIDATE_CURVE) for i in range(n)] == pts       # oracle decoder == oracle encoder
+        assert lib.points_encode(ctx, C.curve_id, group, raws, n, comp) == wire, (C.name, group, "encode", comp)
+        for mode in (Z.VALIDATE_CURVE, Z.VALIDATE_NONE):
+            assert lib.points_decode(ctx, C.curve_id, group, wire, n, comp, mode, rsz) == raws, (C.name, group, "decode", comp, mode)
+        if in_subgroup:
+            assert lib.points_decode(ctx, C.curve_id, group, wire, n, comp, Z.VALIDATE_FULL, rsz) == raws
+        else:
+            with pytest.raises(Exception) as e:
+                lib.points_decode(ctx, C.curve_id, group, wire, n, comp, Z.VALIDATE_FULL, rsz)
+            assert str(e.value).endswith("point[0]: point not in the prime-order subgroup"), str(e.value)
+            for i in (1, n // 2, n - 1):
+                with pytest.raises(Exception) as e:
+                    lib.points_decode(ctx, C.curve_id, group, wire[i * psz:(i + 1) * psz], 1, comp, Z.VALIDATE_FULL, rsz)
+                assert str(e.value).endswith("point[0]: point not in the prime-order subgroup"), str(e.value)
+
+
+def pattern_fixed_base_case(lib, ctx, C, group, seed=79):
+    """ark355_fixed_base_mul with each pattern point as the base: the table is built by doubling and its rows are added, with no
+    step that assumes the order of the base, so scalars below r give k P on the whole curve (expected: the Python group law,
+    whose reduction of k mod r is the identity below r)."""
+    pts, _ = pattern_points(C, group)
+    Gp, raw, from_raw, key = _codec(C, group)
+    rnd = random.Random(seed)
+    psz = lib.sizes(C.curve_id)[key]
+    ks = [1, 2, 3, 255, 256, 1 << 128] + [rnd.randrange(1, C.r) for _ in range(3)]
+    assert all(0 < k < C.r for k in ks)
+    kb = b"".join(Z.fr_canon(C, k) for k in ks)
+    for i in range(0, len(pts), 2):
+        P = pts[i]
+        want = [Gp.mul(P, k) for k in ks]
+        assert want[0] == P
+        for j, (Q, exp) in enumerate(((P, want), (pts[i + 1], [Gp.neg(R) for R in want]))):       # k (-P) = -(k P)
+            out = lib.fixed_base_mul(ctx, C.curve_id, group, raw(C, Q), kb, len(ks), psz)
+            got = [from_raw(C, out[t * psz:(t + 1) * psz]) for t in range(len(ks))]
+            assert got == exp, (C.name, group, "fixed_base_mul, base", i + j)
+
+
+def pattern_pairing_check_case(lib, ctx, policy, C, group):
+    """The on-curve check of ark355_multi_pairing, on the device route and on the host route: pattern points of one group paired
+    with the generator of the other return cleanly (the value of GT is unspecified outside the r-torsion and is not compared);
+    with the low bit of one y flipped the call is refused and names that argument and index."""
+    from snark_amd._binding import EINVAL, Ark355Error
+    pts, _ = pattern_points(C, group)
+    sz = lib.sizes(C.curve_id)
+    n = len(pts)
+    mine = b"".join((Z.g1_raw if group == 1 else Z.g2_raw)(C, P) for P in pts)
+    other = (Z.g2_raw(C, g2(C).gen) if group == 1 else Z.g1_raw(C, g1(C).gen)) * n
+    key = "g1" if group == 1 else "g2"
+    psz = sz[key]
+    for route in (1, 0):
+        policy.setenv("ARK355_PAIRING_DEVICE", route)
+        p, q = (mine, other) if group == 1 else (other, mine)
+        gt, one = lib.multi_pairing(ctx, C.curve_id, p, q, n)
+        assert len(gt) == 12 * sz["fq"] and one in (True, False)
+        for i in (0, n // 2 + 1, n - 1):
+            bad = bytearray(mine)
+            bad[i * psz + psz // 2] ^= 1               # lowest byte of y (G2: of y.c0)
+            p, q = (bytes(bad), other) if group == 1 else (other, bytes(bad))
+            with pytest.raises(Ark355Error) as e:
+                lib.multi_pairing(ctx, C.curve_id, p, q, n)
+            assert e.value.code == EINVAL and "%s[%d]" % (key, i) in str(e.value), (route, str(e.value))
+
+
+def pattern_msm_case(lib, ctx, policy, C, group, to_dev, seed=83):
+    """The pattern points as MSM bases with every scalar at most (r - 1) / 2: the one-shot ark355_msm_g1 / _g2 and resident tables
+    (ark355_bases_load + ark355_msm_dev) with PACK_ROWS 1 and 0.  Signed window digits are an identity of integers and the
+    negation of a scalar happens only above (r - 1) / 2, so the sum is exact on the whole curve, not only in the subgroup;
+    resident tables are the route by which the radix-2^28 base-field arithmetic meets rows made of these operands."""
+    pts, _ = pattern_points(C, group)
+    Gp, raw, from_raw, key = _codec(C, group)
+    rnd = random.Random(seed)
+    n = len(pts)
+    psz = lib.sizes(C.curve_id)[key]
+    raws = b"".join(raw(C, P) for P in pts)
+    half = (C.r - 1) // 2
+    special = [1, half, 2, half - 1, 3, 0, (1 << 32) - 1, 1 << 128, 255, 256]
+    ks = [special[i] if i < len(special) else rnd.randrange(half + 1) for i in range(n)]
+    assert all(0 <= k <= half for k in ks)
+    kb = b"".join(Z.fr_canon(C, k) for k in ks)
+    expect = Gp.msm(pts, ks)
+    assert expect is not None
+    assert from_raw(C, lib.msm(ctx, C.curve_id, group, raws, kb, n, psz)) == expect, (C.name, group, "one-shot msm")
+    ones = b"".join(Z.fr_canon(C, 1) for _ in range(n))
+    assert from_raw(C, lib.msm(ctx, C.curve_id, group, raws, ones, n, psz)) is None       # P and -P are neighbours
+    odd = [1 if i % 2 == 0 else 2 for i in range(n)]
+    assert from_raw(C, lib.msm(ctx, C.curve_id, group, raws, b"".join(Z.fr_canon(C, k) for k in odd), n, psz)) == Gp.msm(pts, odd)
+    for pack in (1, 0):
+        policy.setenv("ARK355_PACK_ROWS", pack)
+        h = lib.bases_load(ctx, C.curve_id, group, raws, n)
+        try:
+            ptr, keep = to_dev(kb)
+            assert from_raw(C, lib.msm_dev(ctx, h, ptr, n, 0, psz)) == expect, (C.name, group, "msm_dev, PACK_ROWS", pack)
+            ptr, keep = to_dev(b"".join(Z.fr_mont(C, k) for k in ks))
+            assert from_raw(C, lib.msm_dev(ctx, h, ptr, n, 1, psz)) == expect, (C.name, group, "msm_dev, Montgomery scalars", pack)
+        finally:
+            lib.dll.ark355_bases_free(h)
+
+
+def pattern_points_group_case(lib, ctx, policy, C, group, to_dev):
+    """The pattern points of one group through every path that is plain group law."""
+    pattern_wire_case(lib, ctx, C, group)
+    pattern_fixed_base_case(lib, ctx, C, group)
+    pattern_pairing_check_case(lib, ctx, policy, C, group)
+    pattern_msm_case(lib, ctx, policy, C, group, to_dev)

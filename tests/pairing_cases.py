@@ -13,6 +13,7 @@ from helpers import g1_vec_raw, z_bytes
 from oracle import groth16 as G, serialize as Z, synthetic as S
 from oracle.curves import g1, g2
 from oracle.pairing import Pairing
+from oracle.serialize import fq2_sqrt
 
 _PAIRING = {}
 _E = {}
@@ -150,36 +151,6 @@ def lines_case(lib, ctx, C, m, seed=47):
     k = (2 * m) // 2 + 1 if m > 1 else 1
     bad[k] = (G1.add(bad[k][0], G1.gen), bad[k][1])
     assert verdict(bad) == O.pairing_product_is_one(bad) == False       # noqa: E712
-
-
-def fq2_sqrt(C, a):
-    """Square root in F_q2 = F_q[u]/(u^2 + 1) for q = 3 mod 4 (both curves), or None."""
-    q = C.q
-    assert q % 4 == 3
-    a0, a1 = a[0] % q, a[1] % q
-
-    def sqrt_fq(v):
-        r = pow(v, (q + 1) // 4, q)
-        return r if r * r % q == v % q else None
-
-    if a1 == 0:
-        r = sqrt_fq(a0)
-        if r is not None:
-            return (r, 0)
-        r = sqrt_fq(-a0 % q)
-        return None if r is None else (0, r)
-    s = sqrt_fq((a0 * a0 + a1 * a1) % q)
-    if s is None:
-        return None
-    inv2 = pow(2, -1, q)
-    for t in ((a0 + s) * inv2 % q, (a0 - s) * inv2 % q):
-        x0 = sqrt_fq(t)
-        if x0 is None or x0 == 0:
-            continue
-        x1 = a1 * pow(2 * x0, -1, q) % q
-        if ((x0 * x0 - x1 * x1) % q, 2 * x0 * x1 % q) == (a0, a1):
-            return (x0, x1)
-    return None
 
 
 def non_subgroup_g2(C, seed=53):

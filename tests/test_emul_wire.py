@@ -42,3 +42,43 @@ def test_c_oracle_key_stream_loads_and_proves(emul_lib, emul_ctx, compressed):
     finally:
         emul_lib.dll.ark355_pk_free(pkh)
         emul_lib.dll.ark355_r1cs_free(rh)
+
+
+# ---- against the oracle's decoder (oracle/serialize.py g1_decode / g2_decode): exact bytes, exact status ---------------------------
+FORMS = [(1, True), (1, False), (2, True), (2, False)]
+FORM_IDS = ["g1-compressed", "g1-uncompressed", "g2-compressed", "g2-uncompressed"]
+
+
+@pytest.mark.parametrize("C", [BLS12_381, BN254], ids=lambda c: c.name)
+def test_constructed_edge_points(emul_lib, emul_ctx, C):
+    W.edge_points_case(emul_lib, emul_ctx, C)
+
+
+@pytest.mark.parametrize("C", [BLS12_381, BN254], ids=lambda c: c.name)
+def test_differential_fuzz(emul_lib, emul_ctx, C):
+    """(half of the GPU tier's count per source: the conditions on the oracle's verdicts hold at either size)"""
+    W.fuzz_case(emul_lib, emul_ctx, C, scale=0.5)
+
+
+@pytest.mark.parametrize("group,comp", FORMS, ids=FORM_IDS)
+@pytest.mark.parametrize("C", [BLS12_381, BN254], ids=lambda c: c.name)
+def test_batch_counts(emul_lib, emul_ctx, C, group, comp):
+    """The counts around one and two wavefronts in every format, without the subgroup test (a 255-bit multiplication per point,
+    which the smaller cases above run); 1000 and 2^16 + 1 points in the one format that costs the emulator neither that nor a
+    square root.  The GPU tier runs all counts in all formats with the subgroup test."""
+    whole = C is BN254 and group == 1 and not comp
+    W.batch_counts_case(emul_lib, emul_ctx, C, group, comp, counts=W.BATCH_COUNTS if whole else W.BATCH_COUNTS[:-2],
+                        modes=(W.VALIDATE_CURVE,))
+
+
+@pytest.mark.parametrize("C,group,comp", [(BLS12_381, 1, True), (BN254, 1, False)], ids=["bls-g1-compressed", "bn-g1-uncompressed"])
+def test_smallest_failing_index_is_reported(emul_lib, emul_ctx, C, group, comp):
+    """One format with a subgroup test and the one group without (the two plans of the case); the GPU tier runs all eight,
+    where lanes really finish out of order."""
+    W.first_failure_case(emul_lib, emul_ctx, C, group, comp)
+
+
+@pytest.mark.parametrize("C,compressed", [(BLS12_381, False), (BLS12_381, True), (BN254, False), (BN254, True)],
+                         ids=["bls-uncompressed", "bls-compressed", "bn-uncompressed", "bn-compressed"])
+def test_key_stream_names_the_damaged_point(emul_lib, emul_ctx, C, compressed):
+    W.key_stream_damage_case(emul_lib, emul_ctx, C, n=12, compressed=compressed)

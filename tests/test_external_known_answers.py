@@ -62,6 +62,40 @@ def test_oracle_wire_format_against_the_zcash_generator_encodings():
     assert Z.g2_compressed(BLS12_381, None) == bytes([0xC0]) + bytes(95)
 
 
+def test_oracle_decoder_against_the_zcash_generator_encodings():
+    """The oracle's DECODER (oracle/serialize.py g1_decode / g2_decode) on the published encodings: the compressed strings
+    above, the uncompressed form (x || y, G2 c1 || c0, big-endian, no flag bit) of the published coordinates, and the two
+    infinity encodings of either form -- in every validation mode."""
+    from oracle import serialize as Z
+    C = BLS12_381
+    g1c = bytes.fromhex("97f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83ff97a1aeffb3af00adb22c6bb")
+    g2c = bytes.fromhex("93e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bbdc7f5049334cf11213945d57e5ac7d055d042b7e"
+                        "024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8")
+    g1u = b"".join(v.to_bytes(48, "big") for v in BLS_G1)
+    g2u = b"".join(v.to_bytes(48, "big") for v in (BLS_G2[0][1], BLS_G2[0][0], BLS_G2[1][1], BLS_G2[1][0]))
+    for mode in (Z.VALIDATE_NONE, Z.VALIDATE_FULL, Z.VALIDATE_CURVE):
+        assert Z.g1_decode(C, g1c, True, mode) == BLS_G1 == tuple(g1(C).gen)
+        assert Z.g1_decode(C, g1u, False, mode) == BLS_G1
+        assert Z.g2_decode(C, g2c, True, mode) == BLS_G2
+        assert Z.g2_decode(C, g2u, False, mode) == BLS_G2
+        assert Z.g1_decode(C, bytes([0xC0]) + bytes(47), True, mode) is None
+        assert Z.g2_decode(C, bytes([0xC0]) + bytes(95), True, mode) is None
+        assert Z.g1_decode(C, bytes([0x40]) + bytes(95), False, mode) is None
+        assert Z.g2_decode(C, bytes([0x40]) + bytes(191), False, mode) is None
+        # the other sign of y is the negated generator
+        flipped = bytes([g1c[0] ^ 0x20]) + g1c[1:]
+        assert Z.g1_decode(C, flipped, True, mode) == (BLS_G1[0], C.q - BLS_G1[1])
+    # alt_bn128: EIP-197's G2 generator and (1, 2), ark-ec SWFlags (little-endian, flags in the last byte)
+    B = BN254
+    assert Z.g1_decode(B, (1).to_bytes(32, "little"), True) == (1, 2)               # 2 < q - 2: the sign bit is clear
+    assert Z.g1_decode(B, (1).to_bytes(31, "little") + b"\x80", True) == (1, B.q - 2)
+    g2u = b"".join(v.to_bytes(32, "little") for v in (BN_G2[0][0], BN_G2[0][1], BN_G2[1][0], BN_G2[1][1]))
+    assert Z.g2_decode(B, g2u, False) == BN_G2
+    assert Z.g2_decode(B, Z.g2_compressed(B, BN_G2), True) == BN_G2
+    for size, dec, comp in ((32, Z.g1_decode, True), (64, Z.g1_decode, False), (64, Z.g2_decode, True), (128, Z.g2_decode, False)):
+        assert dec(B, bytes(size - 1) + b"\x40", comp) is None
+
+
 def test_oracle_group_law_against_published_doublings():
     G = g1(BN254)
     assert G.gen == (1, 2)

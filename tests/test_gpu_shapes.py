@@ -183,6 +183,25 @@ def test_multiplier_patterns_fr(gpu_lib, gpu_ctx, C):
 
 def test_multiplier_patterns_fq_bn254_g1(gpu_lib, gpu_ctx):
     """Fq / Fp28 through points: BN254 G1 (cofactor 1: every curve point is in the subgroup) points whose x is a pattern,
-    through ark355_msm_g1, bases_load + msm_dev, fixed_base_mul and both wire formats.  The other three groups have a
-    cofactor: pattern points there lie outside the prime-order subgroup, which the table paths assume; they are left out."""
+    through ark355_msm_g1, bases_load + msm_dev, fixed_base_mul and both wire formats, with scalars up to r - 1.  The other
+    three groups have a cofactor: their pattern points lie outside the prime-order subgroup and go through the cases below."""
     fe.pattern_points_case(gpu_lib, gpu_ctx, BN254, to_dev)
+
+
+def test_multiplier_patterns_fq_bls12_381_g1(gpu_lib, gpu_ctx, gpu_policy):
+    """The 12-limb multiplier of the production curve (and its radix-2^28 form, through resident tables) on points of
+    BLS12-381 G1 whose x is a pattern: on the curve, outside the prime-order subgroup, so only through paths that are plain
+    group law -- wire codecs, fixed_base_mul, the on-curve check of multi_pairing, MSMs with scalars up to (r - 1) / 2."""
+    fe.pattern_points_group_case(gpu_lib, gpu_ctx, gpu_policy, BLS12_381, 1, to_dev)
+
+
+@pytest.mark.parametrize("C", CURVES, ids=_name)
+def test_multiplier_patterns_fq2_g2(gpu_lib, gpu_ctx, gpu_policy, C):
+    """Fq2 on both curves: twist points whose x.c0 and x.c1 are patterns (each with itself and with its neighbour)"""
+    fe.pattern_points_group_case(gpu_lib, gpu_ctx, gpu_policy, C, 2, to_dev)
+
+
+def test_multiplier_patterns_fq_bn254_g1_on_curve_check(gpu_lib, gpu_ctx, gpu_policy):
+    """The paths test_multiplier_patterns_fq_bn254_g1 does not take: VALIDATE_CURVE / VALIDATE_NONE, the on-curve check of
+    multi_pairing, PACK_ROWS 0"""
+    fe.pattern_points_group_case(gpu_lib, gpu_ctx, gpu_policy, BN254, 1, to_dev)

@@ -89,4 +89,5 @@ def test_key_stream_2p20_malformed(gpu_lib, gpu_ctx):
             bad[off + k * psz + psz - 1] ^= 0x01             # lowest byte of y
         with pytest.raises(Exception) as e:
             lib.pk_load_bytes(ctx, C.curve_id, bytes(bad), compressed=compressed, validate=VALIDATE_CURVE)
-        assert "a_query" in str(e.value) or getattr(e.value, "code", 0) != 0
+        status = "coordinate not reduced" if compressed else "point not on curve"
+        assert e.value.code == -1 and str(e.value).endswith("a_query[%d]: %s" % (k, status)), str(e.value)

@@ -31,6 +31,71 @@ def test_point_encodings_match_oracle_and_round_trip(C, cv):
         assert PS.g2_from_raw(cv, Z.g2_raw(C, P)) == P
 
 
+@pytest.mark.parametrize("C", [BLS12_381, BN254], ids=["bls12_381", "bn254"])
+def test_oracle_decoder_round_trips_oracle_encoder(C):
+    """oracle/serialize.py: decode(encode(P)) == P for both groups, both forms and both signs of y, in every validation mode;
+    the four refusals, each on the smallest change that produces it."""
+    rnd = random.Random(13)
+    for group, Gp, dec, encs in ((1, g1(C), Z.g1_decode, (Z.g1_compressed, Z.g1_uncompressed)),
+                                 (2, g2(C), Z.g2_decode, (Z.g2_compressed, Z.g2_uncompressed))):
+        pts = [None, Gp.gen] + [Gp.mul(Gp.gen, rnd.randrange(1, C.r)) for _ in range(4)]
+        pts += [Gp.neg(P) for P in pts[1:]]
+        signs = set()
+        for P in pts:
+            for comp, enc in ((True, encs[0]), (False, encs[1])):
+                w = enc(C, P)
+                for mode in (Z.VALIDATE_NONE, Z.VALIDATE_FULL, Z.VALIDATE_CURVE):
+                    assert dec(C, w, comp, mode) == P
+            if P is not None:
+                signs.add(Z._fq_gt_neg(P[1], C.q) if group == 1 else Z._fq2_gt_neg(P[1], C.q))
+        assert signs == {True, False}
+        P = pts[2]
+        nb = C.fq_bytes
+        lsb_of_y = (2 * group * nb - 1) if not C.bn_like else (group * nb)      # lowest byte of y (G2: of its first element)
+        bad = bytearray(encs[1](C, P))
+        bad[lsb_of_y] ^= 1
+        for mode, status in ((Z.VALIDATE_FULL, Z.NOT_ON_CURVE), (Z.VALIDATE_CURVE, Z.NOT_ON_CURVE), (Z.VALIDATE_NONE, 0)):
+            assert Z.verdict(C, group, bytes(bad), False, mode)[0] == status
+        both = bytearray(encs[0](C, P))
+        if C.bn_like:
+            both[-1] |= 0xC0
+        else:
+            both[0] |= 0x60
+        q_bytes = C.q.to_bytes(nb, "little" if C.bn_like else "big")
+        big = bytearray(encs[1](C, P))
+        big[nb:2 * nb] = q_bytes                                                # second coordinate == q
+        for mode in (Z.VALIDATE_NONE, Z.VALIDATE_FULL, Z.VALIDATE_CURVE):
+            with pytest.raises(Z.WireError) as e:
+                dec(C, bytes(both), True, mode)
+            assert e.value.status == Z.BAD_FLAGS
+            assert Z.verdict(C, group, bytes(big), False, mode) == (Z.NOT_REDUCED, None)
+
+
+@pytest.mark.parametrize("C", [BLS12_381, BN254], ids=["bls12_381", "bn254"])
+def test_oracle_fq2_sqrt_squares_back(C):
+    """Real, imaginary and general inputs: squares of (r, 0), of (0, r) and of (r, s) have a root that squares back (and is
+    of the same kind for the first two); a non-residue has none."""
+    rnd = random.Random(19)
+    q = C.q
+    F = g2(C).F
+    kinds = {"real": 0, "imaginary": 0, "general": 0, "none": 0}
+    for _ in range(12):
+        r, s = rnd.randrange(1, q), rnd.randrange(1, q)
+        for kind, v in (("real", (r, 0)), ("imaginary", (0, r)), ("general", (r, s))):
+            a = F.sqr(v)
+            y = Z.fq2_sqrt(C, a)
+            assert y is not None and F.eq(F.sqr(y), a), (kind, v)
+            assert y in (tuple(v), tuple(F.neg(v)))
+            if kind != "general":
+                assert a[1] == 0 and (y[1] == 0) == (kind == "real") and (y[0] == 0) == (kind == "imaginary")
+            kinds[kind] += 1
+        t = (rnd.randrange(q), rnd.randrange(1, q))
+        if pow((t[0] * t[0] + t[1] * t[1]) % q, (q - 1) // 2, q) != 1:           # the norm is no square: neither is t
+            assert Z.fq2_sqrt(C, t) is None
+            kinds["none"] += 1
+    assert all(kinds.values()), kinds
+
+
 def test_bls_generator_known_encoding():
     cv = params.BLS12_381
     assert PS.g1_serialize(cv, cv.g1_gen).hex().startswith("97f1d3a73197d794")
