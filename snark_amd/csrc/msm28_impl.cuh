@@ -216,13 +216,29 @@ ARK_HD_NOINLINE typename Fp28<P>::Vec one28_ni() {
 // (tools/code_object_stats.py), and the kernel 11 % slower than round 5's (7.17 against 6.47 ms per 2^20-term launch), whose
 // spills happened to sit in the flush path.  zz and zzz are each read twice and written once per addition, so they are the
 // cheapest state to keep elsewhere, and so are x and y (the new x is dead during the fused Y3 pass, where the pressure peaks;
-// with all four there the listing shows 5 scratch loads + 4 stores per addition): 4 x 4 b128 slots per lane (256 B; 64 KiB for
+// with all four there the listing showed 5 scratch loads + 4 stores per addition, none since the slot addresses are immediates:
+// STRIDE below): 4 x 4 b128 slots per lane (256 B; 64 KiB for
 // 256 lanes, two workgroups per CU), every lane on its own consecutive 16-byte column (hardware counters, run Q: bank-conflict cycles 5.7 % of the
-// LDS-active cycles, LDS waits 0.06 % of the wave cycles): 32 ds_read_b128 +
-// 16 ds_write_b128 per addition of ~7 600 instructions.
+// LDS-active cycles, LDS waits 0.06 % of the wave cycles).  A lane also reads its PARTNER's column of zz, zzz and x (get2: the
+// second factors of the lane-pair products, Pair28): 52 ds_read + 16 ds_write_b128 per addition of ~7 300 instructions.
+
+// the partner lane's copy of a value (lane ^ 1; the lane pairs of the G2 kernels, Pair28 below): N DPP moves
+template <class P>
+ARK_D Fp28<P> pair_xchg28(const Fp28<P>& v) {
+  Fp28<P> r;
+#pragma unroll
+  for (int i = 0; i < Fp28<P>::N; i++) r.l[i] = ark_pair_xchg(v.l[i]);
+  return r;
+}
+// (zz2 / zzz2 / x2: this lane's component and the partner lane's, the form in which a lane-pair product takes its second
+// factor -- lane pairs only)
 template <class P>
 struct ZzRegs {
+  static constexpr bool IN_LDS = false;
   Acc28<P>& a;
+  ARK_D void zz2(Fp28<P>& own, Fp28<P>& par) const { own = a.zz, par = pair_xchg28<P>(a.zz); }
+  ARK_D void zzz2(Fp28<P>& own, Fp28<P>& par) const { own = a.zzz, par = pair_xchg28<P>(a.zzz); }
+  ARK_D void x2(Fp28<P>& own, Fp28<P>& par) const { own = a.x, par = pair_xchg28<P>(a.x); }
   ARK_D Fp28<P> zz() const { return a.zz; }
   ARK_D Fp28<P> zzz() const { return a.zzz; }
   ARK_D Fp28<P> x() const { return a.x; }
@@ -240,10 +256,16 @@ struct ZzLds {
   using F = Fp28<P>;
   static constexpr int N = F::N, QN = (N + 3) / 4;
   static constexpr int VALUES = NV < 2 ? 2 : NV;
+  static constexpr bool IN_LDS = true;
   Acc28<P>& a;        // the coordinates that stay in registers
-  uint4* mine;        // quad q of value s (0: zz, 1: zzz, 2: x, 3: y) sits at mine[(s * QN + q) * stride]
-  uint32_t stride;    // lanes of the workgroup
-  static size_t bytes(uint32_t threads) { return (size_t)VALUES * QN * threads * sizeof(uint4); }
+  uint4* mine;        // quad q of value s (0: zz, 1: zzz, 2: x, 3: y) sits at mine[(s * QN + q) * STRIDE]
+  // Every wave of the workgroup has a block of its own (VALUES * QN rows of 64 columns), so that the row stride is a constant of
+  // the program whatever the workgroup size: all the slots of a lane are reached from ONE address register with immediate
+  // offsets.  (With rows that spanned the workgroup the stride was blockDim.x, every slot kept an address register of its own,
+  // and those registers were what the hot loop still spilled: 5 scratch loads + 4 stores per addition in the listing.)
+  static constexpr uint32_t STRIDE = 64;
+  static size_t bytes(uint32_t threads) { return (size_t)VALUES * QN * ((threads + STRIDE - 1) / STRIDE * STRIDE) * sizeof(uint4); }
+  ARK_D static uint4* column(uint4* lds) { return lds + (threadIdx.x / STRIDE) * (VALUES * QN * STRIDE) + threadIdx.x % STRIDE; }
   // (the barrier keeps the compiler from serving a later read out of registers it loaded earlier: the point of the exercise
   // is that the value is NOT live in between)
   ARK_D F get(int s) const {
@@ -251,7 +273,7 @@ struct ZzLds {
     F r;
 #pragma unroll
     for (int q = 0; q < QN; q++) {
-      const uint4 t = mine[(size_t)(s * QN + q) * stride];
+      const uint4 t = mine[(s * QN + q) * STRIDE];
       r.l[4 * q] = t.x;
       if (4 * q + 1 < N) r.l[4 * q + 1] = t.y;
       if (4 * q + 2 < N) r.l[4 * q + 2] = t.z;
@@ -262,8 +284,34 @@ struct ZzLds {
   ARK_D void put(int s, const F& v) const {
 #pragma unroll
     for (int q = 0; q < QN; q++)
-      mine[(size_t)(s * QN + q) * stride] = make_uint4(v.l[4 * q], 4 * q + 1 < N ? v.l[4 * q + 1] : 0u, 4 * q + 2 < N ? v.l[4 * q + 2] : 0u,
+      mine[(s * QN + q) * STRIDE] = make_uint4(v.l[4 * q], 4 * q + 1 < N ? v.l[4 * q + 1] : 0u, 4 * q + 2 < N ? v.l[4 * q + 2] : 0u,
                                                          4 * q + 3 < N ? v.l[4 * q + 3] : 0u);
+  }
+  // This lane's component and the partner lane's, both straight from LDS: the partner's column is the neighbouring 16 bytes, so
+  // the pair's second copy costs QN more ds_read_b128 and no DPP move.  The two lanes are lanes of one wave: the partner's last
+  // put precedes this read in the wave's instruction stream and its next put follows it (the compiler barriers keep the loads
+  // between the two; ark_pair_sync is the emulator's stand-in for the lockstep).
+  ARK_D void get2(int s, F& own, F& par) const {
+    ark_pair_sync();
+    asm volatile("" ::: "memory");
+    const uint4* theirs = (threadIdx.x & 1u) ? mine - 1 : mine + 1;
+#pragma unroll
+    for (int q = 0; q < QN; q++) {
+      const uint4 t = mine[(s * QN + q) * STRIDE];
+      const uint4 u = theirs[(s * QN + q) * STRIDE];
+      own.l[4 * q] = t.x, par.l[4 * q] = u.x;
+      if (4 * q + 1 < N) own.l[4 * q + 1] = t.y, par.l[4 * q + 1] = u.y;
+      if (4 * q + 2 < N) own.l[4 * q + 2] = t.z, par.l[4 * q + 2] = u.z;
+      if (4 * q + 3 < N) own.l[4 * q + 3] = t.w, par.l[4 * q + 3] = u.w;
+    }
+    asm volatile("" ::: "memory");
+    ark_pair_sync();
+  }
+  ARK_D void zz2(F& own, F& par) const { get2(0, own, par); }
+  ARK_D void zzz2(F& own, F& par) const { get2(1, own, par); }
+  ARK_D void x2(F& own, F& par) const {
+    if constexpr (VALUES > 2) get2(2, own, par);
+    else own = a.x, par = pair_xchg28<P>(a.x);
   }
   ARK_D F zz() const { return get(0); }
   ARK_D F zzz() const { return get(1); }
@@ -649,17 +697,26 @@ table_to28_g2_kernel(const Affine<Fp2<P>>* __restrict__ src, Affine28G2<P, PACKE
   dst[i] = o;
 }
 
-// Fq2 arithmetic of a lane pair on Fp28 components.  KA / BETA describe the PARTNER component of the first
-// operand (value < (KA-1) p, limbs <= BETA (2^28 - 1)): it is negated lazily on the even lane.
+// Fq2 arithmetic of a lane pair on Fp28 components: the even lane computes component 0 of every product, the odd lane component 1,
+//   even: a0 b0 + (-a1) b1          odd: a0 b1 + a1 b0
+// one dual-product pass per lane.  The FIRST factor enters in its "both components" form (Both): c0 is a0 on both lanes (one
+// broadcast, ark_pair_bcast0), s1 is a1 on the odd lane and its lazy negative KA p - a1 on the even lane; KA / BETA describe the
+// operand (value < (KA-1) p, limbs <= BETA (2^28 - 1)).  The SECOND factor enters as this lane's component and the partner's (b, pb).
+// A Both is made once per value and serves every product the value enters (PP: three, PPP: two per mixed addition); a partner
+// copy comes from one exchange (ark_pair_xchg) or, for what lives in LDS, from the partner's column (ZzLds::get2).
 template <class P>
 struct Pair28 {
   using F = Fp28<P>;
   static constexpr int N = F::N;
+  struct Both {
+    F c0, s1;
+  };
   ARK_D static bool odd() { return (threadIdx.x & 1u) != 0; }
-  ARK_D static F xchg(const F& v) {
+  ARK_D static F xchg(const F& v) { return pair_xchg28<P>(v); }
+  ARK_D static F bcast0(const F& v) {
     F r;
 #pragma unroll
-    for (int i = 0; i < N; i++) r.l[i] = ark_pair_xchg(v.l[i]);
+    for (int i = 0; i < N; i++) r.l[i] = ark_pair_bcast0(v.l[i]);
     return r;
   }
   // (both lanes always exchange: a lane that skipped the exchange because its own flag is false would leave its partner
@@ -675,30 +732,40 @@ struct Pair28 {
     for (int i = 0; i < N; i++) r.l[i] = c ? a.l[i] : b.l[i];
     return r;
   }
-  //   even: a0 b0 + (-a1) b1          odd: a0 b1 + a1 b0
+  // The negation happens on the lane that OWNS a1, before the exchange: the exchanged copy then has the select as its only use.
+  template <uint32_t KA, uint32_t BETA>
+  ARK_D static Both both_of(const F& a) {
+    const F pn = xchg(F::template neg<KA, BETA>(a));
+    return Both{bcast0(a), sel(odd(), a, pn)};
+  }
+  // the same where the partner's copy pa = xchg(a) exists already
+  template <uint32_t KA, uint32_t BETA>
+  ARK_D static Both both_with(const F& a, const F& pa) {
+    return Both{bcast0(a), sel(odd(), a, F::template neg<KA, BETA>(pa))};
+  }
+  ARK_D static F mulb(const Both& a, const F& b, const F& pb) { return F::mul2sum(a.c0, b, a.s1, pb); }
+  // a b + c d, four products and one reduction per lane
+  ARK_D static F mul2b(const Both& a, const F& b, const F& pb, const Both& c, const F& d, const F& pd) {
+    return F::mul4sum(a.c0, b, a.s1, pb, c.c0, d, c.s1, pd);
+  }
+  //   even: (a0 + a1)(a0 - a1)        odd: (2 a0) a1            (a normalised, components < (KA-1) p; pa = xchg(a))
+  template <uint32_t KA>
+  ARK_D static F sqr_x(const F& a, const F& pa) {
+    const F u = F::add(bcast0(a), pa);
+    const F d = F::template sub<KA, 1>(a, pa);
+    return F::mul(u, sel(odd(), a, d));
+  }
   template <uint32_t KA, uint32_t BETA>
   ARK_D static F mul(const F& a, const F& b) {
-    const F pa = xchg(a), pb = xchg(b);
-    const F npa = F::template neg<KA, BETA>(pa);
-    const bool o = odd();
-    return F::mul2sum(sel(o, pa, a), b, sel(o, a, npa), pb);
+    return mulb(both_of<KA, BETA>(a), b, xchg(b));
   }
-  //   even: (a0 + a1)(a0 - a1)        odd: (2 a0) a1            (a normalised, components < (KA-1) p)
   template <uint32_t KA>
   ARK_D static F sqr(const F& a) {
-    const F pa = xchg(a);
-    const bool o = odd();
-    const F u = F::add(pa, sel(o, pa, a));
-    const F d = F::template sub<KA, 1>(a, pa);
-    return F::mul(u, sel(o, a, d));
+    return sqr_x<KA>(a, xchg(a));
   }
-  // a b + c d, four products and one reduction per lane
   template <uint32_t KA, uint32_t BA, uint32_t KC, uint32_t BC>
   ARK_D static F mul2(const F& a, const F& b, const F& c, const F& d) {
-    const F pa = xchg(a), pb = xchg(b), pc = xchg(c), pd = xchg(d);
-    const F npa = F::template neg<KA, BA>(pa), npc = F::template neg<KC, BC>(pc);
-    const bool o = odd();
-    return F::mul4sum(sel(o, pa, a), b, sel(o, a, npa), pb, sel(o, pc, c), d, sel(o, c, npc), pd);
+    return mul2b(both_of<KA, BA>(a), b, xchg(b), both_of<KC, BC>(c), d, xchg(d));
   }
 };
 
@@ -749,8 +816,11 @@ ARK_D bool madd28_g2_head(Acc28<P>& acc, const Z& z, bool& empty, const Fp28<P>&
     empty = false;
     return false;
   }
-  const F U2 = L::template mul<2, 1>(px, z.zz());
-  const F S2 = L::template mul<3, 3>(pys, z.zzz());          // pys limbs <= 2^29 - 1
+  F own, par;
+  z.zz2(own, par);
+  const F U2 = L::mulb(L::template both_of<2, 1>(px), own, par);
+  z.zzz2(own, par);
+  const F S2 = L::mulb(L::template both_of<3, 3>(pys), own, par);          // pys limbs <= 2^29 - 1
   Pd = F::norm(F::template sub<8, 1>(U2, z.x()));
   R = F::norm(F::template sub<3, 1>(S2, z.y()));
   if (L::both(Pd.multiple_hint() < 10u)) {
@@ -775,17 +845,36 @@ template <class P, class Z>
 ARK_D void madd28_g2_tail(Acc28<P>& acc, const Z& z, const Fp28<P>& Pd, const Fp28<P>& R) {
   using F = Fp28<P>;
   using L = Pair28<P>;
-  const F PP = L::template sqr<11>(Pd);
-  const F PPP = L::template mul<11, 1>(Pd, PP);
-  const F Q = L::template mul<8, 1>(z.x(), PP);
-  z.set_zz(L::template mul<3, 1>(z.zz(), PP));
-  z.set_zzz(L::template mul<3, 1>(z.zzz(), PPP));
+  // PP and PPP are the FIRST factors of their products (their Both is made once; < 1.05 p, normalised: class <2, 1>);
+  // Pd, X1, ZZ1, ZZZ1, T and 3p - Y1 are the second factors
+  F PPP, own, par;
+  typename L::Both bPP;
+  {
+    const F pPd = L::xchg(Pd);
+    const F PP = L::template sqr_x<11>(Pd, pPd);
+    bPP = L::template both_of<2, 1>(PP);
+    PPP = L::mulb(bPP, Pd, pPd);
+  }
+  const typename L::Both bPPP = L::template both_of<2, 1>(PPP);
+  z.zzz2(own, par);
+  z.set_zzz(L::mulb(bPPP, own, par));
+  z.zz2(own, par);
+  z.set_zz(L::mulb(bPP, own, par));
+  z.x2(own, par);
+  const F Q = L::mulb(bPP, own, par);
   const F W = F::add(PPP, F::add(Q, Q));
-  const F X3 = F::norm(F::add(L::template sqr<6>(R), F::template neg<5, 4>(W)));
+  const F pR = L::xchg(R);
+  const F X3 = F::norm(F::add(L::template sqr_x<6>(R, pR), F::template neg<5, 4>(W)));
   const F T = F::norm(F::template sub<8, 1>(Q, X3));
   const F NY = F::template neg<3, 1>(z.y());
   z.set_x(X3);
-  z.set_y(L::template mul2<6, 1, 4, 3>(R, T, NY, PPP));
+  // Where 14-limb values meet an accumulator that lives wholly in registers (packed BLS12-381 rows) the Both of PPP is not kept
+  // across X3: PPP enters the fused Y3 pass as the second factor and 3p - Y1 as the first, as before (42 instructions more,
+  // a third of the scratch accesses less in the listing).
+  if constexpr (!Z::IN_LDS && F::N > 12)
+    z.set_y(L::mul2b(L::template both_with<6, 1>(R, pR), T, L::xchg(T), L::template both_of<4, 3>(NY), PPP, L::xchg(PPP)));
+  else
+    z.set_y(L::mul2b(L::template both_with<6, 1>(R, pR), T, L::xchg(T), bPPP, NY, L::xchg(NY)));
 }
 template <class P, class Z>
 ARK_D void madd28_g2z(Acc28<P>& acc, const Z& z, bool& empty, const Fp28<P>& px, const Fp28<P>& py, bool negate) {
@@ -807,7 +896,7 @@ ARK_D void madd28_g2(Acc28<P>& acc, bool& empty, const Fp28<P>& px, const Fp28<P
 // Key, row index and this lane's half row are loaded at the top of every iteration: held in registers across the lane-pair
 // addition the half row (28 VGPRs) pushes the hot loop into scratch memory, and loading ahead was measured neutral in
 // round 2 (an addition is 2.2x as long as in G1; waits for memory are a few percent of a wave's cycles).
-// ZLDS: zz / zzz of the accumulator in LDS (ZzLds above; dynamic LDS of ZzLds<P>::bytes(blockDim.x)); the host asks for it
+// ZLDS: the accumulator's coordinates in LDS (ZzLds above; dynamic LDS of ZzLds<P>::bytes(blockDim.x), a block per wave); the host asks for it
 // where the registers do not suffice (g2l28_zz_in_lds: 14-limb fields).
 template <class P>
 constexpr bool g2l28_zz_in_lds() { return ARK_G2L28_LDS_VALUES > 0 && Fp28<P>::N > 12; }
@@ -840,7 +929,7 @@ msm_accumulate_g2l28_kernel(const Affine28G2<P, false>* __restrict__ bases, cons
   acc.zzz = F::zero();
   ARK_DYN_SMEM(uint4, zlds);
   Zt z = [&]() {
-    if constexpr (ZLDS) return ZzLds<P>{acc, zlds + threadIdx.x, blockDim.x};
+    if constexpr (ZLDS) return ZzLds<P>{acc, ZzLds<P>::column(zlds)};
     else return ZzRegs<P>{acc};
   }();
   // always_inline: a closure that is inlined late keeps every captured variable (the accumulator!) in scratch memory
