@@ -1,7 +1,8 @@
 // C++ host-side mirror of `ark_snark::SNARK` (/root/reference/snark/src/lib.rs:22-81) with ONE implementor,
 // Groth16<Curve>, whose `prove` calls the MI355X backend through the C ABI (include/ark355.h).
 //
-//   SNARK::circuit_specific_setup(circuit, rng) -> (ProvingKey, VerifyingKey)     lib.rs:43-46, :87-92
+//   SNARK::circuit_specific_setup(circuit, rng) -> (ProvingKey, VerifyingKey)     lib.rs:43-46, :87-92: ark355_setup
+//       (the generator on the device; the key bytes come back AND stay resident, so the first prove uploads nothing)
 //   SNARK::prove(&pk, circuit, rng) -> Proof                                       lib.rs:50-54
 //   SNARK::verify / verify_with_processed_vk (+ verify_batch)                      lib.rs:59-80: ark355_verify_batch
 //       (random linear combination on the device MSM, Miller loops + final exponentiation on host threads);
@@ -9,8 +10,8 @@
 //
 // `prove` follows the un-vendored ark-groth16 `create_random_proof_with_reduction`: new constraint system,
 // OptimizationGoal::Constraints, generate_constraints, finalize, matrices + assignment, then r and s drawn
-// from the rng IN THAT ORDER, then the device call.  After the first proof of a circuit the CSR matrices are
-// resident and synthesis runs in the witness-only mode of SURVEY.md 3.2
+// from the rng IN THAT ORDER, then the device call.  Once the CSR matrices are resident (after setup here, or after the
+// first proof under a key from elsewhere) synthesis runs in the witness-only mode of SURVEY.md 3.2
 // (SynthesisMode::Prove{construct_matrices: false, generate_lc_assignments: false}).
 #pragma once
 #include <atomic>
@@ -228,7 +229,6 @@ class Groth16 {
     cs.set_mode(g::SynthesisMode::setup());
     circuit.generate_constraints(cs);
     cs.finalize();
-    auto mats = cs.to_matrices().at(g::R1CS_PREDICATE_LABEL);
     const uint64_t n = cs.num_constraints(), ell = cs.num_instance_variables(), w = cs.num_witness_variables(), m = ell + w;
     uint32_t lg = 0;
     while ((1ull << lg) < n + ell) lg++;
@@ -236,64 +236,47 @@ class Groth16 {
       throw ark_relations::SynthesisError(ark_relations::SynthesisErrorKind::PolynomialDegreeTooLarge);
     const uint64_t N = 1ull << lg;
     const Fr tau = rng(), alpha = rng(), beta = rng(), gamma = rng(), delta = rng();
-    // Lagrange coefficients L_k(tau) = Z(tau)/N * w^k / (tau - w^k)
-    Fr root{ark355::fr_from_params_host<typename C::FrP>(&C::FrParams::root)};
-    Fr omega = root;
-    for (uint32_t i = 0; i < (uint32_t)C::FrParams::TWO_ADICITY - lg; i++) omega = omega * omega;
-    Fr zt = tau.pow_u64(N) - Fr::one();
-    std::vector<Fr> wk(N), den(N), pref(N);
-    Fr cur = Fr::one(), acc = Fr::one();
-    for (uint64_t k = 0; k < N; k++) {
-      wk[k] = cur;
-      den[k] = tau - cur;
-      acc = acc * den[k];
-      pref[k] = acc;
-      cur = cur * omega;
-    }
-    Fr inv = acc.inverse();
-    Fr cN = zt * Fr::from_u64(N).inverse();
-    std::vector<Fr> L(N);
-    for (uint64_t k = N; k-- > 0;) {
-      Fr dinv = inv * (k ? pref[k - 1] : Fr::one());
-      inv = inv * den[k];
-      L[k] = cN * wk[k] * dinv;
-    }
-    std::vector<Fr> u(m, Fr::zero()), v(m, Fr::zero()), ww(m, Fr::zero());
-    for (uint64_t i = 0; i < ell; i++) u[i] = L[n + i];
-    std::vector<Fr>* tgt[3] = {&u, &v, &ww};
-    for (int k = 0; k < 3; k++)
-      for (uint64_t i = 0; i < n; i++)
-        for (const auto& cj : mats[k][i]) (*tgt[k])[cj.second] = (*tgt[k])[cj.second] + L[i] * cj.first;
-    const Fr gi = gamma.inverse(), di = delta.inverse();
-    std::vector<Fr> abc(m), gabc(ell), ls(w), hs(N ? N - 1 : 0);
-    for (uint64_t i = 0; i < m; i++) abc[i] = beta * u[i] + alpha * v[i] + ww[i];
-    for (uint64_t i = 0; i < ell; i++) gabc[i] = abc[i] * gi;
-    for (uint64_t i = 0; i < w; i++) ls[i] = abc[ell + i] * di;
-    Fr t = zt * di;
-    for (uint64_t i = 0; i + 1 < N; i++) {
-      hs[i] = t;
-      t = t * tau;
-    }
+    // The generator runs on the device (ark355_setup): Lagrange coefficients at tau, the transposed accumulation over the
+    // resident matrices, the combination and the fixed-base multiplications.  The key bytes come back for the host's
+    // ProvingKey, and the resident handle stays with them, so the first prove uploads nothing.
+    uint8_t td[5 * 32] = {0};
+    const Fr* tds[5] = {&tau, &alpha, &beta, &gamma, &delta};
+    for (int i = 0; i < 5; i++) tds[i]->to_canonical_bytes(td + 32 * i);
     ProvingKey pk;
     pk.ell = ell;
     pk.w = w;
     pk.n = n;
     pk.N = N;
+    auto res = std::make_shared<typename ProvingKey::Resident>();
+    res->r1cs = load_r1cs(cs);
+    pk.vk.alpha_g1.resize(G1);
+    pk.beta_g1.resize(G1);
+    pk.delta_g1.resize(G1);
+    pk.vk.beta_g2.resize(G2);
+    pk.vk.gamma_g2.resize(G2);
+    pk.vk.delta_g2.resize(G2);
+    pk.vk.gamma_abc_g1.resize(ell * G1);
+    pk.a_query.resize(m * G1);
+    pk.b_g1_query.resize(m * G1);
+    pk.b_g2_query.resize(m * G2);
+    pk.h_query.resize((N - 1) * G1);
+    pk.l_query.resize(w * G1);
+    ark355_setup_out out{};
+    out.alpha_g1 = pk.vk.alpha_g1.data();
+    out.beta_g1 = pk.beta_g1.data();
+    out.delta_g1 = pk.delta_g1.data();
+    out.beta_g2 = pk.vk.beta_g2.data();
+    out.gamma_g2 = pk.vk.gamma_g2.data();
+    out.delta_g2 = pk.vk.delta_g2.data();
+    out.gamma_abc_g1 = pk.vk.gamma_abc_g1.data();
+    out.a_query = pk.a_query.data();
+    out.b_g1_query = pk.b_g1_query.data();
+    out.b_g2_query = pk.b_g2_query.data();
+    out.h_query = pk.h_query.data();
+    out.l_query = pk.l_query.data();
     auto g1 = g1_generator(), g2 = g2_generator();
-    auto one1 = fixed_base(1, g1, {alpha, beta, delta});
-    auto one2 = fixed_base(2, g2, {beta, gamma, delta});
-    pk.vk.alpha_g1.assign(one1.begin(), one1.begin() + G1);
-    pk.beta_g1.assign(one1.begin() + G1, one1.begin() + 2 * G1);
-    pk.delta_g1.assign(one1.begin() + 2 * G1, one1.end());
-    pk.vk.beta_g2.assign(one2.begin(), one2.begin() + G2);
-    pk.vk.gamma_g2.assign(one2.begin() + G2, one2.begin() + 2 * G2);
-    pk.vk.delta_g2.assign(one2.begin() + 2 * G2, one2.end());
-    pk.vk.gamma_abc_g1 = fixed_base(1, g1, gabc);
-    pk.a_query = fixed_base(1, g1, u);
-    pk.b_g1_query = fixed_base(1, g1, v);
-    pk.b_g2_query = fixed_base(2, g2, v);
-    pk.h_query = fixed_base(1, g1, hs);
-    pk.l_query = fixed_base(1, g1, ls);
+    be_->check(ark355_setup(be_->ctx(), res->r1cs, g1.data(), g2.data(), td, &out, &res->pk));
+    pk.resident = res;
     return {pk, pk.vk};
   }
 
@@ -558,15 +541,23 @@ class Groth16 {
     return out;
   }
 
-  void load(ProvingKey& pk, const CSRef& cs) const {
+  // the R1CS matrices of a finalized constraint system, resident
+  ark355_r1cs* load_r1cs(const CSRef& cs) const {
     namespace g = ark_relations::gr1cs;
-    auto res = std::make_shared<typename ProvingKey::Resident>();
     Csr csr = to_csr(cs.to_matrices().at(g::R1CS_PREDICATE_LABEL));
     const uint64_t* rp[3] = {csr.row_ptr[0].data(), csr.row_ptr[1].data(), csr.row_ptr[2].data()};
     const uint32_t* cl[3] = {csr.col[0].data(), csr.col[1].data(), csr.col[2].data()};
     const uint8_t* cf[3] = {csr.coeff[0].data(), csr.coeff[1].data(), csr.coeff[2].data()};
+    ark355_r1cs* h = nullptr;
     be_->check(ark355_r1cs_load(be_->ctx(), C::ID, cs.num_constraints(), cs.num_instance_variables(),
-                                cs.num_witness_variables(), rp, cl, cf, &res->r1cs));
+                                cs.num_witness_variables(), rp, cl, cf, &h));
+    return h;
+  }
+
+  // a key that was not generated here (deserialised, or built by another host): matrices and key upload
+  void load(ProvingKey& pk, const CSRef& cs) const {
+    auto res = std::make_shared<typename ProvingKey::Resident>();
+    res->r1cs = load_r1cs(cs);
     ark355_pk_desc d;
     d.num_instance = pk.ell;
     d.num_witness = pk.w;
@@ -653,13 +644,6 @@ class Groth16 {
   }
 
  private:
-  std::vector<uint8_t> fixed_base(int group, const std::vector<uint8_t>& base, const std::vector<Fr>& scalars) const {
-    const size_t psz = group == 1 ? G1 : G2;
-    std::vector<uint8_t> sc(scalars.size() * FR), out(scalars.size() * psz);
-    for (size_t i = 0; i < scalars.size(); i++) scalars[i].to_canonical_bytes(sc.data() + i * FR);
-    be_->check(ark355_fixed_base_mul(be_->ctx(), C::ID, group, base.data(), sc.data(), scalars.size(), out.data()));
-    return out;
-  }
   std::shared_ptr<Backend> be_;
 };
 

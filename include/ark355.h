@@ -441,6 +441,36 @@ int32_t ark355_setup_scalars(int32_t curve, uint64_t n_constraints, uint64_t num
                              const uint8_t* const coeff[3], const uint8_t* trapdoor, uint8_t* out_u, uint8_t* out_v,
                              uint8_t* out_w, uint8_t* out_l, uint8_t* out_gamma_abc, uint8_t* out_h);
 
+/* The Groth16 generator on the device: from the resident matrices and the trapdoor to a resident proving key, without the
+ * key visiting the host unless the caller asks for it.  g1_base / g2_base: raw affine generators (must lie on their curves);
+ * trapdoor as for ark355_setup_scalars, every element below r, gamma and delta non-zero.  The outputs are, byte for byte,
+ * what ark355_setup_scalars + ark355_fixed_base_mul + ark355_pk_load produce from the same inputs (a zero scalar gives the
+ * all-zero point).  `out` (may be NULL): host memory, caller-owned, every pointer optional (NULL = not wanted); *out_pk (may be
+ * NULL) is an ordinary handle under the context's load-time policy, freed with ark355_pk_free.  At least one of the two must
+ * be given.  Work nobody asked for is skipped: without out_pk a query vector whose pointer is NULL is never multiplied out,
+ * and a call that wants only u, v, w runs no curve arithmetic.  ARK355_EINVAL (with a message) for NULL arguments, a trapdoor
+ * element >= r, gamma or delta zero, a base off its curve; ARK355_ENOMEM from the table planner as for ark355_pk_load.
+ * Sharded keys: take the host vectors and call ark355_pk_load_shard.  (Kernels: snark_amd/csrc/setup_impl.cuh.) */
+typedef struct {
+  uint8_t* alpha_g1;      /* 1 G1 each, raw affine */
+  uint8_t* beta_g1;
+  uint8_t* delta_g1;
+  uint8_t* beta_g2;       /* 1 G2 each */
+  uint8_t* gamma_g2;
+  uint8_t* delta_g2;
+  uint8_t* gamma_abc_g1;  /* ell G1 */
+  uint8_t* a_query;       /* (ell+w) G1 */
+  uint8_t* b_g1_query;    /* (ell+w) G1 */
+  uint8_t* b_g2_query;    /* (ell+w) G2 */
+  uint8_t* h_query;       /* (N-1)   G1 */
+  uint8_t* l_query;       /* w       G1 */
+  uint8_t* u;             /* (ell+w) canonical 32-byte scalars each: u_j(tau), v_j(tau), w_j(tau) */
+  uint8_t* v;
+  uint8_t* w;
+} ark355_setup_out;
+int32_t ark355_setup(ark355_ctx* ctx, const ark355_r1cs* r1cs, const uint8_t* g1_base, const uint8_t* g2_base,
+                     const uint8_t* trapdoor, const ark355_setup_out* out, ark355_pk** out_pk);
+
 /* ---- timings of the last prove on this context (ms, measured with HIP events) --------------- */
 typedef struct {
   float total_ms;

@@ -406,3 +406,118 @@ where
     registry().lock().unwrap().insert(fingerprint(pk), res.clone());
     Ok(res)
 }
+
+/// `circuit_specific_setup` on the device (`ark355_setup`): uploads the three R1CS matrices, runs the generator over them and
+/// returns the key as `ark_groth16`'s own type TOGETHER with its resident entry, which is registered under the key's
+/// fingerprint -- the first `prove` of this key uploads nothing.  `trapdoor`: tau, alpha, beta, gamma, delta (canonical,
+/// `marshal::canonical_32`); `g1` / `g2`: the generators the key is built over.
+pub fn generate<E, P1, P2>(
+    matrices: &[Matrix<E::ScalarField>],
+    num_constraints: usize,
+    num_instance: usize,
+    num_witness: usize,
+    trapdoor: &[[u8; 32]; 5],
+    g1: &Affine<P1>,
+    g2: &Affine<P2>,
+) -> Result<(ProvingKey<E>, Arc<Resident>), Mi355xError>
+where
+    E: Mi355xCurve<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: SWCurveConfig,
+    P2: SWCurveConfig,
+    <P1::BaseField as Field>::BasePrimeField: PrimeField,
+    <P2::BaseField as Field>::BasePrimeField: PrimeField,
+{
+    if matrices.len() != 3 {
+        return Err(Mi355xError::InvalidArgument("the R1CS predicate has three matrices".into()));
+    }
+    let (s1, s2) = (2 * E::FQ_BYTES, 4 * E::FQ_BYTES);
+    let m = num_instance + num_witness;
+    let csr: Vec<_> = matrices.iter().map(csr_from_matrix).collect();
+    let td: Vec<u8> = trapdoor.iter().flatten().copied().collect();
+    let (mut b1, mut b2) = (Vec::new(), Vec::new());
+    crate::marshal::push_point(g1, &mut b1);
+    crate::marshal::push_point(g2, &mut b2);
+    let mut single1 = vec![0u8; 3 * s1]; // alpha, beta, delta
+    let mut single2 = vec![0u8; 3 * s2]; // beta, gamma, delta
+    let mut gamma_abc = vec![0u8; num_instance * s1];
+    let (mut a, mut bq1, mut bq2) = (vec![0u8; m * s1], vec![0u8; m * s1], vec![0u8; m * s2]);
+    let mut l = vec![0u8; num_witness * s1];
+    let (res, h) = with_ctx(|ctx| {
+        let row_ptr = [csr[0].row_ptr.as_ptr(), csr[1].row_ptr.as_ptr(), csr[2].row_ptr.as_ptr()];
+        let col = [csr[0].col.as_ptr(), csr[1].col.as_ptr(), csr[2].col.as_ptr()];
+        let coeff =
+            [scalars_image(&csr[0].coeff).as_ptr(), scalars_image(&csr[1].coeff).as_ptr(), scalars_image(&csr[2].coeff).as_ptr()];
+        let mut r1_h = core::ptr::null_mut();
+        check(ctx, unsafe {
+            ffi::ark355_r1cs_load(
+                ctx,
+                E::CURVE_ID,
+                num_constraints as u64,
+                num_instance as u64,
+                num_witness as u64,
+                row_ptr.as_ptr(),
+                col.as_ptr(),
+                coeff.as_ptr(),
+                &mut r1_h,
+            )
+        })?;
+        let domain = unsafe { ffi::ark355_r1cs_domain_size(r1_h) } as usize;
+        let mut h = vec![0u8; (domain - 1) * s1];
+        let out = ffi::ark355_setup_out {
+            alpha_g1: single1.as_mut_ptr(),
+            beta_g1: single1[s1..].as_mut_ptr(),
+            delta_g1: single1[2 * s1..].as_mut_ptr(),
+            beta_g2: single2.as_mut_ptr(),
+            gamma_g2: single2[s2..].as_mut_ptr(),
+            delta_g2: single2[2 * s2..].as_mut_ptr(),
+            gamma_abc_g1: gamma_abc.as_mut_ptr(),
+            a_query: a.as_mut_ptr(),
+            b_g1_query: bq1.as_mut_ptr(),
+            b_g2_query: bq2.as_mut_ptr(),
+            h_query: h.as_mut_ptr(),
+            l_query: l.as_mut_ptr(),
+            u: core::ptr::null_mut(),
+            v: core::ptr::null_mut(),
+            w: core::ptr::null_mut(),
+        };
+        let mut pk_h = core::ptr::null_mut();
+        let rc = unsafe { ffi::ark355_setup(ctx, r1_h, b1.as_ptr(), b2.as_ptr(), td.as_ptr(), &out, &mut pk_h) };
+        if rc != ffi::ARK355_OK {
+            let e = Mi355xError::from_code(rc, last_error(ctx));
+            unsafe { ffi::ark355_r1cs_free(r1_h) };
+            return Err(e);
+        }
+        let res = Resident {
+            pk: pk_h,
+            r1cs: r1_h,
+            num_instance,
+            num_witness,
+            num_constraints,
+            matrices_hash: matrices_hash(matrices, num_constraints),
+            confirmed: Mutex::new(Vec::new()),
+        };
+        Ok((res, h))
+    })?;
+    let pts1 = |b: &[u8]| -> Vec<Affine<P1>> { b.chunks_exact(s1).map(crate::marshal::point_from_image::<P1>).collect() };
+    let pts2 = |b: &[u8]| -> Vec<Affine<P2>> { b.chunks_exact(s2).map(crate::marshal::point_from_image::<P2>).collect() };
+    let (o1, o2) = (pts1(&single1), pts2(&single2));
+    let pk = ProvingKey::<E> {
+        vk: ark_groth16::VerifyingKey::<E> {
+            alpha_g1: o1[0],
+            beta_g2: o2[0],
+            gamma_g2: o2[1],
+            delta_g2: o2[2],
+            gamma_abc_g1: pts1(&gamma_abc),
+        },
+        beta_g1: o1[1],
+        delta_g1: o1[2],
+        a_query: pts1(&a),
+        b_g1_query: pts1(&bq1),
+        b_g2_query: pts2(&bq2),
+        h_query: pts1(&h),
+        l_query: pts1(&l),
+    };
+    let res = Arc::new(res);
+    registry().lock().unwrap().insert(fingerprint(&pk), res.clone());
+    Ok((pk, res))
+}

@@ -131,6 +131,26 @@ pub struct ark355_sched_report {
     pub mean_ms: [f64; 4],
 }
 
+/// Where `ark355_setup` writes what the caller wants of the key: host memory, every pointer optional (null = not wanted).
+#[repr(C)]
+pub struct ark355_setup_out {
+    pub alpha_g1: *mut u8,
+    pub beta_g1: *mut u8,
+    pub delta_g1: *mut u8,
+    pub beta_g2: *mut u8,
+    pub gamma_g2: *mut u8,
+    pub delta_g2: *mut u8,
+    pub gamma_abc_g1: *mut u8,
+    pub a_query: *mut u8,
+    pub b_g1_query: *mut u8,
+    pub b_g2_query: *mut u8,
+    pub h_query: *mut u8,
+    pub l_query: *mut u8,
+    pub u: *mut u8,
+    pub v: *mut u8,
+    pub w: *mut u8,
+}
+
 extern "C" {
     pub fn ark355_ctx_create(device_id: i32, out: *mut *mut ark355_ctx) -> i32;
     pub fn ark355_ctx_destroy(ctx: *mut ark355_ctx);
@@ -416,6 +436,15 @@ extern "C" {
         out_l: *mut u8,
         out_gamma_abc: *mut u8,
         out_h: *mut u8,
+    ) -> i32;
+    pub fn ark355_setup(
+        ctx: *mut ark355_ctx,
+        r1cs: *const ark355_r1cs,
+        g1_base: *const u8,
+        g2_base: *const u8,
+        trapdoor: *const u8,
+        out: *const ark355_setup_out,
+        out_pk: *mut *mut ark355_pk,
     ) -> i32;
 
     pub fn ark355_get_timings(ctx: *const ark355_ctx, out: *mut ark355_timings) -> i32;

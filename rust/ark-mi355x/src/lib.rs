@@ -1,6 +1,6 @@
 //! `ark-mi355x`: the arkworks `SNARK` trait surface (snark/src/lib.rs:22-93) over libark355.so, the MI355X-native
 //! Groth16 prover.  Key, proof and verifying-key types are `ark_groth16`'s own, so bytes are interchangeable with the CPU
-//! prover; setup and verification stay on the CPU implementation, `prove` runs on the GPU.
+//! prover; `circuit_specific_setup` and `prove` run on the GPU, verification stays on the CPU implementation.
 //!
 //! UNCOMPILED in the repository's own build environment (it has no Rust toolchain); the C ABI underneath is exercised
 //! there through the C++ and Python mirrors.  `tests/parity.rs` is the test to run on a machine with both toolchains.
@@ -445,20 +445,65 @@ where
     type ProcessedVerifyingKey = PreparedVerifyingKey<E>; // :36
     type Error = Mi355xError; // :39 -- SynthesisError plus distinct device-side variants
 
-    /// snark/src/lib.rs:43-46.  The generator is the CPU implementation (its five fixed-base loops can be handed to
-    /// `ark355_fixed_base_mul`, as the Python / C++ mirrors of this repository do).
+    /// snark/src/lib.rs:43-46.  The generator runs on the device (`ark355_setup`): the circuit is synthesised in setup mode on
+    /// the host, its R1CS matrices go to the device once, and the key comes back as `ark_groth16`'s own type together with
+    /// its resident handle, so the first `prove` under it uploads nothing.  The toxic waste is drawn in upstream's order
+    /// (`generate_random_parameters_with_reduction`: alpha, beta, gamma, delta, the two generators, then tau outside the
+    /// evaluation domain).
     fn circuit_specific_setup<C: ConstraintSynthesizer<E::ScalarField>, R: RngCore + CryptoRng>(
         circuit: C,
         rng: &mut R,
     ) -> Result<(Self::ProvingKey, Self::VerifyingKey), Self::Error> {
+        use ark_ec::CurveGroup;
+        use ark_ff::{One, Zero};
+        let tname = core::any::type_name::<C>();
+        let cs = ConstraintSystem::<E::ScalarField>::new_ref();
+        cs.set_optimization_goal(OptimizationGoal::Constraints);
+        cs.set_mode(SynthesisMode::Setup);
+        circuit.generate_constraints(cs.clone())?;
+        cs.finalize();
         // Groth16 proves R1CS only: a circuit with a constraint under any other predicate gets no key here (upstream would
         // build one for the R1CS rows alone, and every proof under it would prove a weaker statement)
-        let refused = core::cell::RefCell::new(None);
-        let res = Groth16::<E>::circuit_specific_setup(gr1cs::R1csOnly { circuit, refused: &refused }, rng);
-        if let Some(e) = refused.into_inner() {
-            return Err(e);
+        gr1cs::require_r1cs_only(&cs)?;
+        let mats = cs.to_matrices()?;
+        let r1cs = mats.get(R1CS_PREDICATE_LABEL).ok_or(Mi355xError::Synthesis(SynthesisError::PredicateNotFound))?;
+        let alpha = E::ScalarField::rand(rng);
+        let beta = E::ScalarField::rand(rng);
+        let mut gamma = E::ScalarField::rand(rng);
+        let mut delta = E::ScalarField::rand(rng);
+        while gamma.is_zero() {
+            gamma = E::ScalarField::rand(rng);
         }
-        res.map_err(Mi355xError::from)
+        while delta.is_zero() {
+            delta = E::ScalarField::rand(rng);
+        }
+        let g1 = E::G1::rand(rng).into_affine();
+        let g2 = E::G2::rand(rng).into_affine();
+        // tau outside the domain of N = next_pow2(n + ell) points, as `sample_element_outside_domain` draws it
+        let domain = (cs.num_constraints() + cs.num_instance_variables()).next_power_of_two() as u64;
+        let mut tau = E::ScalarField::rand(rng);
+        while tau.pow([domain]).is_one() {
+            tau = E::ScalarField::rand(rng);
+        }
+        let td = [
+            marshal::canonical_32(&tau),
+            marshal::canonical_32(&alpha),
+            marshal::canonical_32(&beta),
+            marshal::canonical_32(&gamma),
+            marshal::canonical_32(&delta),
+        ];
+        let (pk, res) = cache::generate::<E, P1, P2>(
+            r1cs,
+            cs.num_constraints(),
+            cs.num_instance_variables(),
+            cs.num_witness_variables(),
+            &td,
+            &g1,
+            &g2,
+        )?;
+        res.confirm(tname); // the matrices of the entry ARE this circuit type's: its proofs may take the witness-only path
+        let vk = pk.vk.clone();
+        Ok((pk, vk))
     }
 
     /// snark/src/lib.rs:50-54 -- the accelerated path.

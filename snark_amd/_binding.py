@@ -54,7 +54,7 @@ SYMBOLS = [
     "ark355_prove_sharded", "ark355_prove_sharded_dev", "ark355_point_size", "ark355_pk_load_bytes", "ark355_pk_dims",
     "ark355_pk_table_info",
     "ark355_points_decode", "ark355_points_encode", "ark355_proof_to_bytes", "ark355_proof_from_bytes",
-    "ark355_setup_scalars", "ark355_verify_batch", "ark355_multi_pairing",
+    "ark355_setup_scalars", "ark355_setup", "ark355_verify_batch", "ark355_multi_pairing",
     "ark355_ctx_set_policy", "ark355_ctx_get_policy", "ark355_sched_info", "ark355_sched_reset", "ark355_diag_streams", "ark355_diag_dispatch",
     "ark355_diag_mad_rate", "ark355_diag_clocks",
 ]
@@ -87,6 +87,14 @@ class PredicateDesc(C.Structure):
     _fields_ = [("label", C.c_char_p), ("arity", C.c_uint32), ("n_constraints", C.c_uint64), ("n_terms", C.c_uint32),
                 ("term_coeff", C.c_void_p), ("term_ptr", C.c_void_p), ("term_var", C.c_void_p), ("term_exp", C.c_void_p),
                 ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("coeff", C.c_void_p)]
+
+
+SETUP_OUT_FIELDS = ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1", "a_query",
+                    "b_g1_query", "b_g2_query", "h_query", "l_query", "u", "v", "w")
+
+
+class SetupOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SETUP_OUT_FIELDS]
 
 
 class ProofRaw(C.Structure):
@@ -193,6 +201,7 @@ class Lib:
         d.ark355_proof_to_bytes.argtypes = [i32, P(ProofRaw), i32, vp]
         d.ark355_proof_from_bytes.argtypes = [i32, vp, u64, i32, i32, P(ProofRaw)]
         d.ark355_setup_scalars.argtypes = [i32, u64, u64, u64, P(vp * 3), P(vp * 3), P(vp * 3), vp, vp, vp, vp, vp, vp, vp]
+        d.ark355_setup.argtypes = [vp, vp, vp, vp, vp, P(SetupOut), P(vp)]
         d.ark355_verify_batch.argtypes = [vp, i32, P(VkDesc), vp, vp, vp, u64, P(i32)]
         d.ark355_multi_pairing.argtypes = [vp, i32, vp, vp, u64, vp, P(i32)]
         d.ark355_ctx_set_policy.argtypes = [vp, C.c_char_p, i64]
@@ -642,6 +651,30 @@ class Lib:
                                                        *[outs[k].ctypes.data_as(C.c_void_p) for k in ("u", "v", "w", "l", "gamma_abc", "h")]))
         cnts = {"u": m, "v": m, "w": m, "l": w, "gamma_abc": ell, "h": N - 1}
         return {k: outs[k][:cnts[k] * 32] for k in outs}
+
+    def setup(self, ctx, r1cs, g1_base: bytes, g2_base: bytes, trapdoor: bytes, dims, sizes, want=SETUP_OUT_FIELDS, want_pk=True):
+        """ark355_setup: the Groth16 generator on the device.  r1cs: an ark355_r1cs handle; dims = (ell, w, N) of it; sizes as
+        from sizes(); trapdoor = tau|alpha|beta|gamma|delta (5 x 32 B canonical); want: the fields of ark355_setup_out to
+        fetch (None or empty: out = NULL, the key never visits the host); want_pk: also return the resident key.
+        Returns (dict of numpy byte arrays keyed by field name, ark355_pk handle or None)."""
+        ell, w, N = dims
+        m, g1, g2 = ell + w, sizes["g1"], sizes["g2"]
+        nbytes = dict(alpha_g1=g1, beta_g1=g1, delta_g1=g1, beta_g2=g2, gamma_g2=g2, delta_g2=g2, gamma_abc_g1=ell * g1,
+                      a_query=m * g1, b_g1_query=m * g1, b_g2_query=m * g2, h_query=(N - 1) * g1, l_query=w * g1,
+                      u=m * 32, v=m * 32, w=m * 32)
+        outs, so = {}, None
+        if want:
+            so = SetupOut()
+            for k in want:
+                outs[k] = np.zeros(max(1, nbytes[k]), dtype=np.uint8)
+                setattr(so, k, outs[k].ctypes.data)
+        b1, k1 = _buf(g1_base)
+        b2, k2 = _buf(g2_base)
+        tb, k3 = _buf(trapdoor)
+        h = C.c_void_p()
+        self.check(ctx, self.dll.ark355_setup(ctx, r1cs, b1, b2, tb, C.byref(so) if so is not None else None,
+                                              C.byref(h) if want_pk else None))
+        return {k: outs[k][:nbytes[k]] for k in outs}, (h if want_pk else None)
 
     def verify_batch(self, ctx, curve, vk_parts, proofs, public_inputs: bytes, rho=None) -> bool:
         """ark355_verify_batch.  vk_parts: (alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1) raw images; proofs: list of

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "groth16_impl.cuh"
 #include "gr1cs_impl.cuh"
+#include "setup_impl.cuh"
 #include "wire_impl.cuh"
 #include "pairing_host.hpp"
 #include "pairing_impl.cuh"
@@ -332,10 +333,40 @@ struct Api {
     else xyzz_sum_t<Fq2>(ctx, g, partials, count, out);
   }
 
+  // The affine window table of `d_base` (FB_WINDOWS x FB_ROW rows) on `st`; d_tx is scratch of as many XYZZ rows.
+  template <class F>
+  static void fixed_base_table(const Affine<F>* d_base, XYZZ<F>* d_tx, Affine<F>* d_ta, hipStream_t st) {
+    static_assert(Fr::N * 4 == FB_WINDOWS, "one 8-bit window per scalar byte");
+    const uint32_t rows = FB_WINDOWS * FB_ROW;
+    ARK_LAUNCH((fixed_base_table_kernel<F>), dim3(FB_WINDOWS), dim3(256), 0, st, d_base, d_tx);
+    ARK_CHECK_LAUNCH();
+    ARK_LAUNCH((batch_to_affine_kernel<F>), dim3(((rows + PRE_K - 1) / PRE_K + MSM_THREADS - 1) / MSM_THREADS),
+               dim3(MSM_THREADS), 0, st, (const XYZZ<F>*)d_tx, d_ta, rows);
+    ARK_CHECK_LAUNCH();
+  }
+  // d_out[i] = d_scalars[i] * base for n resident canonical scalars: through the table when there is one (d_ta), else one
+  // double-and-add per lane.  d_xyzz: scratch of n XYZZ points.
+  template <class F>
+  static void fixed_base_mul_dev(const Affine<F>* d_base, const Affine<F>* d_ta, const Fr* d_scalars, uint64_t n,
+                                 XYZZ<F>* d_xyzz, Affine<F>* d_out, hipStream_t st) {
+    if (!n) return;
+    ARK_REQUIRE(n < (1ull << 32), ARK355_EINVAL, "too many scalars");
+    if (d_ta) {
+      ARK_LAUNCH((fixed_base_mul_kernel<F, Fr>), dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, st, d_ta, d_scalars, n, d_xyzz);
+    } else {
+      ARK_LAUNCH((fixed_base_small_kernel<F, Fr>), dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, st, d_base, d_scalars, n, d_xyzz);
+    }
+    ARK_CHECK_LAUNCH();
+    ARK_LAUNCH((batch_to_affine_kernel<F>), dim3((uint32_t)(((n + PRE_K - 1) / PRE_K + MSM_THREADS - 1) / MSM_THREADS)),
+               dim3(MSM_THREADS), 0, st, (const XYZZ<F>*)d_xyzz, d_out, (uint32_t)n);
+    ARK_CHECK_LAUNCH();
+  }
+  // a handful of scalars go without the table: building its 8 160 points would cost more than it saves
+  static constexpr uint64_t FB_TABLE_MIN = 512;
+
   template <class F>
   static void fixed_base_t(ark355_ctx* ctx, GenericScratch& g, const uint8_t* base, const uint8_t* scalars, uint64_t n,
                            uint8_t* out) {
-    static_assert(Fr::N * 4 == FB_WINDOWS, "one 8-bit window per scalar byte");
     hipStream_t st = ctx->stream;
     const uint32_t rows = FB_WINDOWS * FB_ROW;
     DevBuf d_base(sizeof(Affine<F>)), d_tx((size_t)rows * sizeof(XYZZ<F>)), d_ta((size_t)rows * sizeof(Affine<F>));
@@ -346,24 +377,10 @@ struct Api {
     if (n) {
       ARK_REQUIRE(n < (1ull << 32), ARK355_EINVAL, "too many scalars");
       ARK_CHECK_HIP(hipMemcpyAsync(g.b.p, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, st));
-      if (n < 512) {
-        ARK_LAUNCH((fixed_base_small_kernel<F, Fr>), dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, st,
-                   (const Affine<F>*)d_base.as<Affine<F>>(), g.b.as<Fr>(), n, g.a.as<XYZZ<F>>());
-        ARK_CHECK_LAUNCH();
-      } else {
-        ARK_LAUNCH((fixed_base_table_kernel<F>), dim3(FB_WINDOWS), dim3(256), 0, st, (const Affine<F>*)d_base.as<Affine<F>>(),
-                   d_tx.as<XYZZ<F>>());
-        ARK_CHECK_LAUNCH();
-        ARK_LAUNCH((batch_to_affine_kernel<F>), dim3(((rows + PRE_K - 1) / PRE_K + MSM_THREADS - 1) / MSM_THREADS),
-                   dim3(MSM_THREADS), 0, st, (const XYZZ<F>*)d_tx.as<XYZZ<F>>(), d_ta.as<Affine<F>>(), rows);
-        ARK_CHECK_LAUNCH();
-        ARK_LAUNCH((fixed_base_mul_kernel<F, Fr>), dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, st,
-                   (const Affine<F>*)d_ta.as<Affine<F>>(), g.b.as<Fr>(), n, g.a.as<XYZZ<F>>());
-        ARK_CHECK_LAUNCH();
-      }
-      ARK_LAUNCH((batch_to_affine_kernel<F>), dim3((uint32_t)(((n + PRE_K - 1) / PRE_K + MSM_THREADS - 1) / MSM_THREADS)),
-                 dim3(MSM_THREADS), 0, st, (const XYZZ<F>*)g.a.as<XYZZ<F>>(), g.c.as<Affine<F>>(), (uint32_t)n);
-      ARK_CHECK_LAUNCH();
+      const bool table = n >= FB_TABLE_MIN;
+      if (table) fixed_base_table<F>(d_base.as<Affine<F>>(), d_tx.as<XYZZ<F>>(), d_ta.as<Affine<F>>(), st);
+      fixed_base_mul_dev<F>(d_base.as<Affine<F>>(), table ? d_ta.as<Affine<F>>() : nullptr, g.b.as<Fr>(), n, g.a.as<XYZZ<F>>(),
+                            g.c.as<Affine<F>>(), st);
       ARK_CHECK_HIP(hipMemcpyAsync(out, g.c.p, n * sizeof(Affine<F>), hipMemcpyDeviceToHost, st));
     }
     ARK_CHECK_HIP(hipStreamSynchronize(st));       // the table buffers are freed on return
@@ -493,6 +510,166 @@ struct Api {
         p = Fr::mul(p, tau);
       }
     });
+  }
+
+  // ---- Groth16 generator on the device (ark355_setup) ------------------------------------------------------------------
+  // The scalar stages are setup_impl.cuh; here: argument checks, one window table per group and per call, a fixed-base
+  // multiplication per requested vector from the resident canonical scalars (v feeds b_g1_query and b_g2_query), and the
+  // hand-over of the device vectors to pk_upload (the pk_load_bytes pattern).  Returns nullptr when want_pk is false.
+  static bool fr_canonical(const Fr& c) {
+    for (int i = Fr::N - 1; i >= 0; i--) {
+      const uint32_t q = Fr::Params::mod(i);
+      if (c.l[i] < q) return true;
+      if (c.l[i] > q) return false;
+    }
+    return false;
+  }
+  static bool base_on_curve(const Affine<Fq>& p) {
+    return W::is_reduced(p.x) && W::is_reduced(p.y) && Fq::sqr(p.y) == W::curve_rhs(p.x);
+  }
+  static bool base_on_curve(const Affine<Fq2>& p) {
+    return W::is_reduced(p.x.c0) && W::is_reduced(p.x.c1) && W::is_reduced(p.y.c0) && W::is_reduced(p.y.c1) &&
+           Fq2::sqr(p.y) == W::curve_rhs(p.x);
+  }
+
+  // One group's share of a setup call: the base, its window table (when the call multiplies out FB_TABLE_MIN scalars or
+  // more in this group) and the XYZZ scratch of the longest vector.
+  template <class F>
+  struct SetupGroup {
+    DevBuf base, table, xyzz;
+    bool has_table = false;
+    hipStream_t st = nullptr;
+    void init(const Affine<F>& h_base, uint64_t total, uint64_t longest, hipStream_t stream) {
+      st = stream;
+      base.alloc(sizeof(Affine<F>));
+      ARK_CHECK_HIP(hipMemcpyAsync(base.p, &h_base, sizeof(Affine<F>), hipMemcpyHostToDevice, st));
+      xyzz.alloc((longest ? longest : 1) * sizeof(XYZZ<F>));
+      has_table = total >= FB_TABLE_MIN;
+      if (has_table) {
+        const uint32_t rows = FB_WINDOWS * FB_ROW;
+        DevBuf tx((size_t)rows * sizeof(XYZZ<F>));
+        table.alloc((size_t)rows * sizeof(Affine<F>));
+        fixed_base_table<F>(base.as<Affine<F>>(), tx.as<XYZZ<F>>(), table.as<Affine<F>>(), st);
+        ARK_CHECK_HIP(hipStreamSynchronize(st));          // tx is freed here
+      }
+    }
+    void mul(const DevBuf& scalars, uint64_t n, DevBuf& out) {
+      out.alloc((n ? n : 1) * sizeof(Affine<F>));
+      fixed_base_mul_dev<F>(base.as<Affine<F>>(), has_table ? table.as<Affine<F>>() : nullptr, scalars.as<Fr>(), n,
+                            xyzz.as<XYZZ<F>>(), out.as<Affine<F>>(), st);
+    }
+  };
+
+  static PkDev* setup(ark355_ctx* ctx, const R1csDev& r1, const uint8_t* g1_base, const uint8_t* g2_base,
+                      const uint8_t* trapdoor, const ark355_setup_out* out, bool want_pk) {
+    ARK_REQUIRE(r1.curve == Curve::ID, ARK355_EINVAL, "curve mismatch");
+    hipStream_t st = ctx->stream;
+    static const char* const td_name[5] = {"tau", "alpha", "beta", "gamma", "delta"};
+    Fr tdc[5], td[5];
+    for (int i = 0; i < 5; i++) {
+      memcpy(tdc[i].l, trapdoor + 32 * i, sizeof(Fr));
+      if (!fr_canonical(tdc[i])) throw HipError{ARK355_EINVAL, std::string("trapdoor element ") + td_name[i] + " is not below r"};
+      td[i] = Fr::to_mont(tdc[i]);
+    }
+    ARK_REQUIRE(!td[3].is_zero(), ARK355_EINVAL, "trapdoor element gamma is zero: it has no inverse");
+    ARK_REQUIRE(!td[4].is_zero(), ARK355_EINVAL, "trapdoor element delta is zero: it has no inverse");
+    Affine<Fq> b1;
+    Affine<Fq2> b2;
+    memcpy(&b1, g1_base, sizeof(b1));
+    memcpy(&b2, g2_base, sizeof(b2));
+    ARK_REQUIRE(base_on_curve(b1), ARK355_EINVAL, "g1_base is not a point of the G1 curve");
+    ARK_REQUIRE(base_on_curve(b2), ARK355_EINVAL, "g2_base is not a point of the G2 curve");
+
+    static const ark355_setup_out none{};
+    const ark355_setup_out& o = out ? *out : none;
+    const uint64_t ell = r1.ell, w = r1.w, m = r1.m, hn = r1.N - 1;
+    // work nobody asked for is skipped
+    const bool need_a = want_pk || o.a_query, need_b1 = want_pk || o.b_g1_query, need_b2 = want_pk || o.b_g2_query;
+    const bool need_h = want_pk || o.h_query, need_l = want_pk || o.l_query, need_gabc = o.gamma_abc_g1 != nullptr;
+    const bool need_s1 = want_pk || o.alpha_g1 || o.beta_g1 || o.delta_g1;
+    const bool need_s2 = want_pk || o.beta_g2 || o.gamma_g2 || o.delta_g2;
+
+    SetupScalarsDev sc;
+    setup_scalars_dev<Curve>(r1, td, need_h, sc, st);
+    if (o.u) ARK_CHECK_HIP(hipMemcpyAsync(o.u, sc.u.p, m * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    if (o.v) ARK_CHECK_HIP(hipMemcpyAsync(o.v, sc.v.p, m * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    if (o.w) ARK_CHECK_HIP(hipMemcpyAsync(o.w, sc.w.p, m * sizeof(Fr), hipMemcpyDeviceToHost, st));
+
+    DevBuf d_a, d_b1, d_b2, d_h, d_l, d_gabc, d_s1, d_s2;
+    Affine<Fq> h_s1[3] = {};           // alpha, beta, delta
+    Affine<Fq2> h_s2[3] = {};          // beta, gamma, delta
+    const uint64_t total1 = (need_a ? m : 0) + (need_b1 ? m : 0) + (need_h ? hn : 0) + (need_l ? w : 0) + (need_gabc ? ell : 0) +
+                            (need_s1 ? 3 : 0);
+    if (total1) {
+      SetupGroup<Fq> g;
+      g.init(b1, total1, std::max<uint64_t>(std::max(m, hn), 3), st);
+      if (need_a) g.mul(sc.u, m, d_a);
+      if (need_b1) g.mul(sc.v, m, d_b1);
+      if (need_h) g.mul(sc.h, hn, d_h);
+      if (need_l) g.mul(sc.l, w, d_l);
+      if (need_gabc) g.mul(sc.gabc, ell, d_gabc);
+      if (need_s1) {
+        const Fr ks[3] = {tdc[1], tdc[2], tdc[4]};
+        DevBuf d_ks(sizeof(ks));
+        ARK_CHECK_HIP(hipMemcpyAsync(d_ks.p, ks, sizeof(ks), hipMemcpyHostToDevice, st));
+        g.mul(d_ks, 3, d_s1);
+        ARK_CHECK_HIP(hipMemcpyAsync(h_s1, d_s1.p, sizeof(h_s1), hipMemcpyDeviceToHost, st));
+        ARK_CHECK_HIP(hipStreamSynchronize(st));          // ks and d_ks go out of scope
+      }
+      ARK_CHECK_HIP(hipStreamSynchronize(st));            // the group's table and scratch are freed here
+    }
+    const uint64_t total2 = (need_b2 ? m : 0) + (need_s2 ? 3 : 0);
+    if (total2) {
+      SetupGroup<Fq2> g;
+      g.init(b2, total2, std::max<uint64_t>(need_b2 ? m : 0, 3), st);
+      if (need_b2) g.mul(sc.v, m, d_b2);
+      if (need_s2) {
+        const Fr ks[3] = {tdc[2], tdc[3], tdc[4]};
+        DevBuf d_ks(sizeof(ks));
+        ARK_CHECK_HIP(hipMemcpyAsync(d_ks.p, ks, sizeof(ks), hipMemcpyHostToDevice, st));
+        g.mul(d_ks, 3, d_s2);
+        ARK_CHECK_HIP(hipMemcpyAsync(h_s2, d_s2.p, sizeof(h_s2), hipMemcpyDeviceToHost, st));
+        ARK_CHECK_HIP(hipStreamSynchronize(st));
+      }
+      ARK_CHECK_HIP(hipStreamSynchronize(st));
+    }
+    sc = SetupScalarsDev();                                 // the scalars are multiplied out
+
+    constexpr size_t G1 = sizeof(Affine<Fq>), G2 = sizeof(Affine<Fq2>);
+    if (o.alpha_g1) memcpy(o.alpha_g1, &h_s1[0], G1);
+    if (o.beta_g1) memcpy(o.beta_g1, &h_s1[1], G1);
+    if (o.delta_g1) memcpy(o.delta_g1, &h_s1[2], G1);
+    if (o.beta_g2) memcpy(o.beta_g2, &h_s2[0], G2);
+    if (o.gamma_g2) memcpy(o.gamma_g2, &h_s2[1], G2);
+    if (o.delta_g2) memcpy(o.delta_g2, &h_s2[2], G2);
+    // requested vectors: from the staging buffers to the caller's memory
+    auto give = [&](uint8_t* dst, const DevBuf& src, size_t bytes) {
+      if (dst && bytes) ARK_CHECK_HIP(hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, st));
+    };
+    give(o.gamma_abc_g1, d_gabc, ell * G1);
+    give(o.a_query, d_a, m * G1);
+    give(o.b_g1_query, d_b1, m * G1);
+    give(o.b_g2_query, d_b2, m * G2);
+    give(o.h_query, d_h, hn * G1);
+    give(o.l_query, d_l, w * G1);
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+    if (!want_pk) return nullptr;
+    d_gabc.release();
+    ark355_pk_desc d{};
+    d.num_instance = ell;
+    d.num_witness = w;
+    d.domain_size = r1.N;
+    d.a_query = d_a.as<uint8_t>();            // device pointers: pk_upload copies with hipMemcpyDefault
+    d.b_g1_query = d_b1.as<uint8_t>();
+    d.b_g2_query = d_b2.as<uint8_t>();
+    d.h_query = d_h.as<uint8_t>();
+    d.l_query = d_l.as<uint8_t>();
+    d.alpha_g1 = reinterpret_cast<const uint8_t*>(&h_s1[0]);
+    d.beta_g1 = reinterpret_cast<const uint8_t*>(&h_s1[1]);
+    d.delta_g1 = reinterpret_cast<const uint8_t*>(&h_s1[2]);
+    d.beta_g2 = reinterpret_cast<const uint8_t*>(&h_s2[0]);
+    d.delta_g2 = reinterpret_cast<const uint8_t*>(&h_s2[2]);
+    return pk_upload<Curve>(ctx->policy, &d, st);
   }
 
   // ---- pairing (pairing_impl.cuh on the device, pairing_host.hpp on host threads) ------------------------------------

@@ -96,7 +96,7 @@ int32_t guarded(ark355_ctx* ctx, Fn&& fn, bool locked = false) {
 
 extern "C" {
 
-uint32_t ark355_version(void) { return (0u << 16) | 1u; }
+uint32_t ark355_version(void) { return (0u << 16) | 2u; }
 
 int32_t ark355_sizes(int32_t curve, uint32_t what[4]) {
   return guarded(nullptr, [&] { CURVE_DISPATCH(curve, A::sizes(what)); });
@@ -798,6 +798,21 @@ int32_t ark355_setup_scalars(int32_t curve, uint64_t n, uint64_t ell, uint64_t w
     if (!row_ptr[i] || (row_ptr[i][n] && (!col[i] || !coeff[i]))) return ARK355_EINVAL;
   return guarded(nullptr, [&] {
     CURVE_DISPATCH(curve, A::setup_scalars(n, ell, w, row_ptr, col, coeff, trapdoor, out_u, out_v, out_w, out_l, out_gamma_abc, out_h));
+  });
+}
+
+int32_t ark355_setup(ark355_ctx* ctx, const ark355_r1cs* r1cs, const uint8_t* g1_base, const uint8_t* g2_base,
+                     const uint8_t* trapdoor, const ark355_setup_out* out, ark355_pk** out_pk) {
+  if (out_pk) *out_pk = nullptr;
+  if (!ctx) return ARK355_EINVAL;
+  return guarded(ctx, [&] {
+    ARK_REQUIRE(r1cs && r1cs->d, ARK355_EINVAL, "ark355_setup: r1cs is NULL");
+    ARK_REQUIRE(g1_base && g2_base, ARK355_EINVAL, "ark355_setup: a base is NULL");
+    ARK_REQUIRE(trapdoor, ARK355_EINVAL, "ark355_setup: trapdoor is NULL");
+    ARK_REQUIRE(out || out_pk, ARK355_EINVAL, "ark355_setup: neither out nor out_pk is given");
+    PkDev* d = nullptr;
+    CURVE_DISPATCH(r1cs->d->curve, d = A::setup(ctx, *r1cs->d, g1_base, g2_base, trapdoor, out, out_pk != nullptr));
+    if (out_pk) *out_pk = new ark355_pk{d};
   });
 }
 

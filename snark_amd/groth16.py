@@ -3,9 +3,10 @@
 Mirrors ``ark_snark::SNARK`` (/root/reference/snark/src/lib.rs:22-81) for one implementor,
 ``Groth16``:
 
-* ``circuit_specific_setup``  (lib.rs:43-46, :87-92)  -> host computes the QAP scalars
-  (u_i(tau), v_i(tau), w_i(tau), ...; SURVEY.md Appendix A "Setup"), the device performs the
-  fixed-base multiplications (``ark355_fixed_base_mul``);
+* ``circuit_specific_setup``  (lib.rs:43-46, :87-92)  -> ``ark355_setup``: the device computes the QAP scalars
+  (u_i(tau), v_i(tau), w_i(tau), ...; SURVEY.md Appendix A "Setup") from the resident matrices, multiplies them out and
+  keeps the key resident; ``generator="host"`` is the earlier route (``ark355_setup_scalars`` on host threads, then
+  ``ark355_fixed_base_mul`` per vector);
 * ``prove``                   (lib.rs:50-54)           -> ``ark355_prove`` (the hot path);
 * ``verify`` / ``process_vk`` (lib.rs:59-80)           -> ``ark355_verify_batch`` (random linear combination on
   the device MSM, Miller loops and the final exponentiation on host threads); proofs stay byte-compatible
@@ -169,10 +170,16 @@ class Groth16:
             self.ctx = None
 
     # ---- SNARK::circuit_specific_setup (snark/src/lib.rs:43-46) ---------------------------------------
-    def circuit_specific_setup(self, r1cs: R1CS, rng, keep_trapdoor=False) -> Tuple[ProvingKey, VerifyingKey]:
-        """`rng` yields field elements: callable rng() -> int (uniform mod r).  The generator's scalars (Lagrange
-        coefficients at tau, u/v/w, l, gamma_abc, h) come from `ark355_setup_scalars` (host threads, the library's own
-        field code), the query vectors from `ark355_fixed_base_mul` on the device."""
+    def circuit_specific_setup(self, r1cs: R1CS, rng, keep_trapdoor=False, generator="device",
+                               resident=True) -> Tuple[ProvingKey, VerifyingKey]:
+        """`rng` yields field elements: callable rng() -> int (uniform mod r).  generator="device" (default): `ark355_setup`
+        computes the generator's scalars (Lagrange coefficients at tau, u/v/w, l, gamma_abc, h) from the resident matrices,
+        multiplies them out and returns the key bytes TOGETHER with the resident handle, which is attached to the returned
+        key: the following `load_pk` uploads nothing (resident=False returns the bytes alone, e.g. for a key that will only be
+        loaded in shards).  generator="host": the scalars come from `ark355_setup_scalars` (host
+        threads, the library's own field code), the query vectors from `ark355_fixed_base_mul`; same bytes (A/B, tests)."""
+        if generator not in ("device", "host"):
+            raise ValueError("generator must be 'device' or 'host'")
         cv, r = self.curve, self.curve.r
         tau, alpha, beta, gamma, delta = (rng() % r or 1 for _ in range(5))
         ell, m = r1cs.ell, r1cs.m
@@ -180,11 +187,30 @@ class Groth16:
         if N.bit_length() - 1 > cv.two_adicity:
             raise SynthesisError("PolynomialDegreeTooLarge")
         td = b"".join(cv.fr_canon(x) for x in (tau, alpha, beta, gamma, delta))
+        g1, g2 = cv.g1_gen_raw(), cv.g2_gen_raw()
+        if generator == "device":
+            from ._binding import SETUP_OUT_FIELDS
+            want = [k for k in SETUP_OUT_FIELDS if keep_trapdoor or k not in ("u", "v", "w")]
+            rh = self.load_r1cs(r1cs)
+            try:
+                out, h = self.lib.setup(self.ctx, rh, g1, g2, td, (ell, r1cs.w, N), self.sizes, want=want, want_pk=resident)
+            except Ark355Error as e:
+                raise SynthesisError(str(e)) from e
+            o = {k: v.tobytes() for k, v in out.items()}
+            vk = VerifyingKey(alpha_g1=o["alpha_g1"], beta_g2=o["beta_g2"], gamma_g2=o["gamma_g2"], delta_g2=o["delta_g2"],
+                              gamma_abc_g1=o["gamma_abc_g1"])
+            pk = ProvingKey(vk=vk, beta_g1=o["beta_g1"], delta_g1=o["delta_g1"], a_query=o["a_query"],
+                            b_g1_query=o["b_g1_query"], b_g2_query=o["b_g2_query"], h_query=o["h_query"], l_query=o["l_query"],
+                            ell=ell, w=r1cs.w, N=N)
+            if h is not None:
+                self._track(pk, "_ark355_pk", (self, h), self.lib.dll.ark355_pk_free, h)
+            if keep_trapdoor:
+                pk.trapdoor = dict(tau=tau, alpha=alpha, beta=beta, gamma=gamma, delta=delta, u=o["u"], v=o["v"], w=o["w"])
+            return pk, vk
         try:
             sc = self.lib.setup_scalars(cv.curve_id, r1cs.n, ell, r1cs.w, list(zip(r1cs.row_ptr, r1cs.col, r1cs.coeff)), td)
         except Ark355Error as e:
             raise SynthesisError(str(e)) from e
-        g1, g2 = cv.g1_gen_raw(), cv.g2_gen_raw()
 
         def mul(group, scalars, n=None):
             if not isinstance(scalars, np.ndarray):

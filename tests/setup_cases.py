@@ -1,0 +1,386 @@
+"""Cases of the device generator (ark355_setup) shared by the CPU-emulator tier and the GPU tier.  The references are the
+oracle's generators -- `oracle.groth16.setup` / `qap_scalars` (Python) and `oracle.c.cbase` (C) -- never the library:
+every byte of every requested output is compared."""
+from __future__ import annotations
+
+import ctypes as C_
+import functools
+import random
+
+import numpy as np
+
+from helpers import g1_vec_raw, g2_vec_raw, pk_load_from_oracle, r1cs_load_from_rows, z_bytes
+from oracle import groth16 as G, serialize as Z, synthetic as S
+from oracle.fields import BLS12_381, BN254
+from oracle.ntt import Domain
+from snark_amd._binding import SETUP_OUT_FIELDS, SetupOut
+
+CURVES = {"bls12_381": BLS12_381, "bn254": BN254}
+TD = G.Trapdoor(tau=987654321, alpha=5, beta=7, gamma=11, delta=13)
+SCALARS = ("u", "v", "w")
+
+
+def _w0_instance(r):
+    """no witness at all: x * 1 = x over (One, x)"""
+    return [[(1, 1)]], [[(1, 0)]], [[(1, 1)]], [1, 5], 2
+
+
+def _ell1_instance(r):
+    """n = 1, ell = 1: the domain has two points"""
+    return [[(1, 1)]], [[(1, 1)]], [[(1, 2)]], [1, 3, 9], 1
+
+
+# name -> builder(r) of (A, B, C, z, ell)
+INSTANCES = {
+    "mulchain13": lambda r: S.mulchain_direct(r, 13),
+    "bench_lc20": lambda r: S.cs_to_instance(S.bench_lc_cs(r, 20)),          # general coefficients, repeated columns in a row
+    "bench_lc100": lambda r: S.cs_to_instance(S.bench_lc_cs(r, 100)),
+    "dummy16": lambda r: S.cs_to_instance(S.dummy_cs(r, 16)),                # empty rows, variables that occur nowhere
+    "pow2_exact": lambda r: S.mulchain_direct(r, 14),                        # n + ell = 16 exactly
+    "n1": lambda r: S.mulchain_direct(r, 1),
+    "w0": _w0_instance,                                                      # ark355_r1cs_load accepts num_witness = 0
+    "N2": _ell1_instance,
+    "N4": lambda r: S.mulchain_direct(r, 2),
+}
+WHOLE_KEY = ("mulchain13", "bench_lc20", "bench_lc100", "dummy16", "pow2_exact", "n1", "w0")
+
+
+@functools.lru_cache(maxsize=None)
+def instance(curve_name, name):
+    return INSTANCES[name](CURVES[curve_name].r)
+
+
+def td_bytes(C, td):
+    return b"".join(Z.fr_canon(C, x) for x in (td.tau, td.alpha, td.beta, td.gamma, td.delta))
+
+
+def fr_canon_vec(C, xs):
+    return b"".join(Z.fr_canon(C, x) for x in xs)
+
+
+def oracle_fields(C, pk):
+    """the oracle's key as the byte images of ark355_setup_out"""
+    return dict(alpha_g1=Z.g1_raw(C, pk.vk.alpha_g1), beta_g1=Z.g1_raw(C, pk.beta_g1), delta_g1=Z.g1_raw(C, pk.delta_g1),
+                beta_g2=Z.g2_raw(C, pk.vk.beta_g2), gamma_g2=Z.g2_raw(C, pk.vk.gamma_g2), delta_g2=Z.g2_raw(C, pk.vk.delta_g2),
+                gamma_abc_g1=g1_vec_raw(C, pk.vk.gamma_abc_g1), a_query=g1_vec_raw(C, pk.a_query),
+                b_g1_query=g1_vec_raw(C, pk.b_g1_query), b_g2_query=g2_vec_raw(C, pk.b_g2_query),
+                h_query=g1_vec_raw(C, pk.h_query), l_query=g1_vec_raw(C, pk.l_query),
+                u=fr_canon_vec(C, pk.u), v=fr_canon_vec(C, pk.v), w=fr_canon_vec(C, pk.w))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_key(curve_name, name, tau=TD.tau):
+    """(oracle ProvingKey, its byte images) of a named instance; computed once per session"""
+    C = CURVES[curve_name]
+    A, B, Cm, z, ell = instance(curve_name, name)
+    td = G.Trapdoor(tau=tau, alpha=TD.alpha, beta=TD.beta, gamma=TD.gamma, delta=TD.delta)
+    pk = G.setup(C, A, B, Cm, ell, len(z), td)
+    return pk, oracle_fields(C, pk)
+
+
+def device_setup(lib, ctx, C, r1, dims, td, want=SETUP_OUT_FIELDS, want_pk=False):
+    return lib.setup(ctx, r1, Z.g1_raw(C, C.g1_gen), Z.g2_raw(C, C.g2_gen), td_bytes(C, td), dims, lib.sizes(C.curve_id),
+                     want=want, want_pk=want_pk)
+
+
+def assert_fields_equal(got, exp, fields, tag):
+    for k in fields:
+        assert got[k].tobytes() == exp[k], (tag, k)
+
+
+def whole_key_case(lib, ctx, C, name, tau=TD.tau, h_must_be_zero=False):
+    """every field of ark355_setup_out against oracle.groth16.setup, standard generators"""
+    A, B, Cm, z, ell = instance(C.name, name)
+    pk, exp = oracle_key(C.name, name, tau)
+    m, N = len(z), 1 << pk.domain_log
+    td = G.Trapdoor(tau=tau, alpha=TD.alpha, beta=TD.beta, gamma=TD.gamma, delta=TD.delta)
+    r1 = r1cs_load_from_rows(lib, ctx, C, A, B, Cm, ell, m - ell)
+    try:
+        got, h = device_setup(lib, ctx, C, r1, (ell, m - ell, N), td)
+        assert h is None
+        assert_fields_equal(got, exp, SETUP_OUT_FIELDS, (C.name, name, tau))
+        if h_must_be_zero:
+            assert got["h_query"].tobytes() == bytes((N - 1) * lib.sizes(C.curve_id)["g1"])
+    finally:
+        lib.dll.ark355_r1cs_free(r1)
+
+
+def resident_key_proves_case(lib, ctx, C, name="mulchain13"):
+    """The handle of a call with out == NULL proves exactly what ark355_pk_load of the oracle's key proves, the key bytes of
+    a call with out_pk == NULL are the oracle's, and ark355_verify_batch accepts the proof under the returned verifying key."""
+    A, B, Cm, z, ell = instance(C.name, name)
+    pk, exp = oracle_key(C.name, name)
+    m, N = len(z), 1 << pk.domain_log
+    sz = lib.sizes(C.curve_id)
+    r1 = r1cs_load_from_rows(lib, ctx, C, A, B, Cm, ell, m - ell)
+    h = h_ref = None
+    try:
+        none, h = device_setup(lib, ctx, C, r1, (ell, m - ell, N), TD, want=None, want_pk=True)          # handle only
+        assert none == {} and h
+        assert lib.pk_dims(h) == (ell, m - ell, N)
+        got, no_handle = device_setup(lib, ctx, C, r1, (ell, m - ell, N), TD, want_pk=False)             # bytes only
+        assert no_handle is None
+        assert_fields_equal(got, exp, SETUP_OUT_FIELDS, (C.name, name))
+        h_ref = pk_load_from_oracle(lib, ctx, C, pk, ell, m - ell, N)
+        r_, s_ = Z.fr_canon(C, 0x1234567890abcdef % C.r), Z.fr_canon(C, 0xfedcba0987654321aabbccdd % C.r)
+        proof = lib.prove(ctx, h, r1, z_bytes(C, z), m, r_, s_, sz)
+        assert proof == lib.prove(ctx, h_ref, r1, z_bytes(C, z), m, r_, s_, sz)
+        vk = tuple(got[k].tobytes() for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1"))
+        assert lib.verify_batch(ctx, C.curve_id, vk, [proof], z_bytes(C, z[1:ell]))
+        bad = (proof[0], proof[1], proof[0])
+        assert not lib.verify_batch(ctx, C.curve_id, vk, [bad], z_bytes(C, z[1:ell]))
+    finally:
+        for x in (h, h_ref):
+            if x:
+                lib.dll.ark355_pk_free(x)
+        lib.dll.ark355_r1cs_free(r1)
+
+
+def tau_in_domain_positions(C, name):
+    """tau = omega^k for a k below n, one in [n, n + ell) and one at or beyond n + ell"""
+    A, B, Cm, z, ell = instance(C.name, name)
+    n = len(A)
+    dom = Domain.for_size(C, n + ell)
+    assert n + ell < dom.n, "the instance must leave a domain point beyond n + ell"
+    return [pow(dom.omega, k, C.r) for k in (n // 2, n + ell - 1, n + ell)]
+
+
+def heavy_instance(C, n=2500, w=40, seed=0x5e7):
+    """Column 0 (One) in EVERY row of A, B and C with a coefficient != 1, column 3 in every other row, witness column
+    ell + w - 1 nowhere, the remaining entries sparse."""
+    rnd = random.Random(seed)
+    ell = 2
+    m = ell + w
+
+    def matrix(c0):
+        rows = []
+        for i in range(n):
+            row = [(c0 + i, 0)]
+            if i % 2 == 0:
+                row.append((rnd.randrange(2, C.r), 3))
+            if rnd.random() < 0.3:
+                row.append((rnd.choice((1, rnd.randrange(C.r))), rnd.randrange(1, m - 1)))
+            rows.append(row)
+        return rows
+    return matrix(3), matrix(5), matrix(7), ell, m
+
+
+def heavy_columns_case(lib, ctx, C):
+    """scalars only (no curve work): u, v, w against qap_scalars for long, short and empty columns"""
+    A, B, Cm, ell, m = heavy_instance(C)
+    n = len(A)
+    tau = 0xabcdef0123456789 % C.r
+    u, v, w, zt, dom = G.qap_scalars(C, A, B, Cm, n, ell, m, tau)
+    assert dom.n == 4096 and w[m - 1] == 0 and u[m - 1] == 0
+    td = G.Trapdoor(tau=tau, alpha=TD.alpha, beta=TD.beta, gamma=TD.gamma, delta=TD.delta)
+    r1 = r1cs_load_from_rows(lib, ctx, C, A, B, Cm, ell, m - ell)
+    try:
+        got, _ = device_setup(lib, ctx, C, r1, (ell, m - ell, dom.n), td, want=SCALARS)
+        assert sorted(got) == sorted(SCALARS)
+        assert_fields_equal(got, dict(u=fr_canon_vec(C, u), v=fr_canon_vec(C, v), w=fr_canon_vec(C, w)), SCALARS, C.name)
+    finally:
+        lib.dll.ark355_r1cs_free(r1)
+
+
+def run_length_case(lib, ctx, C, name):
+    """domains shorter than one lane's run: the whole key"""
+    whole_key_case(lib, ctx, C, name)
+
+
+def partial_last_run_case(lib, ctx, C, n=(1 << 11) + 1):
+    """2^11 + 1 constraints: N = 2^12, the last constraint and the input rows sit in the run after 2^11.  u, v, w against
+    qap_scalars; h_query (N - 1 points: the window-table path) against the oracle's C fixed-base routine."""
+    from oracle.c import cbase
+    A, B, Cm, z, ell = S.mulchain_direct(C.r, n)
+    m = len(z)
+    u, v, w, zt, dom = G.qap_scalars(C, A, B, Cm, n, ell, m, TD.tau)
+    assert dom.n == 1 << 12
+    h_s, t = [], zt * pow(TD.delta, -1, C.r) % C.r
+    for _ in range(dom.n - 1):
+        h_s.append(t)
+        t = t * TD.tau % C.r
+    h_exp = cbase.fixed_base(C, 1, Z.g1_raw(C, C.g1_gen), fr_canon_vec(C, h_s), dom.n - 1)
+    r1 = r1cs_load_from_rows(lib, ctx, C, A, B, Cm, ell, m - ell)
+    try:
+        want = SCALARS + ("h_query",)
+        got, _ = device_setup(lib, ctx, C, r1, (ell, m - ell, dom.n), TD, want=want)
+        assert_fields_equal(got, dict(u=fr_canon_vec(C, u), v=fr_canon_vec(C, v), w=fr_canon_vec(C, w), h_query=h_exp), want,
+                            C.name)
+    finally:
+        lib.dll.ark355_r1cs_free(r1)
+
+
+def argument_errors_case(lib, ctx, C, name="n1"):
+    """every argument error of the header returns ARK355_EINVAL with a message, and the context still works afterwards"""
+    A, B, Cm, z, ell = instance(C.name, name)
+    pk, exp = oracle_key(C.name, name)
+    m, N = len(z), 1 << pk.domain_log
+    sz = lib.sizes(C.curve_id)
+    r1 = r1cs_load_from_rows(lib, ctx, C, A, B, Cm, ell, m - ell)
+    g1, g2, td = Z.g1_raw(C, C.g1_gen), Z.g2_raw(C, C.g2_gen), td_bytes(C, TD)
+    ubuf = np.zeros(m * 32, dtype=np.uint8)
+    so = SetupOut()
+    so.u = ubuf.ctypes.data
+
+    def call(ctx_=ctx, r1_=r1, g1_=g1, g2_=g2, td_=td, out=so, want_pk=False):
+        h = C_.c_void_p()
+        rc = lib.dll.ark355_setup(ctx_, r1_, g1_, g2_, td_, C_.byref(out) if out is not None else None,
+                                  C_.byref(h) if want_pk else None)
+        assert not h.value or rc == 0
+        return rc, h
+
+    def canon(i, v):
+        return td[:32 * i] + v.to_bytes(32, "little") + td[32 * (i + 1):]
+    try:
+        bad = [dict(ctx_=None), dict(r1_=None), dict(g1_=None), dict(g2_=None), dict(td_=None), dict(out=None, want_pk=False)]
+        bad += [dict(td_=canon(i, C.r)) for i in range(5)] + [dict(td_=canon(0, (1 << 256) - 1))]
+        bad += [dict(td_=canon(3, 0)), dict(td_=canon(4, 0))]
+        off1 = bytearray(g1)
+        off1[0] ^= 1
+        off2 = bytearray(g2)
+        off2[len(g2) // 2] ^= 1
+        bad += [dict(g1_=bytes(off1)), dict(g2_=bytes(off2)), dict(g1_=bytes(len(g1))), dict(g2_=bytes(len(g2)))]
+        for kw in bad:
+            rc, _ = call(**kw)
+            assert rc == -1, (kw.keys(), rc)
+            if kw.get("ctx_", ctx) is not None:
+                assert lib.dll.ark355_last_error(ctx), kw.keys()
+            # the context stays usable: a good call right after
+            rc, _ = call()
+            assert rc == 0 and ubuf.tobytes() == exp["u"], kw.keys()
+            ubuf[:] = 0
+        # alpha = 0 is a legal trapdoor (only gamma and delta need an inverse); u does not depend on it
+        rc, _ = call(td_=canon(1, 0))
+        assert rc == 0 and ubuf.tobytes() == exp["u"]
+    finally:
+        lib.dll.ark355_r1cs_free(r1)
+    assert sz["fr"] == 32
+
+
+def python_mirror_case(lib, cv_name):
+    """snark_amd.groth16.Groth16.circuit_specific_setup: the device route and generator="host" give identical key bytes, and
+    after the device route load_pk makes no ark355_pk_load call (calls counted through a wrapper on the binding object)."""
+    import dataclasses
+    from snark_amd import params, synthetic
+    from snark_amd.groth16 import Groth16
+    cv = params.CURVES[cv_name]
+    r1, z = synthetic.mulchain(cv, 9)
+
+    class Counting:
+        def __init__(self, inner):
+            self._inner, self.pk_loads = inner, 0
+
+        def __getattr__(self, k):
+            return getattr(self._inner, k)
+
+        def pk_load(self, *a, **kw):
+            self.pk_loads += 1
+            return self._inner.pk_load(*a, **kw)
+
+    counting = Counting(lib)
+    g = Groth16(cv, lib=counting)
+    try:
+        seq = iter([11, 22, 33, 44, 55])
+        pk_d, vk_d = g.circuit_specific_setup(r1, lambda: next(seq), keep_trapdoor=True)
+        seq = iter([11, 22, 33, 44, 55])
+        pk_h, vk_h = g.circuit_specific_setup(r1, lambda: next(seq), keep_trapdoor=True, generator="host")
+        assert dataclasses.asdict(vk_d) == dataclasses.asdict(vk_h)
+        dd, dh = dataclasses.asdict(pk_d), dataclasses.asdict(pk_h)
+        assert sorted(dd) == sorted(dh)
+        for k in dd:
+            assert dd[k] == dh[k], k
+        assert all(isinstance(dd[k], bytes) for k in ("a_query", "b_g2_query", "h_query", "l_query", "beta_g1"))
+        proof = g.prove(pk_d, r1, z, r=777, s=888)
+        assert counting.pk_loads == 0, "the device route attaches the resident handle"
+        assert proof == g.prove_closed_form(pk_d, z, 777, 888)
+        assert g.verify(vk_d, z[1:r1.ell], proof)
+        assert proof == g.prove(pk_h, r1, z, r=777, s=888)
+        assert counting.pk_loads == 1, "the host route loads its key once"
+    finally:
+        g.close()
+
+
+# ---- GPU tier: sizes the Python oracle cannot reach, against the oracle's C generator -----------------------------------
+def add_dense_column(C, n, mats, coeffs=(3, 5, 7)):
+    """mats (CSR as for ark355_r1cs_load) with an entry (column 0, coefficient c != 1) in front of every row"""
+    out = []
+    for (rp, col, cf), c in zip(mats, coeffs):
+        rp = np.asarray(rp, dtype=np.uint64)
+        at = rp[:-1].astype(np.int64)
+        col2 = np.insert(np.asarray(col, dtype=np.uint32), at, 0).astype(np.uint32)
+        cf2 = np.insert(np.frombuffer(cf, dtype=np.uint8).reshape(-1, 32), at, np.frombuffer(Z.fr_mont(C, c), dtype=np.uint8), axis=0)
+        out.append((rp + np.arange(n + 1, dtype=np.uint64), col2, cf2.tobytes()))
+    return out
+
+
+def c_setup_scalars(C, n, ell, w, mats, td):
+    """u, v, w of the oracle's C generator (cb_setup_scalars), canonical bytes"""
+    from oracle.c import cbase
+    m = ell + w
+    N = 1
+    while N < n + ell:
+        N <<= 1
+    args, keep = cbase._csr_args(mats)
+    tdb = np.frombuffer(td_bytes(C, td), dtype=np.uint8)
+    outs = {k: np.zeros(max(1, cnt) * 32, dtype=np.uint8)
+            for k, cnt in (("u", m), ("v", m), ("w", m), ("l", w), ("gabc", ell), ("h", N - 1))}
+    rc = cbase.lib().cb_setup_scalars(C.curve_id, C_.c_uint64(n), C_.c_uint64(ell), C_.c_uint64(w), *args,
+                                      tdb.ctypes.data_as(C_.c_void_p),
+                                      *[outs[k].ctypes.data_as(C_.c_void_p) for k in ("u", "v", "w", "l", "gabc", "h")])
+    assert rc == 0
+    return {k: outs[k][:m * 32].tobytes() for k in SCALARS}
+
+
+@functools.lru_cache(maxsize=None)
+def bench_lc_csr(curve_name, n):
+    return S.bench_lc_csr(CURVES[curve_name].r, n)
+
+
+def heavy_columns_large_case(lib, ctx, C, n=1 << 16):
+    """2^16 rows of the bench circuit plus a dense column 0: the device scalars against the library's own host generator
+    and against the oracle's C generator"""
+    n, ell, w, mats, z = bench_lc_csr(C.name, n)
+    mats = add_dense_column(C, n, mats)
+    td = G.Trapdoor(tau=0x1234567 ^ n, alpha=5, beta=7, gamma=11, delta=13)
+    N = 1
+    while N < n + ell:
+        N <<= 1
+    r1 = lib.r1cs_load(ctx, C.curve_id, n, ell, w, mats)
+    try:
+        got, _ = device_setup(lib, ctx, C, r1, (ell, w, N), td, want=SCALARS)
+        host = lib.setup_scalars(C.curve_id, n, ell, w, mats, td_bytes(C, td))
+        ref = c_setup_scalars(C, n, ell, w, mats, td)
+        for k in SCALARS:
+            assert got[k].tobytes() == ref[k], (C.name, k, "oracle C generator")
+            assert got[k].tobytes() == host[k].tobytes(), (C.name, k, "ark355_setup_scalars")
+    finally:
+        lib.dll.ark355_r1cs_free(r1)
+
+
+def moderate_size_case(lib, ctx, C, n=1 << 16):
+    """the whole key of the 2^16-constraint bench circuit against cbase.setup_raw_c, and one proof from the resident handle
+    against the trapdoor closed form"""
+    from oracle.c import cbase
+    n, ell, w, mats, z = bench_lc_csr(C.name, n)
+    m = ell + w
+    td = G.Trapdoor(tau=0x7654321, alpha=0x1111, beta=0x2222, gamma=0x3333, delta=0x4444)
+    exp, sc = cbase.setup_raw_c(C, n, ell, w, mats, td)
+    exp = dict(exp, u=sc["u"], v=sc["v"], w=sc["w"])
+    sz = lib.sizes(C.curve_id)
+    r1 = lib.r1cs_load(ctx, C.curve_id, n, ell, w, mats)
+    h = None
+    try:
+        got, h = device_setup(lib, ctx, C, r1, (ell, w, sc["N"]), td, want_pk=True)
+        for k in SETUP_OUT_FIELDS:
+            assert got[k].tobytes() == bytes(exp[k]), (C.name, k)
+        r_, s_ = 0x1234567890abcdef % C.r, 0xfedcba0987654321aabbccdd % C.r
+        a, b, c = lib.prove(ctx, h, r1, z_bytes(C, z), m, Z.fr_canon(C, r_), Z.fr_canon(C, s_), sz)
+        ints = {k: [int.from_bytes(sc[k][32 * i:32 * i + 32], "little") for i in range(m)] for k in SCALARS}
+        opk = G.ProvingKey(vk=None, beta_g1=None, delta_g1=None, a_query=[], b_g1_query=[], b_g2_query=[], h_query=[], l_query=[],
+                           trapdoor=td, u=ints["u"], v=ints["v"], w=ints["w"])
+        cf = G.prove_closed_form(C, opk, z, ell, r_, s_)
+        assert (a, b, c) == (Z.g1_raw(C, cf.a), Z.g2_raw(C, cf.b), Z.g1_raw(C, cf.c)), C.name
+    finally:
+        if h:
+            lib.dll.ark355_pk_free(h)
+        lib.dll.ark355_r1cs_free(r1)
