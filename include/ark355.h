@@ -81,6 +81,10 @@ int32_t ark355_sizes(int32_t curve, uint32_t what[4]);
  *                 1: ark355_prove / _dev / _batch also compare a_i b_i with c_i on the rows the witness map computes anyway -- the
  *                 check ark-groth16 runs under debug_assert!(cs.is_satisfied()) -- and return ARK355_E_UNSATISFIABLE, with the index
  *                 of the first unsatisfied constraint in ark355_last_error, instead of a proof that cannot verify).
+ *                 H_EVAL (read at the FIRST proof of a whole key, which decides for the life of that key: 1 its h query moves to
+ *                 the evaluation basis of the coset -- a proof then runs four transforms instead of six, same proof bytes --, 0 it
+ *                 stays in the coefficient basis, -1 [default] evaluation basis from domain size 2^16 on; key shards always keep the
+ *                 coefficient basis; see ark355_pk_h_eval),
  *                 PAIRING_DEVICE (0 host threads, 1 device, -1 [default] device from PAIRING_DEVICE_MIN pairs on) and
  *                 PAIRING_DEVICE_MIN: where the Miller loops of ark355_multi_pairing and ark355_verify_batch run.
  * ARK355_EINVAL for an unknown name.  ark355_prove_batch runs its worker contexts under the caller's policy.
@@ -275,6 +279,21 @@ int32_t ark355_pk_dims(const ark355_pk* pk, uint64_t* num_instance, uint64_t* nu
  * (No counterpart in the reference: ark-groth16 keeps `ProvingKey<E>` as plain vectors in host memory.) */
 int32_t ark355_pk_table_info(const ark355_pk* pk, uint32_t* window_bits, uint32_t* windows, uint32_t* table_stride,
                              uint64_t* table_bytes);
+/* The h query of a resident key (policy H_EVAL of ark355_ctx_set_policy): *state = 0 while the key has not proven yet, 1 once it has settled on the
+ * coefficient basis, 2 once its h query is in the evaluation basis of the coset (the key is then bound to the R1CS handle of its
+ * first proof and answers every other handle with ARK355_EINVAL).  *binds: how many conversions the key went through (0 or 1:
+ * contexts whose first proofs on one key start together wait for the one that converts it).  *bind_seconds: what the conversion
+ * took.  Any pointer may be NULL. */
+int32_t ark355_pk_h_eval(const ark355_pk* pk, int32_t* state, uint32_t* binds, float* bind_seconds);
+/* The two transforms over G1 behind that conversion, on host vectors (tests, diagnostics).  h_query: 2^log_n - 1 raw affine
+ * points H_k; index 2^log_n - 1 enters as infinity.  With N = 2^log_n, g the coset generator, w the N-th root of unity:
+ *   out_e[j] = sum_k g^-k w^-jk H_k / (N (g^N - 1)),   out_u[j] = sum_k w^-jk H_k / (N (g^N - 1)),   N raw affine points each.
+ * Either output may be NULL.  1 <= log_n <= 23. */
+int32_t ark355_hbasis_transform(ark355_ctx* ctx, int32_t curve, const uint8_t* h_query, uint32_t log_n, uint8_t* out_e,
+                                uint8_t* out_u);
+/* out_d[i] = sum_j C[j][i] u[j] over the resident matrix C of `r1`: u is domain_size raw affine points, out_d gets
+ * num_instance + num_witness (an empty column gives infinity). */
+int32_t ark355_hbasis_gather(ark355_ctx* ctx, const ark355_r1cs* r1, const uint8_t* u, uint8_t* out_d);
 /* n encoded points <-> n raw affine images (x || y Montgomery; the layout of every other entry point), on the device */
 int32_t ark355_points_decode(ark355_ctx* ctx, int32_t curve, int32_t group, const uint8_t* in, uint64_t n,
                              int32_t compressed, int32_t validate, uint8_t* out_raw);

@@ -289,6 +289,9 @@ extern "C" {
     ) -> i32;
     pub fn ark355_pk_dims(pk: *const ark355_pk, num_instance: *mut u64, num_witness: *mut u64, domain_size: *mut u64) -> i32;
     pub fn ark355_pk_table_info(pk: *const ark355_pk, window_bits: *mut u32, windows: *mut u32, table_stride: *mut u32, table_bytes: *mut u64) -> i32;
+    pub fn ark355_pk_h_eval(pk: *const ark355_pk, state: *mut i32, binds: *mut u32, bind_seconds: *mut f32) -> i32;
+    pub fn ark355_hbasis_transform(ctx: *mut ark355_ctx, curve: i32, h_query: *const u8, log_n: u32, out_e: *mut u8, out_u: *mut u8) -> i32;
+    pub fn ark355_hbasis_gather(ctx: *mut ark355_ctx, r1: *const ark355_r1cs, u: *const u8, out_d: *mut u8) -> i32;
     pub fn ark355_points_decode(
         ctx: *mut ark355_ctx,
         curve: i32,

@@ -52,7 +52,7 @@ SYMBOLS = [
     "ark355_get_kernel_stats", "ark355_pk_load_shard", "ark355_partial_size", "ark355_prove_shard",
     "ark355_prove_combine", "ark355_prove_batch", "ark355_comm_unique_id", "ark355_comm_init", "ark355_comm_destroy",
     "ark355_prove_sharded", "ark355_prove_sharded_dev", "ark355_point_size", "ark355_pk_load_bytes", "ark355_pk_dims",
-    "ark355_pk_table_info",
+    "ark355_pk_table_info", "ark355_pk_h_eval", "ark355_hbasis_transform", "ark355_hbasis_gather",
     "ark355_points_decode", "ark355_points_encode", "ark355_proof_to_bytes", "ark355_proof_from_bytes",
     "ark355_setup_scalars", "ark355_setup", "ark355_verify_batch", "ark355_multi_pairing",
     "ark355_ctx_set_policy", "ark355_ctx_get_policy", "ark355_sched_info", "ark355_sched_reset", "ark355_diag_streams", "ark355_diag_dispatch",
@@ -196,6 +196,9 @@ class Lib:
         d.ark355_pk_load_bytes.argtypes = [vp, i32, vp, u64, i32, i32, P(vp)]
         d.ark355_pk_dims.argtypes = [vp, P(u64), P(u64), P(u64)]
         d.ark355_pk_table_info.argtypes = [vp, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(u64)]
+        d.ark355_pk_h_eval.argtypes = [vp, P(i32), P(C.c_uint32), P(C.c_float)]
+        d.ark355_hbasis_transform.argtypes = [vp, i32, vp, C.c_uint32, vp, vp]
+        d.ark355_hbasis_gather.argtypes = [vp, vp, vp, vp]
         d.ark355_points_decode.argtypes = [vp, i32, i32, vp, u64, i32, i32, vp]
         d.ark355_points_encode.argtypes = [vp, i32, i32, vp, u64, i32, vp]
         d.ark355_proof_to_bytes.argtypes = [i32, P(ProofRaw), i32, vp]
@@ -416,6 +419,31 @@ class Lib:
         c, w, st, by = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
         self.check(None, self.dll.ark355_pk_table_info(pk, C.byref(c), C.byref(w), C.byref(st), C.byref(by)))
         return {"window_bits": c.value, "windows": w.value, "table_stride": st.value, "table_bytes": by.value}
+
+    def pk_h_eval(self, pk):
+        """State of a key's h query: 'undecided' before its first proof, then 'coeff' or 'eval' (policy H_EVAL)."""
+        st, n, sec = C.c_int32(0), C.c_uint32(0), C.c_float(0.0)
+        self.check(None, self.dll.ark355_pk_h_eval(pk, C.byref(st), C.byref(n), C.byref(sec)))
+        return {"state": ("undecided", "coeff", "eval")[st.value], "binds": n.value, "bind_seconds": sec.value}
+
+    def hbasis_transform(self, ctx, curve, h_query, log_n, want_e=True, want_u=True):
+        """(E', U'): the h query (2^log_n - 1 raw affine G1 points) in the evaluation basis of the coset / of the domain."""
+        g1 = self.sizes(curve)["g1"]
+        n = 1 << log_n
+        assert len(h_query) == (n - 1) * g1
+        hb, k = _buf(h_query)
+        oe = (C.c_uint8 * (n * g1))() if want_e else None
+        ou = (C.c_uint8 * (n * g1))() if want_u else None
+        self.check(ctx, self.dll.ark355_hbasis_transform(ctx, curve, hb, log_n, oe, ou))
+        return (bytes(oe) if want_e else None), (bytes(ou) if want_u else None)
+
+    def hbasis_gather(self, ctx, r1cs, curve, u, m):
+        """D_i = sum_j C[j][i] u_j for the m columns of the resident C; u: domain_size raw affine G1 points."""
+        g1 = self.sizes(curve)["g1"]
+        ub, k = _buf(u)
+        out = (C.c_uint8 * (m * g1))()
+        self.check(ctx, self.dll.ark355_hbasis_gather(ctx, r1cs, ub, out))
+        return bytes(out)
 
     def pk_dims(self, pk):
         a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)

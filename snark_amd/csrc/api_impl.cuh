@@ -97,7 +97,7 @@ struct Api {
     return r1cs_upload<Curve>(n, ell, w, rp, col, coeff);
   }
 
-  static void prove(ark355_ctx* ctx, ProverScratch& sc, const PkDev& pk, const R1csDev& r1, const void* z,
+  static void prove(ark355_ctx* ctx, ProverScratch& sc, PkDev& pk, const R1csDev& r1, const void* z,
                     bool on_dev, const uint8_t* r, const uint8_t* s, ark355_proof_raw* out, uint8_t* partials = nullptr,
                     CommDev* cm = nullptr, int shard_mode = 0) {
     prove_run<Curve>(ctx, sc, pk, r1, z, on_dev, r, s, out, partials, cm, shard_mode);
@@ -106,6 +106,37 @@ struct Api {
     combine_partials_host<Curve>(partials, count, r, s, out);
   }
   static size_t partial_size() { return 4 * sizeof(XYZZ<Fq>) + sizeof(XYZZ<Fq2>); }
+
+  // the two group transforms of hbasis_impl.cuh on host vectors (tests, diagnostics): h_query is N - 1 raw affine points, out_e /
+  // out_u N each (either may be null)
+  static void hbasis_transform(ark355_ctx* ctx, const uint8_t* h_query, uint32_t log_n, uint8_t* out_e, uint8_t* out_u) {
+    constexpr size_t G1 = sizeof(Affine<Fq>);
+    ARK_REQUIRE(log_n >= 1 && log_n <= 23, ARK355_EINVAL, "group transform: 2^1 .. 2^23 points");
+    const uint64_t N = 1ull << log_n;
+    hipStream_t st = ctx->stream;
+    DevBuf d_h((N - 1) * G1), d_e, d_u;
+    ARK_CHECK_HIP(hipMemcpy(d_h.p, h_query, (N - 1) * G1, hipMemcpyHostToDevice));
+    if (out_e) d_e.alloc(N * G1);
+    if (out_u) d_u.alloc(N * G1);
+    hbasis_transforms<Curve>(d_h.p, log_n, st, out_e ? d_e.p : nullptr, out_u ? d_u.p : nullptr);
+    if (out_e) ARK_CHECK_HIP(hipMemcpy(out_e, d_e.p, N * G1, hipMemcpyDeviceToHost));
+    if (out_u) ARK_CHECK_HIP(hipMemcpy(out_u, d_u.p, N * G1, hipMemcpyDeviceToHost));
+  }
+  // the column gather D_i = sum_j C[j][i] U_j of hbasis_impl.cuh: u is N raw affine points, out_d gets ell + w
+  static void hbasis_gather_host(ark355_ctx* ctx, const R1csDev& r1, const uint8_t* u, uint8_t* out_d) {
+    constexpr size_t G1 = sizeof(Affine<Fq>);
+    ARK_REQUIRE(r1.curve == Curve::ID, ARK355_EINVAL, "curve mismatch");
+    hipStream_t st = ctx->stream;
+    const uint32_t m = (uint32_t)r1.m;
+    DevBuf d_u(r1.N * G1), d_D((size_t)m * sizeof(XYZZ<Fq>)), d_aff((size_t)m * G1);
+    ARK_CHECK_HIP(hipMemcpy(d_u.p, u, r1.N * G1, hipMemcpyHostToDevice));
+    hbasis_gather<Curve>(r1, d_u.p, st, d_D.p);
+    ARK_LAUNCH((batch_to_affine_kernel<Fq>), dim3(((m + PRE_K - 1) / PRE_K + MSM_THREADS - 1) / MSM_THREADS), dim3(MSM_THREADS), 0, st,
+               d_D.as<const XYZZ<Fq>>(), d_aff.as<Affine<Fq>>(), m);
+    ARK_CHECK_LAUNCH();
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+    ARK_CHECK_HIP(hipMemcpy(out_d, d_aff.p, (size_t)m * G1, hipMemcpyDeviceToHost));
+  }
 
   static void witness_map(ark355_ctx* ctx, ProverScratch& sc, const R1csDev& r1, const uint8_t* z, uint8_t* h_out) {
     hipStream_t st = ctx->stream;

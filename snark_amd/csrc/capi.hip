@@ -96,7 +96,7 @@ int32_t guarded(ark355_ctx* ctx, Fn&& fn, bool locked = false) {
 
 extern "C" {
 
-uint32_t ark355_version(void) { return (0u << 16) | 2u; }
+uint32_t ark355_version(void) { return (0u << 16) | 3u; }
 
 int32_t ark355_sizes(int32_t curve, uint32_t what[4]) {
   return guarded(nullptr, [&] { CURVE_DISPATCH(curve, A::sizes(what)); });
@@ -731,6 +731,25 @@ int32_t ark355_pk_table_info(const ark355_pk* pk, uint32_t* window_bits, uint32_
   if (table_stride) *table_stride = pk->d->wstride;
   if (table_bytes) *table_bytes = pk->d->table_bytes();
   return ARK355_OK;
+}
+
+int32_t ark355_pk_h_eval(const ark355_pk* pk, int32_t* state, uint32_t* binds, float* bind_seconds) {
+  if (!pk || !pk->d) return ARK355_EINVAL;
+  if (state) *state = pk->d->h_state.load();
+  if (binds) *binds = pk->d->binds;
+  if (bind_seconds) *bind_seconds = (float)pk->d->bind_seconds;
+  return ARK355_OK;
+}
+
+int32_t ark355_hbasis_transform(ark355_ctx* ctx, int32_t curve, const uint8_t* h_query, uint32_t log_n, uint8_t* out_e,
+                                uint8_t* out_u) {
+  if (!ctx || !h_query || (!out_e && !out_u)) return ARK355_EINVAL;
+  return guarded(ctx, [&] { CURVE_DISPATCH(curve, A::hbasis_transform(ctx, h_query, log_n, out_e, out_u)); });
+}
+
+int32_t ark355_hbasis_gather(ark355_ctx* ctx, const ark355_r1cs* r1, const uint8_t* u, uint8_t* out_d) {
+  if (!ctx || !r1 || !r1->d || !u || !out_d) return ARK355_EINVAL;
+  return guarded(ctx, [&] { CURVE_DISPATCH(r1->d->curve, A::hbasis_gather_host(ctx, *r1->d, u, out_d)); });
 }
 
 int32_t ark355_points_decode(ark355_ctx* ctx, int32_t curve, int32_t group, const uint8_t* in, uint64_t n,

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "msm_impl.cuh"
 #include "witness_impl.cuh"
+#include "hbasis_impl.cuh"
 #include "comm_impl.cuh"
 #include "witness_dist_impl.cuh"
 #include "diag_impl.cuh"
@@ -50,6 +51,20 @@ struct PkDev {
   // base of coefficient (shard_index M/G + j) + M k2, M = N / shard_count; the row of coefficient N - 1 (which the proof
   // does not use) is the point at infinity.  h_cnt = M on every rank then.
   bool h_dist = false;
+  // The h query in the evaluation basis (hbasis_impl.cuh).  A whole key meets its R1CS at its first proof;
+  // there, under bind_mu, the policy H_EVAL of the proving context decides ONCE for the life of the key: H_COEFF keeps the tables
+  // built at load time, H_EVAL replaces h_query by the window table of E' (N terms, h_cnt = N) and l_ext by the folded L' table.
+  // h_raw / l_raw hold the affine h_query (N - 1) and l_ext (m + 4) vectors until then.  A bound key proves for the R1CS it was
+  // bound to and refuses every other handle (ARK355_EINVAL): E' and D' are functions of the matrices.
+  enum { H_UNDECIDED = 0, H_COEFF = 1, H_EVAL = 2 };
+  std::atomic<int> h_state{H_UNDECIDED};
+  std::mutex bind_mu;
+  uint64_t bound_r1cs = 0;          // R1csDev::uid
+  double bind_seconds = 0.0;
+  uint32_t binds = 0;               // conversions this key went through (0 or 1: concurrent first proofs wait on bind_mu)
+  DevBuf h_raw, l_raw;
+  int32_t load_msm_c = 0, load_msm_c_h = 0;      // policy MSM_C / MSM_C_H the tables were planned with (the new tables must match)
+  bool packed_rows = false;
   uint64_t table_bytes() const {
     return a_ext.table.bytes + b1_ext.table.bytes + b2_ext.table.bytes + h_query.table.bytes + l_ext.table.bytes;
   }
@@ -381,6 +396,11 @@ static PkDev* pk_upload(const TunePolicy& pol, const ark355_pk_desc* d, hipStrea
     }
     const uint32_t ws = pk->wstride;
     const int pkd = packed_rows ? 1 : 0;           // one row format for the five tables of a key (table_pack_default)
+    pk->packed_rows = packed_rows;
+    pk->load_msm_c = pol.msm_c;
+    pk->load_msm_c_h = pol.msm_c_h;
+    // a whole key may move its h query to the evaluation basis at its first proof (pk_bind): it keeps the two vectors that needs
+    const bool may_bind = shard_count == 1 && !pk->h_dist && pk->N >= 2;
     ext(d->a_query, G1, d->alpha_g1, d->delta_g1, nullptr);
     precomp_build<Fq, Fr>(pol, pk->a_ext, (uint8_t*)stage.p + pk->z_lo * G1, pk->z_cnt, stream, z_plan, ws, 0, pkd);
     ext(d->b_g1_query, G1, d->beta_g1, nullptr, d->delta_g1);
@@ -401,6 +421,10 @@ static PkDev* pk_upload(const TunePolicy& pol, const ark355_pk_desc* d, hipStrea
       ARK_CHECK_HIP(hipMemcpy(stage.p, d->h_query + pk->h_lo * G1, pk->h_cnt * G1, hipMemcpyDefault));
     }
     precomp_build<Fq, Fr>(pol, pk->h_query, stage.p, pk->h_cnt, stream, h_plan, ws, pol.msm_c_h, pkd);
+    if (may_bind) {
+      pk->h_raw.alloc(pk->h_cnt * G1);
+      ARK_CHECK_HIP(hipMemcpy(pk->h_raw.p, stage.p, pk->h_cnt * G1, hipMemcpyDeviceToDevice));
+    }
     // l_ext aligned with zx: ell leading infinities (instance variables carry no l term), l_query, delta_1 at
     // the -rs slot, three trailing infinities
     stage.ensure((m + 4) * G1);
@@ -408,6 +432,12 @@ static PkDev* pk_upload(const TunePolicy& pol, const ark355_pk_desc* d, hipStrea
     if (pk->w) ARK_CHECK_HIP(hipMemcpy((uint8_t*)stage.p + pk->ell * G1, d->l_query, pk->w * G1, hipMemcpyDefault));
     ARK_CHECK_HIP(hipMemcpy((uint8_t*)stage.p + m * G1, d->delta_g1, G1, hipMemcpyHostToDevice));
     precomp_build<Fq, Fr>(pol, pk->l_ext, (uint8_t*)stage.p + pk->z_lo * G1, pk->z_cnt, stream, z_plan, ws, 0, pkd);
+    if (may_bind) {
+      pk->l_raw.alloc((m + 4) * G1);
+      ARK_CHECK_HIP(hipMemcpy(pk->l_raw.p, stage.p, (m + 4) * G1, hipMemcpyDeviceToDevice));
+    } else {
+      pk->h_state.store(PkDev::H_COEFF);
+    }
     stage.release();
   } catch (...) {
     delete pk;
@@ -416,17 +446,72 @@ static PkDev* pk_upload(const TunePolicy& pol, const ark355_pk_desc* d, hipStrea
   return pk;
 }
 
+// First proof of a key: decide between the coefficient path and the evaluation basis (PkDev::h_state) and, for the latter, build
+// E' and the folded L' vector and their window tables (hbasis_impl.cuh).  Policy H_EVAL of the calling context: 0 coefficient
+// path, 1 evaluation basis, -1 (default) evaluation basis from N = 2^16 on -- smaller keys gain nothing.  Returns true when the
+// key proves in the evaluation basis.
+constexpr uint64_t H_EVAL_MIN_DOMAIN = 1ull << 16;
+template <class Curve>
+static bool pk_bind(ark355_ctx* ctx, PkDev& pk, const R1csDev& r1) {
+  using Fr = typename Curve::Fr;
+  using Fq = typename Curve::Fq;
+  if (pk.h_state.load() == PkDev::H_UNDECIDED) {
+    std::lock_guard<std::mutex> lk(pk.bind_mu);
+    if (pk.h_state.load() == PkDev::H_UNDECIDED) {
+      const int want = ctx->policy.h_eval;
+      const bool go = want > 0 || (want < 0 && pk.N >= H_EVAL_MIN_DOMAIN);
+      bool bound = false;
+      if (go) {
+        const auto t0 = std::chrono::steady_clock::now();
+        try {
+          TunePolicy bp = ctx->policy;
+          bp.msm_c = pk.load_msm_c;
+          bp.msm_c_h = pk.load_msm_c_h;
+          DevBuf e_aff, l_aff;
+          hbasis_build<Curve>(r1, pk.h_raw.p, pk.l_raw.p, ctx->stream, e_aff, l_aff);
+          PrecompTable th, tl;
+          precomp_build<Fq, Fr>(bp, th, e_aff.p, pk.N, ctx->stream, 0, pk.wstride, bp.msm_c_h, pk.packed_rows ? 1 : 0);
+          e_aff.release();
+          precomp_build<Fq, Fr>(bp, tl, l_aff.p, pk.m + 4, ctx->stream, 0, pk.wstride, 0, pk.packed_rows ? 1 : 0);
+          ARK_REQUIRE(tl.plan.c == pk.a_ext.plan.c && tl.plan.windows == pk.a_ext.plan.windows, ARK355_EINVAL,
+                      "folded L' table planned differently from the key's other tables");
+          pk.h_query = std::move(th);
+          pk.l_ext = std::move(tl);
+          pk.h_cnt = pk.N;
+          pk.bound_r1cs = r1.uid;
+          pk.binds++;
+          bound = true;
+        } catch (const HipError& e) {
+          // by default a key that cannot spare the HBM for the second pair of tables stays on the coefficient path
+          if (!(want < 0 && e.code == ARK355_ENOMEM)) throw;
+        }
+        pk.bind_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (ctx->policy.trace_host)
+          fprintf(stderr, "[ark355] key bound to its R1CS: h query in the evaluation basis, N = %llu, %.3f s%s\n", (unsigned long long)pk.N,
+                  pk.bind_seconds, bound ? "" : " (out of memory: coefficient path)");
+      }
+      pk.h_raw.release();
+      pk.l_raw.release();
+      pk.h_state.store(bound ? PkDev::H_EVAL : PkDev::H_COEFF);
+    }
+  }
+  if (pk.h_state.load() != PkDev::H_EVAL) return false;
+  ARK_REQUIRE(pk.bound_r1cs == r1.uid, ARK355_EINVAL,
+              "this proving key is bound to another R1CS handle (its h query is in the evaluation basis of that instance): load the key again");
+  return true;
+}
+
 // z_src: host or device pointer to m Fr (Montgomery); z_on_device selects the copy kind.
 //
 // Stream plan (MI355X: 256 CUs; the accumulation kernels fill the chip, everything else is small or
 // latency-bound and is tucked underneath them):
 //   sM (ctx stream)  H2D of z and the tail scalars                                  -> evZ
-//   sW               witness map: SpMV, 7 NTTs, pointwise                            -> evH
+//   sW               witness map: SpMV, 6 transforms (4 for a key in the evaluation basis), pointwise -> evH
 //   sS               digits/scan/scatter of zx, then (after evH) of h               -> evSort[0], evSort[2]
 //   sA               bucket accumulation: A, B1, B2, L' (share sort 0), H            -> evAcc[0..4]
 //   sR               merge + bucket reduction + combine per MSM as evAcc[i] fires; D2H of the five XYZZ results
 template <class Curve>
-static void prove_run(ark355_ctx* ctx, ProverScratch& sc, const PkDev& pk, const R1csDev& r1, const void* z_src,
+static void prove_run(ark355_ctx* ctx, ProverScratch& sc, PkDev& pk, const R1csDev& r1, const void* z_src,
                       bool z_on_device, const uint8_t r_canon[32], const uint8_t s_canon[32], ark355_proof_raw* out,
                       uint8_t* partials_out = nullptr, CommDev* cm = nullptr, int shard_mode = 0) {
   using Fr = typename Curve::Fr;
@@ -436,6 +521,8 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, const PkDev& pk, const
   ARK_REQUIRE(pk.ell == r1.ell && pk.w == r1.w && pk.N == r1.N, ARK355_EINVAL,
               "proving key and R1CS dimensions differ");
   const TunePolicy& pol = ctx->policy;          // (the context's mutex is held: the policy cannot change under this proof)
+  // first proof of a whole key: coefficient path or evaluation basis, for the life of the key (pk_bind)
+  const bool h_eval = pk_bind<Curve>(ctx, pk, r1);
   const auto t_enter = std::chrono::steady_clock::now();
   auto since = [&](std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
@@ -617,7 +704,8 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, const PkDev& pk, const
         fprintf(stderr, "[ark355] witness map distributed over %u ranks (rank %u: N / G = %llu elements per vector)%s\n", pk.shard_count,
                 pk.shard_index, (unsigned long long)(pk.N / pk.shard_count), cm ? "" : " -- LOOPBACK exchange, timing only");
     } else {
-      d_h = witness_map_run<Curve>(ctx, r1, sc.zx.p, sc.ws, sW, check_sat);
+      // (a key in the evaluation basis: d_h = a' b' on the coset, N scalars for the N bases of E')
+      d_h = witness_map_run<Curve>(ctx, r1, sc.zx.p, sc.ws, sW, check_sat, h_eval);
       if (pk.h_dist) {
         // a key shard in the distributed layout under the replicated map: pick this rank's coefficients out of h
         const uint64_t M = pk.h_cnt;

@@ -13,7 +13,7 @@
 //   per key load   MSM_C, MSM_C_H, PACK_ROWS, TABLE_STRIDE, HBM_BUDGET_MB, SHARD_DIST_WM
 //                  (read when a key / base set is loaded through the context: the tables are built for them)
 //   per call       MSM_SEG, ACC_THREADS, NTT_RMAX, NTT_DIRECT_MAX, NTT_NOFUSE (A/B and test knobs of the kernels'
-//                  host drivers), CHECK_SATISFIED, PAIRING_DEVICE, PAIRING_DEVICE_MIN (where the Miller loops of ark355_multi_pairing
+//                  host drivers), CHECK_SATISFIED, H_EVAL (read at the first proof of a key), PAIRING_DEVICE, PAIRING_DEVICE_MIN (where the Miller loops of ark355_multi_pairing
 //                  and ark355_verify_batch run)
 #pragma once
 #include <stddef.h>
@@ -72,6 +72,9 @@ struct TunePolicy {
                                   // (one elementwise kernel, the verdict travels with the proof's last copy) and return
                                   // ARK355_E_UNSATISFIABLE instead of a proof that cannot verify; 0 (default): prove whatever z is, as the
                                   // reference's release build does
+  int32_t h_eval = -1;            // read at the FIRST proof of a whole key, which decides for the life of the key (groth16_impl.cuh, pk_bind): 1 the
+                                  // h query moves to the evaluation basis of the coset (four transforms per proof instead of six), 0 it stays in
+                                  // the coefficient basis, -1 (default) evaluation basis from N = 2^16 on.  Key shards keep the coefficient basis.
   int32_t pairing_device = -1;    // Miller loops (and, in ark355_verify_batch, the curve checks and rho_j A_j): 0 host threads, 1 device
                                   // (pairing_impl.cuh), -1 (default) device when the call has at least pairing_device_min pairs
   int32_t pairing_device_min = 256;// measured crossover ("Device pairing"; profiles/pairing_bench.txt): the smallest measured pair
@@ -120,6 +123,7 @@ inline const TunePolicy::Field* TunePolicy::fields(int* count) {
       ARK_POLICY_FIELD32("NTT_DIRECT_MAX", ntt_direct_max),
       ARK_POLICY_FIELD32("CHECK_SATISFIED", check_satisfied),
       ARK_POLICY_FIELD32("NTT_NOFUSE", ntt_nofuse),
+      ARK_POLICY_FIELD32("H_EVAL", h_eval),
       ARK_POLICY_FIELD32("PAIRING_DEVICE", pairing_device),
       ARK_POLICY_FIELD32("PAIRING_DEVICE_MIN", pairing_device_min),
   };

@@ -6,18 +6,26 @@
 //                  Sr1csAdapter::evaluate_constraint (sr1cs/mod.rs:24-56, which skips the multiply when
 //                  the coefficient is one :42-46).  Repeated columns in a row are summed.
 //                  a_{n+j} = z_j for j < ell (input-consistency rows), everything else 0.
-//   K6  6 NTTs     ntt_impl.cuh (the reference runs 7: see witness_map_run)
+//   K6  6 NTTs     ntt_impl.cuh (the reference runs 7: see witness_map_run); 4 for a key whose h query is in the evaluation
+//                  basis (hbasis_impl.cuh): the map then stops at a'_i b'_i
 //   K7  pointwise  a'_i b'_i on the coset, then h_k = (rho_k - c_k) * (g^N - 1)^-1 on coefficients
 //   a9  satisfaction check: first i with a_i b_i != c_i (which_constraint_is_unsatisfied,
 //                  gr1cs/predicate/mod.rs:185-204)
 #pragma once
+#include <atomic>
 #include <unordered_map>
 #include "common.h"
 #include "ntt_impl.cuh"
 
 namespace ark355 {
 
+static inline uint64_t r1cs_next_uid() {
+  static std::atomic<uint64_t> next{1};
+  return next.fetch_add(1);
+}
+
 struct R1csDev {
+  uint64_t uid = r1cs_next_uid();      // identity of this handle for the life of the process (a key bound to it: groth16_impl.cuh)
   int curve = 0;
   uint64_t n = 0, ell = 0, w = 0, m = 0, N = 0;
   uint32_t log_n = 0;
@@ -225,13 +233,14 @@ struct WitnessScratch {
 };
 
 template <class Curve>
+// mats: 3, or 2 to leave C out (grid.y selects the matrix)
 static void spmv_run(const R1csDev& r, const void* d_z, WitnessScratch& ws, hipStream_t stream, uint64_t row0 = 0,
-                     uint64_t row_stride = 1) {
+                     uint64_t row_stride = 1, uint32_t mats = 3) {
   using Fr = typename Curve::Fr;
   const uint64_t rows = r.N / row_stride;
   ws.ensure(rows * sizeof(Fr));
   const uint32_t grid = (uint32_t)((rows + 255) / 256);
-  ARK_LAUNCH((r1cs_spmv_kernel<Fr>), dim3(grid, 3), dim3(256), 0, stream, r.row_ptr[0].as<uint32_t>(),
+  ARK_LAUNCH((r1cs_spmv_kernel<Fr>), dim3(grid, mats), dim3(256), 0, stream, r.row_ptr[0].as<uint32_t>(),
              r.col[0].as<uint32_t>(), r.cidx[0].as<uint32_t>(), r.row_ptr[1].as<uint32_t>(), r.col[1].as<uint32_t>(),
              r.cidx[1].as<uint32_t>(), r.row_ptr[2].as<uint32_t>(), r.col[2].as<uint32_t>(), r.cidx[2].as<uint32_t>(),
              r.pool.as<Fr>(), (const Fr*)d_z, r.n, r.ell, rows, ws.buf[0].as<Fr>(), ws.buf[2].as<Fr>(),
@@ -251,11 +260,13 @@ static void spmv_run(const R1csDev& r, const void* d_z, WitnessScratch& ws, hipS
 // the seven-transform form (one-lane kernels).
 // check_rows: also compare a_i b_i with c_i on the rows the SpMV has just written (policy CHECK_SATISFIED); the index of
 // the first unsatisfied constraint (or ~0) is left in ws.first_bad for the caller to fetch.
+// eval_basis: stop at s = a' b', the N evaluations on the coset (natural order) -- the scalars of a key whose h query is in the
+// evaluation basis (hbasis_impl.cuh).  Four transforms; c is not computed at all unless check_rows wants its rows.
 template <class Curve>
 static void* witness_map_run(ark355_ctx* ctx, const R1csDev& r, const void* d_z, WitnessScratch& ws,
-                             hipStream_t stream, bool check_rows = false) {
+                             hipStream_t stream, bool check_rows = false, bool eval_basis = false) {
   using Fr = typename Curve::Fr;
-  spmv_run<Curve>(r, d_z, ws, stream);
+  spmv_run<Curve>(r, d_z, ws, stream, 0, 1, (eval_basis && !check_rows) ? 2u : 3u);
   if (check_rows) {
     ws.first_bad.ensure(8);
     ARK_CHECK_HIP(hipMemsetAsync(ws.first_bad.p, 0xFF, 8, stream));
@@ -269,6 +280,17 @@ static void* witness_map_run(ark355_ctx* ctx, const R1csDev& r, const void* d_z,
   const uint64_t stride = 2 * r.N;
   void* cur[3];
   void* oth[3];
+  if (eval_basis) {
+    Fr* res0 = (Fr*)ntt_inverse_then_coset<Curve>(ctx, ws.buf[0].p, ws.buf[1].p, r.log_n, stream, 2, stride);
+    const bool swapped = res0 != ws.buf[0].as<Fr>();
+    for (int v = 0; v < 2; v++) {
+      cur[v] = ws.buf[2 * v + (swapped ? 1 : 0)].p;
+      oth[v] = ws.buf[2 * v + (swapped ? 0 : 1)].p;
+    }
+    ARK_LAUNCH((qap_mul_kernel<Fr>), dim3(grid), dim3(256), 0, stream, (const Fr*)cur[0], (const Fr*)cur[1], r.N, (Fr*)oth[0]);
+    ARK_CHECK_LAUNCH();
+    return oth[0];
+  }
   if (r.log_n < 3) {
     Fr* res0 = (Fr*)ntt_inverse_then_coset<Curve>(ctx, ws.buf[0].p, ws.buf[1].p, r.log_n, stream, 3, stride);
     const bool swapped = res0 != ws.buf[0].as<Fr>();
