@@ -86,7 +86,8 @@ int32_t ark355_sizes(int32_t curve, uint32_t what[4]);
  *                 stays in the coefficient basis, -1 [default] evaluation basis from domain size 2^16 on; key shards always keep the
  *                 coefficient basis; see ark355_pk_h_eval),
  *                 PAIRING_DEVICE (0 host threads, 1 device, -1 [default] device from PAIRING_DEVICE_MIN pairs on) and
- *                 PAIRING_DEVICE_MIN: where the Miller loops of ark355_multi_pairing and ark355_verify_batch run.
+ *                 PAIRING_DEVICE_MIN: where the Miller loops of ark355_multi_pairing and ark355_verify_batch run;
+ *                 PAIRING_EACH_MIN: the "from ... on" of ark355_pairing_groups and ark355_verify_each, in groups / proofs.
  * ARK355_EINVAL for an unknown name.  ark355_prove_batch runs its worker contexts under the caller's policy.
  * (No counterpart in the reference: ark-groth16 has no runtime knobs; rayon's thread count is its only one.) */
 int32_t ark355_ctx_set_policy(ark355_ctx* ctx, const char* name, int64_t value);
@@ -449,6 +450,32 @@ int32_t ark355_verify_batch(ark355_ctx* ctx, int32_t curve, const ark355_vk_desc
  * exponentiation runs on the host, once per call. */
 int32_t ark355_multi_pairing(ark355_ctx* ctx, int32_t curve, const uint8_t* g1, const uint8_t* g2, uint64_t n,
                              uint8_t* out_gt /* may be NULL */, int32_t* is_one /* may be NULL */);
+
+/* ark-ec Pairing::pairing, elementwise or per group: groups x group_len consecutive pairs,
+ *   GT_k = final_exponentiation(prod_{i in group k} miller_loop(P_i, Q_i)),
+ * every GT_k byte for byte what ark355_multi_pairing returns for that group's pairs alone (group_len = 1: one pairing per
+ * pair).  g1 / g2: groups * group_len raw affine images, below 2^32 in all; a pair with either point at infinity
+ * contributes one.  out_gt: groups x 12 Fq in the layout of ark355_multi_pairing; is_one: groups bytes, 1 where GT_k is the
+ * identity.  groups == 0 returns ARK355_OK and writes nothing.  ARK355_EINVAL: group_len == 0 or above
+ * ARK355_PAIRING_GROUP_MAX (one long product is ark355_multi_pairing's), a NULL point array with pairs to read, a point
+ * off its curve (ark355_last_error names g1[i] / g2[i], i the index into the flat list).  Subgroup membership is NOT checked.
+ * Policy PAIRING_DEVICE as for ark355_multi_pairing, but "by size" (-1) reads PAIRING_EACH_MIN, counted in groups: on the
+ * device route the final exponentiations run there too, one lane per group (the exact power (q^12 - 1) / r); the host
+ * route pays one of them per group on at most 16 threads and is the slow second checker. */
+#define ARK355_PAIRING_GROUP_MAX 64
+int32_t ark355_pairing_groups(ark355_ctx* ctx, int32_t curve, const uint8_t* g1, const uint8_t* g2, uint64_t groups,
+                              uint32_t group_len, uint8_t* out_gt /* may be NULL */, uint8_t* is_one /* may be NULL */);
+
+/* SNARK::verify (snark/src/lib.rs:59-80) for every proof of ONE key on its own: ok[j] = 1 iff
+ *   e(A_j, B_j) = e(alpha, beta) e(sum_i x_ji gamma_abc_i, gamma) e(C_j, delta),
+ * the verdict of ark355_verify_batch on proof j alone with rho = NULL -- no random combination, no soundness error.
+ * proofs, public_inputs as for ark355_verify_batch (num_instance == 1: no public inputs, public_inputs may be NULL); ok:
+ * count bytes.  A proof with a point off its curve gets ok[j] = 0, the call still returns ARK355_OK and the other verdicts
+ * are unaffected.  The key's own points are checked once: one off its curve gives ARK355_EINVAL naming the field.
+ * Policy PAIRING_DEVICE / PAIRING_EACH_MIN (counted in proofs) as for ark355_pairing_groups: on the device route the curve
+ * checks, the prepared inputs, the 3 count Miller loops and the count final exponentiations are kernels and only ok returns. */
+int32_t ark355_verify_each(ark355_ctx* ctx, int32_t curve, const ark355_vk_desc* vk, const ark355_proof_raw* proofs,
+                           const uint8_t* public_inputs, uint64_t count, uint8_t* ok);
 
 /* The scalars of the Groth16 generator (circuit_specific_setup, snark/src/lib.rs:43-46; upstream
  * generate_parameters_with_qap) from the R1CS matrices in CSR and the five trapdoor elements tau, alpha, beta, gamma,

@@ -55,6 +55,7 @@ pub const ARK355_GR1CS_MAX_TERMS: u32 = 256;
 pub const ARK355_GR1CS_MAX_FACTORS: u32 = 1024;
 pub const ARK355_GR1CS_MAX_PREDICATES: u32 = 1024;
 pub const ARK355_GR1CS_MAX_ROWS: u64 = 4294967295;
+pub const ARK355_PAIRING_GROUP_MAX: u32 = 64;
 
 #[repr(C)]
 pub struct ark355_pk_desc {
@@ -422,6 +423,29 @@ extern "C" {
         n: u64,
         out_gt: *mut u8,
         is_one: *mut i32,
+    ) -> i32;
+
+    /// `Pairing::pairing` per group of `group_len` consecutive pairs; `out_gt` (groups x 12 Fq) and `is_one` (groups bytes) may be null.
+    pub fn ark355_pairing_groups(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        g1: *const u8,
+        g2: *const u8,
+        groups: u64,
+        group_len: u32,
+        out_gt: *mut u8,
+        is_one: *mut u8,
+    ) -> i32;
+
+    /// `SNARK::verify` for every proof of one key on its own: `ok` receives `count` bytes.
+    pub fn ark355_verify_each(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        vk: *const ark355_vk_desc,
+        proofs: *const ark355_proof_raw,
+        public_inputs: *const u8,
+        count: u64,
+        ok: *mut u8,
     ) -> i32;
 
     pub fn ark355_setup_scalars(

@@ -253,6 +253,69 @@ where
         Ok(ok == 1)
     }
 
+    /// Per-proof verification (`ark355_verify_each`): `SNARK::verify` for every proof of ONE verifying key on its own, in
+    /// one call -- three Miller loops and one final exponentiation per proof, all on the device from the policy's
+    /// `PAIRING_EACH_MIN` proofs on.  No random combination: `out[j]` is the verdict of proof `j` alone.  A proof whose
+    /// public inputs have the wrong length gets `false`.
+    pub fn verify_each(
+        vk: &VerifyingKey<E>,
+        public_inputs: &[Vec<E::ScalarField>],
+        proofs: &[Proof<E>],
+    ) -> Result<Vec<bool>, Mi355xError> {
+        let ell = vk.gamma_abc_g1.len();
+        if public_inputs.len() != proofs.len() {
+            return Err(Mi355xError::InvalidArgument("verify_each: one list of public inputs per proof".into()));
+        }
+        let good: Vec<usize> = (0..proofs.len()).filter(|&j| public_inputs[j].len() + 1 == ell).collect();
+        let mut out = vec![false; proofs.len()];
+        if good.is_empty() {
+            return Ok(out);
+        }
+        let one = |p: &Affine<P1>| marshal::flatten_points(core::slice::from_ref(p));
+        let one2 = |p: &Affine<P2>| marshal::flatten_points(core::slice::from_ref(p));
+        let (alpha, beta, gamma, delta) = (one(&vk.alpha_g1), one2(&vk.beta_g2), one2(&vk.gamma_g2), one2(&vk.delta_g2));
+        let gabc = marshal::flatten_points(&vk.gamma_abc_g1);
+        let desc = ffi::ark355_vk_desc {
+            num_instance: ell as u64,
+            alpha_g1: alpha.as_ptr(),
+            beta_g2: beta.as_ptr(),
+            gamma_g2: gamma.as_ptr(),
+            delta_g2: delta.as_ptr(),
+            gamma_abc_g1: gabc.as_ptr(),
+        };
+        let mut raw = Vec::with_capacity(good.len());
+        let mut xs: Vec<E::ScalarField> = Vec::with_capacity(good.len() * (ell - 1));
+        for &j in &good {
+            let p = &proofs[j];
+            let mut r = ffi::ark355_proof_raw { a: [0; 96], b: [0; 192], c: [0; 96] };
+            let (a, b, c) = (one(&p.a), one2(&p.b), one(&p.c));
+            r.a[..a.len()].copy_from_slice(&a);
+            r.b[..b.len()].copy_from_slice(&b);
+            r.c[..c.len()].copy_from_slice(&c);
+            raw.push(r);
+            xs.extend_from_slice(&public_inputs[j]);
+        }
+        let image = marshal::scalars_image(&xs);
+        let mut ok = vec![0u8; good.len()];
+        cache::with_ctx(|ctx| {
+            cache::check(ctx, unsafe {
+                ffi::ark355_verify_each(
+                    ctx,
+                    E::CURVE_ID,
+                    &desc,
+                    raw.as_ptr(),
+                    if xs.is_empty() { core::ptr::null() } else { image.as_ptr() },
+                    good.len() as u64,
+                    ok.as_mut_ptr(),
+                )
+            })
+        })?;
+        for (&j, &v) in good.iter().zip(ok.iter()) {
+            out[j] = v == 1;
+        }
+        Ok(out)
+    }
+
     /// Assignments already synthesised (each `instance || witness`): up to `inflight` proofs share the GPU.
     pub fn prove_assignments<R: RngCore + CryptoRng>(
         res: &cache::Resident,

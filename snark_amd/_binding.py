@@ -54,7 +54,7 @@ SYMBOLS = [
     "ark355_prove_sharded", "ark355_prove_sharded_dev", "ark355_point_size", "ark355_pk_load_bytes", "ark355_pk_dims",
     "ark355_pk_table_info", "ark355_pk_h_eval", "ark355_hbasis_transform", "ark355_hbasis_gather",
     "ark355_points_decode", "ark355_points_encode", "ark355_proof_to_bytes", "ark355_proof_from_bytes",
-    "ark355_setup_scalars", "ark355_setup", "ark355_verify_batch", "ark355_multi_pairing",
+    "ark355_setup_scalars", "ark355_setup", "ark355_verify_batch", "ark355_multi_pairing", "ark355_pairing_groups", "ark355_verify_each",
     "ark355_ctx_set_policy", "ark355_ctx_get_policy", "ark355_sched_info", "ark355_sched_reset", "ark355_diag_streams", "ark355_diag_dispatch",
     "ark355_diag_mad_rate", "ark355_diag_clocks",
 ]
@@ -207,6 +207,8 @@ class Lib:
         d.ark355_setup.argtypes = [vp, vp, vp, vp, vp, P(SetupOut), P(vp)]
         d.ark355_verify_batch.argtypes = [vp, i32, P(VkDesc), vp, vp, vp, u64, P(i32)]
         d.ark355_multi_pairing.argtypes = [vp, i32, vp, vp, u64, vp, P(i32)]
+        d.ark355_pairing_groups.argtypes = [vp, i32, vp, vp, u64, C.c_uint32, vp, vp]
+        d.ark355_verify_each.argtypes = [vp, i32, P(VkDesc), vp, vp, u64, vp]
         d.ark355_ctx_set_policy.argtypes = [vp, C.c_char_p, i64]
         d.ark355_ctx_get_policy.argtypes = [vp, C.c_char_p, P(i64)]
         d.ark355_sched_info.argtypes = [vp, vp, i32, P(SchedReport)]
@@ -726,6 +728,43 @@ class Lib:
         ok = C.c_int32(0)
         self.check(ctx, self.dll.ark355_verify_batch(ctx, curve, C.byref(d), arr, ib, rb, len(proofs), C.byref(ok)))
         return bool(ok.value)
+
+    def _vk_desc(self, vk_parts, keep):
+        alpha, beta2, gamma2, delta2, gabc = vk_parts
+        d = VkDesc()
+        for name, val in (("alpha_g1", alpha), ("beta_g2", beta2), ("gamma_g2", gamma2), ("delta_g2", delta2), ("gamma_abc_g1", gabc)):
+            p, k = _buf(val)
+            keep.append(k)
+            setattr(d, name, p.value)
+        d.num_instance = len(gabc) // len(alpha)
+        return d
+
+    def verify_each(self, ctx, curve, vk_parts, proofs, public_inputs: bytes):
+        """ark355_verify_each: one verdict per proof.  Arguments as for verify_batch (no rho).  Returns a list of bool."""
+        keep = []
+        d = self._vk_desc(vk_parts, keep)
+        arr = (ProofRaw * max(1, len(proofs)))()
+        for i, (a, b, c) in enumerate(proofs):
+            C.memmove(arr[i].a, a, len(a))
+            C.memmove(arr[i].b, b, len(b))
+            C.memmove(arr[i].c, c, len(c))
+        ib, k1 = _buf(public_inputs if len(public_inputs) else None)
+        ok = np.zeros(max(1, len(proofs)), dtype=np.uint8)
+        self.check(ctx, self.dll.ark355_verify_each(ctx, curve, C.byref(d), arr, ib, len(proofs), ok.ctypes.data_as(C.c_void_p)))
+        return [bool(v) for v in ok[:len(proofs)]]
+
+    def pairing_groups(self, ctx, curve, g1: bytes, g2: bytes, groups, group_len=1, want_gt=True):
+        """ark355_pairing_groups over groups x group_len raw affine pairs.  Returns (gt, is_one): gt = groups x 12 Fq as bytes
+        (None with want_gt=False), is_one = list of bool."""
+        fq = self.sizes(curve)["fq"]
+        out = np.zeros(max(1, groups) * 12 * fq, dtype=np.uint8)
+        one = np.zeros(max(1, groups), dtype=np.uint8)
+        b1, k1 = _buf(g1 if g1 else None)
+        b2, k2 = _buf(g2 if g2 else None)
+        self.check(ctx, self.dll.ark355_pairing_groups(ctx, curve, b1, b2, groups, group_len,
+                                                       out.ctypes.data_as(C.c_void_p) if want_gt else None,
+                                                       one.ctypes.data_as(C.c_void_p)))
+        return (out[:groups * 12 * fq].tobytes() if want_gt else None), [bool(v) for v in one[:groups]]
 
     def multi_pairing(self, ctx, curve, g1: bytes, g2: bytes, n, want_gt=True):
         """ark355_multi_pairing over n raw affine pairs.  Returns (gt, is_one): gt = 12 Fq (Montgomery, ark-ff Fp12 order) as

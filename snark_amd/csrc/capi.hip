@@ -805,6 +805,27 @@ int32_t ark355_multi_pairing(ark355_ctx* ctx, int32_t curve, const uint8_t* g1, 
   });
 }
 
+int32_t ark355_pairing_groups(ark355_ctx* ctx, int32_t curve, const uint8_t* g1, const uint8_t* g2, uint64_t groups,
+                              uint32_t group_len, uint8_t* out_gt, uint8_t* is_one) {
+  if (!ctx) return ARK355_EINVAL;
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(curve, A::pairing_groups(ctx, ex.generic, g1, g2, groups, group_len, out_gt, is_one));
+  });
+}
+
+int32_t ark355_verify_each(ark355_ctx* ctx, int32_t curve, const ark355_vk_desc* vk, const ark355_proof_raw* proofs,
+                           const uint8_t* public_inputs, uint64_t count, uint8_t* ok) {
+  if (!ctx || !vk || (count && (!proofs || !ok)) || !vk->alpha_g1 || !vk->beta_g2 || !vk->gamma_g2 || !vk->delta_g2 ||
+      !vk->gamma_abc_g1)
+    return ARK355_EINVAL;
+  if (ok) memset(ok, 0, count);
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(curve, A::verify_each(ctx, ex.generic, vk, proofs, public_inputs, count, ok));
+  });
+}
+
 int32_t ark355_setup_scalars(int32_t curve, uint64_t n, uint64_t ell, uint64_t w, const uint64_t* const row_ptr[3],
                              const uint32_t* const col[3], const uint8_t* const coeff[3], const uint8_t* trapdoor,
                              uint8_t* out_u, uint8_t* out_v, uint8_t* out_w, uint8_t* out_l, uint8_t* out_gamma_abc,

@@ -205,6 +205,8 @@ struct PairingHost {
   struct Consts {
     BigU final_exp;            // (q^6 + 1) / r
     Fq2 frob_x, frob_y;        // BN254: xi^((q-1)/3), xi^((q-1)/2)
+    Fq2 frob12[3][6];          // xi^(k (q^n - 1) / 6) at [n - 1][k]: f^(q^n) coefficient-wise in F_q2[w] / (w^6 - xi), for the
+                               // device final exponentiation (pairing_impl.cuh); n = 2 lies in F_q
   };
   static const Consts& consts() {
     static const Consts c = [] {
@@ -221,6 +223,13 @@ struct PairingHost {
       const Fq2 xi = mul_xi(Fq2::one());
       k.frob_x = pow2(xi, BigU::div(qm1, BigU::small(3)));
       k.frob_y = pow2(xi, BigU::div(qm1, BigU::small(2)));
+      BigU qn = q;
+      for (int n = 0; n < 3; n++) {
+        const Fq2 g = pow2(xi, BigU::div(BigU::sub(qn, BigU::small(1)), BigU::small(6)));
+        k.frob12[n][0] = Fq2::one();
+        for (int i = 1; i < 6; i++) k.frob12[n][i] = Fq2::mul(k.frob12[n][i - 1], g);
+        qn = BigU::mul(qn, q);
+      }
       return k;
     }();
     return c;

@@ -15,6 +15,10 @@
 //                                      The workgroup then multiplies its 64 values with a product tree in LDS.
 //   pass C  pairing_product_kernel     one workgroup multiplies the per-workgroup partial products (second launch).
 //
+//   per group (ark355_pairing_groups, ark355_verify_each): pass B leaves every pair's f in HBM instead of the workgroup
+//   product, and  pairing_final_exp_kernel  multiplies the Miller values of a group and raises the product to
+//   (q^12 - 1) / r, one lane per group; see "final exponentiation" below.
+//
 // F_q12 is held as F_q2[w] / (w^6 - xi), six F_q2 coefficients c_k of w^k.  That is the tower of pairing_host.hpp read
 // differently (v = w^2: c0.c0, c1.c0, c0.c1, c1.c1, c0.c2, c1.c2 are the coefficients of w^0 .. w^5), and it makes every
 // product one double loop: out_k = sum_{i+j=k} a_i b_j + xi sum_{i+j=k+6} a_i b_j.  A line has three non-zero coefficients,
@@ -179,6 +183,52 @@ struct PairingDev {
     }
   }
 
+  // ---- final exponentiation: one lane per GT value ------------------------------------------------------------------
+  // The lane keeps FE_BUFS values of F_q12 in LDS and follows a PROGRAM of three-address instructions over them, formed once
+  // on the host (FeProgram in api_impl.cuh) and read from HBM by the whole wave at once.  The kernel so holds ONE squaring
+  // and ONE multiplication site, like pass B, however long the exponent chain is.  36 KiB (BLS12-381) / 24 KiB (BN254) per
+  // buffer and workgroup: 4 / 6 buffers are 144 KiB of the 160 KiB a workgroup may declare, one wave per CU.
+  static constexpr uint32_t FE_BUFS = BN ? 6 : 4;
+  static constexpr uint32_t B12 = W12 * PAIR_LANES;       // dwords of one buffer of a workgroup
+  // instruction word: op | d << 4 | a << 8 | b << 12
+  enum FeOp : uint32_t {
+    FE_SQR = 0,     // d = a^2
+    FE_MUL = 1,     // d = a * b
+    FE_COPY = 2,    // d = a
+    FE_CONJ = 3,    // d = conj(d)  (w -> -w; the inverse once the easy part is done)
+    FE_FROB = 4,    // d = d^(q^a), a = 1 .. 3
+    FE_INV6 = 5     // d in F_q6 (odd coefficients zero) -> 1 / d
+  };
+  static constexpr uint32_t fe_ins(uint32_t op, uint32_t d, uint32_t a = 0, uint32_t b = 0) {
+    return op | d << 4 | a << 8 | b << 12;
+  }
+
+  ARK_D static void conj12(uint32_t* f) {
+    for (int k = 1; k < 6; k += 2) stc(f, k, Fq2::neg(ldc(f, k)));
+  }
+  // f^(q^n) coefficient-wise: c_k -> c_k^(q^n) * xi^(k (q^n - 1) / 6); frob[(n - 1) * 6 + k] holds the constants
+  ARK_D static void frob12(uint32_t* f, uint32_t n, const Fq2* __restrict__ frob) {
+#pragma unroll 1
+    for (int k = 0; k < 6; k++) {
+      Fq2 c = ldc(f, k);
+      if (n != 2) c.c1 = Fq::neg(c.c1);
+      stc(f, k, Fq2::mul(c, frob[(n - 1) * 6 + k]));
+    }
+  }
+  // the even coefficients of f are an element of F_q6 = F_q2[v] / (v^3 - xi), v = w^2: invert it in place (one Fq::inv)
+  ARK_D static void inv6(uint32_t* f) {
+    const Fq2 a0 = ldc(f, 0), a1 = ldc(f, 2), a2 = ldc(f, 4);
+    const Fq2 c0 = Fq2::sub(Fq2::sqr_ni(a0), mul_xi(Fq2::mul_ni(a1, a2)));
+    const Fq2 c1 = Fq2::sub(mul_xi(Fq2::sqr_ni(a2)), Fq2::mul_ni(a0, a1));
+    const Fq2 c2 = Fq2::sub(Fq2::sqr_ni(a1), Fq2::mul_ni(a0, a2));
+    const Fq2 t = Fq2::add(Fq2::mul_ni(a0, c0), mul_xi(Fq2::add(Fq2::mul_ni(a2, c1), Fq2::mul_ni(a1, c2))));
+    const Fq2 ti = Fq2::inv(t);
+    stc(f, 0, Fq2::mul_ni(c0, ti));
+    stc(f, 2, Fq2::mul_ni(c1, ti));
+    stc(f, 4, Fq2::mul_ni(c2, ti));
+    for (int k = 1; k < 6; k += 2) stc(f, k, Fq2::zero());
+  }
+
   // ---- pass A: the lines ---------------------------------------------------------------------------------------------
   struct Proj {
     Fq2 x, y, z;
@@ -267,8 +317,9 @@ pairing_lines_kernel(const Affine<typename Curve::Fq>* __restrict__ g1, const Af
 }
 
 // f_i = prod over the lines of pair i (squaring before every doubling line); partial[block] = prod of the block's f_i,
-// W12 plain dwords each.
-template <class Curve>
+// W12 plain dwords each.  PER_PAIR: no workgroup product; every pair's f_i stays in HBM instead, dword-transposed with the
+// stride of the lines (partial[d * stride + i]), for pairing_final_exp_kernel.
+template <class Curve, bool PER_PAIR = false>
 __global__ void __launch_bounds__(PAIR_LANES)
 pairing_accumulate_kernel(const Affine<typename Curve::Fq>* __restrict__ g1, const Affine<typename Curve::Fq2>* __restrict__ g2,
                           uint32_t n, uint32_t stride, typename PairingDev<Curve>::Consts k,
@@ -305,9 +356,14 @@ pairing_accumulate_kernel(const Affine<typename Curve::Fq>* __restrict__ g1, con
       g = lds + D::W12 * PAIR_LANES + lane;
     }
   }
-  D::block_product(f, g, lane);
-  if (lane == 0)
-    for (uint32_t d = 0; d < D::W12; d++) partial[(size_t)blockIdx.x * D::W12 + d] = f[d * PAIR_LANES];
+  if constexpr (PER_PAIR) {
+    if (i < n)
+      for (uint32_t d = 0; d < D::W12; d++) partial[(size_t)d * stride + i] = f[d * PAIR_LANES];
+  } else {
+    D::block_product(f, g, lane);
+    if (lane == 0)
+      for (uint32_t d = 0; d < D::W12; d++) partial[(size_t)blockIdx.x * D::W12 + d] = f[d * PAIR_LANES];
+  }
 }
 
 // out (W12 plain dwords) = prod of `count` partial products; one workgroup
@@ -328,6 +384,63 @@ pairing_product_kernel(const uint32_t* __restrict__ partial, uint32_t count, uin
   D::block_product(f, g, lane);
   if (lane == 0)
     for (uint32_t d = 0; d < D::W12; d++) out[d] = f[d * PAIR_LANES];
+}
+
+// GT of `groups` groups of group_len consecutive pairs, one lane per group: the product of the group's Miller values
+// (mill[d * stride + pair], as pairing_accumulate_kernel<Curve, true> leaves them), conjugated on BLS12-381 (x < 0), taken
+// through the program (easy part, then the exact hard exponent (q^4 - q^2 + 1) / r); the result is in buffer 0.
+// out_gt (may be NULL): W12 plain dwords per group in the order of ark355_multi_pairing (w^0, w^2, w^4, w^1, w^3, w^5);
+// verdict (may be NULL): 1 where the value equals target (W12 dwords, w^0 .. w^5) and bad (may be NULL) is not raised.
+template <class Curve>
+__global__ void __launch_bounds__(PAIR_LANES)
+pairing_final_exp_kernel(const uint32_t* __restrict__ mill, uint32_t stride, uint32_t groups, uint32_t group_len,
+                         const uint32_t* __restrict__ prog, uint32_t nsteps, const typename Curve::Fq2* __restrict__ frob,
+                         const uint32_t* __restrict__ target, const uint8_t* __restrict__ bad, uint32_t* __restrict__ out_gt,
+                         uint8_t* __restrict__ verdict) {
+  using D = PairingDev<Curve>;
+  __shared__ uint32_t lds[D::FE_BUFS * D::B12];
+  const uint32_t lane = threadIdx.x, grp = blockIdx.x * PAIR_LANES + lane;
+  if (grp >= groups) return;
+  uint32_t* const b0 = lds + lane;
+  {
+    uint32_t* f = b0;
+    uint32_t* g = b0 + D::B12;
+    D::set_one(f);
+    const uint32_t* in = mill + (size_t)grp * group_len;
+#pragma unroll 1
+    for (uint32_t j = 0; j < group_len; j++) {
+      D::mul12(g, f, in + j, (size_t)D::W2 * stride, stride);
+      uint32_t* t = f;
+      f = g;
+      g = t;
+    }
+    if (f != b0) D::copy12(b0, f);
+    if (!D::BN) D::conj12(b0);
+  }
+#pragma unroll 1
+  for (uint32_t s = 0; s < nsteps; s++) {
+    const uint32_t ins = prog[s], a = (ins >> 8) & 15u;
+    uint32_t* const pd = b0 + ((ins >> 4) & 15u) * D::B12;
+    const uint32_t* const pa = b0 + a * D::B12;
+    switch (ins & 15u) {
+      case D::FE_SQR: D::sqr12(pd, pa); break;
+      case D::FE_MUL: D::mul12(pd, pa, b0 + ((ins >> 12) & 15u) * D::B12, D::CK, PAIR_LANES); break;
+      case D::FE_COPY: D::copy12(pd, pa); break;
+      case D::FE_CONJ: D::conj12(pd); break;
+      case D::FE_FROB: D::frob12(pd, a, frob); break;
+      default: D::inv6(pd); break;
+    }
+  }
+  bool same = true;
+  for (uint32_t d = 0; d < D::W12; d++) same = same && b0[d * PAIR_LANES] == target[d];
+  if (verdict) verdict[grp] = same && !(bad && bad[grp]) ? 1 : 0;
+  if (out_gt) {
+    uint32_t* o = out_gt + (size_t)grp * D::W12;
+    for (uint32_t sl = 0; sl < 6; sl++) {
+      const uint32_t k = sl < 3 ? 2 * sl : 2 * (sl - 3) + 1;
+      for (uint32_t d = 0; d < D::W2; d++) o[sl * D::W2 + d] = b0[(k * D::W2 + d) * PAIR_LANES];
+    }
+  }
 }
 
 // out[j] = s[j] * P[j] in G1 (canonical scalars), affine: the rho_j A_j of batch verification
@@ -370,6 +483,66 @@ on_curve_kernel(const Affine<typename Curve::Fq>* __restrict__ g1, uint64_t n1, 
       cur = prev;
     }
   }
+}
+
+// the same equations, one byte per point: flags[i] = 1 where G1 point i / G2 point i - n1 is off its curve
+template <class Curve>
+__global__ void __launch_bounds__(128)
+on_curve_flags_kernel(const Affine<typename Curve::Fq>* __restrict__ g1, uint64_t n1, const Affine<typename Curve::Fq2>* __restrict__ g2,
+                      uint64_t n2, uint8_t* __restrict__ flags) {
+  using W = Wire<Curve>;
+  using Fq = typename Curve::Fq;
+  using Fq2 = typename Curve::Fq2;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n1 + n2) return;
+  bool good;
+  if (i < n1) {
+    const Affine<Fq> a = g1[i];
+    good = a.is_inf() || Fq::sqr_ni(a.y) == W::curve_rhs(a.x);
+  } else {
+    const Affine<Fq2> a = g2[i - n1];
+    good = a.is_inf() || Fq2::sqr_ni(a.y) == W::curve_rhs(a.x);
+  }
+  flags[i] = good ? 0 : 1;
+}
+
+// prod[j * m + i] = x_ji * gamma_abc_{i+1}: the terms of the prepared inputs of ark355_verify_each, one lane per product; the
+// public inputs arrive in Montgomery form and are made canonical here
+template <class Curve>
+__global__ void __launch_bounds__(128)
+prepared_input_terms_kernel(const Affine<typename Curve::Fq>* __restrict__ gamma_abc, const typename Curve::Fr* __restrict__ x,
+                            uint64_t count, uint32_t m, XYZZ<typename Curve::Fq>* __restrict__ prod) {
+  using Fq = typename Curve::Fq;
+  using Fr = typename Curve::Fr;
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= count * m) return;
+  const Fr k = Fr::from_mont(x[t]);
+  prod[t] = xyzz_mul_scalar(XYZZ<Fq>::from_affine(gamma_abc[1 + t % m]), k.l, Fr::N);
+}
+
+// one lane per proof: acc_j = gamma_abc_0 + sum_i prod[j * m + i], then the three pairs of the proof,
+// (A_j, B_j), (-acc_j, gamma), (-C_j, delta), at 3 j .. 3 j + 2 of p / q, and bad[j] from the flags of A_j, C_j, B_j
+// (ac = A_0 .. A_{count-1}, C_0 .. C_{count-1}; flags in the order on_curve_flags_kernel saw them: ac, then b)
+template <class Curve>
+__global__ void __launch_bounds__(128)
+verify_each_pairs_kernel(const Affine<typename Curve::Fq>* __restrict__ gamma_abc, const XYZZ<typename Curve::Fq>* __restrict__ prod,
+                         uint32_t m, const Affine<typename Curve::Fq>* __restrict__ ac, const Affine<typename Curve::Fq2>* __restrict__ b,
+                         const Affine<typename Curve::Fq2>* __restrict__ gamma_delta, const uint8_t* __restrict__ flags, uint64_t count,
+                         Affine<typename Curve::Fq>* __restrict__ p, Affine<typename Curve::Fq2>* __restrict__ q,
+                         uint8_t* __restrict__ bad) {
+  using Fq = typename Curve::Fq;
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  XYZZ<Fq> acc = XYZZ<Fq>::from_affine(gamma_abc[0]);
+  for (uint32_t i = 0; i < m; i++) acc = xyzz_add(acc, prod[j * m + i]);
+  const Affine<Fq> s = xyzz_to_affine(acc), c = ac[count + j];
+  p[3 * j] = ac[j];
+  p[3 * j + 1] = s.is_inf() ? s : Affine<Fq>::neg(s);
+  p[3 * j + 2] = c.is_inf() ? c : Affine<Fq>::neg(c);
+  q[3 * j] = b[j];
+  q[3 * j + 1] = gamma_delta[0];
+  q[3 * j + 2] = gamma_delta[1];
+  bad[j] = flags[j] | flags[count + j] | flags[2 * count + j];
 }
 
 }  // namespace ark355

@@ -14,7 +14,7 @@
 //                  (read when a key / base set is loaded through the context: the tables are built for them)
 //   per call       MSM_SEG, ACC_THREADS, NTT_RMAX, NTT_DIRECT_MAX, NTT_NOFUSE (A/B and test knobs of the kernels'
 //                  host drivers), CHECK_SATISFIED, H_EVAL (read at the first proof of a key), PAIRING_DEVICE, PAIRING_DEVICE_MIN (where the Miller loops of ark355_multi_pairing
-//                  and ark355_verify_batch run)
+//                  and ark355_verify_batch run), PAIRING_EACH_MIN (the same for ark355_pairing_groups and ark355_verify_each)
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -79,6 +79,8 @@ struct TunePolicy {
                                   // (pairing_impl.cuh), -1 (default) device when the call has at least pairing_device_min pairs
   int32_t pairing_device_min = 256;// measured crossover ("Device pairing"; profiles/pairing_bench.txt): the smallest measured pair
                                   // count from which the device route wins by 10 % at that count and every larger one, on the slower curve
+  int32_t pairing_each_min = 256; // the same rule for ark355_pairing_groups and ark355_verify_each, counted in groups / proofs: the host route
+                                  // pays one final exponentiation per group there (an estimate until its table is measured)
 
   struct Field {
     const char* name;
@@ -126,6 +128,7 @@ inline const TunePolicy::Field* TunePolicy::fields(int* count) {
       ARK_POLICY_FIELD32("H_EVAL", h_eval),
       ARK_POLICY_FIELD32("PAIRING_DEVICE", pairing_device),
       ARK_POLICY_FIELD32("PAIRING_DEVICE_MIN", pairing_device_min),
+      ARK_POLICY_FIELD32("PAIRING_EACH_MIN", pairing_each_min),
   };
   *count = (int)(sizeof(tab) / sizeof(tab[0]));
   return tab;

@@ -372,6 +372,42 @@ class Groth16:
         """The `alpha_g1_beta_g2` of ark-groth16's `PreparedVerifyingKey`: e(alpha_g1, beta_g2) in GT."""
         return self.multi_pairing([vk.alpha_g1], [vk.beta_g2])
 
+    def pairings(self, g1_points: Sequence[bytes], g2_points: Sequence[bytes], group_len: int = 1) -> list:
+        """`ark355_pairing_groups`: one GT value per group of `group_len` consecutive pairs (group_len = 1: ark-ec
+        `Pairing::pairing`, elementwise), each as `multi_pairing` returns it for those pairs alone."""
+        n = len(g1_points)
+        if n != len(g2_points) or group_len < 1 or n % group_len:
+            raise ValueError("pairings needs as many G1 as G2 points, a whole number of groups of them")
+        try:
+            gt, _ = self.lib.pairing_groups(self.ctx, self.curve.curve_id, b"".join(g1_points), b"".join(g2_points),
+                                            n // group_len, group_len)
+        except Ark355Error as e:
+            raise SynthesisError(str(e)) from e
+        w = 12 * self.sizes["fq"]
+        return [gt[k * w:(k + 1) * w] for k in range(n // group_len)]
+
+    def verify_each(self, vk: VerifyingKey, public_inputs, proofs) -> list:
+        """`ark355_verify_each`: `SNARK::verify` for every proof of ONE verifying key on its own -> list[bool].  No random
+        combination: each verdict is that proof's.  A wrong input length gives False for that proof."""
+        cv = self.curve
+        if len(public_inputs) != len(proofs):
+            raise ValueError("verify_each needs one list of public inputs per proof")
+        ell = len(vk.gamma_abc_g1) // self.sizes["g1"]
+        good = [j for j, x in enumerate(public_inputs) if len(x) + 1 == ell]
+        out = [False] * len(proofs)
+        if not good:
+            return out
+        xs = b"".join(cv.fr_mont(v) for j in good for v in public_inputs[j])
+        try:
+            oks = self.lib.verify_each(self.ctx, cv.curve_id,
+                                       (vk.alpha_g1, vk.beta_g2, vk.gamma_g2, vk.delta_g2, vk.gamma_abc_g1),
+                                       [(proofs[j].a, proofs[j].b, proofs[j].c) for j in good], xs)
+        except Ark355Error as e:
+            raise SynthesisError(str(e)) from e
+        for j, ok in zip(good, oks):
+            out[j] = ok
+        return out
+
     def verify_batch(self, vk: VerifyingKey, public_inputs, proofs, rng=None) -> bool:
         """`ark355_verify_batch`: all proofs of ONE verifying key checked with a random linear combination (count + 3
         Miller loops, one final exponentiation).  `rng` yields the 128-bit coefficients; required for more than one proof."""

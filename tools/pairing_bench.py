@@ -14,8 +14,17 @@ oracle-made proofs of one key, cycled, each with its own 128-bit rho.
 The last lines give, per curve and entry, the smallest size from which the device route is at least 10 % faster at that size
 and at every larger one: policy.h's PAIRING_DEVICE_MIN is that figure for the slower curve.
 
+--each measures the per-group entries by the same protocol: `ark355_pairing_groups(n, 1)` and `ark355_verify_each(n)`, host
+route (one final exponentiation per group on at most 16 host threads; run up to --host-max groups only, beyond that it is
+seconds per call) against device route (final exponentiations in pairing_final_exp_kernel), with the `ark355_verify_batch`
+device time of the same n proofs beside it: what a per-proof answer costs over a yes/no.  policy.h's PAIRING_EACH_MIN is the
+crossover of the slower curve and the slower entry.
+
 One child process per curve, each under its own `timeout`.  Dev tool; run on an MI355X:
   python tools/pairing_bench.py [--reps 5] [--out profiles/pairing_bench.txt]
+  python tools/pairing_bench.py --each [--reps 5] [--out profiles/pairing_each_bench.txt]
+  rocprofv3 --kernel-trace --stats --output-format csv -- python tools/pairing_bench.py --one-verify-each 4096
+                                      (one BLS12-381 verify_each, for profiles/pairing_each_kernel_stats.csv)
   rocprofv3 --kernel-trace --stats --output-format csv -- python tools/pairing_bench.py --one-verify 4096
                                       (one BLS12-381 verify_batch under the default policy, for profiles/pairing_kernel_stats.csv)"""
 import argparse
@@ -33,6 +42,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 SIZES = [1, 4, 16, 64, 256, 1024, 4096, 16384]
+EACH_SIZES = [1, 4, 16, 32, 64, 128, 256, 512, 1024, 4096]
 PHASE = re.compile(r"\[ark355\] (\w+) route=(\w+) pairs=(\d+) check_ms=([\d.]+) scalar_mul_ms=([\d.]+)"
                    r"(?: miller_ms=([\d.]+) final_exp_ms=([\d.]+))?")
 
@@ -123,6 +133,96 @@ def child(curve_name, reps, sizes):
     print("", flush=True)
 
 
+def child_each(curve_name, reps, sizes, host_max):
+    import snark_amd
+    import pairing_cases as P
+    from oracle import serialize as Z
+    from oracle.fields import BLS12_381, BN254
+    C = {"bls12_381": BLS12_381, "bn254": BN254}[curve_name]
+    lib = snark_amd.lib()
+    ctx = lib.ctx_create(0)
+    sz = lib.sizes(C.curve_id)
+    rnd = random.Random(71)
+    nmax = max(sizes)
+    a = [rnd.randrange(1, C.r) for _ in range(nmax)]
+    b = [rnd.randrange(1, C.r) for _ in range(nmax)]
+    g1, g2 = P.points_with_dlogs(lib, ctx, C, a, b, cross_check=1)
+    vk, proofs, inputs, _, _ = P.oracle_batch(C, 8)
+    rho = [Z.fr_canon(C, rnd.randrange(1, 1 << 128)) for _ in range(nmax)]
+    rows = []
+    for n in sizes:
+        p1, p2 = g1[:n * sz["g1"]], g2[:n * sz["g2"]]
+        ps = [proofs[j % 8] for j in range(n)]
+        xs = b"".join(inputs[j % 8] for j in range(n))
+        rh = rho[:n] if n > 1 else None
+
+        def pg(route):
+            lib.ctx_set_policy(ctx, "PAIRING_DEVICE", route)
+            return lib.pairing_groups(ctx, C.curve_id, p1, p2, n, 1)
+
+        def ve(route):
+            lib.ctx_set_policy(ctx, "PAIRING_DEVICE", route)
+            assert all(lib.verify_each(ctx, C.curve_id, vk, ps, xs))
+
+        def vb():
+            lib.ctx_set_policy(ctx, "PAIRING_DEVICE", 1)
+            assert lib.verify_batch(ctx, C.curve_id, vk, ps, xs, rh)
+
+        calls = [("pg_dev", lambda: pg(1)), ("ve_dev", lambda: ve(1)), ("vb_dev", vb)]
+        if n <= host_max:
+            calls += [("pg_host", lambda: pg(0)), ("ve_host", lambda: ve(0))]
+            assert pg(0) == pg(1)                      # warm-up of both routes, and they agree byte for byte
+            ve(0)
+        else:
+            pg(1)
+        ve(1)
+        vb()
+        t = {k: [] for k, _ in calls}
+        for _ in range(reps):
+            for k, f in calls:
+                t0 = time.perf_counter()
+                f()
+                t[k].append((time.perf_counter() - t0) * 1e3)
+        rows.append((n, {k: statistics.median(v) for k, v in t.items()}))
+    lib.ctx_destroy(ctx)
+    print("curve %s: ms per call, median of %d interleaved runs (host clock); speed-up = host / device" % (C.name, reps))
+    print("%7s | %11s %11s %8s | %11s %11s %8s | %11s %9s"
+          % ("n", "pg host", "pg device", "speed-up", "ve host", "ve device", "speed-up", "vb device", "ve / vb"))
+    nan = float("nan")
+    for n, med in rows:
+        ph, vh = med.get("pg_host", nan), med.get("ve_host", nan)
+        print("%7d | %11.3f %11.3f %8.2f | %11.3f %11.3f %8.2f | %11.3f %9.2f"
+              % (n, ph, med["pg_dev"], ph / med["pg_dev"], vh, med["ve_dev"], vh / med["ve_dev"], med["vb_dev"],
+                 med["ve_dev"] / med["vb_dev"]))
+    measured = [r for r in rows if "pg_host" in r[1]]
+    for entry, h, d in (("pairing_groups", "pg_host", "pg_dev"), ("verify_each", "ve_host", "ve_dev")):
+        cross = None
+        for n, med in reversed(measured):
+            if med[d] * 1.10 <= med[h]:
+                cross = n
+            else:
+                break
+        print("crossover %s %s: device route at least 10 %% faster from %s groups / proofs on" % (C.name, entry, cross))
+    print("", flush=True)
+
+
+def one_verify_each(count):
+    """one ark355_verify_each of `count` BLS12-381 proofs on the device route, in this process (for a kernel trace)"""
+    import snark_amd
+    import pairing_cases as P
+    from oracle.fields import BLS12_381 as C
+    lib = snark_amd.lib()
+    ctx = lib.ctx_create(0)
+    lib.ctx_set_policy(ctx, "PAIRING_DEVICE", 1)
+    vk, proofs, inputs, _, _ = P.oracle_batch(C, 8)
+    ps = [proofs[j % 8] for j in range(count)]
+    xs = b"".join(inputs[j % 8] for j in range(count))
+    ok = lib.verify_each(ctx, C.curve_id, vk, ps, xs)
+    lib.ctx_destroy(ctx)
+    print("verify_each of %d proofs: %d accepted" % (count, sum(ok)))
+    return 0 if all(ok) else 1
+
+
 def one_verify(count):
     """one ark355_verify_batch of `count` BLS12-381 proofs under the default policy, in this process (for a kernel trace)"""
     import snark_amd
@@ -151,18 +251,30 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None)
     ap.add_argument("--one-verify", type=int, default=0, metavar="COUNT")
+    ap.add_argument("--each", action="store_true", help="the per-group entries: pairing_groups(n, 1) and verify_each(n)")
+    ap.add_argument("--host-max", type=int, default=1024, help="--each: largest n the host route is run at")
+    ap.add_argument("--one-verify-each", type=int, default=0, metavar="COUNT")
     a = ap.parse_args()
     if a.one_verify:
         return one_verify(a.one_verify)
+    if a.one_verify_each:
+        return one_verify_each(a.one_verify_each)
+    if a.each and a.sizes == ",".join(str(s) for s in SIZES):
+        a.sizes = ",".join(str(s) for s in EACH_SIZES)
     sizes = [int(s) for s in a.sizes.split(",")]
     if a.child:
-        child(a.child, a.reps, sizes)
+        if a.each:
+            child_each(a.child, a.reps, sizes, a.host_max)
+        else:
+            child(a.child, a.reps, sizes)
         return 0
     text = []
     rc = 0
     for curve in a.curves.split(","):
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", curve,
                "--reps", str(a.reps), "--sizes", a.sizes]
+        if a.each:
+            cmd += ["--each", "--host-max", str(a.host_max)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         print(r.stdout, end="", flush=True)
         text.append(r.stdout)
@@ -173,7 +285,8 @@ def main():
     if a.out and rc == 0:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
-            f.write("pairing_bench: host route (PAIRING_DEVICE=0) against device route (PAIRING_DEVICE=1), one process per curve\n\n")
+            f.write("pairing_bench%s: host route (PAIRING_DEVICE=0) against device route (PAIRING_DEVICE=1), one process per curve\n\n"
+                    % (" --each" if a.each else ""))
             f.write("".join(text))
     return rc
 
