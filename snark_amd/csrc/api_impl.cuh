@@ -8,8 +8,7 @@
 #include "gr1cs_impl.cuh"
 #include "setup_impl.cuh"
 #include "wire_impl.cuh"
-#include "pairing_host.hpp"
-#include "pairing_impl.cuh"
+#include "verify_impl.cuh"
 
 namespace ark355 {
 
@@ -70,9 +69,7 @@ struct GenericScratch {
   MsmBuckets bk;
   DevBuf a, b, c;
   DevBuf rows;       // the 28-bit rows of a one-shot MSM's bases (msm_host)
-  DevBuf pg1, pg2, plines, ppart, pout, psc;      // device pairing (pairing_impl.cuh): points, lines, partial products, scalars
-  DevBuf pmill, pfe, pgt, pverd;                  // per-group pairings: Miller values of a chunk, program + constants, GT values, verdicts
-  DevBuf pabc, pprod, pflags;                     // ark355_verify_each: gamma_abc, the terms of the prepared inputs, per-point flags
+  PairingScratch pair;   // the device routes of the pairing entries (verify_impl.cuh)
 };
 
 template <class Curve>
@@ -705,704 +702,25 @@ struct Api {
     return pk_upload<Curve>(ctx->policy, &d, st);
   }
 
-  // ---- pairing (pairing_impl.cuh on the device, pairing_host.hpp on host threads) ------------------------------------
-  using PH = PairingHost<Curve>;
-  using PD = PairingDev<Curve>;
-  using Gt = typename PH::Fq12;
-
-  // policy PAIRING_DEVICE: 0 host threads, 1 device, -1 device from PAIRING_DEVICE_MIN pairs on
-  static bool pairing_on_device(const TunePolicy& pol, uint64_t pairs) {
-    if (pol.pairing_device == 0) return false;
-    if (pol.pairing_device > 0) return true;
-    return pairs >= (uint64_t)std::max<int64_t>(pol.pairing_device_min, 0);
-  }
-  static unsigned host_threads() {
-    unsigned nt = std::thread::hardware_concurrency();
-    if (nt == 0) nt = 4;
-    return nt > 16 ? 16 : nt;
-  }
-  static double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  }
-
-  // prod_i miller_loop(P_i, Q_i) on host threads (the loop of PairingHost::product_is_one, value kept)
-  static Gt miller_product_host(const std::vector<Affine<Fq>>& Ps, const std::vector<Affine<Fq2>>& Qs) {
-    const size_t n = Ps.size();
-    const unsigned threads = (unsigned)std::min<size_t>(host_threads(), n);
-    std::vector<Gt> part(threads ? threads : 1, Gt::one());
-    (void)PH::consts();
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < threads; t++)
-      th.emplace_back([&, t] {
-        Gt acc = Gt::one();
-        for (size_t i = t; i < n; i += threads) acc = Gt::mul(acc, PH::miller_loop(Ps[i], Qs[i]));
-        part[t] = acc;
-      });
-    for (auto& x : th) x.join();
-    Gt f = Gt::one();
-    for (const auto& p : part) f = Gt::mul(f, p);
-    return f;
-  }
-
-  // y^2 = x^3 + b on the device for n1 + n2 resident points; returns the kernel's word (0: all on their curves)
-  static unsigned long long on_curve_dev(GenericScratch& g, const void* d_g1, uint64_t n1, const void* d_g2, uint64_t n2,
-                                         hipStream_t st) {
-    if (n1 + n2 == 0) return 0;
-    g.c.ensure(8);
-    ARK_CHECK_HIP(hipMemsetAsync(g.c.p, 0, 8, st));
-    ARK_LAUNCH((on_curve_kernel<Curve>), dim3((uint32_t)((n1 + n2 + 127) / 128)), dim3(128), 0, st,
-               reinterpret_cast<const Affine<Fq>*>(d_g1), n1, reinterpret_cast<const Affine<Fq2>*>(d_g2), n2,
-               g.c.as<unsigned long long>());
-    ARK_CHECK_LAUNCH();
-    unsigned long long e = 0;
-    ARK_CHECK_HIP(hipMemcpyAsync(&e, g.c.p, 8, hipMemcpyDeviceToHost, st));
-    ARK_CHECK_HIP(hipStreamSynchronize(st));
-    return e;
-  }
-
-  // prod_i miller_loop(P_i, Q_i) for n resident pairs (g.pg1 / g.pg2), every point on its curve.  At most PAIR_CHUNK pairs
-  // have their lines in HBM at a time (about 20 KB per pair); the partial products of all chunks meet in one last launch.
-  static constexpr uint64_t PAIR_CHUNK = 1u << 15;
-  static Gt multi_miller_dev(GenericScratch& g, const Affine<Fq>* d1, const Affine<Fq2>* d2, uint64_t n, hipStream_t st) {
-    if (n == 0) return Gt::one();
-    typename PD::Consts k{};
-    PD::schedule(&k);
-    k.two_inv = Fq::inv(Fq::add(Fq::one(), Fq::one()));
-    k.frob_x = PH::consts().frob_x;
-    k.frob_y = PH::consts().frob_y;
-    const uint64_t blocks_total = (n + PAIR_LANES - 1) / PAIR_LANES;
-    const uint64_t cap = std::min<uint64_t>(n, PAIR_CHUNK);
-    const uint32_t stride = (uint32_t)((cap + PAIR_LANES - 1) / PAIR_LANES * PAIR_LANES);
-    g.plines.ensure((size_t)k.steps * 3 * PD::W2 * stride * sizeof(uint32_t));
-    g.ppart.ensure(blocks_total * PD::W12 * sizeof(uint32_t));
-    g.pout.ensure(PD::W12 * sizeof(uint32_t));
-    for (uint64_t off = 0; off < n; off += PAIR_CHUNK) {
-      const uint32_t m = (uint32_t)std::min<uint64_t>(PAIR_CHUNK, n - off);
-      const dim3 grid((m + PAIR_LANES - 1) / PAIR_LANES);
-      ARK_LAUNCH((pairing_lines_kernel<Curve>), grid, dim3(PAIR_LANES), 0, st, d1 + off, d2 + off, m, stride, k,
-                 g.plines.template as<uint32_t>());
-      ARK_CHECK_LAUNCH();
-      ARK_LAUNCH((pairing_accumulate_kernel<Curve>), grid, dim3(PAIR_LANES), 0, st, d1 + off, d2 + off, m, stride, k,
-                 (const uint32_t*)g.plines.template as<uint32_t>(), g.ppart.template as<uint32_t>() + (off / PAIR_LANES) * PD::W12);
-      ARK_CHECK_LAUNCH();
-    }
-    ARK_LAUNCH((pairing_product_kernel<Curve>), dim3(1), dim3(PAIR_LANES), 0, st, (const uint32_t*)g.ppart.template as<uint32_t>(),
-               (uint32_t)blocks_total, g.pout.template as<uint32_t>());
-    ARK_CHECK_LAUNCH();
-    Fq2 c[6];
-    ARK_CHECK_HIP(hipMemcpyAsync(c, g.pout.p, sizeof(c), hipMemcpyDeviceToHost, st));
-    ARK_CHECK_HIP(hipStreamSynchronize(st));
-    // coefficients of w^0 .. w^5 -> the tower of pairing_host.hpp (v = w^2)
-    Gt f{{c[0], c[2], c[4]}, {c[1], c[3], c[5]}};
-    return BN ? f : Gt::conj(f);      // BLS12-381: x < 0
-  }
-  static constexpr bool BN = Curve::ID == ARK355_BN254;
-
-  static Gt final_exp(const Gt& f) {
-    ARK_REQUIRE(!PH::consts().final_exp.l.empty(), ARK355_EINVAL, "the final exponent could not be formed");
-    return PH::final_exponentiation(f);
-  }
-  static void trace_pairing(const ark355_ctx* ctx, const char* what, int device, uint64_t n, double check_ms, double mul_ms,
-                            double miller_ms, double fe_ms) {
-    if (ctx->policy.trace_host)
-      fprintf(stderr, "[ark355] %s route=%s pairs=%llu check_ms=%.3f scalar_mul_ms=%.3f miller_ms=%.3f final_exp_ms=%.3f\n", what,
-              device ? "device" : "host", (unsigned long long)n, check_ms, mul_ms, miller_ms, fe_ms);
-  }
-
-  // ark-ec Pairing::multi_pairing over raw affine images
+  // ---- pairings and verification (verify_impl.cuh) -----------------------------------------------------------------------
   static void multi_pairing(ark355_ctx* ctx, GenericScratch& g, const uint8_t* g1, const uint8_t* g2, uint64_t n, uint8_t* out_gt,
                             int32_t* is_one) {
-    hipStream_t st = ctx->stream;
-    const bool dev = n > 0 && pairing_on_device(ctx->policy, n);
-    const double t0 = now_ms();
-    double t1 = t0;
-    Gt f = Gt::one();
-    auto refuse = [](int group, uint64_t idx) {
-      throw HipError{ARK355_EINVAL, std::string(group == 1 ? "g1[" : "g2[") + std::to_string(idx) + "]: point not on curve"};
-    };
-    if (dev) {
-      g.pg1.ensure(n * sizeof(Affine<Fq>));
-      g.pg2.ensure(n * sizeof(Affine<Fq2>));
-      ARK_CHECK_HIP(hipMemcpyAsync(g.pg1.p, g1, n * sizeof(Affine<Fq>), hipMemcpyHostToDevice, st));
-      ARK_CHECK_HIP(hipMemcpyAsync(g.pg2.p, g2, n * sizeof(Affine<Fq2>), hipMemcpyHostToDevice, st));
-      const unsigned long long e = on_curve_dev(g, g.pg1.p, n, g.pg2.p, n, st);
-      if (e) refuse((int)(e & 15), (e >> 4) - 1);
-      t1 = now_ms();
-      f = multi_miller_dev(g, g.pg1.template as<Affine<Fq>>(), g.pg2.template as<Affine<Fq2>>(), n, st);
-    } else if (n > 0) {
-      std::vector<Affine<Fq>> Ps(n);
-      std::vector<Affine<Fq2>> Qs(n);
-      memcpy(Ps.data(), g1, n * sizeof(Affine<Fq>));
-      memcpy(Qs.data(), g2, n * sizeof(Affine<Fq2>));
-      for (uint64_t i = 0; i < n; i++) {
-        if (!Ps[i].is_inf() && !(Fq::sqr_ni(Ps[i].y) == W::curve_rhs(Ps[i].x))) refuse(1, i);
-        if (!Qs[i].is_inf() && !(Fq2::sqr_ni(Qs[i].y) == W::curve_rhs(Qs[i].x))) refuse(2, i);
-      }
-      t1 = now_ms();
-      f = miller_product_host(Ps, Qs);
-    }
-    const double t2 = now_ms();
-    const Gt gt = final_exp(f);
-    trace_pairing(ctx, "multi_pairing", dev, n, t1 - t0, 0.0, t2 - t1, now_ms() - t2);
-    if (out_gt) memcpy(out_gt, &gt, sizeof(gt));
-    if (is_one) *is_one = gt == Gt::one() ? 1 : 0;
+    Verify<Curve>{ctx, g.pair, g.c}.multi_pairing(g1, g2, n, out_gt, is_one);
   }
-
-  // ---- per-group pairings: ark355_pairing_groups, ark355_verify_each ----------------------------------------------------
-  // policy PAIRING_DEVICE as above; "by size" reads PAIRING_EACH_MIN, counted in groups / proofs (the host pays one final
-  // exponentiation per group here, so the crossover is not that of the entries above)
-  static bool each_on_device(const TunePolicy& pol, uint64_t units) {
-    if (pol.pairing_device == 0) return false;
-    if (pol.pairing_device > 0) return true;
-    return units >= (uint64_t)std::max<int64_t>(pol.pairing_each_min, 0);
-  }
-
-  // The program pairing_final_exp_kernel follows (instruction set: PairingDev::FeOp).  Buffer 0 holds f on entry and
-  // f^((q^12 - 1) / r) on exit; the buffers in between are handed out here, so that the kernel needs no more than FE_BUFS.
-  struct FeProgram {
-    std::vector<uint32_t> code;
-    uint32_t free_mask = (1u << PD::FE_BUFS) - 1u;
-    uint32_t take() {
-      for (uint32_t b = 0; b < PD::FE_BUFS; b++)
-        if ((free_mask >> b) & 1u) {
-          free_mask &= ~(1u << b);
-          return b;
-        }
-      throw HipError{ARK355_EINVAL, "final exponentiation program: out of buffers"};
-    }
-    void drop(uint32_t b) { free_mask |= 1u << b; }
-    void drop(uint32_t a, uint32_t b) { drop(a), drop(b); }
-    uint32_t sqr(uint32_t a) {
-      const uint32_t d = take();
-      code.push_back(PD::fe_ins(PD::FE_SQR, d, a));
-      return d;
-    }
-    uint32_t mul(uint32_t a, uint32_t b) {
-      const uint32_t d = take();
-      code.push_back(PD::fe_ins(PD::FE_MUL, d, a, b));
-      return d;
-    }
-    uint32_t copy(uint32_t a) {
-      const uint32_t d = take();
-      code.push_back(PD::fe_ins(PD::FE_COPY, d, a));
-      return d;
-    }
-    void conj(uint32_t d) { code.push_back(PD::fe_ins(PD::FE_CONJ, d)); }
-    void frob(uint32_t d, uint32_t n) { code.push_back(PD::fe_ins(PD::FE_FROB, d, n)); }
-    void inv6(uint32_t d) { code.push_back(PD::fe_ins(PD::FE_INV6, d)); }
-    // a new buffer with base^e (e > 0), square-and-multiply from the top bit; base stays.  Base, result and one more buffer.
-    uint32_t pow(uint32_t base, unsigned __int128 e) {
-      int top = 127;
-      while (!((e >> top) & 1)) top--;
-      uint32_t acc = copy(base);
-      for (int i = top - 1; i >= 0; i--) {
-        uint32_t t = sqr(acc);
-        drop(acc);
-        acc = t;
-        if ((e >> i) & 1) {
-          t = mul(acc, base);
-          drop(acc);
-          acc = t;
-        }
-      }
-      return acc;
-    }
-  };
-
-  static const std::vector<uint32_t>& fe_program() {
-    static const std::vector<uint32_t> prog = [] {
-      FeProgram p;
-      const uint32_t f = p.take();                       // buffer 0: the conjugated Miller product
-      // easy part: f^(q^6 - 1) = conj(f) / f with 1 / f = conj(f) / (f conj(f)) and f conj(f) in F_q6; then ^(q^2 + 1)
-      const uint32_t c = p.copy(f);
-      p.conj(c);
-      const uint32_t n = p.mul(f, c);
-      p.drop(f);
-      p.inv6(n);
-      const uint32_t fi = p.mul(c, n);
-      p.drop(n);
-      const uint32_t f1 = p.mul(c, fi);
-      p.drop(c, fi);
-      const uint32_t g = p.copy(f1);
-      p.frob(g, 2);
-      const uint32_t m = p.mul(g, f1);
-      p.drop(g, f1);
-      // hard part: the exact exponent (q^4 - q^2 + 1) / r; from here on an inverse is a conjugation
-      uint32_t res;
-      if (!BN) {
-        // ((x - 1)^2 / 3) (x + q) (x^2 + q^2 - 1) + 1,  x = -X
-        const unsigned __int128 X = 0xd201000000010000ull, C3 = (X + 1) * (X + 1) / 3;
-        const uint32_t y0 = p.pow(m, C3);
-        uint32_t t = p.pow(y0, X);
-        p.conj(t);                                       // y0^x
-        p.frob(y0, 1);
-        const uint32_t y1 = p.mul(t, y0);                // y0^(x + q)
-        p.drop(t, y0);
-        const uint32_t u = p.copy(y1);
-        p.frob(u, 2);
-        p.conj(y1);
-        const uint32_t v = p.mul(u, y1);                 // y1^(q^2 - 1)
-        p.conj(y1);
-        p.drop(u);
-        const uint32_t vm = p.mul(v, m);
-        p.drop(v, m);
-        t = p.pow(y1, X);
-        p.drop(y1);
-        const uint32_t t2 = p.pow(t, X);                 // y1^(x^2): the two signs cancel
-        p.drop(t);
-        res = p.mul(t2, vm);
-        p.drop(t2, vm);
-      } else {
-        // q^3 + (6 x^2 + 1) q^2 + (-36 x^3 - 18 x^2 - 12 x + 1) q + (-36 x^3 - 30 x^2 - 18 x - 2), by Horner in x:
-        // ((-36 (q + 1) x + (6 q^2 - 18 q - 30)) x + (-12 q - 18)) x + (q^3 + q^2 + q - 2)
-        const unsigned __int128 X = 4965661367192848881ull;
-        uint32_t u = p.copy(m);
-        p.frob(u, 1);
-        uint32_t t = p.mul(u, m);
-        p.drop(u);
-        uint32_t r = p.pow(t, 36);
-        p.drop(t);
-        p.conj(r);                                       // m^(-36 (q + 1))
-        uint32_t P = p.pow(r, X);
-        p.drop(r);
-        {                                                // * (m^(q^2) / (m^(3 q) m^5))^6
-          u = p.copy(m);
-          p.frob(u, 1);
-          const uint32_t u3 = p.pow(u, 3);
-          p.drop(u);
-          const uint32_t m5 = p.pow(m, 5);
-          const uint32_t v = p.mul(u3, m5);
-          p.drop(u3, m5);
-          p.conj(v);
-          const uint32_t w = p.copy(m);
-          p.frob(w, 2);
-          const uint32_t s = p.mul(w, v);
-          p.drop(w, v);
-          const uint32_t s6 = p.pow(s, 6);
-          p.drop(s);
-          r = p.mul(P, s6);
-          p.drop(P, s6);
-        }
-        P = p.pow(r, X);
-        p.drop(r);
-        {                                                // / (m^(2 q) m^3)^6
-          u = p.copy(m);
-          p.frob(u, 1);
-          const uint32_t u2 = p.sqr(u);
-          p.drop(u);
-          const uint32_t m3 = p.pow(m, 3);
-          const uint32_t v = p.mul(u2, m3);
-          p.drop(u2, m3);
-          const uint32_t s6 = p.pow(v, 6);
-          p.drop(v);
-          p.conj(s6);
-          r = p.mul(P, s6);
-          p.drop(P, s6);
-        }
-        P = p.pow(r, X);
-        p.drop(r);
-        {                                                // * m^(q^3) m^(q^2) m^q / m^2
-          const uint32_t a = p.copy(m);
-          p.frob(a, 1);
-          const uint32_t b = p.copy(m);
-          p.frob(b, 2);
-          const uint32_t ab = p.mul(a, b);
-          p.drop(a, b);
-          const uint32_t c3 = p.copy(m);
-          p.frob(c3, 3);
-          const uint32_t abc = p.mul(ab, c3);
-          p.drop(ab, c3);
-          const uint32_t m2 = p.sqr(m);
-          p.drop(m);
-          p.conj(m2);
-          const uint32_t s0 = p.mul(abc, m2);
-          p.drop(abc, m2);
-          res = p.mul(P, s0);
-          p.drop(P, s0);
-        }
-      }
-      if (res != 0) p.code.push_back(PD::fe_ins(PD::FE_COPY, 0, res));
-      return p.code;
-    }();
-    return prog;
-  }
-
-  // GT in the kernels' order, the coefficients of w^0 .. w^5
-  static void gt_to_coeffs(const Gt& t, Fq2 c[6]) {
-    c[0] = t.c0.c0, c[2] = t.c0.c1, c[4] = t.c0.c2;
-    c[1] = t.c1.c0, c[3] = t.c1.c1, c[5] = t.c1.c2;
-  }
-
-  // GT of `groups` groups of group_len consecutive resident pairs (every point on its curve, or its group marked in d_bad).
-  // out_gt: groups x 12 Fq (host, may be NULL); verdict: groups bytes (host), 1 where GT == target and the group is not bad.
-  // A chunk of at most PAIR_CHUNK pairs (whole groups) has its lines and Miller values in HBM at a time.
-  static void groups_dev(GenericScratch& g, const Affine<Fq>* d1, const Affine<Fq2>* d2, uint64_t groups, uint32_t group_len,
-                         const Gt& target, const uint8_t* d_bad, uint8_t* out_gt, uint8_t* verdict, hipStream_t st) {
-    typename PD::Consts k{};
-    PD::schedule(&k);
-    k.two_inv = Fq::inv(Fq::add(Fq::one(), Fq::one()));
-    k.frob_x = PH::consts().frob_x;
-    k.frob_y = PH::consts().frob_y;
-    const std::vector<uint32_t>& prog = fe_program();
-    // program + constants: 18 Frobenius constants, the target, the instructions
-    const size_t frob_bytes = 18 * sizeof(Fq2), tgt_bytes = PD::W12 * sizeof(uint32_t);
-    std::vector<uint8_t> blob(frob_bytes + tgt_bytes + prog.size() * sizeof(uint32_t));
-    memcpy(blob.data(), PH::consts().frob12, frob_bytes);
-    Fq2 tc[6];
-    gt_to_coeffs(target, tc);
-    memcpy(blob.data() + frob_bytes, tc, tgt_bytes);
-    memcpy(blob.data() + frob_bytes + tgt_bytes, prog.data(), prog.size() * sizeof(uint32_t));
-    g.pfe.ensure(blob.size());
-    ARK_CHECK_HIP(hipMemcpyAsync(g.pfe.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    const Fq2* d_frob = g.pfe.template as<Fq2>();
-    const uint32_t* d_tgt = reinterpret_cast<const uint32_t*>(g.pfe.template as<uint8_t>() + frob_bytes);
-    const uint32_t* d_prog = d_tgt + PD::W12;
-
-    const uint64_t chunk_groups = PAIR_CHUNK / group_len;
-    const uint64_t cap = std::min<uint64_t>(groups, chunk_groups) * group_len;
-    const uint32_t stride = (uint32_t)((cap + PAIR_LANES - 1) / PAIR_LANES * PAIR_LANES);
-    g.plines.ensure((size_t)k.steps * 3 * PD::W2 * stride * sizeof(uint32_t));
-    g.pmill.ensure((size_t)PD::W12 * stride * sizeof(uint32_t));
-    if (out_gt) g.pgt.ensure(groups * PD::W12 * sizeof(uint32_t));
-    g.pverd.ensure(groups);
-    for (uint64_t g0 = 0; g0 < groups; g0 += chunk_groups) {
-      const uint32_t ng = (uint32_t)std::min<uint64_t>(chunk_groups, groups - g0), m = ng * group_len;
-      const uint64_t off = g0 * group_len;
-      const dim3 grid((m + PAIR_LANES - 1) / PAIR_LANES);
-      ARK_LAUNCH((pairing_lines_kernel<Curve>), grid, dim3(PAIR_LANES), 0, st, d1 + off, d2 + off, m, stride, k,
-                 g.plines.template as<uint32_t>());
-      ARK_CHECK_LAUNCH();
-      ARK_LAUNCH((pairing_accumulate_kernel<Curve, true>), grid, dim3(PAIR_LANES), 0, st, d1 + off, d2 + off, m, stride, k,
-                 (const uint32_t*)g.plines.template as<uint32_t>(), g.pmill.template as<uint32_t>());
-      ARK_CHECK_LAUNCH();
-      ARK_LAUNCH((pairing_final_exp_kernel<Curve>), dim3((ng + PAIR_LANES - 1) / PAIR_LANES), dim3(PAIR_LANES), 0, st,
-                 (const uint32_t*)g.pmill.template as<uint32_t>(), stride, ng, group_len, d_prog, (uint32_t)prog.size(), d_frob,
-                 d_tgt, d_bad ? d_bad + g0 : nullptr, out_gt ? g.pgt.template as<uint32_t>() + g0 * PD::W12 : nullptr,
-                 g.pverd.template as<uint8_t>() + g0);
-      ARK_CHECK_LAUNCH();
-    }
-    if (out_gt) ARK_CHECK_HIP(hipMemcpyAsync(out_gt, g.pgt.p, groups * PD::W12 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    ARK_CHECK_HIP(hipMemcpyAsync(verdict, g.pverd.p, groups, hipMemcpyDeviceToHost, st));
-    ARK_CHECK_HIP(hipStreamSynchronize(st));
-  }
-
-  // `units` independent jobs on at most 16 host threads
-  template <class Fn>
-  static void host_each(uint64_t units, Fn&& fn) {
-    const unsigned threads = (unsigned)std::min<uint64_t>(host_threads(), units);
-    (void)PH::consts();
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < threads; t++)
-      th.emplace_back([&, t] {
-        for (uint64_t u = t; u < units; u += threads) fn(u);
-      });
-    for (auto& x : th) x.join();
-  }
-
-  // ark-ec Pairing::pairing per group of group_len consecutive pairs
   static void pairing_groups(ark355_ctx* ctx, GenericScratch& g, const uint8_t* g1, const uint8_t* g2, uint64_t groups,
                              uint32_t group_len, uint8_t* out_gt, uint8_t* is_one) {
-    ARK_REQUIRE(group_len >= 1 && group_len <= ARK355_PAIRING_GROUP_MAX, ARK355_EINVAL,
-                "group_len must be 1 .. 64 (one long product is ark355_multi_pairing's)");
-    if (groups == 0) return;
-    ARK_REQUIRE(groups <= 0xFFFFFFFFull / group_len, ARK355_EINVAL, "groups * group_len must stay below 2^32");
-    ARK_REQUIRE(g1 && g2, ARK355_EINVAL, "a point array is NULL");
-    ARK_REQUIRE(!PH::consts().final_exp.l.empty(), ARK355_EINVAL, "the final exponent could not be formed");
-    hipStream_t st = ctx->stream;
-    const uint64_t n = groups * group_len;
-    const bool dev = each_on_device(ctx->policy, groups);
-    const double t0 = now_ms();
-    double t1 = t0;
-    auto refuse = [](int group, uint64_t idx) {
-      throw HipError{ARK355_EINVAL, std::string(group == 1 ? "g1[" : "g2[") + std::to_string(idx) + "]: point not on curve"};
-    };
-    std::vector<uint8_t> verdict(groups);
-    if (dev) {
-      g.pg1.ensure(n * sizeof(Affine<Fq>));
-      g.pg2.ensure(n * sizeof(Affine<Fq2>));
-      ARK_CHECK_HIP(hipMemcpyAsync(g.pg1.p, g1, n * sizeof(Affine<Fq>), hipMemcpyHostToDevice, st));
-      ARK_CHECK_HIP(hipMemcpyAsync(g.pg2.p, g2, n * sizeof(Affine<Fq2>), hipMemcpyHostToDevice, st));
-      const unsigned long long e = on_curve_dev(g, g.pg1.p, n, g.pg2.p, n, st);
-      if (e) refuse((int)(e & 15), (e >> 4) - 1);
-      t1 = now_ms();
-      groups_dev(g, g.pg1.template as<Affine<Fq>>(), g.pg2.template as<Affine<Fq2>>(), groups, group_len, Gt::one(), nullptr,
-                 out_gt, verdict.data(), st);
-    } else {
-      const Affine<Fq>* Ps = reinterpret_cast<const Affine<Fq>*>(g1);
-      const Affine<Fq2>* Qs = reinterpret_cast<const Affine<Fq2>*>(g2);
-      for (uint64_t i = 0; i < n; i++) {
-        Affine<Fq> P;
-        Affine<Fq2> Q;
-        memcpy(&P, Ps + i, sizeof(P));
-        memcpy(&Q, Qs + i, sizeof(Q));
-        if (!P.is_inf() && !(Fq::sqr_ni(P.y) == W::curve_rhs(P.x))) refuse(1, i);
-        if (!Q.is_inf() && !(Fq2::sqr_ni(Q.y) == W::curve_rhs(Q.x))) refuse(2, i);
-      }
-      t1 = now_ms();
-      host_each(groups, [&](uint64_t k) {
-        Gt f = Gt::one();
-        for (uint32_t j = 0; j < group_len; j++) {
-          Affine<Fq> P;
-          Affine<Fq2> Q;
-          memcpy(&P, Ps + k * group_len + j, sizeof(P));
-          memcpy(&Q, Qs + k * group_len + j, sizeof(Q));
-          f = Gt::mul(f, PH::miller_loop(P, Q));
-        }
-        const Gt gt = PH::final_exponentiation(f);
-        if (out_gt) memcpy(out_gt + k * sizeof(Gt), &gt, sizeof(gt));
-        verdict[k] = gt == Gt::one() ? 1 : 0;
-      });
-    }
-    if (is_one) memcpy(is_one, verdict.data(), groups);
-    trace_pairing(ctx, "pairing_groups", dev, n, t1 - t0, 0.0, now_ms() - t1, 0.0);
+    Verify<Curve>{ctx, g.pair, g.c}.pairing_groups(g1, g2, groups, group_len, out_gt, is_one);
   }
-
-  // ark-groth16 verify_proof for every proof of one key on its own: e(A_j, B_j) e(-acc_j, gamma) e(-C_j, delta) == e(alpha, beta)
   static void verify_each(ark355_ctx* ctx, GenericScratch& g, const ark355_vk_desc* vk, const ark355_proof_raw* proofs,
                           const uint8_t* inputs, uint64_t count, uint8_t* ok) {
-    const uint64_t ell = vk->num_instance;
-    ARK_REQUIRE(ell >= 1, ARK355_EINVAL, "empty key");
-    if (count == 0) return;
-    ARK_REQUIRE(ell == 1 || inputs, ARK355_EINVAL, "public_inputs is NULL");
-    ARK_REQUIRE(count <= 0xFFFFFFFFull / 3, ARK355_EINVAL, "3 * count must stay below 2^32");
-    ARK_REQUIRE(!PH::consts().final_exp.l.empty(), ARK355_EINVAL, "the final exponent could not be formed");
-    const uint32_t m = (uint32_t)(ell - 1);
-    auto g1_of = [](const uint8_t* p) {
-      Affine<Fq> a;
-      memcpy(&a, p, sizeof(a));
-      return a;
-    };
-    auto g2_of = [](const uint8_t* p) {
-      Affine<Fq2> a;
-      memcpy(&a, p, sizeof(a));
-      return a;
-    };
-    auto on1 = [](const Affine<Fq>& a) { return a.is_inf() || Fq::sqr_ni(a.y) == W::curve_rhs(a.x); };
-    auto on2 = [](const Affine<Fq2>& a) { return a.is_inf() || Fq2::sqr_ni(a.y) == W::curve_rhs(a.x); };
-    // the key's own points, once
-    const double t0 = now_ms();
-    const Affine<Fq> alpha = g1_of(vk->alpha_g1);
-    const Affine<Fq2> beta = g2_of(vk->beta_g2), gamma = g2_of(vk->gamma_g2), delta = g2_of(vk->delta_g2);
-    ARK_REQUIRE(on1(alpha), ARK355_EINVAL, "vk.alpha_g1: point not on curve");
-    ARK_REQUIRE(on2(beta), ARK355_EINVAL, "vk.beta_g2: point not on curve");
-    ARK_REQUIRE(on2(gamma), ARK355_EINVAL, "vk.gamma_g2: point not on curve");
-    ARK_REQUIRE(on2(delta), ARK355_EINVAL, "vk.delta_g2: point not on curve");
-    std::vector<Affine<Fq>> abc(ell);
-    memcpy(abc.data(), vk->gamma_abc_g1, ell * sizeof(Affine<Fq>));
-    for (uint64_t i = 0; i < ell; i++)
-      if (!on1(abc[i])) throw HipError{ARK355_EINVAL, "vk.gamma_abc_g1[" + std::to_string(i) + "]: point not on curve"};
-    const Gt target = PH::final_exponentiation(PH::miller_loop(alpha, beta));
-    const double t1 = now_ms();
-    const bool dev = each_on_device(ctx->policy, count);
-    if (dev) {
-      hipStream_t st = ctx->stream;
-      // g.pg1 = A_0 .. A_{count-1}, C_0 .. C_{count-1}, then the 3 count first arguments; g.pg2 = B_j, the 3 count second
-      // arguments, gamma, delta
-      std::vector<Affine<Fq>> ac(2 * count);
-      std::vector<Affine<Fq2>> bs(count);
-      for (uint64_t j = 0; j < count; j++) {
-        ac[j] = g1_of(proofs[j].a);
-        ac[count + j] = g1_of(proofs[j].c);
-        bs[j] = g2_of(proofs[j].b);
-      }
-      const Affine<Fq2> gd[2] = {gamma, delta};
-      g.pg1.ensure(5 * count * sizeof(Affine<Fq>));
-      g.pg2.ensure((4 * count + 2) * sizeof(Affine<Fq2>));
-      g.pabc.ensure(ell * sizeof(Affine<Fq>));
-      g.pflags.ensure(4 * count);
-      Affine<Fq>* d_ac = g.pg1.template as<Affine<Fq>>();
-      Affine<Fq2>* d_b = g.pg2.template as<Affine<Fq2>>();
-      uint8_t* d_flags = g.pflags.template as<uint8_t>();
-      ARK_CHECK_HIP(hipMemcpyAsync(d_ac, ac.data(), 2 * count * sizeof(Affine<Fq>), hipMemcpyHostToDevice, st));
-      ARK_CHECK_HIP(hipMemcpyAsync(d_b, bs.data(), count * sizeof(Affine<Fq2>), hipMemcpyHostToDevice, st));
-      ARK_CHECK_HIP(hipMemcpyAsync(d_b + 4 * count, gd, sizeof(gd), hipMemcpyHostToDevice, st));
-      ARK_CHECK_HIP(hipMemcpyAsync(g.pabc.p, abc.data(), ell * sizeof(Affine<Fq>), hipMemcpyHostToDevice, st));
-      ARK_LAUNCH((on_curve_flags_kernel<Curve>), dim3((uint32_t)((3 * count + 127) / 128)), dim3(128), 0, st,
-                 (const Affine<Fq>*)d_ac, 2 * count, (const Affine<Fq2>*)d_b, count, d_flags);
-      ARK_CHECK_LAUNCH();
-      if (m) {
-        g.psc.ensure(count * m * sizeof(Fr));
-        g.pprod.ensure(count * m * sizeof(XYZZ<Fq>));
-        ARK_CHECK_HIP(hipMemcpyAsync(g.psc.p, inputs, count * m * sizeof(Fr), hipMemcpyHostToDevice, st));
-        ARK_LAUNCH((prepared_input_terms_kernel<Curve>), dim3((uint32_t)((count * m + 127) / 128)), dim3(128), 0, st,
-                   (const Affine<Fq>*)g.pabc.template as<Affine<Fq>>(), (const Fr*)g.psc.template as<Fr>(), count, m,
-                   g.pprod.template as<XYZZ<Fq>>());
-        ARK_CHECK_LAUNCH();
-      }
-      ARK_LAUNCH((verify_each_pairs_kernel<Curve>), dim3((uint32_t)((count + 127) / 128)), dim3(128), 0, st,
-                 (const Affine<Fq>*)g.pabc.template as<Affine<Fq>>(), (const XYZZ<Fq>*)g.pprod.template as<XYZZ<Fq>>(), m,
-                 (const Affine<Fq>*)d_ac, (const Affine<Fq2>*)d_b, (const Affine<Fq2>*)(d_b + 4 * count), (const uint8_t*)d_flags,
-                 count, d_ac + 2 * count, d_b + count, d_flags + 3 * count);
-      ARK_CHECK_LAUNCH();
-      groups_dev(g, d_ac + 2 * count, d_b + count, count, 3, target, d_flags + 3 * count, nullptr, ok, st);
-    } else {
-      host_each(count, [&](uint64_t j) {
-        const Affine<Fq> a = g1_of(proofs[j].a), c = g1_of(proofs[j].c);
-        const Affine<Fq2> b = g2_of(proofs[j].b);
-        ok[j] = 0;
-        if (!on1(a) || !on1(c) || !on2(b)) return;
-        XYZZ<Fq> acc = XYZZ<Fq>::from_affine(abc[0]);
-        for (uint32_t i = 0; i < m; i++) {
-          Fr x;
-          memcpy(x.l, inputs + ((size_t)j * m + i) * sizeof(Fr), sizeof(Fr));
-          const Fr kx = Fr::from_mont(x);
-          acc = xyzz_add(acc, xyzz_mul_scalar(XYZZ<Fq>::from_affine(abc[1 + i]), kx.l, Fr::N));
-        }
-        const Affine<Fq> s = xyzz_to_affine(acc);
-        Gt f = PH::miller_loop(a, b);
-        f = Gt::mul(f, PH::miller_loop(s.is_inf() ? s : Affine<Fq>::neg(s), gamma));
-        f = Gt::mul(f, PH::miller_loop(c.is_inf() ? c : Affine<Fq>::neg(c), delta));
-        ok[j] = PH::final_exponentiation(f) == target ? 1 : 0;
-      });
-    }
-    trace_pairing(ctx, "verify_each", dev, 3 * count, t1 - t0, 0.0, now_ms() - t1, 0.0);
+    Verify<Curve>{ctx, g.pair, g.c}.verify_each(vk, proofs, inputs, count, ok);
   }
-
-  // ---- batch verification (pairing_host.hpp) --------------------------------------------------------------------------
-  // sum_j rho_j [ e(A_j, B_j) = e(alpha, beta) e(acc_j, gamma) e(C_j, delta) ]  <=>
-  //   prod_j e(rho_j A_j, B_j) * e(-(sum rho_j) alpha, beta) * e(-sum_i (sum_j rho_j x_ji) gamma_abc_i, gamma)
-  //                            * e(-sum_j rho_j C_j, delta) = 1
-  // (k + 3 Miller loops and one final exponentiation for k proofs).  The two multi-scalar sums run on the device.
   static bool verify_batch(ark355_ctx* ctx, GenericScratch& g, const ark355_vk_desc* vk, const ark355_proof_raw* proofs,
                            const uint8_t* inputs, const uint8_t* rho, uint64_t count) {
-    using PH = PairingHost<Curve>;
-    const uint64_t ell = vk->num_instance;
-    ARK_REQUIRE(ell >= 1 && count >= 1, ARK355_EINVAL, "empty batch or key");
-    ARK_REQUIRE(rho || count == 1, ARK355_EINVAL, "a batch needs one random coefficient per proof");
-    auto g1_of = [](const uint8_t* p) {
-      Affine<Fq> a;
-      memcpy(&a, p, sizeof(a));
-      return a;
-    };
-    auto g2_of = [](const uint8_t* p) {
-      Affine<Fq2> a;
-      memcpy(&a, p, sizeof(a));
-      return a;
-    };
-    // The raw entry point takes Montgomery images, not validated encodings: a point off the curve must not reach the
-    // affine Miller loop (its line functions never use the curve constant, (0, y) / y = 0 cases would divide by zero
-    // silently).  Three curve equations per proof on the host; subgroup membership is ark355_proof_from_bytes' job
-    // (ARK355_VALIDATE_FULL), as upstream splits it between deserialization and verification.
-    // Device route (policy PAIRING_DEVICE): the same three equations, rho_j A_j and the count + 3 Miller loops as kernels of
-    // pairing_impl.cuh; g.pg1 = A_0 .. A_{count-1}, C_0 .. C_{count-1}, then room for the count + 3 first arguments of the loops.
-    const bool dev = pairing_on_device(ctx->policy, count + 3);
-    hipStream_t st = ctx->stream;
-    const double t0 = now_ms();
-    if (dev) {
-      std::vector<Affine<Fq>> ac(2 * count);
-      std::vector<Affine<Fq2>> bs(count);
-      for (uint64_t j = 0; j < count; j++) {
-        ac[j] = g1_of(proofs[j].a);
-        ac[count + j] = g1_of(proofs[j].c);
-        bs[j] = g2_of(proofs[j].b);
-      }
-      g.pg1.ensure((3 * count + 3) * sizeof(Affine<Fq>));
-      g.pg2.ensure((count + 3) * sizeof(Affine<Fq2>));
-      ARK_CHECK_HIP(hipMemcpyAsync(g.pg1.p, ac.data(), 2 * count * sizeof(Affine<Fq>), hipMemcpyHostToDevice, st));
-      ARK_CHECK_HIP(hipMemcpyAsync(g.pg2.p, bs.data(), count * sizeof(Affine<Fq2>), hipMemcpyHostToDevice, st));
-      if (on_curve_dev(g, g.pg1.p, 2 * count, g.pg2.p, count, st) != 0) return false;
-    } else
-    for (uint64_t j = 0; j < count; j++) {
-      const Affine<Fq> a = g1_of(proofs[j].a), c = g1_of(proofs[j].c);
-      const Affine<Fq2> b = g2_of(proofs[j].b);
-      if (!a.is_inf() && !(Fq::sqr_ni(a.y) == W::curve_rhs(a.x))) return false;
-      if (!c.is_inf() && !(Fq::sqr_ni(c.y) == W::curve_rhs(c.x))) return false;
-      if (!b.is_inf() && !(Fq2::sqr_ni(b.y) == W::curve_rhs(b.x))) return false;
-    }
-    const double t1 = now_ms();
-    std::vector<Fr> r(count), coef(ell, Fr::zero());
-    for (uint64_t j = 0; j < count; j++) {
-      if (rho) {
-        Fr c;
-        memcpy(c.l, rho + 32 * j, sizeof(Fr));
-        r[j] = Fr::to_mont(c);
-        ARK_REQUIRE(!r[j].is_zero(), ARK355_EINVAL, "zero random coefficient");
-      } else {
-        r[j] = Fr::one();
-      }
-      coef[0] = Fr::add(coef[0], r[j]);
-      for (uint64_t i = 1; i < ell; i++) {
-        Fr x;
-        memcpy(x.l, inputs + ((size_t)j * (ell - 1) + (i - 1)) * sizeof(Fr), sizeof(Fr));
-        coef[i] = Fr::add(coef[i], Fr::mul(r[j], x));
-      }
-    }
-    // device MSMs over canonical scalars
-    std::vector<uint8_t> sc(std::max<uint64_t>(ell, count) * sizeof(Fr)), cpts(count * sizeof(Affine<Fq>));
-    Affine<Fq> acc, csum;
-    for (uint64_t i = 0; i < ell; i++) {
-      const Fr c = Fr::from_mont(coef[i]);
-      memcpy(sc.data() + i * sizeof(Fr), c.l, sizeof(Fr));
-    }
-    msm_host(ctx, g, 1, vk->gamma_abc_g1, sc.data(), ell, reinterpret_cast<uint8_t*>(&acc));
-    for (uint64_t j = 0; j < count; j++) {
-      const Fr c = Fr::from_mont(r[j]);
-      memcpy(sc.data() + j * sizeof(Fr), c.l, sizeof(Fr));
-      memcpy(cpts.data() + j * sizeof(Affine<Fq>), proofs[j].c, sizeof(Affine<Fq>));
-    }
-    msm_host(ctx, g, 1, cpts.data(), sc.data(), count, reinterpret_cast<uint8_t*>(&csum));
-    std::vector<Affine<Fq>> Ps(count + 3);
-    std::vector<Affine<Fq2>> Qs(count + 3);
-    unsigned nt = std::thread::hardware_concurrency();
-    if (nt == 0) nt = 4;
-    if (nt > 16) nt = 16;
-    const double t2 = now_ms();
-    if (dev) {
-      // rho_j A_j: one lane per proof, canonical rho_j (sc holds them since the second sum), into the slots after the C_j
-      Affine<Fq>* dP = g.pg1.template as<Affine<Fq>>() + 2 * count;
-      if (rho) {
-        g.psc.ensure(count * sizeof(Fr));
-        ARK_CHECK_HIP(hipMemcpyAsync(g.psc.p, sc.data(), count * sizeof(Fr), hipMemcpyHostToDevice, st));
-        ARK_LAUNCH((g1_scalar_mul_kernel<Curve>), dim3((uint32_t)((count + 127) / 128)), dim3(128), 0, st,
-                   (const Affine<Fq>*)g.pg1.template as<Affine<Fq>>(), (const Fr*)g.psc.template as<Fr>(), count, dP);
-        ARK_CHECK_LAUNCH();
-      } else {
-        ARK_CHECK_HIP(hipMemcpyAsync(dP, g.pg1.p, count * sizeof(Affine<Fq>), hipMemcpyDeviceToDevice, st));
-      }
-    } else
-    {
-      // rho_j A_j on host threads (one 255-bit scalar multiplication each)
-      std::vector<std::thread> th;
-      const unsigned k = (unsigned)std::min<uint64_t>(nt, count);
-      for (unsigned t = 0; t < k; t++)
-        th.emplace_back([&, t] {
-          for (uint64_t j = t; j < count; j += k) {
-            const Affine<Fq> a = g1_of(proofs[j].a);
-            const Fr c = Fr::from_mont(r[j]);
-            Ps[j] = rho ? xyzz_to_affine(xyzz_mul_scalar(XYZZ<Fq>::from_affine(a), c.l, Fr::N)) : a;
-            Qs[j] = g2_of(proofs[j].b);
-          }
+    return Verify<Curve>{ctx, g.pair, g.c}.verify_batch(
+        vk, proofs, inputs, rho, count, [&](const uint8_t* bases, const uint8_t* scalars, uint64_t n, Affine<Fq>* out) {
+          msm_host(ctx, g, 1, bases, scalars, n, reinterpret_cast<uint8_t*>(out));
         });
-      for (auto& x : th) x.join();
-    }
-    const Fr s0 = Fr::from_mont(coef[0]);
-    const Affine<Fq> alpha = g1_of(vk->alpha_g1);
-    Ps[count] = Affine<Fq>::neg(xyzz_to_affine(xyzz_mul_scalar(XYZZ<Fq>::from_affine(alpha), s0.l, Fr::N)));
-    Qs[count] = g2_of(vk->beta_g2);
-    Ps[count + 1] = acc.is_inf() ? acc : Affine<Fq>::neg(acc);
-    Qs[count + 1] = g2_of(vk->gamma_g2);
-    Ps[count + 2] = csum.is_inf() ? csum : Affine<Fq>::neg(csum);
-    Qs[count + 2] = g2_of(vk->delta_g2);
-    if (dev) {
-      ARK_CHECK_HIP(hipMemcpyAsync(g.pg1.template as<Affine<Fq>>() + 3 * count, Ps.data() + count, 3 * sizeof(Affine<Fq>),
-                                   hipMemcpyHostToDevice, st));
-      ARK_CHECK_HIP(hipMemcpyAsync(g.pg2.template as<Affine<Fq2>>() + count, Qs.data() + count, 3 * sizeof(Affine<Fq2>),
-                                   hipMemcpyHostToDevice, st));
-      ARK_CHECK_HIP(hipStreamSynchronize(st));
-      const double t3 = now_ms();
-      const Gt f = multi_miller_dev(g, g.pg1.template as<Affine<Fq>>() + 2 * count, g.pg2.template as<Affine<Fq2>>(), count + 3, st);
-      const double t4 = now_ms();
-      const bool good = final_exp(f) == Gt::one();
-      trace_pairing(ctx, "verify_batch", 1, count + 3, t1 - t0, t3 - t2, t4 - t3, now_ms() - t4);
-      return good;
-    }
-    if (ctx->policy.trace_host) {
-      // the same phases for the host route (timing only: the verdict below is PairingHost::product_is_one's)
-      const double t3 = now_ms();
-      fprintf(stderr, "[ark355] verify_batch route=host pairs=%llu check_ms=%.3f scalar_mul_ms=%.3f\n",
-              (unsigned long long)(count + 3), t1 - t0, t3 - t2);
-    }
-    return PH::product_is_one(Ps, Qs, nt);
   }
 
   // ---- ark-serialize wire formats (wire_impl.cuh) ------------------------------------------------------------------

@@ -3,8 +3,8 @@
 //
 // What runs where: the random linear combination of a batch is group arithmetic in G1 -- the two multi-scalar sums go
 // through the device MSM like every other MSM of this library.  ONE Miller loop is a sequential chain of tower-field
-// arithmetic with no width to fill a GPU, and that is what this file computes, on host threads in the library's own
-// host-compiled field code; a BATCH of k + 3 loops is k + 3 independent chains, which pairing_impl.cuh runs one lane each
+// arithmetic with no width to fill a GPU, and that is what this file computes, in the library's own host-compiled field
+// code (verify_impl.cuh spreads the loops of a call over host threads); a BATCH of k + 3 loops is k + 3 independent chains, which pairing_impl.cuh runs one lane each
 // on the device from PAIRING_DEVICE_MIN pairs on (policy.h; ark355_verify_batch and ark355_multi_pairing).  The ONE final
 // exponentiation of a call stays here on both routes.  This file is also the checker the device route is pinned to: both
 // routes give the same GT byte for byte (tests/pairing_cases.py, routes_agree_case).
@@ -15,7 +15,6 @@
 // BN254: optimal ate over 6x + 2 with the two Frobenius steps; final exponentiation = (conj(f) / f)^((q^6 + 1) / r) with
 // the exponent computed once by long division.
 #pragma once
-#include <thread>
 #include <vector>
 #include "common.h"
 
@@ -288,27 +287,6 @@ struct PairingHost {
   static Fq12 final_exponentiation(const Fq12& f) {
     const Fq12 f1 = Fq12::mul(Fq12::conj(f), Fq12::inv(f));          // f^(q^6 - 1)
     return Fq12::pow(f1, consts().final_exp);
-  }
-
-  // prod e(P_i, Q_i) == 1, Miller loops on `threads` host threads, one final exponentiation
-  static bool product_is_one(const std::vector<Affine<Fq>>& Ps, const std::vector<Affine<Fq2>>& Qs, unsigned threads) {
-    const size_t n = Ps.size();
-    if (threads < 1) threads = 1;
-    if (threads > n) threads = (unsigned)n;
-    std::vector<Fq12> part(threads ? threads : 1, Fq12::one());
-    (void)consts();                                   // build the constants before the threads start
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < threads; t++)
-      th.emplace_back([&, t] {
-        Fq12 acc = Fq12::one();
-        for (size_t i = t; i < n; i += threads) acc = Fq12::mul(acc, miller_loop(Ps[i], Qs[i]));
-        part[t] = acc;
-      });
-    for (auto& x : th) x.join();
-    Fq12 f = Fq12::one();
-    for (const auto& p : part) f = Fq12::mul(f, p);
-    if (consts().final_exp.l.empty()) return false;   // the exponent could not be formed: never accept
-    return final_exponentiation(f) == Fq12::one();
   }
 };
 

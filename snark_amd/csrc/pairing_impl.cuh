@@ -185,8 +185,8 @@ struct PairingDev {
 
   // ---- final exponentiation: one lane per GT value ------------------------------------------------------------------
   // The lane keeps FE_BUFS values of F_q12 in LDS and follows a PROGRAM of three-address instructions over them, formed once
-  // on the host (FeProgram in api_impl.cuh) and read from HBM by the whole wave at once.  The kernel so holds ONE squaring
-  // and ONE multiplication site, like pass B, however long the exponent chain is.  36 KiB (BLS12-381) / 24 KiB (BN254) per
+  // on the host (FeProgram below) and read from HBM by the whole wave at once.  The kernel so holds ONE squaring and ONE
+  // multiplication site, like pass B, however long the exponent chain is.  36 KiB (BLS12-381) / 24 KiB (BN254) per
   // buffer and workgroup: 4 / 6 buffers are 144 KiB of the 160 KiB a workgroup may declare, one wave per CU.
   static constexpr uint32_t FE_BUFS = BN ? 6 : 4;
   static constexpr uint32_t B12 = W12 * PAIR_LANES;       // dwords of one buffer of a workgroup
@@ -201,6 +201,176 @@ struct PairingDev {
   };
   static constexpr uint32_t fe_ins(uint32_t op, uint32_t d, uint32_t a = 0, uint32_t b = 0) {
     return op | d << 4 | a << 8 | b << 12;
+  }
+
+  // The program pairing_final_exp_kernel follows, built on the host (host code: never called from a kernel).  Buffer 0 holds
+  // f on entry and f^((q^12 - 1) / r) on exit; the buffers in between are handed out here, so that the kernel needs no more than FE_BUFS.
+  struct FeProgram {
+    std::vector<uint32_t> code;
+    uint32_t free_mask = (1u << FE_BUFS) - 1u;
+    uint32_t take() {
+      for (uint32_t b = 0; b < FE_BUFS; b++)
+        if ((free_mask >> b) & 1u) {
+          free_mask &= ~(1u << b);
+          return b;
+        }
+      throw HipError{ARK355_EINVAL, "final exponentiation program: out of buffers"};
+    }
+    void drop(uint32_t b) { free_mask |= 1u << b; }
+    void drop(uint32_t a, uint32_t b) { drop(a), drop(b); }
+    uint32_t sqr(uint32_t a) {
+      const uint32_t d = take();
+      code.push_back(fe_ins(FE_SQR, d, a));
+      return d;
+    }
+    uint32_t mul(uint32_t a, uint32_t b) {
+      const uint32_t d = take();
+      code.push_back(fe_ins(FE_MUL, d, a, b));
+      return d;
+    }
+    uint32_t copy(uint32_t a) {
+      const uint32_t d = take();
+      code.push_back(fe_ins(FE_COPY, d, a));
+      return d;
+    }
+    void conj(uint32_t d) { code.push_back(fe_ins(FE_CONJ, d)); }
+    void frob(uint32_t d, uint32_t n) { code.push_back(fe_ins(FE_FROB, d, n)); }
+    void inv6(uint32_t d) { code.push_back(fe_ins(FE_INV6, d)); }
+    // a new buffer with base^e (e > 0), square-and-multiply from the top bit; base stays.  Base, result and one more buffer.
+    uint32_t pow(uint32_t base, unsigned __int128 e) {
+      int top = 127;
+      while (!((e >> top) & 1)) top--;
+      uint32_t acc = copy(base);
+      for (int i = top - 1; i >= 0; i--) {
+        uint32_t t = sqr(acc);
+        drop(acc);
+        acc = t;
+        if ((e >> i) & 1) {
+          t = mul(acc, base);
+          drop(acc);
+          acc = t;
+        }
+      }
+      return acc;
+    }
+  };
+
+  static const std::vector<uint32_t>& fe_program() {
+    static const std::vector<uint32_t> prog = [] {
+      FeProgram p;
+      const uint32_t f = p.take();                       // buffer 0: the conjugated Miller product
+      // easy part: f^(q^6 - 1) = conj(f) / f with 1 / f = conj(f) / (f conj(f)) and f conj(f) in F_q6; then ^(q^2 + 1)
+      const uint32_t c = p.copy(f);
+      p.conj(c);
+      const uint32_t n = p.mul(f, c);
+      p.drop(f);
+      p.inv6(n);
+      const uint32_t fi = p.mul(c, n);
+      p.drop(n);
+      const uint32_t f1 = p.mul(c, fi);
+      p.drop(c, fi);
+      const uint32_t g = p.copy(f1);
+      p.frob(g, 2);
+      const uint32_t m = p.mul(g, f1);
+      p.drop(g, f1);
+      // hard part: the exact exponent (q^4 - q^2 + 1) / r; from here on an inverse is a conjugation
+      uint32_t res;
+      if (!BN) {
+        // ((x - 1)^2 / 3) (x + q) (x^2 + q^2 - 1) + 1,  x = -X
+        const unsigned __int128 X = 0xd201000000010000ull, C3 = (X + 1) * (X + 1) / 3;
+        const uint32_t y0 = p.pow(m, C3);
+        uint32_t t = p.pow(y0, X);
+        p.conj(t);                                       // y0^x
+        p.frob(y0, 1);
+        const uint32_t y1 = p.mul(t, y0);                // y0^(x + q)
+        p.drop(t, y0);
+        const uint32_t u = p.copy(y1);
+        p.frob(u, 2);
+        p.conj(y1);
+        const uint32_t v = p.mul(u, y1);                 // y1^(q^2 - 1)
+        p.conj(y1);
+        p.drop(u);
+        const uint32_t vm = p.mul(v, m);
+        p.drop(v, m);
+        t = p.pow(y1, X);
+        p.drop(y1);
+        const uint32_t t2 = p.pow(t, X);                 // y1^(x^2): the two signs cancel
+        p.drop(t);
+        res = p.mul(t2, vm);
+        p.drop(t2, vm);
+      } else {
+        // q^3 + (6 x^2 + 1) q^2 + (-36 x^3 - 18 x^2 - 12 x + 1) q + (-36 x^3 - 30 x^2 - 18 x - 2), by Horner in x:
+        // ((-36 (q + 1) x + (6 q^2 - 18 q - 30)) x + (-12 q - 18)) x + (q^3 + q^2 + q - 2)
+        const unsigned __int128 X = 4965661367192848881ull;
+        uint32_t u = p.copy(m);
+        p.frob(u, 1);
+        uint32_t t = p.mul(u, m);
+        p.drop(u);
+        uint32_t r = p.pow(t, 36);
+        p.drop(t);
+        p.conj(r);                                       // m^(-36 (q + 1))
+        uint32_t P = p.pow(r, X);
+        p.drop(r);
+        {                                                // * (m^(q^2) / (m^(3 q) m^5))^6
+          u = p.copy(m);
+          p.frob(u, 1);
+          const uint32_t u3 = p.pow(u, 3);
+          p.drop(u);
+          const uint32_t m5 = p.pow(m, 5);
+          const uint32_t v = p.mul(u3, m5);
+          p.drop(u3, m5);
+          p.conj(v);
+          const uint32_t w = p.copy(m);
+          p.frob(w, 2);
+          const uint32_t s = p.mul(w, v);
+          p.drop(w, v);
+          const uint32_t s6 = p.pow(s, 6);
+          p.drop(s);
+          r = p.mul(P, s6);
+          p.drop(P, s6);
+        }
+        P = p.pow(r, X);
+        p.drop(r);
+        {                                                // / (m^(2 q) m^3)^6
+          u = p.copy(m);
+          p.frob(u, 1);
+          const uint32_t u2 = p.sqr(u);
+          p.drop(u);
+          const uint32_t m3 = p.pow(m, 3);
+          const uint32_t v = p.mul(u2, m3);
+          p.drop(u2, m3);
+          const uint32_t s6 = p.pow(v, 6);
+          p.drop(v);
+          p.conj(s6);
+          r = p.mul(P, s6);
+          p.drop(P, s6);
+        }
+        P = p.pow(r, X);
+        p.drop(r);
+        {                                                // * m^(q^3) m^(q^2) m^q / m^2
+          const uint32_t a = p.copy(m);
+          p.frob(a, 1);
+          const uint32_t b = p.copy(m);
+          p.frob(b, 2);
+          const uint32_t ab = p.mul(a, b);
+          p.drop(a, b);
+          const uint32_t c3 = p.copy(m);
+          p.frob(c3, 3);
+          const uint32_t abc = p.mul(ab, c3);
+          p.drop(ab, c3);
+          const uint32_t m2 = p.sqr(m);
+          p.drop(m);
+          p.conj(m2);
+          const uint32_t s0 = p.mul(abc, m2);
+          p.drop(abc, m2);
+          res = p.mul(P, s0);
+          p.drop(P, s0);
+        }
+      }
+      if (res != 0) p.code.push_back(fe_ins(FE_COPY, 0, res));
+      return p.code;
+    }();
+    return prog;
   }
 
   ARK_D static void conj12(uint32_t* f) {

@@ -1,0 +1,498 @@
+// Host drivers of the pairing entry points: ark355_multi_pairing, ark355_pairing_groups, ark355_verify_each and
+// ark355_verify_batch.  Each has a host route (pairing_host.hpp on at most 16 host threads) and a device route (the kernels
+// of pairing_impl.cuh); policy PAIRING_DEVICE chooses.  Api<Curve> (api_impl.cuh) forwards here.
+#pragma once
+#include <chrono>
+#include <thread>
+#include "common.h"
+#include "wire_impl.cuh"
+#include "pairing_host.hpp"
+#include "pairing_impl.cuh"
+
+namespace ark355 {
+
+// grow-only device buffers of the device routes (a member of GenericScratch)
+struct PairingScratch {
+  DevBuf pg1, pg2, plines, ppart, pout, psc;      // points, lines, partial products, the Miller product, scalars
+  DevBuf pmill, pfe, pgt, pverd;                  // per-group pairings: Miller values of a chunk, program + constants, GT values, verdicts
+  DevBuf pabc, pprod, pflags;                     // ark355_verify_each: gamma_abc, the terms of the prepared inputs, per-point flags
+};
+
+template <class Curve>
+struct Verify {
+  using Fr = typename Curve::Fr;
+  using Fq = typename Curve::Fq;
+  using Fq2 = typename Curve::Fq2;
+  using G1 = Affine<Fq>;
+  using G2 = Affine<Fq2>;
+  using W = Wire<Curve>;
+  using PH = PairingHost<Curve>;
+  using PD = PairingDev<Curve>;
+  using Gt = typename PH::Fq12;
+  static constexpr bool BN = Curve::ID == ARK355_BN254;
+  // At most PAIR_CHUNK pairs have their lines in HBM at a time (about 20 KB per pair).
+  static constexpr uint64_t PAIR_CHUNK = 1u << 15;
+
+  ark355_ctx* ctx;
+  PairingScratch& s;
+  DevBuf& word;            // GenericScratch::c: the 8 bytes on_curve_kernel reports with
+
+  // ---- shared helpers ------------------------------------------------------------------------------------------------
+  // policy PAIRING_DEVICE: 0 host threads, 1 device, -1 device from `threshold` units on.  PAIRING_DEVICE_MIN counts pairs
+  // (n for multi_pairing, count + 3 for verify_batch); PAIRING_EACH_MIN counts groups / proofs (the host pays one final
+  // exponentiation per group there, so the crossover is not that of the two entries with one exponentiation per call).
+  bool on_device(int32_t threshold, uint64_t units) const {
+    if (ctx->policy.pairing_device == 0) return false;
+    if (ctx->policy.pairing_device > 0) return true;
+    return units >= (uint64_t)std::max<int64_t>(threshold, 0);
+  }
+  static double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  }
+  void trace(const char* what, bool device, uint64_t n, double check_ms, double mul_ms, double miller_ms, double fe_ms) const {
+    if (ctx->policy.trace_host)
+      fprintf(stderr, "[ark355] %s route=%s pairs=%llu check_ms=%.3f scalar_mul_ms=%.3f miller_ms=%.3f final_exp_ms=%.3f\n", what,
+              device ? "device" : "host", (unsigned long long)n, check_ms, mul_ms, miller_ms, fe_ms);
+  }
+
+  static G1 load_g1(const uint8_t* p) {
+    G1 a;
+    memcpy(&a, p, sizeof(a));
+    return a;
+  }
+  static G2 load_g2(const uint8_t* p) {
+    G2 a;
+    memcpy(&a, p, sizeof(a));
+    return a;
+  }
+  // y^2 = x^3 + b (infinity passes).  The raw entry points take Montgomery images, not validated encodings: a point off the
+  // curve must not reach the Miller loop (its line functions never use the curve constant, (0, y) / y = 0 cases would divide
+  // by zero silently).  Subgroup membership is ark355_proof_from_bytes' job (ARK355_VALIDATE_FULL), as upstream splits it
+  // between deserialization and verification.
+  template <class F>
+  static bool on_curve(const Affine<F>& a) {
+    return a.is_inf() || F::sqr_ni(a.y) == W::curve_rhs(a.x);
+  }
+  [[noreturn]] static void refuse(const std::string& what) { throw HipError{ARK355_EINVAL, what + ": point not on curve"}; }
+  static std::string at(const char* array, uint64_t i) { return std::string(array) + "[" + std::to_string(i) + "]"; }
+  // the word of on_curve_kernel: (index + 1) << 4 | group of the first failing point
+  static void refuse_word(unsigned long long e) { refuse(at((e & 15) == 1 ? "g1" : "g2", (e >> 4) - 1)); }
+  static bool exponent_formed() { return !PH::consts().final_exp.l.empty(); }
+  static Gt final_exp(const Gt& f) {
+    ARK_REQUIRE(exponent_formed(), ARK355_EINVAL, "the final exponent could not be formed");
+    return PH::final_exponentiation(f);
+  }
+
+  static unsigned host_threads() {
+    unsigned nt = std::thread::hardware_concurrency();
+    if (nt == 0) nt = 4;
+    return nt > 16 ? 16 : nt;
+  }
+  // `units` independent jobs on at most 16 host threads, thread t of T taking units t, t + T, ...
+  template <class Fn>
+  static void host_each(uint64_t units, Fn&& fn) {
+    const unsigned threads = (unsigned)std::min<uint64_t>(host_threads(), units);
+    (void)PH::consts();                               // build the constants before the threads start
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < threads; t++)
+      th.emplace_back([&, t] {
+        for (uint64_t u = t; u < units; u += threads) fn(u);
+      });
+    for (auto& x : th) x.join();
+  }
+  // prod_i miller_loop(P_i, Q_i): as many strands as host_each has threads, one partial product each
+  static Gt miller_product_host(const std::vector<G1>& Ps, const std::vector<G2>& Qs) {
+    const size_t n = Ps.size();
+    std::vector<Gt> part(std::min<size_t>(host_threads(), n), Gt::one());
+    host_each(part.size(), [&](uint64_t t) {
+      for (size_t i = t; i < n; i += part.size()) part[t] = Gt::mul(part[t], PH::miller_loop(Ps[i], Qs[i]));
+    });
+    Gt f = Gt::one();
+    for (const auto& p : part) f = Gt::mul(f, p);
+    return f;
+  }
+
+  // ---- device stages -------------------------------------------------------------------------------------------------
+  // both point arrays of a call into s.pg1 / s.pg2; the first point off its curve is refused by name
+  void upload_checked(const uint8_t* g1, const uint8_t* g2, uint64_t n) {
+    hipStream_t st = ctx->stream;
+    s.pg1.ensure(n * sizeof(G1));
+    s.pg2.ensure(n * sizeof(G2));
+    ARK_CHECK_HIP(hipMemcpyAsync(s.pg1.p, g1, n * sizeof(G1), hipMemcpyHostToDevice, st));
+    ARK_CHECK_HIP(hipMemcpyAsync(s.pg2.p, g2, n * sizeof(G2), hipMemcpyHostToDevice, st));
+    if (const unsigned long long e = on_curve_dev(s.pg1.p, n, s.pg2.p, n)) refuse_word(e);
+  }
+  // the curve equation on the device for n1 + n2 resident points; returns the kernel's word (0: all on their curves)
+  unsigned long long on_curve_dev(const void* d_g1, uint64_t n1, const void* d_g2, uint64_t n2) {
+    if (n1 + n2 == 0) return 0;
+    hipStream_t st = ctx->stream;
+    word.ensure(8);
+    ARK_CHECK_HIP(hipMemsetAsync(word.p, 0, 8, st));
+    ARK_LAUNCH((on_curve_kernel<Curve>), dim3((uint32_t)((n1 + n2 + 127) / 128)), dim3(128), 0, st,
+               reinterpret_cast<const G1*>(d_g1), n1, reinterpret_cast<const G2*>(d_g2), n2, word.as<unsigned long long>());
+    ARK_CHECK_LAUNCH();
+    unsigned long long e = 0;
+    ARK_CHECK_HIP(hipMemcpyAsync(&e, word.p, 8, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+    return e;
+  }
+
+  // The proofs of a call staged as the kernels read them: s.pg1 = A_0 .. A_{count-1}, C_0 .. C_{count-1}, s.pg2 = B_j, with
+  // room for cap1 / cap2 points (what the entry puts behind them).  The uploads are asynchronous: the caller keeps the
+  // returned host copies until it has synchronised the stream.
+  struct StagedProofs {
+    std::vector<G1> ac;
+    std::vector<G2> bs;
+  };
+  StagedProofs stage_proofs(const ark355_proof_raw* proofs, uint64_t count, uint64_t cap1, uint64_t cap2) {
+    StagedProofs h{std::vector<G1>(2 * count), std::vector<G2>(count)};
+    for (uint64_t j = 0; j < count; j++) {
+      h.ac[j] = load_g1(proofs[j].a);
+      h.ac[count + j] = load_g1(proofs[j].c);
+      h.bs[j] = load_g2(proofs[j].b);
+    }
+    s.pg1.ensure(cap1 * sizeof(G1));
+    s.pg2.ensure(cap2 * sizeof(G2));
+    ARK_CHECK_HIP(hipMemcpyAsync(s.pg1.p, h.ac.data(), 2 * count * sizeof(G1), hipMemcpyHostToDevice, ctx->stream));
+    ARK_CHECK_HIP(hipMemcpyAsync(s.pg2.p, h.bs.data(), count * sizeof(G2), hipMemcpyHostToDevice, ctx->stream));
+    return h;
+  }
+
+  static typename PD::Consts dev_consts() {
+    typename PD::Consts k{};
+    PD::schedule(&k);
+    k.two_inv = Fq::inv(Fq::add(Fq::one(), Fq::one()));
+    k.frob_x = PH::consts().frob_x;
+    k.frob_y = PH::consts().frob_y;
+    return k;
+  }
+
+  // Passes A and B of pairing_impl.cuh over `pairs` resident pairs (every point on its curve), `chunk` <= PAIR_CHUNK at a
+  // time.  PER_PAIR: every pair's Miller value of the chunk is left in s.pmill (dword-transposed, stride as handed to
+  // per_chunk); otherwise the product of workgroup b of the whole call is left at s.ppart + b * W12.
+  // per_chunk(first pair, pairs of the chunk, stride) runs after the two launches of each chunk.
+  template <bool PER_PAIR, class PerChunk>
+  void miller_chunks(const G1* d1, const G2* d2, uint64_t pairs, uint64_t chunk, PerChunk&& per_chunk) {
+    hipStream_t st = ctx->stream;
+    const typename PD::Consts k = dev_consts();
+    const uint32_t stride = (uint32_t)((std::min(pairs, chunk) + PAIR_LANES - 1) / PAIR_LANES * PAIR_LANES);
+    s.plines.ensure((size_t)k.steps * 3 * PD::W2 * stride * sizeof(uint32_t));
+    if (PER_PAIR) s.pmill.ensure((size_t)PD::W12 * stride * sizeof(uint32_t));
+    else s.ppart.ensure((pairs + PAIR_LANES - 1) / PAIR_LANES * PD::W12 * sizeof(uint32_t));
+    for (uint64_t off = 0; off < pairs; off += chunk) {
+      const uint32_t m = (uint32_t)std::min(chunk, pairs - off);
+      const dim3 grid((m + PAIR_LANES - 1) / PAIR_LANES);
+      ARK_LAUNCH((pairing_lines_kernel<Curve>), grid, dim3(PAIR_LANES), 0, st, d1 + off, d2 + off, m, stride, k,
+                 s.plines.as<uint32_t>());
+      ARK_CHECK_LAUNCH();
+      ARK_LAUNCH((pairing_accumulate_kernel<Curve, PER_PAIR>), grid, dim3(PAIR_LANES), 0, st, d1 + off, d2 + off, m, stride, k,
+                 (const uint32_t*)s.plines.as<uint32_t>(),
+                 PER_PAIR ? s.pmill.as<uint32_t>() : s.ppart.as<uint32_t>() + (off / PAIR_LANES) * PD::W12);
+      ARK_CHECK_LAUNCH();
+      per_chunk(off, m, stride);
+    }
+  }
+
+  // prod_i miller_loop(P_i, Q_i) for n resident pairs; the partial products of all chunks meet in one last launch
+  Gt multi_miller_dev(const G1* d1, const G2* d2, uint64_t n) {
+    if (n == 0) return Gt::one();
+    hipStream_t st = ctx->stream;
+    s.pout.ensure(PD::W12 * sizeof(uint32_t));
+    miller_chunks<false>(d1, d2, n, PAIR_CHUNK, [](uint64_t, uint32_t, uint32_t) {});
+    ARK_LAUNCH((pairing_product_kernel<Curve>), dim3(1), dim3(PAIR_LANES), 0, st, (const uint32_t*)s.ppart.as<uint32_t>(),
+               (uint32_t)((n + PAIR_LANES - 1) / PAIR_LANES), s.pout.as<uint32_t>());
+    ARK_CHECK_LAUNCH();
+    Fq2 c[6];
+    ARK_CHECK_HIP(hipMemcpyAsync(c, s.pout.p, sizeof(c), hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+    // coefficients of w^0 .. w^5 -> the tower of pairing_host.hpp (v = w^2)
+    Gt f{{c[0], c[2], c[4]}, {c[1], c[3], c[5]}};
+    return BN ? f : Gt::conj(f);      // BLS12-381: x < 0
+  }
+
+  // GT of `groups` groups of group_len consecutive resident pairs (every point on its curve, or its group marked in d_bad).
+  // out_gt: groups x 12 Fq (host, may be NULL); verdict: groups bytes (host), 1 where GT == target and the group is not bad.
+  // A chunk holds whole groups; its lines and Miller values are in HBM at a time.
+  void groups_dev(const G1* d1, const G2* d2, uint64_t groups, uint32_t group_len, const Gt& target, const uint8_t* d_bad,
+                  uint8_t* out_gt, uint8_t* verdict) {
+    hipStream_t st = ctx->stream;
+    const std::vector<uint32_t>& prog = PD::fe_program();
+    // program + constants: 18 Frobenius constants, the target (the kernels' order: coefficients of w^0 .. w^5), the instructions
+    const size_t frob_bytes = 18 * sizeof(Fq2), tgt_bytes = PD::W12 * sizeof(uint32_t);
+    std::vector<uint8_t> blob(frob_bytes + tgt_bytes + prog.size() * sizeof(uint32_t));
+    memcpy(blob.data(), PH::consts().frob12, frob_bytes);
+    const Fq2 tc[6] = {target.c0.c0, target.c1.c0, target.c0.c1, target.c1.c1, target.c0.c2, target.c1.c2};
+    memcpy(blob.data() + frob_bytes, tc, tgt_bytes);
+    memcpy(blob.data() + frob_bytes + tgt_bytes, prog.data(), prog.size() * sizeof(uint32_t));
+    s.pfe.ensure(blob.size());
+    ARK_CHECK_HIP(hipMemcpyAsync(s.pfe.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const Fq2* d_frob = s.pfe.as<Fq2>();
+    const uint32_t* d_tgt = reinterpret_cast<const uint32_t*>(s.pfe.as<uint8_t>() + frob_bytes);
+    const uint32_t* d_prog = d_tgt + PD::W12;
+    if (out_gt) s.pgt.ensure(groups * PD::W12 * sizeof(uint32_t));
+    s.pverd.ensure(groups);
+    miller_chunks<true>(d1, d2, groups * group_len, PAIR_CHUNK / group_len * group_len, [&](uint64_t off, uint32_t m, uint32_t stride) {
+      const uint64_t g0 = off / group_len;
+      const uint32_t ng = m / group_len;
+      ARK_LAUNCH((pairing_final_exp_kernel<Curve>), dim3((ng + PAIR_LANES - 1) / PAIR_LANES), dim3(PAIR_LANES), 0, st,
+                 (const uint32_t*)s.pmill.as<uint32_t>(), stride, ng, group_len, d_prog, (uint32_t)prog.size(), d_frob, d_tgt,
+                 d_bad ? d_bad + g0 : nullptr, out_gt ? s.pgt.as<uint32_t>() + g0 * PD::W12 : nullptr, s.pverd.as<uint8_t>() + g0);
+      ARK_CHECK_LAUNCH();
+    });
+    if (out_gt) ARK_CHECK_HIP(hipMemcpyAsync(out_gt, s.pgt.p, groups * PD::W12 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipMemcpyAsync(verdict, s.pverd.p, groups, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+
+  // the host route's curve checks of two raw point arrays, refused by name like the device route's
+  static void check_host(const uint8_t* g1, const uint8_t* g2, uint64_t n) {
+    for (uint64_t i = 0; i < n; i++) {
+      if (!on_curve(load_g1(g1 + i * sizeof(G1)))) refuse(at("g1", i));
+      if (!on_curve(load_g2(g2 + i * sizeof(G2)))) refuse(at("g2", i));
+    }
+  }
+
+  // ---- the entry points ----------------------------------------------------------------------------------------------
+  // ark-ec Pairing::multi_pairing over raw affine images
+  void multi_pairing(const uint8_t* g1, const uint8_t* g2, uint64_t n, uint8_t* out_gt, int32_t* is_one) {
+    const bool dev = n > 0 && on_device(ctx->policy.pairing_device_min, n);
+    const double t0 = now_ms();
+    double t1 = t0;
+    Gt f = Gt::one();
+    if (dev) {
+      upload_checked(g1, g2, n);
+      t1 = now_ms();
+      f = multi_miller_dev(s.pg1.as<G1>(), s.pg2.as<G2>(), n);
+    } else if (n > 0) {
+      check_host(g1, g2, n);
+      std::vector<G1> Ps(n);
+      std::vector<G2> Qs(n);
+      memcpy(Ps.data(), g1, n * sizeof(G1));
+      memcpy(Qs.data(), g2, n * sizeof(G2));
+      t1 = now_ms();
+      f = miller_product_host(Ps, Qs);
+    }
+    const double t2 = now_ms();
+    const Gt gt = final_exp(f);
+    trace("multi_pairing", dev, n, t1 - t0, 0.0, t2 - t1, now_ms() - t2);
+    if (out_gt) memcpy(out_gt, &gt, sizeof(gt));
+    if (is_one) *is_one = gt == Gt::one() ? 1 : 0;
+  }
+
+  // ark-ec Pairing::pairing per group of group_len consecutive pairs
+  void pairing_groups(const uint8_t* g1, const uint8_t* g2, uint64_t groups, uint32_t group_len, uint8_t* out_gt, uint8_t* is_one) {
+    ARK_REQUIRE(group_len >= 1 && group_len <= ARK355_PAIRING_GROUP_MAX, ARK355_EINVAL,
+                "group_len must be 1 .. 64 (one long product is ark355_multi_pairing's)");
+    if (groups == 0) return;
+    ARK_REQUIRE(groups <= 0xFFFFFFFFull / group_len, ARK355_EINVAL, "groups * group_len must stay below 2^32");
+    ARK_REQUIRE(g1 && g2, ARK355_EINVAL, "a point array is NULL");
+    ARK_REQUIRE(exponent_formed(), ARK355_EINVAL, "the final exponent could not be formed");
+    const uint64_t n = groups * group_len;
+    const bool dev = on_device(ctx->policy.pairing_each_min, groups);
+    const double t0 = now_ms();
+    double t1 = t0;
+    std::vector<uint8_t> verdict(groups);
+    if (dev) {
+      upload_checked(g1, g2, n);
+      t1 = now_ms();
+      groups_dev(s.pg1.as<G1>(), s.pg2.as<G2>(), groups, group_len, Gt::one(), nullptr, out_gt, verdict.data());
+    } else {
+      check_host(g1, g2, n);
+      t1 = now_ms();
+      host_each(groups, [&](uint64_t k) {
+        Gt f = Gt::one();
+        for (uint64_t i = k * group_len; i < (k + 1) * group_len; i++)
+          f = Gt::mul(f, PH::miller_loop(load_g1(g1 + i * sizeof(G1)), load_g2(g2 + i * sizeof(G2))));
+        const Gt gt = PH::final_exponentiation(f);
+        if (out_gt) memcpy(out_gt + k * sizeof(Gt), &gt, sizeof(gt));
+        verdict[k] = gt == Gt::one() ? 1 : 0;
+      });
+    }
+    if (is_one) memcpy(is_one, verdict.data(), groups);
+    trace("pairing_groups", dev, n, t1 - t0, 0.0, now_ms() - t1, 0.0);
+  }
+
+  // ark-groth16 verify_proof for every proof of one key on its own: e(A_j, B_j) e(-acc_j, gamma) e(-C_j, delta) == e(alpha, beta)
+  void verify_each(const ark355_vk_desc* vk, const ark355_proof_raw* proofs, const uint8_t* inputs, uint64_t count, uint8_t* ok) {
+    const uint64_t ell = vk->num_instance;
+    ARK_REQUIRE(ell >= 1, ARK355_EINVAL, "empty key");
+    if (count == 0) return;
+    ARK_REQUIRE(ell == 1 || inputs, ARK355_EINVAL, "public_inputs is NULL");
+    ARK_REQUIRE(count <= 0xFFFFFFFFull / 3, ARK355_EINVAL, "3 * count must stay below 2^32");
+    ARK_REQUIRE(exponent_formed(), ARK355_EINVAL, "the final exponent could not be formed");
+    const uint32_t m = (uint32_t)(ell - 1);
+    // the key's own points, once
+    const double t0 = now_ms();
+    const G1 alpha = load_g1(vk->alpha_g1);
+    const G2 beta = load_g2(vk->beta_g2), gamma = load_g2(vk->gamma_g2), delta = load_g2(vk->delta_g2);
+    if (!on_curve(alpha)) refuse("vk.alpha_g1");
+    if (!on_curve(beta)) refuse("vk.beta_g2");
+    if (!on_curve(gamma)) refuse("vk.gamma_g2");
+    if (!on_curve(delta)) refuse("vk.delta_g2");
+    std::vector<G1> abc(ell);
+    memcpy(abc.data(), vk->gamma_abc_g1, ell * sizeof(G1));
+    for (uint64_t i = 0; i < ell; i++)
+      if (!on_curve(abc[i])) refuse(at("vk.gamma_abc_g1", i));
+    const Gt target = PH::final_exponentiation(PH::miller_loop(alpha, beta));
+    const double t1 = now_ms();
+    const bool dev = on_device(ctx->policy.pairing_each_min, count);
+    if (dev) {
+      hipStream_t st = ctx->stream;
+      // behind the staged proofs: s.pg1 the 3 count first arguments; s.pg2 the 3 count second arguments, gamma, delta
+      const StagedProofs staged = stage_proofs(proofs, count, 5 * count, 4 * count + 2);
+      const G2 gd[2] = {gamma, delta};
+      s.pabc.ensure(ell * sizeof(G1));
+      s.pflags.ensure(4 * count);
+      G1* d_ac = s.pg1.as<G1>();
+      G2* d_b = s.pg2.as<G2>();
+      uint8_t* d_flags = s.pflags.as<uint8_t>();
+      ARK_CHECK_HIP(hipMemcpyAsync(d_b + 4 * count, gd, sizeof(gd), hipMemcpyHostToDevice, st));
+      ARK_CHECK_HIP(hipMemcpyAsync(s.pabc.p, abc.data(), ell * sizeof(G1), hipMemcpyHostToDevice, st));
+      ARK_LAUNCH((on_curve_flags_kernel<Curve>), dim3((uint32_t)((3 * count + 127) / 128)), dim3(128), 0, st, (const G1*)d_ac,
+                 2 * count, (const G2*)d_b, count, d_flags);
+      ARK_CHECK_LAUNCH();
+      if (m) {
+        s.psc.ensure(count * m * sizeof(Fr));
+        s.pprod.ensure(count * m * sizeof(XYZZ<Fq>));
+        ARK_CHECK_HIP(hipMemcpyAsync(s.psc.p, inputs, count * m * sizeof(Fr), hipMemcpyHostToDevice, st));
+        ARK_LAUNCH((prepared_input_terms_kernel<Curve>), dim3((uint32_t)((count * m + 127) / 128)), dim3(128), 0, st,
+                   (const G1*)s.pabc.as<G1>(), (const Fr*)s.psc.as<Fr>(), count, m, s.pprod.as<XYZZ<Fq>>());
+        ARK_CHECK_LAUNCH();
+      }
+      ARK_LAUNCH((verify_each_pairs_kernel<Curve>), dim3((uint32_t)((count + 127) / 128)), dim3(128), 0, st,
+                 (const G1*)s.pabc.as<G1>(), (const XYZZ<Fq>*)s.pprod.as<XYZZ<Fq>>(), m, (const G1*)d_ac, (const G2*)d_b,
+                 (const G2*)(d_b + 4 * count), (const uint8_t*)d_flags, count, d_ac + 2 * count, d_b + count, d_flags + 3 * count);
+      ARK_CHECK_LAUNCH();
+      groups_dev(d_ac + 2 * count, d_b + count, count, 3, target, d_flags + 3 * count, nullptr, ok);
+    } else {
+      host_each(count, [&](uint64_t j) {
+        const G1 a = load_g1(proofs[j].a), c = load_g1(proofs[j].c);
+        const G2 b = load_g2(proofs[j].b);
+        ok[j] = 0;
+        if (!on_curve(a) || !on_curve(c) || !on_curve(b)) return;
+        XYZZ<Fq> acc = XYZZ<Fq>::from_affine(abc[0]);
+        for (uint32_t i = 0; i < m; i++) {
+          Fr x;
+          memcpy(x.l, inputs + ((size_t)j * m + i) * sizeof(Fr), sizeof(Fr));
+          const Fr kx = Fr::from_mont(x);
+          acc = xyzz_add(acc, xyzz_mul_scalar(XYZZ<Fq>::from_affine(abc[1 + i]), kx.l, Fr::N));
+        }
+        const G1 sum = xyzz_to_affine(acc);
+        Gt f = PH::miller_loop(a, b);
+        f = Gt::mul(f, PH::miller_loop(sum.is_inf() ? sum : G1::neg(sum), gamma));
+        f = Gt::mul(f, PH::miller_loop(c.is_inf() ? c : G1::neg(c), delta));
+        ok[j] = PH::final_exponentiation(f) == target ? 1 : 0;
+      });
+    }
+    trace("verify_each", dev, 3 * count, t1 - t0, 0.0, now_ms() - t1, 0.0);
+  }
+
+  // Batch verification:
+  // sum_j rho_j [ e(A_j, B_j) = e(alpha, beta) e(acc_j, gamma) e(C_j, delta) ]  <=>
+  //   prod_j e(rho_j A_j, B_j) * e(-(sum rho_j) alpha, beta) * e(-sum_i (sum_j rho_j x_ji) gamma_abc_i, gamma)
+  //                            * e(-sum_j rho_j C_j, delta) = 1
+  // (k + 3 Miller loops and one final exponentiation for k proofs).  The two multi-scalar sums run on the device on both
+  // routes: msm(bases, canonical scalars, n, out) is the caller's one-shot G1 MSM.  Three curve equations per proof (see
+  // on_curve); a proof off its curve makes the batch false, it is not the caller's error.
+  // Device route: the same three equations, rho_j A_j and the count + 3 Miller loops as kernels of pairing_impl.cuh; behind the
+  // staged proofs s.pg1 has room for the count + 3 first arguments of the loops.
+  template <class Msm>
+  bool verify_batch(const ark355_vk_desc* vk, const ark355_proof_raw* proofs, const uint8_t* inputs, const uint8_t* rho,
+                    uint64_t count, Msm&& msm) {
+    const uint64_t ell = vk->num_instance;
+    ARK_REQUIRE(ell >= 1 && count >= 1, ARK355_EINVAL, "empty batch or key");
+    ARK_REQUIRE(rho || count == 1, ARK355_EINVAL, "a batch needs one random coefficient per proof");
+    const bool dev = on_device(ctx->policy.pairing_device_min, count + 3);
+    hipStream_t st = ctx->stream;
+    const double t0 = now_ms();
+    StagedProofs staged;
+    if (dev) {
+      staged = stage_proofs(proofs, count, 3 * count + 3, count + 3);
+      if (on_curve_dev(s.pg1.p, 2 * count, s.pg2.p, count) != 0) return false;
+    } else {
+      for (uint64_t j = 0; j < count; j++)
+        if (!on_curve(load_g1(proofs[j].a)) || !on_curve(load_g1(proofs[j].c)) || !on_curve(load_g2(proofs[j].b))) return false;
+    }
+    const double t1 = now_ms();
+    std::vector<Fr> r(count), coef(ell, Fr::zero());
+    for (uint64_t j = 0; j < count; j++) {
+      if (rho) {
+        Fr c;
+        memcpy(c.l, rho + 32 * j, sizeof(Fr));
+        r[j] = Fr::to_mont(c);
+        ARK_REQUIRE(!r[j].is_zero(), ARK355_EINVAL, "zero random coefficient");
+      } else {
+        r[j] = Fr::one();
+      }
+      coef[0] = Fr::add(coef[0], r[j]);
+      for (uint64_t i = 1; i < ell; i++) {
+        Fr x;
+        memcpy(x.l, inputs + ((size_t)j * (ell - 1) + (i - 1)) * sizeof(Fr), sizeof(Fr));
+        coef[i] = Fr::add(coef[i], Fr::mul(r[j], x));
+      }
+    }
+    // device MSMs over canonical scalars
+    std::vector<uint8_t> sc(std::max<uint64_t>(ell, count) * sizeof(Fr)), cpts(count * sizeof(G1));
+    G1 acc, csum;
+    for (uint64_t i = 0; i < ell; i++) {
+      const Fr c = Fr::from_mont(coef[i]);
+      memcpy(sc.data() + i * sizeof(Fr), c.l, sizeof(Fr));
+    }
+    msm(vk->gamma_abc_g1, sc.data(), ell, &acc);
+    for (uint64_t j = 0; j < count; j++) {
+      const Fr c = Fr::from_mont(r[j]);
+      memcpy(sc.data() + j * sizeof(Fr), c.l, sizeof(Fr));
+      memcpy(cpts.data() + j * sizeof(G1), proofs[j].c, sizeof(G1));
+    }
+    msm(cpts.data(), sc.data(), count, &csum);
+    std::vector<G1> Ps(count + 3);
+    std::vector<G2> Qs(count + 3);
+    const double t2 = now_ms();
+    if (dev) {
+      // rho_j A_j: one lane per proof, canonical rho_j (sc holds them since the second sum), into the slots after the C_j
+      G1* dP = s.pg1.as<G1>() + 2 * count;
+      if (rho) {
+        s.psc.ensure(count * sizeof(Fr));
+        ARK_CHECK_HIP(hipMemcpyAsync(s.psc.p, sc.data(), count * sizeof(Fr), hipMemcpyHostToDevice, st));
+        ARK_LAUNCH((g1_scalar_mul_kernel<Curve>), dim3((uint32_t)((count + 127) / 128)), dim3(128), 0, st,
+                   (const G1*)s.pg1.as<G1>(), (const Fr*)s.psc.as<Fr>(), count, dP);
+        ARK_CHECK_LAUNCH();
+      } else {
+        ARK_CHECK_HIP(hipMemcpyAsync(dP, s.pg1.p, count * sizeof(G1), hipMemcpyDeviceToDevice, st));
+      }
+    } else {
+      // rho_j A_j on host threads (one 255-bit scalar multiplication each)
+      host_each(count, [&](uint64_t j) {
+        const G1 a = load_g1(proofs[j].a);
+        const Fr c = Fr::from_mont(r[j]);
+        Ps[j] = rho ? xyzz_to_affine(xyzz_mul_scalar(XYZZ<Fq>::from_affine(a), c.l, Fr::N)) : a;
+        Qs[j] = load_g2(proofs[j].b);
+      });
+    }
+    const Fr s0 = Fr::from_mont(coef[0]);
+    Ps[count] = G1::neg(xyzz_to_affine(xyzz_mul_scalar(XYZZ<Fq>::from_affine(load_g1(vk->alpha_g1)), s0.l, Fr::N)));
+    Qs[count] = load_g2(vk->beta_g2);
+    Ps[count + 1] = acc.is_inf() ? acc : G1::neg(acc);
+    Qs[count + 1] = load_g2(vk->gamma_g2);
+    Ps[count + 2] = csum.is_inf() ? csum : G1::neg(csum);
+    Qs[count + 2] = load_g2(vk->delta_g2);
+    if (dev) {
+      ARK_CHECK_HIP(hipMemcpyAsync(s.pg1.as<G1>() + 3 * count, Ps.data() + count, 3 * sizeof(G1), hipMemcpyHostToDevice, st));
+      ARK_CHECK_HIP(hipMemcpyAsync(s.pg2.as<G2>() + count, Qs.data() + count, 3 * sizeof(G2), hipMemcpyHostToDevice, st));
+      ARK_CHECK_HIP(hipStreamSynchronize(st));
+      const double t3 = now_ms();
+      const Gt f = multi_miller_dev(s.pg1.as<G1>() + 2 * count, s.pg2.as<G2>(), count + 3);
+      const double t4 = now_ms();
+      const bool good = final_exp(f) == Gt::one();
+      trace("verify_batch", true, count + 3, t1 - t0, t3 - t2, t4 - t3, now_ms() - t4);
+      return good;
+    }
+    if (ctx->policy.trace_host)      // the host route reports the phases up to here only
+      fprintf(stderr, "[ark355] verify_batch route=host pairs=%llu check_ms=%.3f scalar_mul_ms=%.3f\n",
+              (unsigned long long)(count + 3), t1 - t0, now_ms() - t2);
+    const Gt f = miller_product_host(Ps, Qs);
+    return exponent_formed() && PH::final_exponentiation(f) == Gt::one();      // no exponent: never accept
+  }
+};
+
+}  // namespace ark355
