@@ -477,6 +477,48 @@ int32_t ark355_pairing_groups(ark355_ctx* ctx, int32_t curve, const uint8_t* g1,
 int32_t ark355_verify_each(ark355_ctx* ctx, int32_t curve, const ark355_vk_desc* vk, const ark355_proof_raw* proofs,
                            const uint8_t* public_inputs, uint64_t count, uint8_t* ok);
 
+/* ---- processed verifying key (type ProcessedVerifyingKey, SNARK::process_vk, SNARK::verify_with_processed_vk;
+ * snark/src/lib.rs:36,69-80; upstream ark-groth16 PreparedVerifyingKey) -------------------------------------------------
+ * A verifier holds a handful of keys and sees proofs forever: ark355_vk_process does the per-key work of ark355_verify_each
+ * once and keeps the result resident, and the *_pvk entries verify against the handle.
+ *   - the curve checks of the key's 4 + num_instance points (ARK355_EINVAL naming the field, as ark355_verify_each refuses them);
+ *   - e(alpha, beta), the alpha_g1_beta_g2 of PreparedVerifyingKey;
+ *   - gamma_abc_g1 in HBM;
+ *   - the P-independent line coefficients of beta, gamma and delta (ark-ec G2Prepared), which the Miller loops against
+ *     these points read instead of walking the point again for every proof.
+ * A key point at infinity is legal, as it is for ark355_verify_each: its pairs contribute one.  num_instance == 0 and NULL
+ * pointers are ARK355_EINVAL.  The handle belongs to the DEVICE of the creating context, not to the context: it is immutable
+ * and may be used from any context of that device, from several at once, and after the creating context is destroyed; a
+ * context of another device gets ARK355_EINVAL.  Free it with ark355_pvk_free once no call uses it.
+ * Upstream's ProcessedVerifyingKey is serializable; the handle is NOT.  The serializable object remains the VerifyingKey it
+ * was made from (process it again after loading), exactly as ark355_pk relates to ProvingKey. */
+typedef struct ark355_pvk ark355_pvk;
+/* SNARK::process_vk (snark/src/lib.rs:69-73) */
+int32_t ark355_vk_process(ark355_ctx* ctx, int32_t curve, const ark355_vk_desc* vk, ark355_pvk** out);
+void ark355_pvk_free(ark355_pvk* pvk);
+/* curve id, gamma_abc_g1 length, bytes of HBM the handle holds; any pointer may be NULL */
+int32_t ark355_pvk_info(const ark355_pvk* pvk, int32_t* curve, uint64_t* num_instance, uint64_t* resident_bytes);
+/* PreparedVerifyingKey::alpha_g1_beta_g2: 12 Fq in the layout of ark355_multi_pairing, byte for byte what that entry
+ * returns for the one pair (alpha_g1, beta_g2) */
+int32_t ark355_pvk_alpha_beta(const ark355_pvk* pvk, uint8_t* out_gt);
+/* ark-ec Pairing::pairing against one G2Prepared, elementwise: GT_i = e(P_i, Q) with Q the key's beta (which = 0), gamma (1)
+ * or delta (2).  Each value is byte for byte what ark355_pairing_groups returns for the n pairs (P_i, Q) with group_len 1.
+ * g1: n raw affine G1 images; P_i off its curve is ARK355_EINVAL naming g1[i]; P_i or Q at infinity gives one.  n == 0
+ * returns ARK355_OK and writes nothing; a NULL g1 with n > 0 and which outside 0 .. 2 are ARK355_EINVAL.  Route policy as
+ * for ark355_pairing_groups (PAIRING_DEVICE / PAIRING_EACH_MIN, counted in pairs); the host route walks Q again per pair. */
+int32_t ark355_pvk_pairings(ark355_ctx* ctx, const ark355_pvk* pvk, int32_t which /* 0 beta, 1 gamma, 2 delta */,
+                            const uint8_t* g1, uint64_t n, uint8_t* out_gt /* may be NULL */, uint8_t* is_one /* may be NULL */);
+/* SNARK::verify_with_processed_vk (snark/src/lib.rs:76-80), per proof: ok[j] is ark355_verify_each's on the same key, proofs
+ * and inputs, on both routes and under the same rules (a proof off its curve gets ok[j] = 0 and the call returns ARK355_OK;
+ * count == 0 writes nothing; num_instance == 1 allows public_inputs == NULL).  count == 1 is verify_with_processed_vk itself.
+ * Policy PAIRING_DEVICE / PAIRING_EACH_MIN as for ark355_verify_each.  On the device route only the count pairs (A_j, B_j)
+ * walk a G2 point; the 2 count pairs against gamma and delta read the handle's lines. */
+int32_t ark355_verify_each_pvk(ark355_ctx* ctx, const ark355_pvk* pvk, const ark355_proof_raw* proofs,
+                               const uint8_t* public_inputs, uint64_t count, uint8_t* ok);
+/* ark355_verify_batch with the key taken from the handle (its points were checked at process time): the same verdict. */
+int32_t ark355_verify_batch_pvk(ark355_ctx* ctx, const ark355_pvk* pvk, const ark355_proof_raw* proofs,
+                                const uint8_t* public_inputs, const uint8_t* rho, uint64_t count, int32_t* ok);
+
 /* The scalars of the Groth16 generator (circuit_specific_setup, snark/src/lib.rs:43-46; upstream
  * generate_parameters_with_qap) from the R1CS matrices in CSR and the five trapdoor elements tau, alpha, beta, gamma,
  * delta (5 x 32 B canonical): u_j(tau), v_j(tau), w_j(tau) (num_instance + num_witness each), l_j (num_witness),

@@ -28,6 +28,10 @@ pub struct ark355_comm {
 pub struct ark355_bases {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct ark355_pvk {
+    _p: [u8; 0],
+}
 
 pub const ARK355_BLS12_381: i32 = 0;
 pub const ARK355_BN254: i32 = 1;
@@ -446,6 +450,41 @@ extern "C" {
         public_inputs: *const u8,
         count: u64,
         ok: *mut u8,
+    ) -> i32;
+
+    /// `SNARK::process_vk`: the per-key work of verification, once; the handle is resident and immutable.
+    pub fn ark355_vk_process(ctx: *mut ark355_ctx, curve: i32, vk: *const ark355_vk_desc, out: *mut *mut ark355_pvk) -> i32;
+    pub fn ark355_pvk_free(pvk: *mut ark355_pvk);
+    pub fn ark355_pvk_info(pvk: *const ark355_pvk, curve: *mut i32, num_instance: *mut u64, resident_bytes: *mut u64) -> i32;
+    /// `PreparedVerifyingKey::alpha_g1_beta_g2` (12 Fq, ark-ff `Fp12` memory order)
+    pub fn ark355_pvk_alpha_beta(pvk: *const ark355_pvk, out_gt: *mut u8) -> i32;
+    /// `Pairing::pairing` of n G1 points against one prepared point of the key (0 beta, 1 gamma, 2 delta)
+    pub fn ark355_pvk_pairings(
+        ctx: *mut ark355_ctx,
+        pvk: *const ark355_pvk,
+        which: i32,
+        g1: *const u8,
+        n: u64,
+        out_gt: *mut u8,
+        is_one: *mut u8,
+    ) -> i32;
+    /// `SNARK::verify_with_processed_vk` for every proof on its own: `ok` receives `count` bytes.
+    pub fn ark355_verify_each_pvk(
+        ctx: *mut ark355_ctx,
+        pvk: *const ark355_pvk,
+        proofs: *const ark355_proof_raw,
+        public_inputs: *const u8,
+        count: u64,
+        ok: *mut u8,
+    ) -> i32;
+    pub fn ark355_verify_batch_pvk(
+        ctx: *mut ark355_ctx,
+        pvk: *const ark355_pvk,
+        proofs: *const ark355_proof_raw,
+        public_inputs: *const u8,
+        rho: *const u8,
+        count: u64,
+        ok: *mut i32,
     ) -> i32;
 
     pub fn ark355_setup_scalars(

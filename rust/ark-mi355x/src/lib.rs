@@ -63,6 +63,34 @@ fn synthesize<F: PrimeField, C: ConstraintSynthesizer<F>>(circuit: C, witness_on
     Ok(Synthesized { cs, z })
 }
 
+/// A processed verifying key resident on the device (`ark355_pvk`, made by `Mi355xGroth16::process_vk_device`).
+pub struct DevicePvk<E> {
+    handle: *mut ffi::ark355_pvk,
+    num_instance: usize,
+    _curve: core::marker::PhantomData<E>,
+}
+// SAFETY: the handle is immutable after `ark355_vk_process` and the library allows concurrent readers from any context of
+// its device (include/ark355.h).
+unsafe impl<E> Send for DevicePvk<E> {}
+unsafe impl<E> Sync for DevicePvk<E> {}
+impl<E> DevicePvk<E> {
+    /// `gamma_abc_g1.len()` of the key it was made from
+    pub fn num_instance(&self) -> usize {
+        self.num_instance
+    }
+    /// bytes of HBM the handle holds (`ark355_pvk_info`)
+    pub fn resident_bytes(&self) -> u64 {
+        let mut n = 0u64;
+        unsafe { ffi::ark355_pvk_info(self.handle, core::ptr::null_mut(), core::ptr::null_mut(), &mut n) };
+        n
+    }
+}
+impl<E> Drop for DevicePvk<E> {
+    fn drop(&mut self) {
+        unsafe { ffi::ark355_pvk_free(self.handle) }
+    }
+}
+
 impl<E, P1, P2> Mi355xGroth16<E>
 where
     E: Mi355xCurve<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
@@ -303,6 +331,78 @@ where
                     ctx,
                     E::CURVE_ID,
                     &desc,
+                    raw.as_ptr(),
+                    if xs.is_empty() { core::ptr::null() } else { image.as_ptr() },
+                    good.len() as u64,
+                    ok.as_mut_ptr(),
+                )
+            })
+        })?;
+        for (&j, &v) in good.iter().zip(ok.iter()) {
+            out[j] = v == 1;
+        }
+        Ok(out)
+    }
+
+    /// `SNARK::process_vk` on the device (`ark355_vk_process`): the key's curve checks, `e(alpha, beta)`, `gamma_abc_g1` in
+    /// HBM and the prepared lines of `beta`, `gamma`, `delta`, once.  The handle is resident on the calling thread's device
+    /// and may be used from any thread of that device; it is not serializable -- the `VerifyingKey` stays the object to store.
+    pub fn process_vk_device(vk: &VerifyingKey<E>) -> Result<DevicePvk<E>, Mi355xError> {
+        let one = |p: &Affine<P1>| marshal::flatten_points(core::slice::from_ref(p));
+        let one2 = |p: &Affine<P2>| marshal::flatten_points(core::slice::from_ref(p));
+        let (alpha, beta, gamma, delta) = (one(&vk.alpha_g1), one2(&vk.beta_g2), one2(&vk.gamma_g2), one2(&vk.delta_g2));
+        let gabc = marshal::flatten_points(&vk.gamma_abc_g1);
+        let desc = ffi::ark355_vk_desc {
+            num_instance: vk.gamma_abc_g1.len() as u64,
+            alpha_g1: alpha.as_ptr(),
+            beta_g2: beta.as_ptr(),
+            gamma_g2: gamma.as_ptr(),
+            delta_g2: delta.as_ptr(),
+            gamma_abc_g1: gabc.as_ptr(),
+        };
+        let mut handle: *mut ffi::ark355_pvk = core::ptr::null_mut();
+        cache::with_ctx(|ctx| cache::check(ctx, unsafe { ffi::ark355_vk_process(ctx, E::CURVE_ID, &desc, &mut handle) }))?;
+        Ok(DevicePvk { handle, num_instance: vk.gamma_abc_g1.len(), _curve: core::marker::PhantomData })
+    }
+
+    /// `SNARK::verify_with_processed_vk` for every proof on its own (`ark355_verify_each_pvk`): the verdicts of
+    /// `verify_each` without the per-key work -- only the pairs `(A_j, B_j)` walk a G2 point, the pairs against `gamma` and
+    /// `delta` read the handle's lines.  A proof whose public inputs have the wrong length gets `false`.
+    pub fn verify_each_pvk(
+        pvk: &DevicePvk<E>,
+        public_inputs: &[Vec<E::ScalarField>],
+        proofs: &[Proof<E>],
+    ) -> Result<Vec<bool>, Mi355xError> {
+        let ell = pvk.num_instance;
+        if public_inputs.len() != proofs.len() {
+            return Err(Mi355xError::InvalidArgument("verify_each_pvk: one list of public inputs per proof".into()));
+        }
+        let good: Vec<usize> = (0..proofs.len()).filter(|&j| public_inputs[j].len() + 1 == ell).collect();
+        let mut out = vec![false; proofs.len()];
+        if good.is_empty() {
+            return Ok(out);
+        }
+        let one = |p: &Affine<P1>| marshal::flatten_points(core::slice::from_ref(p));
+        let one2 = |p: &Affine<P2>| marshal::flatten_points(core::slice::from_ref(p));
+        let mut raw = Vec::with_capacity(good.len());
+        let mut xs: Vec<E::ScalarField> = Vec::with_capacity(good.len() * (ell - 1));
+        for &j in &good {
+            let p = &proofs[j];
+            let mut r = ffi::ark355_proof_raw { a: [0; 96], b: [0; 192], c: [0; 96] };
+            let (a, b, c) = (one(&p.a), one2(&p.b), one(&p.c));
+            r.a[..a.len()].copy_from_slice(&a);
+            r.b[..b.len()].copy_from_slice(&b);
+            r.c[..c.len()].copy_from_slice(&c);
+            raw.push(r);
+            xs.extend_from_slice(&public_inputs[j]);
+        }
+        let image = marshal::scalars_image(&xs);
+        let mut ok = vec![0u8; good.len()];
+        cache::with_ctx(|ctx| {
+            cache::check(ctx, unsafe {
+                ffi::ark355_verify_each_pvk(
+                    ctx,
+                    pvk.handle,
                     raw.as_ptr(),
                     if xs.is_empty() { core::ptr::null() } else { image.as_ptr() },
                     good.len() as u64,
@@ -581,12 +681,15 @@ where
         Self::prove_with_rs(pk, circuit, r, s)
     }
 
-    /// snark/src/lib.rs:70-73
+    /// snark/src/lib.rs:70-73.  The trait's `ProcessedVerifyingKey` stays upstream's serializable `PreparedVerifyingKey`
+    /// (CPU); the resident counterpart is `DevicePvk` from `Mi355xGroth16::process_vk_device`, which cannot be serialized
+    /// and therefore cannot stand in for the associated type.
     fn process_vk(vk: &Self::VerifyingKey) -> Result<Self::ProcessedVerifyingKey, Self::Error> {
         Groth16::<E>::process_vk(vk).map_err(Mi355xError::from)
     }
 
-    /// snark/src/lib.rs:76-80 -- unchanged CPU verifier; proofs are byte-compatible.
+    /// snark/src/lib.rs:76-80 -- unchanged CPU verifier over upstream's type; proofs are byte-compatible.  On the device:
+    /// `Mi355xGroth16::verify_each_pvk` with a `DevicePvk` (one proof: `verify_with_processed_vk` itself).
     fn verify_with_processed_vk(
         pvk: &Self::ProcessedVerifyingKey,
         public_input: &[E::ScalarField],

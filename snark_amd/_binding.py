@@ -55,6 +55,8 @@ SYMBOLS = [
     "ark355_pk_table_info", "ark355_pk_h_eval", "ark355_hbasis_transform", "ark355_hbasis_gather",
     "ark355_points_decode", "ark355_points_encode", "ark355_proof_to_bytes", "ark355_proof_from_bytes",
     "ark355_setup_scalars", "ark355_setup", "ark355_verify_batch", "ark355_multi_pairing", "ark355_pairing_groups", "ark355_verify_each",
+    "ark355_vk_process", "ark355_pvk_free", "ark355_pvk_info", "ark355_pvk_alpha_beta", "ark355_pvk_pairings",
+    "ark355_verify_each_pvk", "ark355_verify_batch_pvk",
     "ark355_ctx_set_policy", "ark355_ctx_get_policy", "ark355_sched_info", "ark355_sched_reset", "ark355_diag_streams", "ark355_diag_dispatch",
     "ark355_diag_mad_rate", "ark355_diag_clocks",
 ]
@@ -209,6 +211,14 @@ class Lib:
         d.ark355_multi_pairing.argtypes = [vp, i32, vp, vp, u64, vp, P(i32)]
         d.ark355_pairing_groups.argtypes = [vp, i32, vp, vp, u64, C.c_uint32, vp, vp]
         d.ark355_verify_each.argtypes = [vp, i32, P(VkDesc), vp, vp, u64, vp]
+        d.ark355_vk_process.argtypes = [vp, i32, P(VkDesc), P(vp)]
+        d.ark355_pvk_free.argtypes = [vp]
+        d.ark355_pvk_free.restype = None
+        d.ark355_pvk_info.argtypes = [vp, P(i32), P(u64), P(u64)]
+        d.ark355_pvk_alpha_beta.argtypes = [vp, vp]
+        d.ark355_pvk_pairings.argtypes = [vp, vp, i32, vp, u64, vp, vp]
+        d.ark355_verify_each_pvk.argtypes = [vp, vp, vp, vp, u64, vp]
+        d.ark355_verify_batch_pvk.argtypes = [vp, vp, vp, vp, vp, u64, P(i32)]
         d.ark355_ctx_set_policy.argtypes = [vp, C.c_char_p, i64]
         d.ark355_ctx_get_policy.argtypes = [vp, C.c_char_p, P(i64)]
         d.ark355_sched_info.argtypes = [vp, vp, i32, P(SchedReport)]
@@ -752,6 +762,65 @@ class Lib:
         ok = np.zeros(max(1, len(proofs)), dtype=np.uint8)
         self.check(ctx, self.dll.ark355_verify_each(ctx, curve, C.byref(d), arr, ib, len(proofs), ok.ctypes.data_as(C.c_void_p)))
         return [bool(v) for v in ok[:len(proofs)]]
+
+    # ---- the processed verifying key (include/ark355.h "processed verifying key") -----------------------------------------
+    @staticmethod
+    def _proof_array(proofs):
+        arr = (ProofRaw * max(1, len(proofs)))()
+        for i, (a, b, c) in enumerate(proofs):
+            C.memmove(arr[i].a, a, len(a))
+            C.memmove(arr[i].b, b, len(b))
+            C.memmove(arr[i].c, c, len(c))
+        return arr
+
+    def vk_process(self, ctx, curve, vk_parts):
+        """ark355_vk_process: vk_parts as for verify_batch -> the handle (free it with pvk_free)."""
+        keep = []
+        d = self._vk_desc(vk_parts, keep)
+        h = C.c_void_p()
+        self.check(ctx, self.dll.ark355_vk_process(ctx, curve, C.byref(d), C.byref(h)))
+        return h
+
+    def pvk_free(self, pvk):
+        self.dll.ark355_pvk_free(pvk)
+
+    def pvk_info(self, pvk):
+        curve, ell, nbytes = C.c_int32(-1), C.c_uint64(0), C.c_uint64(0)
+        self.check(None, self.dll.ark355_pvk_info(pvk, C.byref(curve), C.byref(ell), C.byref(nbytes)))
+        return {"curve": int(curve.value), "num_instance": int(ell.value), "resident_bytes": int(nbytes.value)}
+
+    def pvk_alpha_beta(self, pvk) -> bytes:
+        """ark355_pvk_alpha_beta: e(alpha_g1, beta_g2) as multi_pairing returns it."""
+        out = np.zeros(12 * self.sizes(self.pvk_info(pvk)["curve"])["fq"], dtype=np.uint8)
+        self.check(None, self.dll.ark355_pvk_alpha_beta(pvk, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()
+
+    def pvk_pairings(self, ctx, pvk, which, g1: bytes, n, want_gt=True):
+        """ark355_pvk_pairings: e(P_i, Q_which) for n raw G1 images.  Returns (gt, is_one) as pairing_groups does."""
+        fq = self.sizes(self.pvk_info(pvk)["curve"])["fq"]
+        out = np.zeros(max(1, n) * 12 * fq, dtype=np.uint8)
+        one = np.zeros(max(1, n), dtype=np.uint8)
+        b1, k1 = _buf(g1 if g1 else None)
+        self.check(ctx, self.dll.ark355_pvk_pairings(ctx, pvk, which, b1, n, out.ctypes.data_as(C.c_void_p) if want_gt else None,
+                                                     one.ctypes.data_as(C.c_void_p)))
+        return (out[:n * 12 * fq].tobytes() if want_gt else None), [bool(v) for v in one[:n]]
+
+    def verify_each_pvk(self, ctx, pvk, proofs, public_inputs: bytes):
+        """ark355_verify_each_pvk: one verdict per proof against a processed key.  Returns a list of bool."""
+        arr = self._proof_array(proofs)
+        ib, k1 = _buf(public_inputs if len(public_inputs) else None)
+        ok = np.zeros(max(1, len(proofs)), dtype=np.uint8)
+        self.check(ctx, self.dll.ark355_verify_each_pvk(ctx, pvk, arr, ib, len(proofs), ok.ctypes.data_as(C.c_void_p)))
+        return [bool(v) for v in ok[:len(proofs)]]
+
+    def verify_batch_pvk(self, ctx, pvk, proofs, public_inputs: bytes, rho=None) -> bool:
+        """ark355_verify_batch_pvk: verify_batch against a processed key."""
+        arr = self._proof_array(proofs)
+        ib, k1 = _buf(public_inputs if len(public_inputs) else None)
+        rb, k2 = _buf(b"".join(rho) if rho else None)
+        ok = C.c_int32(0)
+        self.check(ctx, self.dll.ark355_verify_batch_pvk(ctx, pvk, arr, ib, rb, len(proofs), C.byref(ok)))
+        return bool(ok.value)
 
     def pairing_groups(self, ctx, curve, g1: bytes, g2: bytes, groups, group_len=1, want_gt=True):
         """ark355_pairing_groups over groups x group_len raw affine pairs.  Returns (gt, is_one): gt = groups x 12 Fq as bytes

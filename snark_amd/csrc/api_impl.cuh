@@ -723,6 +723,26 @@ struct Api {
         });
   }
 
+  // ---- the processed verifying key (verify_impl.cuh) -------------------------------------------------------------------
+  static PvkDev* vk_process(ark355_ctx* ctx, GenericScratch& g, const ark355_vk_desc* vk) {
+    return Verify<Curve>{ctx, g.pair, g.c}.vk_process(vk);
+  }
+  static void pvk_pairings(ark355_ctx* ctx, GenericScratch& g, const PvkDev& pvk, int which, const uint8_t* g1, uint64_t n,
+                           uint8_t* out_gt, uint8_t* is_one) {
+    Verify<Curve>{ctx, g.pair, g.c}.pvk_pairings(pvk, which, g1, n, out_gt, is_one);
+  }
+  static void verify_each_pvk(ark355_ctx* ctx, GenericScratch& g, const PvkDev& pvk, const ark355_proof_raw* proofs,
+                              const uint8_t* inputs, uint64_t count, uint8_t* ok) {
+    Verify<Curve>{ctx, g.pair, g.c}.verify_each_pvk(pvk, proofs, inputs, count, ok);
+  }
+  static bool verify_batch_pvk(ark355_ctx* ctx, GenericScratch& g, const PvkDev& pvk, const ark355_proof_raw* proofs,
+                               const uint8_t* inputs, const uint8_t* rho, uint64_t count) {
+    return Verify<Curve>{ctx, g.pair, g.c}.verify_batch_pvk(
+        pvk, proofs, inputs, rho, count, [&](const uint8_t* bases, const uint8_t* scalars, uint64_t n, Affine<Fq>* out) {
+          msm_host(ctx, g, 1, bases, scalars, n, reinterpret_cast<uint8_t*>(out));
+        });
+  }
+
   // ---- ark-serialize wire formats (wire_impl.cuh) ------------------------------------------------------------------
   static size_t point_size(int group, bool compressed) { return group == 1 ? W::g1_size(compressed) : W::g2_size(compressed); }
   static size_t raw_size(int group) { return group == 1 ? sizeof(Affine<Fq>) : sizeof(Affine<Fq2>); }

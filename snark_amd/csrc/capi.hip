@@ -30,6 +30,9 @@ struct ark355_bases {
 struct ark355_comm {
   CommDev* d;
 };
+struct ark355_pvk {
+  PvkDev* d;
+};
 
 namespace {
 struct CtxExtra {
@@ -823,6 +826,70 @@ int32_t ark355_verify_each(ark355_ctx* ctx, int32_t curve, const ark355_vk_desc*
   return guarded(ctx, [&] {
     CtxExtra& ex = extra(ctx);
     CURVE_DISPATCH(curve, A::verify_each(ctx, ex.generic, vk, proofs, public_inputs, count, ok));
+  });
+}
+
+int32_t ark355_vk_process(ark355_ctx* ctx, int32_t curve, const ark355_vk_desc* vk, ark355_pvk** out) {
+  if (out) *out = nullptr;
+  if (!ctx || !vk || !out || !vk->alpha_g1 || !vk->beta_g2 || !vk->gamma_g2 || !vk->delta_g2 || !vk->gamma_abc_g1)
+    return ARK355_EINVAL;
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    PvkDev* d = nullptr;
+    CURVE_DISPATCH(curve, d = A::vk_process(ctx, ex.generic, vk));
+    *out = new ark355_pvk{d};
+  });
+}
+
+void ark355_pvk_free(ark355_pvk* pvk) {
+  if (!pvk) return;
+  if (pvk->d) (void)hipSetDevice(pvk->d->device);
+  delete pvk->d;
+  delete pvk;
+}
+
+int32_t ark355_pvk_info(const ark355_pvk* pvk, int32_t* curve, uint64_t* num_instance, uint64_t* resident_bytes) {
+  if (!pvk || !pvk->d) return ARK355_EINVAL;
+  if (curve) *curve = pvk->d->curve;
+  if (num_instance) *num_instance = pvk->d->ell;
+  if (resident_bytes) *resident_bytes = pvk->d->resident_bytes();
+  return ARK355_OK;
+}
+
+int32_t ark355_pvk_alpha_beta(const ark355_pvk* pvk, uint8_t* out_gt) {
+  if (!pvk || !pvk->d || !out_gt) return ARK355_EINVAL;
+  memcpy(out_gt, pvk->d->alpha_beta.data(), pvk->d->alpha_beta.size());
+  return ARK355_OK;
+}
+
+int32_t ark355_pvk_pairings(ark355_ctx* ctx, const ark355_pvk* pvk, int32_t which, const uint8_t* g1, uint64_t n, uint8_t* out_gt,
+                            uint8_t* is_one) {
+  if (!ctx || !pvk || !pvk->d) return ARK355_EINVAL;
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(pvk->d->curve, A::pvk_pairings(ctx, ex.generic, *pvk->d, which, g1, n, out_gt, is_one));
+  });
+}
+
+int32_t ark355_verify_each_pvk(ark355_ctx* ctx, const ark355_pvk* pvk, const ark355_proof_raw* proofs, const uint8_t* public_inputs,
+                               uint64_t count, uint8_t* ok) {
+  if (!ctx || !pvk || !pvk->d || (count && (!proofs || !ok))) return ARK355_EINVAL;
+  if (ok) memset(ok, 0, count);
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(pvk->d->curve, A::verify_each_pvk(ctx, ex.generic, *pvk->d, proofs, public_inputs, count, ok));
+  });
+}
+
+int32_t ark355_verify_batch_pvk(ark355_ctx* ctx, const ark355_pvk* pvk, const ark355_proof_raw* proofs, const uint8_t* public_inputs,
+                                const uint8_t* rho, uint64_t count, int32_t* ok) {
+  if (!ctx || !pvk || !pvk->d || !proofs || !ok || (pvk->d->ell > 1 && !public_inputs)) return ARK355_EINVAL;
+  *ok = 0;
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    bool good = false;
+    CURVE_DISPATCH(pvk->d->curve, good = A::verify_batch_pvk(ctx, ex.generic, *pvk->d, proofs, public_inputs, rho, count));
+    *ok = good ? 1 : 0;
   });
 }
 

@@ -410,8 +410,22 @@ struct PairingDev {
     st(p + (size_t)W2 * stride, stride, l1);
     st(p + (size_t)2 * W2 * stride, stride, l2);
   }
-  // T <- 2T, tangent at T evaluated at P
-  ARK_D static void dbl_step(Proj& T, const Fq& xp, const Fq& yp, const Fq& two_inv, uint32_t* out, size_t stride, uint32_t s) {
+  // Where a line is evaluated.  AtP: at the G1 point of the pair, the x-term times xp and the y-term times yp (pass A per pair).
+  // Unevaluated: not yet -- the P-independent coefficients of a prepared G2 point (ark-ec G2Prepared), which
+  // pairing_accumulate_key_kernel multiplies by xp and yp when it reads them.
+  struct AtP {
+    const Fq& xp;
+    const Fq& yp;
+    ARK_D Fq2 x(const Fq2& a) const { return mul_fq(a, xp); }
+    ARK_D Fq2 y(const Fq2& a) const { return mul_fq(a, yp); }
+  };
+  struct Unevaluated {
+    ARK_D Fq2 x(const Fq2& a) const { return a; }
+    ARK_D Fq2 y(const Fq2& a) const { return a; }
+  };
+  // T <- 2T, tangent at T: (i, 3 x^2 . xp, -(h . yp)) in the coefficient order of the curve
+  template <class Eval>
+  ARK_D static void dbl_step(Proj& T, const Eval& at, const Fq& two_inv, uint32_t* out, size_t stride, uint32_t s) {
     const Fq2 a = mul_fq(Fq2::mul(T.x, T.y), two_inv);
     const Fq2 b = Fq2::sqr(T.y);
     const Fq2 c = Fq2::sqr(T.z);
@@ -420,8 +434,8 @@ struct PairingDev {
     const Fq2 g = mul_fq(Fq2::add(b, f), two_inv);
     const Fq2 h = Fq2::sub(Fq2::sqr(Fq2::add(T.y, T.z)), Fq2::add(b, c));
     const Fq2 i = Fq2::sub(e, b);
-    const Fq2 j3 = mul_fq(Fq2::mul3(Fq2::sqr(T.x)), xp);
-    const Fq2 hy = Fq2::neg(mul_fq(h, yp));
+    const Fq2 j3 = at.x(Fq2::mul3(Fq2::sqr(T.x)));
+    const Fq2 hy = Fq2::neg(at.y(h));
     if (BN) put_line(out, stride, s, hy, j3, i);
     else put_line(out, stride, s, i, j3, hy);
     const Fq2 e2 = Fq2::sqr(e);
@@ -429,15 +443,15 @@ struct PairingDev {
     T.y = Fq2::sub(Fq2::sqr(g), Fq2::mul3(e2));
     T.z = Fq2::mul(b, h);
   }
-  // T <- T + Q (Q affine), line through T and Q evaluated at P
-  ARK_D static void add_step(Proj& T, const Fq2& qx, const Fq2& qy, const Fq& xp, const Fq& yp, uint32_t* out, size_t stride,
-                             uint32_t s) {
+  // T <- T + Q (Q affine), line through T and Q: (j, -(theta . xp), lambda . yp)
+  template <class Eval>
+  ARK_D static void add_step(Proj& T, const Fq2& qx, const Fq2& qy, const Eval& at, uint32_t* out, size_t stride, uint32_t s) {
     const Fq2 theta = Fq2::sub(T.y, Fq2::mul(qy, T.z));
     const Fq2 lambda = Fq2::sub(T.x, Fq2::mul(qx, T.z));
     {
       const Fq2 j = Fq2::sub(Fq2::mul(theta, qx), Fq2::mul(lambda, qy));
-      const Fq2 tx = Fq2::neg(mul_fq(theta, xp));
-      const Fq2 ly = mul_fq(lambda, yp);
+      const Fq2 tx = Fq2::neg(at.x(theta));
+      const Fq2 ly = at.y(lambda);
       if (BN) put_line(out, stride, s, ly, tx, j);
       else put_line(out, stride, s, j, tx, ly);
     }
@@ -466,13 +480,16 @@ pairing_lines_kernel(const Affine<typename Curve::Fq>* __restrict__ g1, const Af
   const Affine<Fq> P = g1[i];
   const Affine<Fq2> Q = g2[i];
   if (P.is_inf() || Q.is_inf()) return;
+  // The walk stays in the body of this kernel and pairing_key_lines_kernel repeats it: moved into a shared function it is laid
+  // out differently (BN254: other branch polarities around the loop), and this kernel's code object is to stay what it was.
+  const typename D::AtP at{P.x, P.y};
   typename D::Proj T{Q.x, Q.y, Fq2::one()};
   uint32_t* out = lines + i;
   uint32_t s = 0;
 #pragma unroll 1
   for (int b = D::LOOP_TOP - 1; b >= 0; b--) {
-    D::dbl_step(T, P.x, P.y, k.two_inv, out, stride, s++);
-    if ((D::LOOP_LO >> b) & 1ull) D::add_step(T, Q.x, Q.y, P.x, P.y, out, stride, s++);
+    D::dbl_step(T, at, k.two_inv, out, stride, s++);
+    if ((D::LOOP_LO >> b) & 1ull) D::add_step(T, Q.x, Q.y, at, out, stride, s++);
   }
   if (D::BN) {
     // Q1 = pi(Q), Q2 = -pi^2(Q)
@@ -481,7 +498,7 @@ pairing_lines_kernel(const Affine<typename Curve::Fq>* __restrict__ g1, const Af
     for (int r = 0; r < 2; r++) {
       x = Fq2::mul(Fq2{x.c0, Fq::neg(x.c1)}, k.frob_x);
       y = Fq2::mul(Fq2{y.c0, Fq::neg(y.c1)}, k.frob_y);
-      D::add_step(T, x, r ? Fq2::neg(y) : y, P.x, P.y, out, stride, s++);
+      D::add_step(T, x, r ? Fq2::neg(y) : y, at, out, stride, s++);
     }
   }
 }
@@ -534,6 +551,112 @@ pairing_accumulate_kernel(const Affine<typename Curve::Fq>* __restrict__ g1, con
     if (lane == 0)
       for (uint32_t d = 0; d < D::W12; d++) partial[(size_t)blockIdx.x * D::W12 + d] = f[d * PAIR_LANES];
   }
+}
+
+// ---- a prepared G2 point (ark-ec G2Prepared; the gamma and delta of a processed verifying key) ----------------------------
+// Pass A without a P: lane i < n walks T = [k]q[i] and writes the P-independent coefficients of its lines, (i, 3 x^2, -h)
+// and (j, -theta, lambda) in the coefficient order of the curve, PLAIN (not lane-transposed): point i at
+// lines + i * steps * 3 * W2, line s at + 3 s W2, three F_q2 as they lie in memory.  Every lane of pass B reads the same
+// address, so one address per wave-load is what is wanted.  Cold: one launch per key.  A point at infinity writes nothing.
+template <class Curve>
+__global__ void __launch_bounds__(PAIR_LANES)
+pairing_key_lines_kernel(const Affine<typename Curve::Fq2>* __restrict__ q, uint32_t n, typename PairingDev<Curve>::Consts k,
+                         uint32_t* __restrict__ lines) {
+  using D = PairingDev<Curve>;
+  using Fq = typename Curve::Fq;
+  using Fq2 = typename Curve::Fq2;
+  const uint32_t i = blockIdx.x * PAIR_LANES + threadIdx.x;
+  if (i >= n) return;
+  const Affine<Fq2> Q = q[i];
+  if (Q.is_inf()) return;
+  // the walk of pairing_lines_kernel with the lines left unevaluated, plain layout (stride 1)
+  const typename D::Unevaluated at{};
+  typename D::Proj T{Q.x, Q.y, Fq2::one()};
+  uint32_t* out = lines + (size_t)i * k.steps * 3 * D::W2;
+  uint32_t s = 0;
+#pragma unroll 1
+  for (int b = D::LOOP_TOP - 1; b >= 0; b--) {
+    D::dbl_step(T, at, k.two_inv, out, 1, s++);
+    if ((D::LOOP_LO >> b) & 1ull) D::add_step(T, Q.x, Q.y, at, out, 1, s++);
+  }
+  if (D::BN) {
+    Fq2 x = Q.x, y = Q.y;
+#pragma unroll 1
+    for (int r = 0; r < 2; r++) {
+      x = Fq2::mul(Fq2{x.c0, Fq::neg(x.c1)}, k.frob_x);
+      y = Fq2::mul(Fq2{y.c0, Fq::neg(y.c1)}, k.frob_y);
+      D::add_step(T, x, r ? Fq2::neg(y) : y, at, out, 1, s++);
+    }
+  }
+}
+
+// Pass B against prepared points: the PER_PAIR form of pairing_accumulate_kernel for pairs (P_i, Q) whose Q is one of two
+// prepared points.  The first blocks_a workgroups take the na points pa[i] against the lines la, the others the nb points
+// pb[i] against lb: the selector is uniform over a workgroup, so a wave loads one address per coefficient.  A NULL la / lb
+// says that the prepared point is at infinity (every pair of that range contributes one).  Per line the lane multiplies
+// the x-term by xp and the y-term by yp -- both fully reduced, and (-h) yp = -(h yp) in the field, so f_i is bit for bit what
+// pass A per pair followed by pairing_accumulate_kernel leaves.  xp and yp are read again at every line (96 B from L2
+// against 18 F_q2 products) instead of living in 24 registers across the loop.
+// f_i goes to mill[d * stride + i * omul + ooff_a / ooff_b]: where pairing_final_exp_kernel expects a member of group i.
+template <class Curve>
+__global__ void __launch_bounds__(PAIR_LANES)
+pairing_accumulate_key_kernel(const Affine<typename Curve::Fq>* __restrict__ pa, uint32_t na, const uint32_t* __restrict__ la,
+                              const Affine<typename Curve::Fq>* __restrict__ pb, uint32_t nb, const uint32_t* __restrict__ lb,
+                              uint32_t blocks_a, uint32_t stride, uint32_t omul, uint32_t ooff_a, uint32_t ooff_b,
+                              typename PairingDev<Curve>::Consts k, uint32_t* __restrict__ mill) {
+  using D = PairingDev<Curve>;
+  using Fq = typename Curve::Fq;
+  __shared__ uint32_t lds[2 * D::W12 * PAIR_LANES];
+  const bool second = blockIdx.x >= blocks_a;
+  const uint32_t lane = threadIdx.x, i = (blockIdx.x - (second ? blocks_a : 0u)) * PAIR_LANES + lane;
+  const uint32_t n = second ? nb : na;
+  const Affine<Fq>* __restrict__ g1 = second ? pb : pa;
+  const uint32_t* __restrict__ in = second ? lb : la;
+  uint32_t* f = lds + lane;
+  uint32_t* g = lds + D::W12 * PAIR_LANES + lane;
+  D::set_one(f);
+  bool live = i < n && in != nullptr;
+  if (live) live = !g1[i].is_inf();
+  if (live) {
+#pragma unroll 1
+    for (uint32_t s = 0; s < k.steps; s++) {
+      if ((k.sqr_mask[s >> 6] >> (s & 63)) & 1ull) {
+        D::sqr12(g, f);
+        uint32_t* t = f;
+        f = g;
+        g = t;
+      }
+      const uint32_t* p = in + (size_t)(3 * s) * D::W2;
+      auto l0 = D::ld(p, 1), l1 = D::ld(p + D::W2, 1), l2 = D::ld(p + 2 * D::W2, 1);
+      l1 = D::mul_fq(l1, g1[i].x);
+      if (D::BN) l0 = D::mul_fq(l0, g1[i].y);
+      else l2 = D::mul_fq(l2, g1[i].y);
+      D::mul12_sparse(g, f, l0, l1, l2);
+      uint32_t* t = f;
+      f = g;
+      g = t;
+    }
+    if (f != lds + lane) {
+      D::copy12(g, f);
+      f = lds + lane;
+    }
+  }
+  if (i < n) {
+    uint32_t* o = mill + (size_t)i * omul + (second ? ooff_b : ooff_a);
+    for (uint32_t d = 0; d < D::W12; d++) o[(size_t)d * stride] = f[d * PAIR_LANES];
+  }
+}
+
+// mill[d * stride + i * omul] = src[d * src_stride + i], i < n: the Miller values pairing_accumulate_kernel<Curve, true>
+// left for n pairs, moved to where member 0 of group i belongs (the other members come from pairing_accumulate_key_kernel)
+template <class Curve>
+__global__ void __launch_bounds__(256)
+miller_spread_kernel(const uint32_t* __restrict__ src, uint32_t src_stride, uint32_t n, uint32_t stride, uint32_t omul,
+                     uint32_t* __restrict__ mill) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  for (uint32_t d = 0; d < PairingDev<Curve>::W12; d++)
+    mill[(size_t)d * stride + (size_t)i * omul] = src[(size_t)d * src_stride + i];
 }
 
 // out (W12 plain dwords) = prod of `count` partial products; one workgroup
@@ -712,6 +835,26 @@ verify_each_pairs_kernel(const Affine<typename Curve::Fq>* __restrict__ gamma_ab
   q[3 * j] = b[j];
   q[3 * j + 1] = gamma_delta[0];
   q[3 * j + 2] = gamma_delta[1];
+  bad[j] = flags[j] | flags[count + j] | flags[2 * count + j];
+}
+
+// ark355_verify_each_pvk, one lane per proof: nacc[j] = -(gamma_abc_0 + sum_i prod[j * m + i]) and negc[j] = -C_j, the first
+// arguments of the pairs against the prepared gamma and delta, and bad[j] as verify_each_pairs_kernel forms it.  The pair
+// (A_j, B_j) is read where it was staged; nothing of the key is copied next to the proofs.
+template <class Curve>
+__global__ void __launch_bounds__(128)
+verify_each_key_pairs_kernel(const Affine<typename Curve::Fq>* __restrict__ gamma_abc, const XYZZ<typename Curve::Fq>* __restrict__ prod,
+                             uint32_t m, const Affine<typename Curve::Fq>* __restrict__ ac, const uint8_t* __restrict__ flags,
+                             uint64_t count, Affine<typename Curve::Fq>* __restrict__ nacc, Affine<typename Curve::Fq>* __restrict__ negc,
+                             uint8_t* __restrict__ bad) {
+  using Fq = typename Curve::Fq;
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  XYZZ<Fq> acc = XYZZ<Fq>::from_affine(gamma_abc[0]);
+  for (uint32_t i = 0; i < m; i++) acc = xyzz_add(acc, prod[j * m + i]);
+  const Affine<Fq> s = xyzz_to_affine(acc), c = ac[count + j];
+  nacc[j] = s.is_inf() ? s : Affine<Fq>::neg(s);
+  negc[j] = c.is_inf() ? c : Affine<Fq>::neg(c);
   bad[j] = flags[j] | flags[count + j] | flags[2 * count + j];
 }
 

@@ -1,6 +1,7 @@
 // Host drivers of the pairing entry points: ark355_multi_pairing, ark355_pairing_groups, ark355_verify_each and
-// ark355_verify_batch.  Each has a host route (pairing_host.hpp on at most 16 host threads) and a device route (the kernels
-// of pairing_impl.cuh); policy PAIRING_DEVICE chooses.  Api<Curve> (api_impl.cuh) forwards here.
+// ark355_verify_batch, and of the processed verifying key (ark355_vk_process and the ark355_*_pvk entries).  Each has a host
+// route (pairing_host.hpp on at most 16 host threads) and a device route (the kernels of pairing_impl.cuh); policy
+// PAIRING_DEVICE chooses.  Api<Curve> (api_impl.cuh) forwards here.
 #pragma once
 #include <chrono>
 #include <thread>
@@ -16,6 +17,23 @@ struct PairingScratch {
   DevBuf pg1, pg2, plines, ppart, pout, psc;      // points, lines, partial products, the Miller product, scalars
   DevBuf pmill, pfe, pgt, pverd;                  // per-group pairings: Miller values of a chunk, program + constants, GT values, verdicts
   DevBuf pabc, pprod, pflags;                     // ark355_verify_each: gamma_abc, the terms of the prepared inputs, per-point flags
+  DevBuf pkmill;                                  // the *_pvk entries: Miller values of a chunk, three members per proof
+};
+
+// ark355_pvk: what SNARK::process_vk computes once per key.  Immutable after ark355_vk_process; the device buffers belong to
+// the handle, not to the context that made it, so any context of `device` may use it, the creating one destroyed or not.
+struct PvkDev {
+  int curve = 0, device = 0;
+  uint64_t ell = 0;
+  uint32_t steps = 0;                 // lines per prepared point
+  bool inf[3] = {false, false, false};   // beta, gamma, delta at infinity: no lines, the pairs contribute one
+  std::vector<uint8_t> alpha, g2;     // host: alpha_g1; beta_g2, gamma_g2, delta_g2 (raw images)
+  std::vector<uint8_t> abc_host;      // host: gamma_abc_g1, the bases of ark355_verify_batch_pvk's one-shot MSM and of the host route
+  std::vector<uint8_t> alpha_beta;    // host: e(alpha, beta), 12 Fq in the layout of ark355_multi_pairing
+  DevBuf abc;                         // ell G1
+  DevBuf lines;                       // 3 x steps x 3 F_q2, plain: the P-independent line coefficients of beta, gamma, delta
+  size_t abc_bytes = 0, lines_bytes = 0;
+  size_t resident_bytes() const { return abc_bytes + lines_bytes; }
 };
 
 template <class Curve>
@@ -32,6 +50,11 @@ struct Verify {
   static constexpr bool BN = Curve::ID == ARK355_BN254;
   // At most PAIR_CHUNK pairs have their lines in HBM at a time (about 20 KB per pair).
   static constexpr uint64_t PAIR_CHUNK = 1u << 15;
+  // ark355_verify_each_pvk: proofs per chunk.  One pair in three still has lines of its own, so a chunk holds as many proofs
+  // as PAIR_CHUNK holds pairs (the same HBM for lines, three Miller values per proof: 56 MB on BLS12-381).
+  static constexpr uint64_t PVK_EACH_CHUNK = PAIR_CHUNK;
+  // ark355_pvk_pairings: pairs per chunk; no lines at all, the chunk bounds the Miller values in HBM (576 B per pair)
+  static constexpr uint64_t PVK_PAIR_CHUNK = 1u << 17;
 
   ark355_ctx* ctx;
   PairingScratch& s;
@@ -215,9 +238,26 @@ struct Verify {
   // A chunk holds whole groups; its lines and Miller values are in HBM at a time.
   void groups_dev(const G1* d1, const G2* d2, uint64_t groups, uint32_t group_len, const Gt& target, const uint8_t* d_bad,
                   uint8_t* out_gt, uint8_t* verdict) {
-    hipStream_t st = ctx->stream;
+    const FeDev fe = fe_upload(target);
+    if (out_gt) s.pgt.ensure(groups * PD::W12 * sizeof(uint32_t));
+    s.pverd.ensure(groups);
+    miller_chunks<true>(d1, d2, groups * group_len, PAIR_CHUNK / group_len * group_len, [&](uint64_t off, uint32_t m, uint32_t stride) {
+      fe_launch(fe, s.pmill.as<uint32_t>(), stride, off / group_len, m / group_len, group_len, d_bad, out_gt != nullptr);
+    });
+    fe_download(groups, out_gt, verdict);
+  }
+
+  // the final exponentiation's program and constants in s.pfe: 18 Frobenius constants, the target (the kernels' order:
+  // coefficients of w^0 .. w^5), the instructions
+  struct FeDev {
+    const Fq2* frob;
+    const uint32_t* tgt;
+    const uint32_t* prog;
+    uint32_t nsteps;
+    std::vector<uint8_t> blob;      // the host image: the upload is asynchronous, the caller keeps this until it has synchronised
+  };
+  FeDev fe_upload(const Gt& target) {
     const std::vector<uint32_t>& prog = PD::fe_program();
-    // program + constants: 18 Frobenius constants, the target (the kernels' order: coefficients of w^0 .. w^5), the instructions
     const size_t frob_bytes = 18 * sizeof(Fq2), tgt_bytes = PD::W12 * sizeof(uint32_t);
     std::vector<uint8_t> blob(frob_bytes + tgt_bytes + prog.size() * sizeof(uint32_t));
     memcpy(blob.data(), PH::consts().frob12, frob_bytes);
@@ -225,20 +265,20 @@ struct Verify {
     memcpy(blob.data() + frob_bytes, tc, tgt_bytes);
     memcpy(blob.data() + frob_bytes + tgt_bytes, prog.data(), prog.size() * sizeof(uint32_t));
     s.pfe.ensure(blob.size());
-    ARK_CHECK_HIP(hipMemcpyAsync(s.pfe.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    const Fq2* d_frob = s.pfe.as<Fq2>();
+    ARK_CHECK_HIP(hipMemcpyAsync(s.pfe.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
     const uint32_t* d_tgt = reinterpret_cast<const uint32_t*>(s.pfe.as<uint8_t>() + frob_bytes);
-    const uint32_t* d_prog = d_tgt + PD::W12;
-    if (out_gt) s.pgt.ensure(groups * PD::W12 * sizeof(uint32_t));
-    s.pverd.ensure(groups);
-    miller_chunks<true>(d1, d2, groups * group_len, PAIR_CHUNK / group_len * group_len, [&](uint64_t off, uint32_t m, uint32_t stride) {
-      const uint64_t g0 = off / group_len;
-      const uint32_t ng = m / group_len;
-      ARK_LAUNCH((pairing_final_exp_kernel<Curve>), dim3((ng + PAIR_LANES - 1) / PAIR_LANES), dim3(PAIR_LANES), 0, st,
-                 (const uint32_t*)s.pmill.as<uint32_t>(), stride, ng, group_len, d_prog, (uint32_t)prog.size(), d_frob, d_tgt,
-                 d_bad ? d_bad + g0 : nullptr, out_gt ? s.pgt.as<uint32_t>() + g0 * PD::W12 : nullptr, s.pverd.as<uint8_t>() + g0);
-      ARK_CHECK_LAUNCH();
-    });
+    return FeDev{s.pfe.as<Fq2>(), d_tgt, d_tgt + PD::W12, (uint32_t)prog.size(), std::move(blob)};
+  }
+  // groups g0 .. g0 + ng - 1 of the call from the Miller values of a chunk (mill[d * stride + pair]) into s.pgt / s.pverd
+  void fe_launch(const FeDev& fe, const uint32_t* mill, uint32_t stride, uint64_t g0, uint32_t ng, uint32_t group_len,
+                 const uint8_t* d_bad, bool want_gt) {
+    ARK_LAUNCH((pairing_final_exp_kernel<Curve>), dim3((ng + PAIR_LANES - 1) / PAIR_LANES), dim3(PAIR_LANES), 0, ctx->stream, mill,
+               stride, ng, group_len, fe.prog, fe.nsteps, fe.frob, fe.tgt, d_bad ? d_bad + g0 : nullptr,
+               want_gt ? s.pgt.as<uint32_t>() + g0 * PD::W12 : nullptr, s.pverd.as<uint8_t>() + g0);
+    ARK_CHECK_LAUNCH();
+  }
+  void fe_download(uint64_t groups, uint8_t* out_gt, uint8_t* verdict) {
+    hipStream_t st = ctx->stream;
     if (out_gt) ARK_CHECK_HIP(hipMemcpyAsync(out_gt, s.pgt.p, groups * PD::W12 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     ARK_CHECK_HIP(hipMemcpyAsync(verdict, s.pverd.p, groups, hipMemcpyDeviceToHost, st));
     ARK_CHECK_HIP(hipStreamSynchronize(st));
@@ -312,6 +352,29 @@ struct Verify {
     trace("pairing_groups", dev, n, t1 - t0, 0.0, now_ms() - t1, 0.0);
   }
 
+  // the host route of ark355_verify_each and ark355_verify_each_pvk: one proof per unit of host_each
+  static void each_host(const G1* abc, uint32_t m, const G2& gamma, const G2& delta, const Gt& target, const ark355_proof_raw* proofs,
+                        const uint8_t* inputs, uint64_t count, uint8_t* ok) {
+    host_each(count, [&](uint64_t j) {
+      const G1 a = load_g1(proofs[j].a), c = load_g1(proofs[j].c);
+      const G2 b = load_g2(proofs[j].b);
+      ok[j] = 0;
+      if (!on_curve(a) || !on_curve(c) || !on_curve(b)) return;
+      XYZZ<Fq> acc = XYZZ<Fq>::from_affine(abc[0]);
+      for (uint32_t i = 0; i < m; i++) {
+        Fr x;
+        memcpy(x.l, inputs + ((size_t)j * m + i) * sizeof(Fr), sizeof(Fr));
+        const Fr kx = Fr::from_mont(x);
+        acc = xyzz_add(acc, xyzz_mul_scalar(XYZZ<Fq>::from_affine(abc[1 + i]), kx.l, Fr::N));
+      }
+      const G1 sum = xyzz_to_affine(acc);
+      Gt f = PH::miller_loop(a, b);
+      f = Gt::mul(f, PH::miller_loop(sum.is_inf() ? sum : G1::neg(sum), gamma));
+      f = Gt::mul(f, PH::miller_loop(c.is_inf() ? c : G1::neg(c), delta));
+      ok[j] = PH::final_exponentiation(f) == target ? 1 : 0;
+    });
+  }
+
   // ark-groth16 verify_proof for every proof of one key on its own: e(A_j, B_j) e(-acc_j, gamma) e(-C_j, delta) == e(alpha, beta)
   void verify_each(const ark355_vk_desc* vk, const ark355_proof_raw* proofs, const uint8_t* inputs, uint64_t count, uint8_t* ok) {
     const uint64_t ell = vk->num_instance;
@@ -365,24 +428,7 @@ struct Verify {
       ARK_CHECK_LAUNCH();
       groups_dev(d_ac + 2 * count, d_b + count, count, 3, target, d_flags + 3 * count, nullptr, ok);
     } else {
-      host_each(count, [&](uint64_t j) {
-        const G1 a = load_g1(proofs[j].a), c = load_g1(proofs[j].c);
-        const G2 b = load_g2(proofs[j].b);
-        ok[j] = 0;
-        if (!on_curve(a) || !on_curve(c) || !on_curve(b)) return;
-        XYZZ<Fq> acc = XYZZ<Fq>::from_affine(abc[0]);
-        for (uint32_t i = 0; i < m; i++) {
-          Fr x;
-          memcpy(x.l, inputs + ((size_t)j * m + i) * sizeof(Fr), sizeof(Fr));
-          const Fr kx = Fr::from_mont(x);
-          acc = xyzz_add(acc, xyzz_mul_scalar(XYZZ<Fq>::from_affine(abc[1 + i]), kx.l, Fr::N));
-        }
-        const G1 sum = xyzz_to_affine(acc);
-        Gt f = PH::miller_loop(a, b);
-        f = Gt::mul(f, PH::miller_loop(sum.is_inf() ? sum : G1::neg(sum), gamma));
-        f = Gt::mul(f, PH::miller_loop(c.is_inf() ? c : G1::neg(c), delta));
-        ok[j] = PH::final_exponentiation(f) == target ? 1 : 0;
-      });
+      each_host(abc.data(), m, gamma, delta, target, proofs, inputs, count, ok);
     }
     trace("verify_each", dev, 3 * count, t1 - t0, 0.0, now_ms() - t1, 0.0);
   }
@@ -492,6 +538,193 @@ struct Verify {
               (unsigned long long)(count + 3), t1 - t0, now_ms() - t2);
     const Gt f = miller_product_host(Ps, Qs);
     return exponent_formed() && PH::final_exponentiation(f) == Gt::one();      // no exponent: never accept
+  }
+
+  // ---- the processed verifying key (SNARK::process_vk / verify_with_processed_vk, snark/src/lib.rs:36,69-80) ----------------
+  // The per-key work of verify_each, once: the curve checks of the 4 + ell points (refused as verify_each refuses them),
+  // e(alpha, beta) on the host (cold), gamma_abc into HBM and the P-independent lines of beta, gamma and delta
+  // (pairing_key_lines_kernel).  A key point at infinity is legal: it gets no lines and its pairs contribute one.
+  PvkDev* vk_process(const ark355_vk_desc* vk) {
+    const uint64_t ell = vk->num_instance;
+    ARK_REQUIRE(ell >= 1, ARK355_EINVAL, "empty key");
+    ARK_REQUIRE(exponent_formed(), ARK355_EINVAL, "the final exponent could not be formed");
+    const G1 alpha = load_g1(vk->alpha_g1);
+    const G2 q[3] = {load_g2(vk->beta_g2), load_g2(vk->gamma_g2), load_g2(vk->delta_g2)};
+    if (!on_curve(alpha)) refuse("vk.alpha_g1");
+    if (!on_curve(q[0])) refuse("vk.beta_g2");
+    if (!on_curve(q[1])) refuse("vk.gamma_g2");
+    if (!on_curve(q[2])) refuse("vk.delta_g2");
+    std::unique_ptr<PvkDev> d(new PvkDev());
+    d->curve = Curve::ID;
+    d->device = ctx->device;
+    d->ell = ell;
+    d->abc_host.assign(vk->gamma_abc_g1, vk->gamma_abc_g1 + ell * sizeof(G1));
+    for (uint64_t i = 0; i < ell; i++)
+      if (!on_curve(load_g1(d->abc_host.data() + i * sizeof(G1)))) refuse(at("vk.gamma_abc_g1", i));
+    d->alpha.assign(vk->alpha_g1, vk->alpha_g1 + sizeof(G1));
+    d->g2.resize(sizeof(q));
+    memcpy(d->g2.data(), q, sizeof(q));
+    for (int i = 0; i < 3; i++) d->inf[i] = q[i].is_inf();
+    const Gt target = PH::final_exponentiation(PH::miller_loop(alpha, q[0]));
+    d->alpha_beta.resize(sizeof(Gt));
+    memcpy(d->alpha_beta.data(), &target, sizeof(Gt));
+    const typename PD::Consts k = dev_consts();
+    d->steps = k.steps;
+    d->abc_bytes = ell * sizeof(G1);
+    d->lines_bytes = (size_t)3 * k.steps * 3 * PD::W2 * sizeof(uint32_t);
+    d->abc.alloc(d->abc_bytes);
+    d->lines.alloc(d->lines_bytes);
+    hipStream_t st = ctx->stream;
+    DevBuf dq(sizeof(q));
+    ARK_CHECK_HIP(hipMemcpyAsync(d->abc.p, d->abc_host.data(), d->abc_bytes, hipMemcpyHostToDevice, st));
+    ARK_CHECK_HIP(hipMemcpyAsync(dq.p, q, sizeof(q), hipMemcpyHostToDevice, st));
+    ARK_CHECK_HIP(hipMemsetAsync(d->lines.p, 0, d->lines_bytes, st));
+    ARK_LAUNCH((pairing_key_lines_kernel<Curve>), dim3(1), dim3(PAIR_LANES), 0, st, (const G2*)dq.as<G2>(), 3u, k,
+               d->lines.as<uint32_t>());
+    ARK_CHECK_LAUNCH();
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+    return d.release();
+  }
+
+  static G2 pvk_point(const PvkDev& pvk, int which) { return load_g2(pvk.g2.data() + (size_t)which * sizeof(G2)); }
+  static Gt pvk_target(const PvkDev& pvk) {
+    Gt t;
+    memcpy(&t, pvk.alpha_beta.data(), sizeof(Gt));
+    return t;
+  }
+  // the lines of prepared point `which` (0 beta, 1 gamma, 2 delta); NULL where the point is at infinity
+  static const uint32_t* pvk_lines(const PvkDev& pvk, int which) {
+    return pvk.inf[which] ? nullptr : pvk.lines.as<uint32_t>() + (size_t)which * pvk.steps * 3 * PD::W2;
+  }
+  void pvk_usable(const PvkDev& pvk) const {
+    ARK_REQUIRE(pvk.device == ctx->device, ARK355_EINVAL, "the processed key is resident on another device than this context's");
+  }
+
+  // ark-ec Pairing::pairing against one G2Prepared: GT_i = e(P_i, Q_which), byte for byte ark355_pairing_groups' value
+  void pvk_pairings(const PvkDev& pvk, int which, const uint8_t* g1, uint64_t n, uint8_t* out_gt, uint8_t* is_one) {
+    pvk_usable(pvk);
+    ARK_REQUIRE(which >= 0 && which <= 2, ARK355_EINVAL, "which must be 0 (beta), 1 (gamma) or 2 (delta)");
+    if (n == 0) return;
+    ARK_REQUIRE(n <= 0xFFFFFFFFull, ARK355_EINVAL, "n must stay below 2^32");
+    ARK_REQUIRE(g1, ARK355_EINVAL, "a point array is NULL");
+    const bool dev = on_device(ctx->policy.pairing_each_min, n);
+    const double t0 = now_ms();
+    double t1 = t0;
+    std::vector<uint8_t> verdict(n);
+    if (dev) {
+      hipStream_t st = ctx->stream;
+      s.pg1.ensure(n * sizeof(G1));
+      ARK_CHECK_HIP(hipMemcpyAsync(s.pg1.p, g1, n * sizeof(G1), hipMemcpyHostToDevice, st));
+      if (const unsigned long long e = on_curve_dev(s.pg1.p, n, nullptr, 0)) refuse_word(e);
+      t1 = now_ms();
+      const FeDev fe = fe_upload(Gt::one());
+      const typename PD::Consts k = dev_consts();
+      const uint32_t stride = (uint32_t)((std::min(n, PVK_PAIR_CHUNK) + PAIR_LANES - 1) / PAIR_LANES * PAIR_LANES);
+      s.pkmill.ensure((size_t)PD::W12 * stride * sizeof(uint32_t));
+      if (out_gt) s.pgt.ensure(n * PD::W12 * sizeof(uint32_t));
+      s.pverd.ensure(n);
+      for (uint64_t off = 0; off < n; off += PVK_PAIR_CHUNK) {
+        const uint32_t m = (uint32_t)std::min(PVK_PAIR_CHUNK, n - off);
+        const uint32_t blocks = (m + PAIR_LANES - 1) / PAIR_LANES;
+        ARK_LAUNCH((pairing_accumulate_key_kernel<Curve>), dim3(blocks), dim3(PAIR_LANES), 0, st, (const G1*)s.pg1.as<G1>() + off, m,
+                   pvk_lines(pvk, which), (const G1*)nullptr, 0u, (const uint32_t*)nullptr, blocks, stride, 1u, 0u, 0u, k,
+                   s.pkmill.as<uint32_t>());
+        ARK_CHECK_LAUNCH();
+        fe_launch(fe, s.pkmill.as<uint32_t>(), stride, off, m, 1, nullptr, out_gt != nullptr);
+      }
+      fe_download(n, out_gt, verdict.data());
+    } else {
+      for (uint64_t i = 0; i < n; i++)
+        if (!on_curve(load_g1(g1 + i * sizeof(G1)))) refuse(at("g1", i));
+      t1 = now_ms();
+      const G2 Q = pvk_point(pvk, which);
+      host_each(n, [&](uint64_t i) {
+        const Gt gt = PH::final_exponentiation(PH::miller_loop(load_g1(g1 + i * sizeof(G1)), Q));
+        if (out_gt) memcpy(out_gt + i * sizeof(Gt), &gt, sizeof(gt));
+        verdict[i] = gt == Gt::one() ? 1 : 0;
+      });
+    }
+    if (is_one) memcpy(is_one, verdict.data(), n);
+    trace("pvk_pairings", dev, n, t1 - t0, 0.0, now_ms() - t1, 0.0);
+  }
+
+  // SNARK::verify_with_processed_vk for every proof on its own: verify_each without the per-key work.  Device route: pass A
+  // and the per-pair pass B over the count pairs (A_j, B_j) only; the 2 count pairs (-acc_j, gamma), (-C_j, delta) go through
+  // pairing_accumulate_key_kernel against the handle's lines; one final exponentiation per proof over its three Miller values.
+  void verify_each_pvk(const PvkDev& pvk, const ark355_proof_raw* proofs, const uint8_t* inputs, uint64_t count, uint8_t* ok) {
+    pvk_usable(pvk);
+    const uint64_t ell = pvk.ell;
+    if (count == 0) return;
+    ARK_REQUIRE(ell == 1 || inputs, ARK355_EINVAL, "public_inputs is NULL");
+    ARK_REQUIRE(count <= 0xFFFFFFFFull / 3, ARK355_EINVAL, "3 * count must stay below 2^32");
+    const uint32_t m = (uint32_t)(ell - 1);
+    const Gt target = pvk_target(pvk);
+    const double t0 = now_ms();
+    const bool dev = on_device(ctx->policy.pairing_each_min, count);
+    if (dev) {
+      hipStream_t st = ctx->stream;
+      // behind the staged proofs: s.pg1 the -acc_j and the -C_j
+      const StagedProofs staged = stage_proofs(proofs, count, 4 * count, count);
+      s.pflags.ensure(4 * count);
+      G1* d_ac = s.pg1.as<G1>();
+      G2* d_b = s.pg2.as<G2>();
+      G1* d_nacc = d_ac + 2 * count;
+      G1* d_negc = d_ac + 3 * count;
+      uint8_t* d_flags = s.pflags.as<uint8_t>();
+      const G1* d_abc = pvk.abc.as<G1>();
+      ARK_LAUNCH((on_curve_flags_kernel<Curve>), dim3((uint32_t)((3 * count + 127) / 128)), dim3(128), 0, st, (const G1*)d_ac,
+                 2 * count, (const G2*)d_b, count, d_flags);
+      ARK_CHECK_LAUNCH();
+      if (m) {
+        s.psc.ensure(count * m * sizeof(Fr));
+        s.pprod.ensure(count * m * sizeof(XYZZ<Fq>));
+        ARK_CHECK_HIP(hipMemcpyAsync(s.psc.p, inputs, count * m * sizeof(Fr), hipMemcpyHostToDevice, st));
+        ARK_LAUNCH((prepared_input_terms_kernel<Curve>), dim3((uint32_t)((count * m + 127) / 128)), dim3(128), 0, st, d_abc,
+                   (const Fr*)s.psc.as<Fr>(), count, m, s.pprod.as<XYZZ<Fq>>());
+        ARK_CHECK_LAUNCH();
+      }
+      ARK_LAUNCH((verify_each_key_pairs_kernel<Curve>), dim3((uint32_t)((count + 127) / 128)), dim3(128), 0, st, d_abc,
+                 (const XYZZ<Fq>*)s.pprod.as<XYZZ<Fq>>(), m, (const G1*)d_ac, (const uint8_t*)d_flags, count, d_nacc, d_negc,
+                 d_flags + 3 * count);
+      ARK_CHECK_LAUNCH();
+      const FeDev fe = fe_upload(target);
+      const typename PD::Consts k = dev_consts();
+      s.pverd.ensure(count);
+      const uint32_t* lg = pvk_lines(pvk, 1);
+      const uint32_t* ld = pvk_lines(pvk, 2);
+      miller_chunks<true>(d_ac, d_b, count, PVK_EACH_CHUNK, [&](uint64_t off, uint32_t n, uint32_t stride) {
+        // the group layout of the chunk: proof j of it at 3 j .. 3 j + 2 of a row of 3 * stride
+        const uint32_t row = 3 * stride, blocks = (n + PAIR_LANES - 1) / PAIR_LANES;
+        s.pkmill.ensure((size_t)PD::W12 * row * sizeof(uint32_t));
+        ARK_LAUNCH((miller_spread_kernel<Curve>), dim3((n + 255) / 256), dim3(256), 0, st, (const uint32_t*)s.pmill.as<uint32_t>(),
+                   stride, n, row, 3u, s.pkmill.as<uint32_t>());
+        ARK_CHECK_LAUNCH();
+        ARK_LAUNCH((pairing_accumulate_key_kernel<Curve>), dim3(2 * blocks), dim3(PAIR_LANES), 0, st, (const G1*)d_nacc + off, n, lg,
+                   (const G1*)d_negc + off, n, ld, blocks, row, 3u, 1u, 2u, k, s.pkmill.as<uint32_t>());
+        ARK_CHECK_LAUNCH();
+        fe_launch(fe, s.pkmill.as<uint32_t>(), row, off, n, 3, d_flags + 3 * count, false);
+      });
+      fe_download(count, nullptr, ok);
+    } else {
+      each_host(reinterpret_cast<const G1*>(pvk.abc_host.data()), m, pvk_point(pvk, 1), pvk_point(pvk, 2), target, proofs, inputs,
+                count, ok);
+    }
+    trace("verify_each_pvk", dev, 3 * count, 0.0, 0.0, now_ms() - t0, 0.0);
+  }
+
+  // ark355_verify_batch over the handle's copies of the key (unchecked, as ark355_verify_batch leaves the key unchecked)
+  template <class Msm>
+  bool verify_batch_pvk(const PvkDev& pvk, const ark355_proof_raw* proofs, const uint8_t* inputs, const uint8_t* rho, uint64_t count,
+                        Msm&& msm) {
+    pvk_usable(pvk);
+    ark355_vk_desc vk{};
+    vk.num_instance = pvk.ell;
+    vk.alpha_g1 = pvk.alpha.data();
+    vk.beta_g2 = pvk.g2.data();
+    vk.gamma_g2 = pvk.g2.data() + sizeof(G2);
+    vk.delta_g2 = pvk.g2.data() + 2 * sizeof(G2);
+    vk.gamma_abc_g1 = pvk.abc_host.data();
+    return verify_batch(&vk, proofs, inputs, rho, count, msm);
   }
 };
 

@@ -8,9 +8,12 @@ Mirrors ``ark_snark::SNARK`` (/root/reference/snark/src/lib.rs:22-81) for one im
   keeps the key resident; ``generator="host"`` is the earlier route (``ark355_setup_scalars`` on host threads, then
   ``ark355_fixed_base_mul`` per vector);
 * ``prove``                   (lib.rs:50-54)           -> ``ark355_prove`` (the hot path);
-* ``verify`` / ``process_vk`` (lib.rs:59-80)           -> ``ark355_verify_batch`` (random linear combination on
+* ``verify``                  (lib.rs:59-67)           -> ``ark355_verify_batch`` (random linear combination on
   the device MSM, Miller loops and the final exponentiation on host threads); proofs stay byte-compatible
-  with the arkworks CPU verifier.
+  with the arkworks CPU verifier;
+* ``process_vk`` / ``verify_with_processed_vk`` (lib.rs:36,69-80) -> ``ark355_vk_process`` / ``ark355_verify_each_pvk``: the
+  per-key work (curve checks, e(alpha, beta), gamma_abc in HBM, the lines of gamma and delta) happens once and stays
+  resident in a handle attached to the key.
 
 Inputs come from the unchanged ``ark-relations`` constraint system on the host:
 ``R1CS.from_rows`` takes exactly what ``ConstraintSystem::to_matrices()["R1CS"]`` returns
@@ -349,11 +352,24 @@ class Groth16:
         """`public_inputs` excludes the leading One, as in `SNARK::verify`.  One proof = a batch of one."""
         return self.verify_batch(vk, [public_inputs], [proof])
 
+    def _vk_parts(self, vk: VerifyingKey):
+        return (vk.alpha_g1, vk.beta_g2, vk.gamma_g2, vk.delta_g2, vk.gamma_abc_g1)
+
     def process_vk(self, vk: VerifyingKey) -> VerifyingKey:
-        """Nothing is precomputed on the host side of this backend: the processed key is the key (lib.rs:70-73)."""
+        """`SNARK::process_vk` (lib.rs:69-73) -> `ark355_vk_process`.  The processed key is the SAME object, with the resident
+        handle attached to it (as `load_pk` attaches one to a proving key): the serializable object stays the key."""
+        if self._cached(vk, "_ark355_pvk") is None:
+            try:
+                h = self.lib.vk_process(self.ctx, self.curve.curve_id, self._vk_parts(vk))
+            except Ark355Error as e:
+                raise SynthesisError(str(e)) from e
+            self._track(vk, "_ark355_pvk", (self, h), self.lib.dll.ark355_pvk_free, h)
         return vk
 
-    verify_with_processed_vk = verify
+    def verify_with_processed_vk(self, vk: VerifyingKey, public_inputs: Sequence[int], proof: Proof) -> bool:
+        """`SNARK::verify_with_processed_vk` (lib.rs:76-80) -> `ark355_verify_each_pvk` with count = 1 against the handle
+        `process_vk` attached (a key that was not processed yet is processed first)."""
+        return self.verify_each(self.process_vk(vk), [public_inputs], [proof])[0]
 
     # ---- ark-ec Pairing::multi_pairing ----------------------------------------------------------------------------------
     def multi_pairing(self, g1_points: Sequence[bytes], g2_points: Sequence[bytes]) -> bytes:
@@ -369,7 +385,11 @@ class Groth16:
         return gt
 
     def alpha_g1_beta_g2(self, vk: VerifyingKey) -> bytes:
-        """The `alpha_g1_beta_g2` of ark-groth16's `PreparedVerifyingKey`: e(alpha_g1, beta_g2) in GT."""
+        """The `alpha_g1_beta_g2` of ark-groth16's `PreparedVerifyingKey`: e(alpha_g1, beta_g2) in GT (read from the handle of
+        a processed key)."""
+        h = self._cached(vk, "_ark355_pvk")
+        if h is not None:
+            return self.lib.pvk_alpha_beta(h)
         return self.multi_pairing([vk.alpha_g1], [vk.beta_g2])
 
     def pairings(self, g1_points: Sequence[bytes], g2_points: Sequence[bytes], group_len: int = 1) -> list:
@@ -388,7 +408,8 @@ class Groth16:
 
     def verify_each(self, vk: VerifyingKey, public_inputs, proofs) -> list:
         """`ark355_verify_each`: `SNARK::verify` for every proof of ONE verifying key on its own -> list[bool].  No random
-        combination: each verdict is that proof's.  A wrong input length gives False for that proof."""
+        combination: each verdict is that proof's.  A wrong input length gives False for that proof.  A key that went through
+        `process_vk` is verified against its handle (`ark355_verify_each_pvk`)."""
         cv = self.curve
         if len(public_inputs) != len(proofs):
             raise ValueError("verify_each needs one list of public inputs per proof")
@@ -398,10 +419,13 @@ class Groth16:
         if not good:
             return out
         xs = b"".join(cv.fr_mont(v) for j in good for v in public_inputs[j])
+        raw = [(proofs[j].a, proofs[j].b, proofs[j].c) for j in good]
+        h = self._cached(vk, "_ark355_pvk")
         try:
-            oks = self.lib.verify_each(self.ctx, cv.curve_id,
-                                       (vk.alpha_g1, vk.beta_g2, vk.gamma_g2, vk.delta_g2, vk.gamma_abc_g1),
-                                       [(proofs[j].a, proofs[j].b, proofs[j].c) for j in good], xs)
+            if h is not None:
+                oks = self.lib.verify_each_pvk(self.ctx, h, raw, xs)
+            else:
+                oks = self.lib.verify_each(self.ctx, cv.curve_id, self._vk_parts(vk), raw, xs)
         except Ark355Error as e:
             raise SynthesisError(str(e)) from e
         for j, ok in zip(good, oks):
@@ -424,9 +448,10 @@ class Groth16:
                 raise ValueError("batch verification needs an rng for the random coefficients")
             rho = [cv.fr_canon((rng() % ((1 << 128) - 1)) + 1) for _ in range(count)]
         xs = b"".join(cv.fr_mont(v) for row in public_inputs for v in row)
+        h = self._cached(vk, "_ark355_pvk")
         try:
-            return self.lib.verify_batch(self.ctx, cv.curve_id,
-                                         (vk.alpha_g1, vk.beta_g2, vk.gamma_g2, vk.delta_g2, vk.gamma_abc_g1),
-                                         [(p.a, p.b, p.c) for p in proofs], xs, rho)
+            if h is not None:
+                return self.lib.verify_batch_pvk(self.ctx, h, [(p.a, p.b, p.c) for p in proofs], xs, rho)
+            return self.lib.verify_batch(self.ctx, cv.curve_id, self._vk_parts(vk), [(p.a, p.b, p.c) for p in proofs], xs, rho)
         except Ark355Error as e:
             raise SynthesisError(str(e)) from e

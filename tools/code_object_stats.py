@@ -40,11 +40,15 @@ KERNELS = [
     (r"pairing_accumulate_kernelINS_8BlsCurveELb1E", "bls12_381.pairing_accumulate_per_pair"),
     (r"pairing_final_exp_kernelINS_8BlsCurve", "bls12_381.pairing_final_exp"),
     (r"pairing_product_kernelINS_8BlsCurve", "bls12_381.pairing_product"),
+    (r"pairing_key_lines_kernelINS_8BlsCurve", "bls12_381.pairing_key_lines"),
+    (r"pairing_accumulate_key_kernelINS_8BlsCurve", "bls12_381.pairing_accumulate_key"),
     (r"pairing_lines_kernelINS_7BnCurve", "bn254.pairing_lines"),
     (r"pairing_accumulate_kernelINS_7BnCurveELb0E", "bn254.pairing_accumulate"),
     (r"pairing_accumulate_kernelINS_7BnCurveELb1E", "bn254.pairing_accumulate_per_pair"),
     (r"pairing_final_exp_kernelINS_7BnCurve", "bn254.pairing_final_exp"),
     (r"pairing_product_kernelINS_7BnCurve", "bn254.pairing_product"),
+    (r"pairing_key_lines_kernelINS_7BnCurve", "bn254.pairing_key_lines"),
+    (r"pairing_accumulate_key_kernelINS_7BnCurve", "bn254.pairing_accumulate_key"),
 ]
 
 

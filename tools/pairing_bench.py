@@ -20,9 +20,16 @@ seconds per call) against device route (final exponentiations in pairing_final_e
 device time of the same n proofs beside it: what a per-proof answer costs over a yes/no.  policy.h's PAIRING_EACH_MIN is the
 crossover of the slower curve and the slower entry.
 
+--pvk measures the processed verifying key by the same protocol: `ark355_verify_each` (the yardstick: this entry redoes the
+per-key work on every call) beside `ark355_verify_each_pvk` on a handle made once, and `ark355_vk_process` itself (process +
+free), at 1 proof on the host route and 256 .. 16384 proofs on the device route.  Besides the medians it prints the spread
+(min .. max) of the yardstick's readings: the processed entry does strictly less work, so it must not be slower than the
+yardstick by more than that spread.
+
 One child process per curve, each under its own `timeout`.  Dev tool; run on an MI355X:
   python tools/pairing_bench.py [--reps 5] [--out profiles/pairing_bench.txt]
   python tools/pairing_bench.py --each [--reps 5] [--out profiles/pairing_each_bench.txt]
+  python tools/pairing_bench.py --pvk [--reps 5] [--out profiles/pvk_bench.txt]
   rocprofv3 --kernel-trace --stats --output-format csv -- python tools/pairing_bench.py --one-verify-each 4096
                                       (one BLS12-381 verify_each, for profiles/pairing_each_kernel_stats.csv)
   rocprofv3 --kernel-trace --stats --output-format csv -- python tools/pairing_bench.py --one-verify 4096
@@ -43,6 +50,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 SIZES = [1, 4, 16, 64, 256, 1024, 4096, 16384]
 EACH_SIZES = [1, 4, 16, 32, 64, 128, 256, 512, 1024, 4096]
+PVK_SIZES = [1, 256, 1024, 4096, 16384]          # 1: the host route (verify_with_processed_vk of one proof); the others: device
 PHASE = re.compile(r"\[ark355\] (\w+) route=(\w+) pairs=(\d+) check_ms=([\d.]+) scalar_mul_ms=([\d.]+)"
                    r"(?: miller_ms=([\d.]+) final_exp_ms=([\d.]+))?")
 
@@ -206,6 +214,58 @@ def child_each(curve_name, reps, sizes, host_max):
     print("", flush=True)
 
 
+def child_pvk(curve_name, reps, sizes):
+    import snark_amd
+    import pairing_cases as P
+    from oracle.fields import BLS12_381, BN254
+    C = {"bls12_381": BLS12_381, "bn254": BN254}[curve_name]
+    lib = snark_amd.lib()
+    ctx = lib.ctx_create(0)
+    vk, proofs, inputs, _, _ = P.oracle_batch(C, 8)
+    pvk = lib.vk_process(ctx, C.curve_id, vk)
+    info = lib.pvk_info(pvk)
+    rows = []
+    for n in sizes:
+        route = 0 if n == 1 else 1
+        lib.ctx_set_policy(ctx, "PAIRING_DEVICE", route)
+        ps = [proofs[j % 8] for j in range(n)]
+        xs = b"".join(inputs[j % 8] for j in range(n))
+
+        def ve():
+            return lib.verify_each(ctx, C.curve_id, vk, ps, xs)
+
+        def vp():
+            return lib.verify_each_pvk(ctx, pvk, ps, xs)
+
+        def pr():
+            lib.pvk_free(lib.vk_process(ctx, C.curve_id, vk))
+
+        calls = [("ve", ve), ("ve_pvk", vp), ("process", pr)]
+        assert ve() == vp() == [True] * n              # warm-up of both entries, and they agree
+        pr()
+        t = {k: [] for k, _ in calls}
+        for _ in range(reps):
+            for k, f in calls:
+                t0 = time.perf_counter()
+                f()
+                t[k].append((time.perf_counter() - t0) * 1e3)
+        rows.append((n, route, t))
+    lib.pvk_free(pvk)
+    lib.ctx_destroy(ctx)
+    print("curve %s: ms per call, median of %d interleaved runs (host clock); the handle holds %d bytes of HBM (num_instance %d)"
+          % (C.name, reps, info["resident_bytes"], info["num_instance"]))
+    print("%7s %6s | %11s %19s | %15s %8s %9s | %11s | %s"
+          % ("proofs", "route", "verify_each", "(min .. max)", "verify_each_pvk", "saved", "speed-up", "vk_process", "verdict"))
+    for n, route, t in rows:
+        ve, vp = statistics.median(t["ve"]), statistics.median(t["ve_pvk"])
+        spread = max(t["ve"]) - min(t["ve"])
+        verdict = "ok" if vp <= ve + spread else "SLOWER than the yardstick by more than its spread"
+        print("%7d %6s | %11.3f %19s | %15.3f %8.3f %9.2f | %11.3f | %s"
+              % (n, "device" if route else "host", ve, "(%.3f .. %.3f)" % (min(t["ve"]), max(t["ve"])), vp, ve - vp, ve / vp,
+                 statistics.median(t["process"]), verdict))
+    print("", flush=True)
+
+
 def one_verify_each(count):
     """one ark355_verify_each of `count` BLS12-381 proofs on the device route, in this process (for a kernel trace)"""
     import snark_amd
@@ -254,6 +314,7 @@ def main():
     ap.add_argument("--each", action="store_true", help="the per-group entries: pairing_groups(n, 1) and verify_each(n)")
     ap.add_argument("--host-max", type=int, default=1024, help="--each: largest n the host route is run at")
     ap.add_argument("--one-verify-each", type=int, default=0, metavar="COUNT")
+    ap.add_argument("--pvk", action="store_true", help="verify_each against verify_each_pvk and vk_process")
     a = ap.parse_args()
     if a.one_verify:
         return one_verify(a.one_verify)
@@ -261,9 +322,13 @@ def main():
         return one_verify_each(a.one_verify_each)
     if a.each and a.sizes == ",".join(str(s) for s in SIZES):
         a.sizes = ",".join(str(s) for s in EACH_SIZES)
+    if a.pvk and a.sizes == ",".join(str(s) for s in SIZES):
+        a.sizes = ",".join(str(s) for s in PVK_SIZES)
     sizes = [int(s) for s in a.sizes.split(",")]
     if a.child:
-        if a.each:
+        if a.pvk:
+            child_pvk(a.child, a.reps, sizes)
+        elif a.each:
             child_each(a.child, a.reps, sizes, a.host_max)
         else:
             child(a.child, a.reps, sizes)
@@ -275,6 +340,8 @@ def main():
                "--reps", str(a.reps), "--sizes", a.sizes]
         if a.each:
             cmd += ["--each", "--host-max", str(a.host_max)]
+        if a.pvk:
+            cmd += ["--pvk"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         print(r.stdout, end="", flush=True)
         text.append(r.stdout)
@@ -285,8 +352,11 @@ def main():
     if a.out and rc == 0:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
-            f.write("pairing_bench%s: host route (PAIRING_DEVICE=0) against device route (PAIRING_DEVICE=1), one process per curve\n\n"
-                    % (" --each" if a.each else ""))
+            if a.pvk:
+                f.write("pairing_bench --pvk: ark355_verify_each against ark355_verify_each_pvk on one handle, one process per curve\n\n")
+            else:
+                f.write("pairing_bench%s: host route (PAIRING_DEVICE=0) against device route (PAIRING_DEVICE=1), one process per curve\n\n"
+                        % (" --each" if a.each else ""))
             f.write("".join(text))
     return rc
 
