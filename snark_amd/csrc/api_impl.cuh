@@ -258,7 +258,7 @@ struct Api {
       const uint32_t parts = msm_parts_count(g.sort.plan);
       g.c.ensure((size_t)parts * sizeof(XYZZ<F>));
       XYZZ<F>* d_res = g.c.as<XYZZ<F>>();
-      msm_accumulate_phase<F>(ctx, g.sort, g.bk, d_rows, packed, st, n ? e0 : nullptr, n ? e1 : nullptr);
+      msm_accumulate_phase<F>(ctx, g.sort, g.bk, d_rows, packed, st, 0, n ? e0 : nullptr, n ? e1 : nullptr);
       msm_reduce_phase<F>(ctx, g.sort, g.bk, d_res, st);
       // The last 2c group operations per bucket set (Horner over the bit sums) and the one inversion of the normalisation run
       // in the library's host-compiled field code: ~1 us per group operation against ~12 us for a device lane, tens of

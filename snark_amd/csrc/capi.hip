@@ -317,9 +317,14 @@ void ark355_r1cs_free(ark355_r1cs* r) {
 }
 uint64_t ark355_r1cs_domain_size(const ark355_r1cs* r) { return r ? r->d->N : 0; }
 
+// locked: the caller already holds ctx->mu (the parent lane of ark355_prove_batch)
 static int32_t prove_common(ark355_ctx* ctx, const ark355_pk* pk, const ark355_r1cs* r1, const void* z, uint64_t z_len,
-                            bool on_dev, const uint8_t* r, const uint8_t* s, ark355_proof_raw* out) {
-  if (!ctx || !pk || !r1 || !z || !r || !s || !out) return ARK355_EINVAL;
+                            bool on_dev, const uint8_t* r, const uint8_t* s, ark355_proof_raw* out, bool locked = false) {
+  if (!ctx || !pk || !r1 || !r || !s || !out) return ARK355_EINVAL;
+  if (!z) {
+    ctx->last_error = "null assignment pointer";
+    return ARK355_EINVAL;
+  }
   if (z_len < r1->d->m) {
     ctx->last_error = "assignment shorter than num_instance + num_witness";
     return ARK355_E_ASSIGNMENT_MISSING;
@@ -331,7 +336,7 @@ static int32_t prove_common(ark355_ctx* ctx, const ark355_pk* pk, const ark355_r
   return guarded(ctx, [&] {
     CtxExtra& ex = extra(ctx);
     CURVE_DISPATCH(pk->d->curve, A::prove(ctx, ex.prover, *pk->d, *r1->d, z, on_dev, r, s, out));
-  });
+  }, locked);
 }
 
 int32_t ark355_prove(ark355_ctx* ctx, const ark355_pk* pk, const ark355_r1cs* r1, const uint8_t* z, uint64_t z_len,
@@ -370,26 +375,8 @@ int32_t ark355_prove_batch(ark355_ctx* ctx, const ark355_pk* pk, const ark355_r1
       for (;;) {
         const uint64_t i = next.fetch_add(1);
         if (i >= count) return;
-        int32_t e;
-        if (lane == ctx) {
-          // the parent's mutex is already held by this call: run its share on the calling thread, unguarded path
-          e = ARK355_OK;
-          try {
-            if (!z[i]) throw HipError{ARK355_EINVAL, "null assignment pointer"};
-            if (z_len < r1->d->m) throw HipError{ARK355_E_ASSIGNMENT_MISSING, "assignment shorter than num_instance + num_witness"};
-            if (pk->d->shard_count != 1) throw HipError{ARK355_EINVAL, "this key handle is an MSM shard"};
-            (void)hipSetDevice(ctx->device);
-            CURVE_DISPATCH(pk->d->curve, A::prove(ctx, ex.prover, *pk->d, *r1->d, z[i], false, r + 32 * i, s + 32 * i, out + i));
-          } catch (const HipError& he) {
-            e = he.code;
-            ctx->last_error = he.what;
-          } catch (const std::exception& se) {
-            e = ARK355_EINVAL;
-            ctx->last_error = se.what();
-          }
-        } else {
-          e = z[i] ? prove_common(lane, pk, r1, z[i], z_len, false, r + 32 * i, s + 32 * i, out + i) : ARK355_EINVAL;
-        }
+        // (the parent's mutex is already held by this call: its share runs on the calling thread)
+        const int32_t e = prove_common(lane, pk, r1, z[i], z_len, false, r + 32 * i, s + 32 * i, out + i, /*locked=*/lane == ctx);
         if (e != ARK355_OK) {
           std::lock_guard<std::mutex> lk(err_mu);
           if (first_err == ARK355_OK) {

@@ -32,6 +32,7 @@
 #include "witness_dist_impl.cuh"
 #include "diag_impl.cuh"
 #include "sched_tuner.h"
+#include "prove_plan.h"
 #include <thread>
 
 namespace ark355 {
@@ -193,14 +194,12 @@ struct ProverScratch {
   DwmScratch dwm;   // one rank of the distributed witness map (sharded proofs)
   DevBuf zx;        // extended scalar vector
   DevBuf results;   // XYZZ results: A, B1, L, H (G1) then B2 (G2)
-  DevBuf proof;     // raw affine proof A | B | C
-  DevBuf rs;        // canonical r, s (2 x Fr)
   // Page-locked landing zone of the proof's last copy (five XYZZ sums, or the three affine points).  A D2H copy into
   // pageable memory is not asynchronous: hipMemcpyAsync then blocks -- spinning -- until everything queued before it on
   // the stream has run, i.e. for the whole proof (profiles/r02_host_wait.txt: one host core per proof in flight).
   void* h_pinned = nullptr;
   size_t h_pinned_bytes = 0;
-  // page-locked staging area of the proof's small H2D copies (tail scalars, r, s): from pageable memory (the stack) such a
+  // page-locked staging area of the proof's small H2D copies (tail scalars, a rank's shard plan): from pageable memory (the stack) such a
   // copy is not asynchronous either -- the runtime stages it and waits for the stream
   void* h_stage = nullptr;
   static constexpr size_t STAGE_BYTES = 1024;
@@ -330,6 +329,25 @@ static void combine_partials_host(const uint8_t* partials, uint64_t count, const
   finalize_host<Curve>(g1, g2, rc, sc, out);
 }
 
+// Window stride of the five tables: 1 (a table per window) whenever that fits next to the scratch of the proving
+// contexts that will work on this key (four of them: two sort areas of 16 B per (term, window), nine N-element NTT
+// buffers / tables each), otherwise the smallest stride that does; ARK355_ENOMEM when not even the bare vectors fit.
+// The shards of one key must reach the SAME stride on every rank (the bucket-level exchange adds bucket arrays of
+// different ranks): they plan from the device size alone and with the LARGEST shard's lengths (z_plan, h_plan) -- the actual
+// shard lengths differ by one between ranks.  Sets pk.wstride; returns whether the rows of the tables are bit-packed.
+template <class Curve>
+static bool pk_plan_tables(const TunePolicy& pol, PkDev& pk, uint64_t z_plan, uint64_t h_plan) {
+  const uint64_t zn = pk.shard_count > 1 ? z_plan : pk.z_cnt, hn = pk.shard_count > 1 ? h_plan : pk.h_cnt;
+  const TableNeed need[5] = {{zn, z_plan, false}, {zn, z_plan, false}, {zn, z_plan, true}, {hn, h_plan, false, pol.msm_c_h}, {zn, z_plan, false}};
+  const size_t scratch = 4 * ((size_t)16 * 17 * (zn + hn) + (size_t)9 * 32 * pk.N);
+  std::string why;
+  bool packed_rows = false;
+  pk.wstride = table_stride_plan<typename Curve::Fq, typename Curve::Fq2, typename Curve::Fr>(
+      pol, need, 5, table_budget_bytes(pol, scratch, pk.shard_count == 1), &why, &packed_rows);
+  if (pk.wstride == 0) throw HipError{ARK355_ENOMEM, "proving key: " + why};
+  return packed_rows;
+}
+
 template <class Curve>
 static PkDev* pk_upload(const TunePolicy& pol, const ark355_pk_desc* d, hipStream_t stream, uint32_t shard_index = 0,
                         uint32_t shard_count = 1) {
@@ -378,22 +396,7 @@ static PkDev* pk_upload(const TunePolicy& pol, const ark355_pk_desc* d, hipStrea
     // every shard of a key uses the window size of the largest shard (see precomp_build)
     const uint64_t z_plan = shard_count > 1 ? (m + 4 + shard_count - 1) / shard_count : 0;
     const uint64_t h_plan = shard_count > 1 ? (pk->h_dist ? pk->h_cnt : (hn + shard_count - 1) / shard_count) : 0;
-    bool packed_rows = false;
-    {
-      // Window stride of the five tables: 1 (a table per window) whenever that fits next to the scratch of the proving
-      // contexts that will work on this key (four of them: two sort areas of 16 B per (term, window), nine N-element NTT
-      // buffers / tables each), otherwise the smallest stride that does; ARK355_ENOMEM when not even the bare vectors fit.
-      // The shards of one key must reach the SAME stride on every rank (the bucket-level exchange adds bucket arrays of
-      // different ranks): they plan from the device size alone and with the LARGEST shard's lengths -- the actual shard
-      // lengths differ by one between ranks.
-      const uint64_t zn = shard_count > 1 ? z_plan : pk->z_cnt, hn_ = shard_count > 1 ? h_plan : pk->h_cnt;
-      const TableNeed need[5] = {{zn, z_plan, false}, {zn, z_plan, false}, {zn, z_plan, true},
-                                 {hn_, h_plan, false, pol.msm_c_h}, {zn, z_plan, false}};
-      const size_t scratch = 4 * ((size_t)16 * 17 * (zn + hn_) + (size_t)9 * 32 * pk->N);
-      std::string why;
-      pk->wstride = table_stride_plan<Fq, Fq2, Fr>(pol, need, 5, table_budget_bytes(pol, scratch, shard_count == 1), &why, &packed_rows);
-      if (pk->wstride == 0) throw HipError{ARK355_ENOMEM, "proving key: " + why};
-    }
+    const bool packed_rows = pk_plan_tables<Curve>(pol, *pk, z_plan, h_plan);
     const uint32_t ws = pk->wstride;
     const int pkd = packed_rows ? 1 : 0;           // one row format for the five tables of a key (table_pack_default)
     pk->packed_rows = packed_rows;
@@ -501,124 +504,186 @@ static bool pk_bind(ark355_ctx* ctx, PkDev& pk, const R1csDev& r1) {
   return true;
 }
 
-// z_src: host or device pointer to m Fr (Montgomery); z_on_device selects the copy kind.
+// One proof.  prove_run (below) runs the stages in queue order; what they share lives here.  Every schedule decision is in `plan`
+// (prove_plan.h: computed once, unit-tested on the host) and every stream is reached through on(role).
 //
-// Stream plan (MI355X: 256 CUs; the accumulation kernels fill the chip, everything else is small or
+// Stream plan of the five-stream pipeline (MI355X: 256 CUs; the accumulation kernels fill the chip, everything else is small or
 // latency-bound and is tucked underneath them):
-//   sM (ctx stream)  H2D of z and the tail scalars                                  -> evZ
-//   sW               witness map: SpMV, 6 transforms (4 for a key in the evaluation basis), pointwise -> evH
-//   sS               digits/scan/scatter of zx, then (after evH) of h               -> evSort[0], evSort[2]
-//   sA               bucket accumulation: A, B1, B2, L' (share sort 0), H            -> evAcc[0..4]
-//   sR               merge + bucket reduction + combine per MSM as evAcc[i] fires; D2H of the five XYZZ results
+//   MAIN (ctx stream)  H2D of z and the tail scalars; bucket accumulation: B2, A, B1, L' (share the sort of zx), H
+//   W                  witness map: SpMV, 6 transforms (4 for a key in the evaluation basis), pointwise
+//   S                  digits/scan/scatter of zx, then (after the witness map) of h
+//   R                  merge + bucket reduction + combine per MSM as its accumulation ends; D2H of the partial sums
+// A one-stream proof has every role on its lane, except what the plan moves aside for a proof alone on the device.
 template <class Curve>
-static void prove_run(ark355_ctx* ctx, ProverScratch& sc, PkDev& pk, const R1csDev& r1, const void* z_src,
-                      bool z_on_device, const uint8_t r_canon[32], const uint8_t s_canon[32], ark355_proof_raw* out,
-                      uint8_t* partials_out = nullptr, CommDev* cm = nullptr, int shard_mode = 0) {
+struct ProveRun {
   using Fr = typename Curve::Fr;
   using Fq = typename Curve::Fq;
   using Fq2 = typename Curve::Fq2;
-  ARK_REQUIRE(pk.curve == Curve::ID && r1.curve == Curve::ID, ARK355_EINVAL, "curve mismatch");
-  ARK_REQUIRE(pk.ell == r1.ell && pk.w == r1.w && pk.N == r1.N, ARK355_EINVAL,
-              "proving key and R1CS dimensions differ");
+  using Clock = std::chrono::steady_clock;
+  enum { E_START, E_Z, E_ZS, E_H, E_SORT0, E_SORT2, E_G2T, E_FILL, E_HT, E_ACC_DONE0, E_END = E_ACC_DONE0 + 5, E_COUNT };
+  static_assert(E_COUNT + 10 <= ProverScratch::N_EVENTS, "event pool too small");
+  // one rank's five sums as they travel (ark355_prove_shard, the all-gather): A, B1, L', H in G1, then B2 in G2
+  static constexpr size_t SUMS_BYTES = 4 * sizeof(XYZZ<Fq>) + sizeof(XYZZ<Fq2>);
+
+  ark355_ctx* const ctx;
+  ProverScratch& sc;
+  PkDev& pk;
+  const R1csDev& r1;
+  const void* const z_src;
+  const bool z_on_device;
+  const uint8_t* const r_canon;
+  const uint8_t* const s_canon;
+  ark355_proof_raw* const out;
+  uint8_t* const partials_out;
+  CommDev* const cm;
+  const int shard_mode;
+  const bool h_eval;
+  // (an aggregate: prove_run gives the members above, everything below starts from them)
   const TunePolicy& pol = ctx->policy;          // (the context's mutex is held: the policy cannot change under this proof)
-  // first proof of a whole key: coefficient path or evaluation basis, for the life of the key (pk_bind)
-  const bool h_eval = pk_bind<Curve>(ctx, pk, r1);
-  const auto t_enter = std::chrono::steady_clock::now();
-  auto since = [&](std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-  };
-  const bool trace_host = pol.trace_host != 0;
-  double t_launched = 0, t_synced = 0, t_tail = 0;
-  hipStream_t sM = ctx->stream;
-  // Schedule.  A proof ALONE on the device runs best as the five-stream pipeline below (the latency-bound tails of one MSM
-  // hide under the next MSM's accumulation: 26.9 against 31.7 ms for a single 2^20 proof).  With OTHER proofs in flight the
-  // same proof runs best on ONE stream: the gaps are filled by the other proofs' kernels anyway, and the pipeline's
-  // cross-stream waits cost more than they buy -- HIP maps its streams onto a few in-order hardware queues, so a kernel that
-  // waits for an event of its own proof blocks the ready kernels of other proofs queued behind it (the 2^18 x 8 timeline
-  // shows a kernel running 99.9 % of the time but an accumulation only 77 %).  Measured, same box
-  // (profiles/r03_one_stream_ab.txt): BLS12-381 2^20 23.81 -> 23.42 ms per proof at four in flight on 0.14 instead of 0.93
-  // host cores, BN254 2^20 16.1 -> 15.0 ms, 2^18 8.28 -> 7.38 ms at six in flight.  Those are the STATIC defaults; with
-  // policy SCHED = AUTO (the default) they are only the starting point of a measured choice per class (SchedTuner above),
-  // and SCHED = 0..3 forces one schedule for every proof of the context.
-  struct InFlight {
-    std::atomic<int>& c;
-    int mine;
-    explicit InFlight(std::atomic<int>& counter) : c(counter), mine(++counter) {}
-    ~InFlight() { --c; }
-  };
-  static std::atomic<int> g_inflight[64];
-  InFlight inflight(g_inflight[(unsigned)ctx->device & 63u]);
+  const uint64_t m = pk.m, shape = prove_shape(Curve::ID, pk.N, pk.m);
+  const Clock::time_point t_enter = Clock::now();
+  InFlight inflight{ctx->device};
   const bool concurrent = inflight.mine >= 2;
-  const uint64_t shape = prove_shape(Curve::ID, pk.N, pk.m);
-  // measured regimes of the pipeline's epilogue (profiles/r03_epilogue_ab.txt): BLS12-381 N = 2^21 / 2^22 / 2^23 win without
-  // the stream synchronises, small proofs and BN254 with them
-  // (only a sharded proof still starts from the pipeline: its witness-map exchanges and the copy of the assignment overlap the
-  // accumulations of the rank.  Since round 4 a proof alone runs best on one stream as well -- batched G1 tails, G2 tails on
-  // the side stream: 26.0-26.6 against 27.0-27.4 ms at 2^20 on every box measured -- so one stream is the default everywhere
-  // and the measured choice only leaves it for a 5 % win.)
-  const int static_alone = (pk.N >= (1ull << 20) && sizeof(Fq) >= 48) ? SCHED_PIPELINE : SCHED_PIPELINE_SYNC;
-  const int static_sched = cm ? static_alone : SCHED_ONE_STREAM;
-  int sched = pol.sched;
-  bool exploring = false;
-  const uint64_t tune_key = SchedTuner::key(shape, concurrent);
-  if (cm) {
-    // a sharded proof is a collective: every rank must queue the same operations in the same order on the same kind of
-    // stream, so the choice cannot depend on one rank's measurements
-    if (sched < 0 || sched >= SCHED_COUNT) sched = static_sched;
-  } else if (sched < 0 || sched >= SCHED_COUNT) {
-    const bool warm = sc.warm_shape == shape;
-    sched = warm ? SchedTuner::of(ctx->device).pick(tune_key, concurrent, pol.sched_explore, static_sched, &exploring)
-                 : static_sched;
-  }
-  sc.warm_shape = shape;
-  ctx->last_sched = sched;
-  // an exploring proof that leaves by exception must hand its sample slot back, or the class never latches (ADVICE round 4)
+
+  // an exploring proof that leaves by exception must hand its sample slot back, or the class never latches
   struct ExploreGuard {
-    int device;
-    uint64_t key;
-    int sched;
-    bool armed;
+    int device = 0;
+    uint64_t key = 0;
+    int sched = 0;
+    bool armed = false;
     ~ExploreGuard() {
       if (armed) SchedTuner::of(device).unstart(key, sched);
     }
-  } explore_guard{ctx->device, tune_key, sched, exploring};
-  const bool one_stream = sched == SCHED_ONE_STREAM || sched == SCHED_ONE_STREAM_SPIN;
-  const bool spin = pol.wait_spin != 0 || sched == SCHED_ONE_STREAM_SPIN;
-  // The short kernels that feed the accumulations (witness map, sorts) and the latency-bound reductions outrank the
-  // long accumulation launches: when workgroup slots free up, a waiting NTT pass or sort of ANOTHER proof in flight
-  // is dispatched before the next round of accumulation workgroups, which keeps an accumulation queued at all times.
-  // Policy STREAM_PRIO=0 turns it off (A/B).
-  if (!one_stream) sc.ensure_streams(pol.stream_prio != 0);
-  if (one_stream) {
-    // one-stream proofs run on a "lane": a stream of the device's pool, probed at start-up to sit on its own hardware queue
-    if (!sc.lane_asked) {
-      sc.lane = LanePool::of(ctx->device).acquire();
-      sc.lane_asked = true;
-    }
-    if (sc.lane) sM = sc.lane;
+  } explore;
+  int sched = 0, static_sched = 0;
+  ProvePlan plan;
+  hipStream_t stream[ROLE_COUNT] = {};
+  hipEvent_t* const ev = (sc.ensure_events(), sc.events);      // events of one proof, created once per context
+  hipEvent_t* const acc0 = ev + E_COUNT;                       // start / end of each accumulation kernel (timings)
+  hipEvent_t* const acc1 = ev + E_COUNT + 5;
+
+  Fr rc, scn;                      // canonical r, s
+  void* d_h = nullptr;             // what the H MSM multiplies: the witness map's result
+  // what the five MSMs leave for the host (c partial sums per bucket set and MSM: tails28_impl.cuh), A, B1, L', H, then B2
+  ProofParts<Curve> parts;
+  XYZZ<Fq>* g1res[4] = {};
+  XYZZ<Fq2>* g2res = nullptr;
+  uint8_t* land = nullptr;         // page-locked landing zone: parts | a sharded proof's sums, own then all | CHECK_SATISFIED verdict
+  uint8_t* land_sat = nullptr;
+  uint64_t pts = 0;
+  bool h_tails_aside = false;      // the tails of H were queued on the sort stream: E_HT is that stream's last event
+  double t_launched = 0, t_synced = 0, t_tail = 0;
+
+  struct Msm {
+    int sort_ev;
+    const MsmSort* sort;
+    MsmBuckets* bk;
+    bool g2;
+    const PrecompTable* tab;
+    int res;
+  };
+  // G2 first: its bucket reduction is the longest latency-bound tail (~4-6 ms on a few workgroups) and hides under the four G1
+  // accumulations that follow
+  const Msm msms[5] = {
+      {E_SORT0, &sc.sortZ, &sc.bkB2, true, &pk.b2_ext, 0}, {E_SORT0, &sc.sortZ, &sc.bkA, false, &pk.a_ext, 0},
+      {E_SORT0, &sc.sortZ, &sc.bkB1, false, &pk.b1_ext, 1}, {E_SORT0, &sc.sortZ, &sc.bkL, false, &pk.l_ext, 2},
+      {E_SORT2, &sc.sortH, &sc.bkH, false, &pk.h_query, 3},
+  };
+
+  hipStream_t on(StreamRole r) const { return stream[r]; }
+  double since_enter() const { return std::chrono::duration<double, std::milli>(Clock::now() - t_enter).count(); }
+  // the one place that names both groups: fn(tag) with tag.type = Fq2 or Fq
+  template <class F>
+  struct Group {
+    using type = F;
+  };
+  template <class Fn>
+  static void by_group(bool g2, Fn&& fn) {
+    if (g2) fn(Group<Fq2>{});
+    else fn(Group<Fq>{});
   }
-  // A one-stream proof that is ALONE on the device (round 5, policy SIDE_WM): nothing but the H MSM needs h, so the witness map
-  // and the sort of h go to the context's witness-map stream and run BESIDE the sort of z and the accumulations of B2, A, B1 and
-  // L' instead of in front of them (2.4 ms of a 25 ms proof); the proof's stream meets them again at the H accumulation.  With
-  // other proofs in flight everything stays on the one stream.
-  const bool side_wm = one_stream && !concurrent && !cm && !partials_out && pol.side_wm != 0;
-  if (side_wm) sc.ensure_streams(pol.stream_prio != 0);
-  hipStream_t sW = one_stream ? (side_wm ? sc.sW : sM) : sc.sW, sS = one_stream ? sM : sc.sS, sA = sM, sR = one_stream ? sM : sc.sR;
-  hipStream_t sSH = side_wm ? sc.sW : sS;            // the stream the sort of h runs on
-  const uint64_t m = pk.m, ell = pk.ell;
-  // policy CHECK_SATISFIED: whole proofs of a whole key only (a rank of a sharded proof sees 1/G of the rows, and the ranks of a
-  // collective must not disagree on its outcome)
-  const bool check_sat = pol.check_satisfied != 0 && !cm && !partials_out && pk.shard_count <= 1;
-  if (cm && cm->world > 1) {
-    // Every rank must have planned the same window size and table stride for its shard: the bucket-level exchange adds
-    // bucket arrays of different ranks element by element.  The planners are deterministic functions of the key's
-    // dimensions and the device size, but a policy override on one rank (MSM_C, TABLE_STRIDE, HBM_BUDGET_MB) would break
-    // that silently -- so the ranks compare notes over the communicator, on EVERY sharded proof: a per-process "already
-    // checked" flag could differ between ranks (one rank reloaded its shard, or failed before it set the flag), and then
-    // only some ranks would enter this all-gather while the others went on to the ring steps -- mismatched collectives on
-    // one communicator.  16 bytes per rank and one stream synchronise: ~50 us against a proof of tens of milliseconds.
-    // (the layout of the h_query shard rides along: a rank that loaded its shard with policy SHARD_DIST_WM = 0 would skip the
-    // witness map's all-to-alls while the others wait in them)
+  template <class F>
+  XYZZ<F>* result_of(const Msm& jb) const {
+    if constexpr (std::is_same<F, Fq2>::value) return g2res;
+    else return g1res[jb.res];
+  }
+
+  // Schedule.  A proof ALONE on the device runs best as the five-stream pipeline (the latency-bound tails of one MSM hide under
+  // the next MSM's accumulation: 26.9 against 31.7 ms for a single 2^20 proof).  With OTHER proofs in flight the same proof runs
+  // best on ONE stream: the gaps are filled by the other proofs' kernels anyway, and the pipeline's cross-stream waits cost more
+  // than they buy -- HIP maps its streams onto a few in-order hardware queues, so a kernel that waits for an event of its own
+  // proof blocks the ready kernels of other proofs queued behind it (the 2^18 x 8 timeline shows a kernel running 99.9 % of the
+  // time but an accumulation only 77 %).  Measured, same box (profiles/r03_one_stream_ab.txt): BLS12-381 2^20 23.81 -> 23.42 ms
+  // per proof at four in flight on 0.14 instead of 0.93 host cores, BN254 2^20 16.1 -> 15.0 ms, 2^18 8.28 -> 7.38 ms at six in
+  // flight.  Those are the STATIC defaults; with policy SCHED = AUTO (the default) they are only the starting point of a measured
+  // choice per class (SchedTuner), and SCHED = 0..3 forces one schedule for every proof of the context.
+  void pick_schedule() {
+    // measured regimes of the pipeline's epilogue (profiles/r03_epilogue_ab.txt): BLS12-381 N = 2^21 / 2^22 / 2^23 win without
+    // the stream synchronises, small proofs and BN254 with them
+    // (only a sharded proof still starts from the pipeline: its witness-map exchanges and the copy of the assignment overlap the
+    // accumulations of the rank.  Since round 4 a proof alone runs best on one stream as well -- batched G1 tails, G2 tails on
+    // the side stream: 26.0-26.6 against 27.0-27.4 ms at 2^20 on every box measured -- so one stream is the default everywhere
+    // and the measured choice only leaves it for a 5 % win.)
+    const int static_alone = (pk.N >= (1ull << 20) && sizeof(Fq) >= 48) ? SCHED_PIPELINE : SCHED_PIPELINE_SYNC;
+    static_sched = cm ? static_alone : SCHED_ONE_STREAM;
+    sched = pol.sched;
+    bool exploring = false;
+    explore.key = SchedTuner::key(shape, concurrent);
+    if (cm) {
+      // a sharded proof is a collective: every rank must queue the same operations in the same order on the same kind of
+      // stream, so the choice cannot depend on one rank's measurements
+      if (sched < 0 || sched >= SCHED_COUNT) sched = static_sched;
+    } else if (sched < 0 || sched >= SCHED_COUNT) {
+      const bool warm = sc.warm_shape == shape;
+      sched = warm ? SchedTuner::of(ctx->device).pick(explore.key, concurrent, pol.sched_explore, static_sched, &exploring)
+                   : static_sched;
+    }
+    sc.warm_shape = shape;
+    ctx->last_sched = sched;
+    explore.device = ctx->device;
+    explore.sched = sched;
+    explore.armed = exploring;
+    ProveCase k;
+    k.sched = sched;
+    k.concurrent = concurrent;
+    k.comm = cm != nullptr;
+    k.ring = shard_mode == ARK355_SHARD_BUCKET_RING;
+    k.partials = partials_out != nullptr;
+    k.h_dist = pk.h_dist;
+    k.shard_count = pk.shard_count;
+    plan = prove_plan(pol, k);
+    hipStream_t main = ctx->stream;
+    if (plan.one_stream) {
+      // one-stream proofs run on a "lane": a stream of the device's pool, probed at start-up to sit on its own hardware queue
+      if (!sc.lane_asked) {
+        sc.lane = LanePool::of(ctx->device).acquire();
+        sc.lane_asked = true;
+      }
+      if (sc.lane) main = sc.lane;
+    }
+    // The short kernels that feed the accumulations (witness map, sorts) and the latency-bound reductions outrank the
+    // long accumulation launches: when workgroup slots free up, a waiting NTT pass or sort of ANOTHER proof in flight
+    // is dispatched before the next round of accumulation workgroups, which keeps an accumulation queued at all times.
+    // Policy STREAM_PRIO=0 turns it off (A/B).
+    if (plan.needs_feeders) sc.ensure_streams(pol.stream_prio != 0);
+    stream[ROLE_MAIN] = main;
+    stream[ROLE_W] = sc.sW;
+    stream[ROLE_S] = sc.sS;
+    stream[ROLE_R] = sc.sR;
+  }
+
+  // Every rank must have planned the same window size and table stride for its shard: the bucket-level exchange adds
+  // bucket arrays of different ranks element by element.  The planners are deterministic functions of the key's
+  // dimensions and the device size, but a policy override on one rank (MSM_C, TABLE_STRIDE, HBM_BUDGET_MB) would break
+  // that silently -- so the ranks compare notes over the communicator, on EVERY sharded proof: a per-process "already
+  // checked" flag could differ between ranks (one rank reloaded its shard, or failed before it set the flag), and then
+  // only some ranks would enter this all-gather while the others went on to the ring steps -- mismatched collectives on
+  // one communicator.  16 bytes per rank and one stream synchronise: ~50 us against a proof of tens of milliseconds.
+  // (the layout of the h_query shard rides along: a rank that loaded its shard with policy SHARD_DIST_WM = 0 would skip the
+  // witness map's all-to-alls while the others wait in them)
+  void check_shard_plans() {
+    if (!cm || cm->world <= 1) return;
+    hipStream_t sM = on(ROLE_MAIN);
     const uint32_t mine[4] = {pk.a_ext.plan.c, pk.a_ext.plan.wstride, pk.h_query.plan.c,
                               pk.h_query.plan.wstride | (pk.h_dist ? 0x10000u : 0u)};
     cm->gather.ensure(sizeof(mine) * (size_t)(cm->world + 1));
@@ -635,32 +700,21 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, PkDev& pk, const R1csD
         ARK_REQUIRE(all[4 * (size_t)g + k] == mine[k], ARK355_EINVAL,
                     "key shards of different ranks were planned with different window sizes / table strides / witness-map layouts");
   }
-  enum { E_START, E_Z, E_ZS, E_H, E_SORT0, E_SORT1, E_SORT2, E_G2T, E_FILL, E_HT, E_ACC_DONE0, E_END = E_ACC_DONE0 + 5, E_COUNT };
-  static_assert(E_COUNT + 10 <= ProverScratch::N_EVENTS, "event pool too small");
-  sc.ensure_events();
-  hipEvent_t* ev = sc.events;
-  hipEvent_t* acc0 = sc.events + E_COUNT;
-  hipEvent_t* acc1 = sc.events + E_COUNT + 5;
-  bool h_tails_aside = false;       // the tails of the H MSM were queued on the sort stream (E_HT is its last event then)
-  {
-    // r, s -> Montgomery on the host (the library's own field code); tail = [-rs, 1, r, s]
-    Fr rc, scn;
+
+  // zx = [z, -rs, 1, r, s] on the device (r, s -> Montgomery on the host, the library's own field code)
+  void queue_inputs() {
+    hipStream_t sM = on(ROLE_MAIN), sW = on(plan.wm);
     memcpy(rc.l, r_canon, sizeof(Fr));
     memcpy(scn.l, s_canon, sizeof(Fr));
-    Fr rm = Fr::to_mont(rc), sm = Fr::to_mont(scn);
-    Fr tail[4] = {Fr::neg(Fr::mul(rm, sm)), Fr::one(), rm, sm};
-    Fr rs_c[2] = {rc, scn};
+    const Fr rm = Fr::to_mont(rc), sm = Fr::to_mont(scn);
+    const Fr tail[4] = {Fr::neg(Fr::mul(rm, sm)), Fr::one(), rm, sm};
     sc.zx.ensure((m + 4) * sizeof(Fr));
-    sc.rs.ensure(2 * sizeof(Fr));
-    sc.proof.ensure(2 * sizeof(Affine<Fq>) + sizeof(Affine<Fq2>));
-
     ARK_CHECK_HIP(hipEventRecord(ev[E_START], sM));
     const auto zkind = z_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     // (the previous proof of this context has drained: its staging area is free)
-    static_assert(sizeof(tail) + sizeof(rs_c) <= ProverScratch::STAGE_BYTES, "staging area too small");
-    uint8_t* stg = static_cast<uint8_t*>(sc.stage());
+    static_assert(sizeof(tail) <= ProverScratch::STAGE_BYTES, "staging area too small");
+    void* stg = sc.stage();
     memcpy(stg, tail, sizeof(tail));
-    memcpy(stg + sizeof(tail), rs_c, sizeof(rs_c));
     // A key shard sorts only ITS slice of zx: that slice (and the four tail scalars) goes first and releases the sort and the
     // accumulations (E_ZS); the rest of the assignment, which only the witness map needs, follows (E_Z).  From host memory a
     // 2^22-constraint assignment is 134 MB = 2.5 ms of PCIe time in front of a rank's 17 ms (section 5 of DESIGN.md).
@@ -674,7 +728,6 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, PkDev& pk, const R1csD
     if (split) copy_z(s_lo, s_hi, sM);
     else copy_z(0, m, sM);
     ARK_CHECK_HIP(hipMemcpyAsync((uint8_t*)sc.zx.p + m * sizeof(Fr), stg, sizeof(tail), hipMemcpyHostToDevice, sM));
-    ARK_CHECK_HIP(hipMemcpyAsync(sc.rs.p, stg + sizeof(tail), sizeof(rs_c), hipMemcpyHostToDevice, sM));
     ARK_CHECK_HIP(hipEventRecord(ev[E_ZS], sM));
     if (split) {
       // the rest travels on the WITNESS-MAP stream (its only consumer): the context's stream carries the accumulations, which
@@ -686,26 +739,29 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, PkDev& pk, const R1csD
     } else {
       ARK_CHECK_HIP(hipEventRecord(ev[E_Z], sM));
     }
+  }
 
-    // witness map -> h
+  // witness map -> d_h.  Alone on one stream (plan.side_wm, round 5) it runs on the witness-map stream BESIDE the sort of z and
+  // the first four accumulations: nothing but the H MSM needs h (2.4 ms of a 25 ms proof); the proof's stream meets it again at
+  // the H accumulation.
+  void queue_witness_map() {
+    hipStream_t sW = on(plan.wm);
     ARK_CHECK_HIP(hipStreamWaitEvent(sW, ev[E_Z], 0));
-    void* d_h;
-    if (pk.h_dist && ((cm && shard_mode != ARK355_SHARD_BUCKET_RING) || (!cm && pol.dwm_loopback))) {
+    if (plan.dist_wm) {
       // the witness map sharded like the MSMs: this rank's 1/G of every vector, three all-to-all exchanges on the
       // witness-map stream (witness_dist_impl.cuh).  They are ordered against the prover's other collectives by data
-      // dependence (the plan check above has completed; the all-gather of the partial sums waits for the H MSM), so the one
-      // communicator serves them all.  The bucket-ring exchange interleaves its own send / receive steps with the MSMs
-      // and therefore keeps the replicated map.
+      // dependence (the plan check has completed; the all-gather of the partial sums waits for the H MSM), so the one
+      // communicator serves them all.
       d_h = witness_map_dist_run<Curve>(ctx, r1, sc.zx.p, sc.dwm, cm, pk.shard_count, pk.shard_index, sW, /*loopback=*/!cm,
                                         // a whole key in the distributed layout exists only when it was loaded under policy
                                         // RCCL_SELF: the KEY says that the rank is its own peer, whatever the policy reads now
                                         /*self_rccl=*/cm && pk.shard_count == 1);
-      if (trace_host)
+      if (pol.trace_host)
         fprintf(stderr, "[ark355] witness map distributed over %u ranks (rank %u: N / G = %llu elements per vector)%s\n", pk.shard_count,
                 pk.shard_index, (unsigned long long)(pk.N / pk.shard_count), cm ? "" : " -- LOOPBACK exchange, timing only");
     } else {
       // (a key in the evaluation basis: d_h = a' b' on the coset, N scalars for the N bases of E')
-      d_h = witness_map_run<Curve>(ctx, r1, sc.zx.p, sc.ws, sW, check_sat, h_eval);
+      d_h = witness_map_run<Curve>(ctx, r1, sc.zx.p, sc.ws, sW, plan.check_sat, h_eval);
       if (pk.h_dist) {
         // a key shard in the distributed layout under the replicated map: pick this rank's coefficients out of h
         const uint64_t M = pk.h_cnt;
@@ -718,10 +774,12 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, PkDev& pk, const R1csD
       }
     }
     ARK_CHECK_HIP(hipEventRecord(ev[E_H], sW));
+  }
 
-    // sorts.  Everything the two sorts and the five bucket sets need cleared is planned first and cleared by ONE fill
-    // dispatch (FillBatch, msm_impl.cuh) at the head of the sort stream: the scratch belongs to this context and the
-    // previous proof on it has drained.
+  // Everything the two sorts and the five bucket sets need cleared is planned first and cleared by ONE fill dispatch (FillBatch,
+  // msm_impl.cuh) at the head of the sort stream: the scratch belongs to this context and the previous proof on it has drained.
+  void queue_sorts() {
+    hipStream_t sS = on(plan.sort_z), sSH = on(plan.sort_h);
     {
       FillBatch fb(sS);
       msm_sort_plan<Fr>(ctx, sc.sortZ, pk.z_cnt, sS, &pk.a_ext, &fb);
@@ -734,224 +792,198 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, PkDev& pk, const R1csD
       msm_prepare_phase<Fq>(pol, sc.sortH, sc.bkH, sS, &fb);
       fb.flush();
     }
-    // what the five MSMs leave for the host (c partial sums per bucket set and MSM: tails28_impl.cuh), A, B1, L', H, then B2
-    ProofParts<Curve> parts;
-    {
-      const MsmSort* so[5] = {&sc.sortZ, &sc.sortZ, &sc.sortZ, &sc.sortH, &sc.sortZ};
-      for (int i = 0; i < 5; i++) parts.plan[i] = so[i]->plan;
-      parts.layout();
-    }
+    const MsmSort* so[5] = {&sc.sortZ, &sc.sortZ, &sc.sortZ, &sc.sortH, &sc.sortZ};
+    for (int i = 0; i < 5; i++) parts.plan[i] = so[i]->plan;
+    parts.layout();
     sc.results.ensure(parts.bytes);
     uint8_t* const res_base = sc.results.as<uint8_t>();
-    XYZZ<Fq>* const g1res[4] = {reinterpret_cast<XYZZ<Fq>*>(res_base + parts.off[0]), reinterpret_cast<XYZZ<Fq>*>(res_base + parts.off[1]),
-                                reinterpret_cast<XYZZ<Fq>*>(res_base + parts.off[2]), reinterpret_cast<XYZZ<Fq>*>(res_base + parts.off[3])};
-    XYZZ<Fq2>* const g2res = reinterpret_cast<XYZZ<Fq2>*>(res_base + parts.off[4]);
+    for (int i = 0; i < 4; i++) g1res[i] = reinterpret_cast<XYZZ<Fq>*>(res_base + parts.off[i]);
+    g2res = reinterpret_cast<XYZZ<Fq2>*>(res_base + parts.off[4]);
     if (sSH != sS) ARK_CHECK_HIP(hipEventRecord(ev[E_FILL], sS));      // (the sort of h on another stream must see its counters cleared)
     ARK_CHECK_HIP(hipStreamWaitEvent(sS, ev[E_ZS], 0));
     msm_sort_run<Fr>(ctx, sc.sortZ, (const uint8_t*)sc.zx.p + pk.z_lo * sizeof(Fr), pk.z_cnt, 1, sS, &pk.a_ext);
-    ARK_CHECK_HIP(hipEventRecord(ev[E_SORT0], sS));
-    ARK_CHECK_HIP(hipEventRecord(ev[E_SORT1], sS));     // (L' shares the sort of zx)
+    ARK_CHECK_HIP(hipEventRecord(ev[E_SORT0], sS));      // (A, B1, B2 and L' share the sort of zx)
     if (sSH != sS) ARK_CHECK_HIP(hipStreamWaitEvent(sSH, ev[E_FILL], 0));
     ARK_CHECK_HIP(hipStreamWaitEvent(sSH, ev[E_H], 0));
     msm_sort_run<Fr>(ctx, sc.sortH, (const uint8_t*)d_h + pk.h_lo * sizeof(Fr), pk.h_cnt, 1, sSH, &pk.h_query);
     ARK_CHECK_HIP(hipEventRecord(ev[E_SORT2], sSH));
+  }
 
-    // accumulations (A, B1, B2 share the sort of zx) and, per MSM, its reduction on sR
-    struct Job {
-      int sort_ev;
-      const MsmSort* sort;
-      MsmBuckets* bk;
-      bool g2;
-      const PrecompTable* tab;
-      int res;
-    } jobs[5] = {
-        // G2 first: its bucket reduction is the longest latency-bound tail (~4-6 ms on a few workgroups) and
-        // hides under the four G1 accumulations that follow
-        {E_SORT0, &sc.sortZ, &sc.bkB2, true, &pk.b2_ext, 0},
-        {E_SORT0, &sc.sortZ, &sc.bkA, false, &pk.a_ext, 0},
-        {E_SORT0, &sc.sortZ, &sc.bkB1, false, &pk.b1_ext, 1},
-        {E_SORT0, &sc.sortZ, &sc.bkL, false, &pk.l_ext, 2},
-        {E_SORT2, &sc.sortH, &sc.bkH, false, &pk.h_query, 3},
-    };
-    uint64_t pts = 0;
-    // one wave per workgroup for a proof alone on one stream, 256 lanes otherwise (msm_accumulate_phase; policy ACC_THREADS)
-    struct HintGuard {
-      ark355_ctx* c;
-      ~HintGuard() { c->acc_threads_hint = 0; }
-    } hint_guard{ctx};
-    ctx->acc_threads_hint = (one_stream && !concurrent) ? 64 : 256;
-    // One-stream proofs: the five accumulations first, then the G2 tails and the tails of the four G1 MSMs as ONE launch
-    // per step (msm_reduce_phase_batch) -- 8 tail dispatches instead of 20, and the four latency-bound G1 chains side by
-    // side instead of one after the other.  (The pipeline hides each MSM's tails under the next accumulation instead.)
-    const bool batch_tails = one_stream && !cm && pol.batch_tails != 0;
+  // The five accumulations on the proof's own stream.  One-stream proofs then run their tails as a batch (queue_batched_tails);
+  // the pipeline hides each MSM's tails under the next accumulation instead (queue_tails_of).
+  void queue_msms() {
+    hipStream_t sA = on(plan.acc);
     for (int j = 0; j < 5; j++) {
-      const Job& jb = jobs[j];
+      const Msm& jb = msms[j];
       ARK_CHECK_HIP(hipStreamWaitEvent(sA, ev[jb.sort_ev], 0));
-      const MsmSort* red_sort = jb.sort;          // what the reduction reads offsets / counts from
-      if (jb.g2) {
-        msm_accumulate_phase<Fq2>(ctx, *jb.sort, *jb.bk, jb.tab->table.p, jb.tab->packed, sA, acc0[j], acc1[j]);
-      } else {
-        msm_accumulate_phase<Fq>(ctx, *jb.sort, *jb.bk, jb.tab->table.p, jb.tab->packed, sA, acc0[j], acc1[j]);
-      }
+      by_group(jb.g2, [&](auto g) {
+        using F = typename decltype(g)::type;
+        msm_accumulate_phase<F>(ctx, *jb.sort, *jb.bk, jb.tab->table.p, jb.tab->packed, sA, plan.acc_threads, acc0[j], acc1[j]);
+      });
       ARK_CHECK_HIP(hipEventRecord(ev[E_ACC_DONE0 + j], sA));
       pts += (uint64_t)jb.sort->plan.windows * jb.sort->plan.n;
-      if (batch_tails) continue;
-      // Multi-stream schedules: the tails of the LAST MSM (H) go to the sort stream, which has been idle since the sort of h,
-      // instead of queueing behind the tails of L' on the reduction stream.  The tails run starved under the accumulations
-      // (2.4 ms per MSM instead of 1.2), so with short accumulations -- a rank of a sharded proof: 2 ms each -- the reduction
-      // stream falls behind and the tails of H, the end of the proof's critical path, started 0.8 ms after its accumulation had
-      // ended (kernel trace of run M).  Not with the bucket ring: its grouped sends must be queued in one order on every rank.
-      const bool ring = cm && shard_mode == ARK355_SHARD_BUCKET_RING;
-      const bool side_tail = j == 4 && !one_stream && !ring && sS != sR && pol.side_h_tails != 0;
-      hipStream_t sT = side_tail ? sS : sR;
-      ARK_CHECK_HIP(hipStreamWaitEvent(sT, ev[E_ACC_DONE0 + j], 0));
-      if (ring) {
-        // bucket-level exchange: the ranks run their MSMs in the same order, so the ring steps pair up
-        if (jb.g2)
-          msm_reduce_phase<Fq2>(ctx, *red_sort, *jb.bk, g2res, sT, [&](void* bk, uint32_t nb, hipStream_t st) {
-            ring_reduce_scatter_buckets<Fq2>(*cm, bk, nb, st, pol.rccl_self != 0);
-          });
-        else
-          msm_reduce_phase<Fq>(ctx, *red_sort, *jb.bk, g1res[jb.res], sT, [&](void* bk, uint32_t nb, hipStream_t st) {
-            ring_reduce_scatter_buckets<Fq>(*cm, bk, nb, st, pol.rccl_self != 0);
-          });
-      } else if (jb.g2) {
-        msm_reduce_phase<Fq2>(ctx, *red_sort, *jb.bk, g2res, sT);
-      } else {
-        msm_reduce_phase<Fq>(ctx, *red_sort, *jb.bk, g1res[jb.res], sT);
-      }
-      if (side_tail) {
-        h_tails_aside = true;
-        ARK_CHECK_HIP(hipEventRecord(ev[E_HT], sT));
-        ARK_CHECK_HIP(hipStreamWaitEvent(sR, ev[E_HT], 0));      // everything still drains into sR
-      }
+      if (!plan.batch_tails) queue_tails_of(j);
     }
-    if (batch_tails) {
-      // A one-stream proof that is ALONE on the device has nobody to fill the gaps of its latency-bound tails: its G2 tails
-      // (the longest chain: merge + reduction + combination on lane pairs, 1.9 ms at 2^20) go to the context's reduction
-      // stream and run underneath the four G1 accumulations; the proof's stream picks the result up before its last copy.
-      // With other proofs in flight everything stays on the one stream (a second stream per proof is exactly what the
-      // one-stream schedule exists to avoid).  Policy SIDE_G2_TAILS=0: always on the proof's stream.
-      const bool side_g2 = !concurrent && pol.side_g2_tails != 0;
-      if (side_g2) {
-        sc.ensure_streams(pol.stream_prio != 0);
-        ARK_CHECK_HIP(hipStreamWaitEvent(sc.sR, ev[E_ACC_DONE0 + 0], 0));
-        msm_reduce_phase<Fq2>(ctx, sc.sortZ, sc.bkB2, g2res, sc.sR);
-        ARK_CHECK_HIP(hipEventRecord(ev[E_G2T], sc.sR));
-      } else {
-        msm_reduce_phase<Fq2>(ctx, sc.sortZ, sc.bkB2, g2res, sR);
-      }
-      const MsmSort* sorts[4] = {&sc.sortZ, &sc.sortZ, &sc.sortZ, &sc.sortH};
-      MsmBuckets* bks[4] = {&sc.bkA, &sc.bkB1, &sc.bkL, &sc.bkH};
-      XYZZ<Fq>* outs[4] = {g1res[0], g1res[1], g1res[2], g1res[3]};
-      // Policy SIDE_G1_TAILS (lone proofs): the tails of A, B1, L' as a batch of three on the second stream, behind the G2 tails and
-      // under the H accumulation; the proof's stream ends with H's own tails alone.
-      const bool side_g1 = side_g2 && pol.side_g1_tails != 0;
-      bool batched;
-      if (side_g1) {
-        ARK_CHECK_HIP(hipStreamWaitEvent(sc.sR, ev[E_ACC_DONE0 + 3], 0));
-        batched = msm_reduce_phase_batch<Fq>(ctx, 3, sorts, bks, outs, sc.sR);
-        if (!batched)
-          for (int i = 0; i < 3; i++) msm_reduce_phase<Fq>(ctx, *sorts[i], *bks[i], outs[i], sc.sR);
-        ARK_CHECK_HIP(hipEventRecord(ev[E_G2T], sc.sR));        // (re-recorded: now behind the G2 tails AND the batch of three)
-        msm_reduce_phase<Fq>(ctx, *sorts[3], *bks[3], outs[3], sR);
-      } else {
-        batched = msm_reduce_phase_batch<Fq>(ctx, 4, sorts, bks, outs, sR);
-        if (!batched)
-          for (int i = 0; i < 4; i++) msm_reduce_phase<Fq>(ctx, *sorts[i], *bks[i], outs[i], sR);
-      }
-      if (trace_host)
-        fprintf(stderr, "[ark355] G1 tails: %s%s\n", batched ? "one launch per step" : "per MSM", side_g1 ? " (A, B1, L' aside, H at the end)" : " for the four MSMs");
-      if (side_g2) ARK_CHECK_HIP(hipStreamWaitEvent(sR, ev[E_G2T], 0));
-    }
+    if (plan.batch_tails) queue_batched_tails();
+  }
 
+  // Multi-stream schedules: the tails of the LAST MSM (H) go to the sort stream, which has been idle since the sort of h,
+  // instead of queueing behind the tails of L' on the reduction stream.  The tails run starved under the accumulations
+  // (2.4 ms per MSM instead of 1.2), so with short accumulations -- a rank of a sharded proof: 2 ms each -- the reduction
+  // stream falls behind and the tails of H, the end of the proof's critical path, started 0.8 ms after its accumulation had
+  // ended (kernel trace of run M).
+  void queue_tails_of(int j) {
+    const Msm& jb = msms[j];
+    hipStream_t sR = on(plan.reduce), sT = j == 4 ? on(plan.h_tails) : sR;
+    ARK_CHECK_HIP(hipStreamWaitEvent(sT, ev[E_ACC_DONE0 + j], 0));
+    by_group(jb.g2, [&](auto g) {
+      using F = typename decltype(g)::type;
+      if (plan.ring) {
+        // bucket-level exchange: the ranks run their MSMs in the same order, so the ring steps pair up
+        msm_reduce_phase<F>(ctx, *jb.sort, *jb.bk, result_of<F>(jb), sT, [&](void* bk, uint32_t nb, hipStream_t st) {
+          ring_reduce_scatter_buckets<F>(*cm, bk, nb, st, pol.rccl_self != 0);
+        });
+      } else {
+        msm_reduce_phase<F>(ctx, *jb.sort, *jb.bk, result_of<F>(jb), sT);
+      }
+    });
+    if (sT != sR) {
+      h_tails_aside = true;
+      ARK_CHECK_HIP(hipEventRecord(ev[E_HT], sT));
+      ARK_CHECK_HIP(hipStreamWaitEvent(sR, ev[E_HT], 0));      // everything still drains into sR
+    }
+  }
+
+  // One-stream proofs: the G2 tails and the tails of the four G1 MSMs as ONE launch per step (msm_reduce_phase_batch) -- 8 tail
+  // dispatches instead of 20, and the four latency-bound G1 chains side by side instead of one after the other.
+  // A one-stream proof that is ALONE on the device has nobody to fill the gaps of its latency-bound tails: its G2 tails (the
+  // longest chain: merge + reduction + combination on lane pairs, 1.9 ms at 2^20) go to the context's reduction stream and run
+  // underneath the four G1 accumulations (plan.side_g2; policy SIDE_G2_TAILS=0: always on the proof's stream); the proof's
+  // stream picks the result up before its last copy.
+  void queue_batched_tails() {
+    hipStream_t sR = on(plan.reduce), sG2 = on(plan.g2_tails), sG1 = on(plan.g1_side_tails);
+    if (plan.side_g2) ARK_CHECK_HIP(hipStreamWaitEvent(sG2, ev[E_ACC_DONE0 + 0], 0));
+    msm_reduce_phase<Fq2>(ctx, sc.sortZ, sc.bkB2, g2res, sG2);
+    if (plan.side_g2) ARK_CHECK_HIP(hipEventRecord(ev[E_G2T], sG2));
+    const MsmSort* sorts[4] = {&sc.sortZ, &sc.sortZ, &sc.sortZ, &sc.sortH};
+    MsmBuckets* bks[4] = {&sc.bkA, &sc.bkB1, &sc.bkL, &sc.bkH};
+    // Policy SIDE_G1_TAILS (lone proofs): the tails of A, B1, L' as a batch of three on the second stream, behind the G2 tails and
+    // under the H accumulation; the proof's stream ends with H's own tails alone.
+    const int aside = plan.side_g1 ? 3 : 4;
+    if (plan.side_g1) ARK_CHECK_HIP(hipStreamWaitEvent(sG1, ev[E_ACC_DONE0 + 3], 0));
+    const bool batched = msm_reduce_phase_batch<Fq>(ctx, aside, sorts, bks, g1res, sG1);
+    if (!batched)
+      for (int i = 0; i < aside; i++) msm_reduce_phase<Fq>(ctx, *sorts[i], *bks[i], g1res[i], sG1);
+    if (plan.side_g1) {
+      ARK_CHECK_HIP(hipEventRecord(ev[E_G2T], sG1));        // (re-recorded: now behind the G2 tails AND the batch of three)
+      msm_reduce_phase<Fq>(ctx, *sorts[3], *bks[3], g1res[3], sR);
+    }
+    if (pol.trace_host)
+      fprintf(stderr, "[ark355] G1 tails: %s%s\n", batched ? "one launch per step" : "per MSM",
+              plan.side_g1 ? " (A, B1, L' aside, H at the end)" : " for the four MSMs");
+    if (plan.side_g2) ARK_CHECK_HIP(hipStreamWaitEvent(sR, ev[E_G2T], 0));
+  }
+
+  // The proof's last copy: the partial sums of the five MSMs (~15 KB at c = 17) into page-locked memory; the host then runs the
+  // Horner pass of every bucket reduction and the O(1) tail (ProofParts::finish, finalize_host).
+  void finish() {
+    hipStream_t sR = on(plan.reduce);
     if (out) memset(out, 0, sizeof(*out));
-    // The proof's last copy: the partial sums of the five MSMs (~15 KB at c = 17) into page-locked memory; the host then runs the
-    // Horner pass of every bucket reduction and the O(1) tail (ProofParts::finish, finalize_host).
-    const size_t psz = 4 * sizeof(XYZZ<Fq>) + sizeof(XYZZ<Fq2>);
-    uint8_t* land = static_cast<uint8_t*>(sc.pinned(parts.bytes + 8 + (cm ? psz * (size_t)(cm->world + 1) : 0)));
-    ARK_CHECK_HIP(hipMemcpyAsync(land, res_base, parts.bytes, hipMemcpyDeviceToHost, sR));
-    uint8_t* const land_sat = land + parts.bytes + (cm ? psz * (size_t)(cm->world + 1) : 0);
+    const size_t gather_bytes = cm ? SUMS_BYTES * (size_t)(cm->world + 1) : 0;
+    land = static_cast<uint8_t*>(sc.pinned(parts.bytes + gather_bytes + 8));
+    land_sat = land + parts.bytes + gather_bytes;
+    ARK_CHECK_HIP(hipMemcpyAsync(land, sc.results.p, parts.bytes, hipMemcpyDeviceToHost, sR));
     // (sR has everything of the witness-map stream behind it: the H accumulation waited for the sort of h, which waited for h)
-    if (check_sat) ARK_CHECK_HIP(hipMemcpyAsync(land_sat, sc.ws.first_bad.p, 8, hipMemcpyDeviceToHost, sR));
+    if (plan.check_sat) ARK_CHECK_HIP(hipMemcpyAsync(land_sat, sc.ws.first_bad.p, 8, hipMemcpyDeviceToHost, sR));
     ARK_CHECK_HIP(hipEventRecord(ev[E_END], sR));
-    t_launched = since(t_enter);
+    t_launched = since_enter();
     bool overslept = false;
-    const bool plain = !cm && !partials_out;
-    wait_event_polite(ev[E_END], spin, (plain && epi_sleep_ok(pk.N)) ? sc.drain_hint(pol.wait_adapt != 0, shape) : 0.0, &overslept);
-    t_synced = since(t_enter);
-    if (plain) sc.drain_record(shape, t_synced - t_launched, overslept);
+    wait_event_polite(ev[E_END], plan.spin, (plan.plain && epi_sleep_ok(pk.N)) ? sc.drain_hint(pol.wait_adapt != 0, shape) : 0.0, &overslept);
+    t_synced = since_enter();
+    if (plan.plain) sc.drain_record(shape, t_synced - t_launched, overslept);
     XYZZ<Fq> h1[4];
     XYZZ<Fq2> h2;
     parts.finish(land, h1, h2);
     if (cm) {
-      // sharded prove: this rank's five XYZZ sums (A, B1, L', H in G1, then B2 in G2; 960 B for BLS12-381) go back to HBM, ONE
-      // ncclAllGather on the reduction stream, then the O(world) additions and the O(1) tail on the host -- on every rank
-      uint8_t* mine = land + parts.bytes;
-      memcpy(mine, h1, sizeof(h1));
-      memcpy(mine + sizeof(h1), &h2, sizeof(h2));
-      cm->gather.ensure(psz * (size_t)(cm->world + 1));
-      uint8_t* d_mine = cm->gather.as<uint8_t>() + psz * (size_t)cm->world;
-      ARK_CHECK_HIP(hipMemcpyAsync(d_mine, mine, psz, hipMemcpyHostToDevice, sR));
-      ARK_CHECK_NCCL(ncclAllGather(d_mine, cm->gather.p, psz, ncclUint8, cm->comm, sR));
-      const size_t all_bytes = psz * (size_t)cm->world;
-      uint8_t* all = mine + psz;
-      ARK_CHECK_HIP(hipMemcpyAsync(all, cm->gather.p, all_bytes, hipMemcpyDeviceToHost, sR));
-      ARK_CHECK_HIP(hipEventRecord(ev[E_END], sR));
-      wait_event_polite(ev[E_END], spin);
-      combine_partials_host<Curve>(all, (uint64_t)cm->world, r_canon, s_canon, out);
+      gather_and_combine(h1, h2);
     } else if (partials_out) {
-      // sharded prove: hand back the five XYZZ partial sums (A, B1, L', H in G1, then B2 in G2)
+      // ark355_prove_shard: hand back the five XYZZ sums (A, B1, L', H in G1, then B2 in G2)
       memcpy(partials_out, h1, sizeof(h1));
       memcpy(partials_out + sizeof(h1), &h2, sizeof(h2));
     } else {
       finalize_host<Curve>(h1, h2, rc, scn, out);
     }
-    t_tail = since(t_enter);
-    // Every stream has drained into sR through the event chain: E_END completes only after the last event of sW (E_H),
-    // sS (E_SORT2) and the accumulation stream (E_ACC_DONE0 + 4); nothing else is queued on them.  The prover used to call
-    // hipStreamSynchronize on the feeder streams here.  That is NOT free: HIP streams share a handful of hardware queues, and
-    // a synchronise on an idle stream of this proof waits -- spinning -- for the other proofs' kernels in the same queue: 22
-    // and 82 ms in two of six traced 2^20 proofs with four in flight (profiles/r03_host_cpu.txt).  Measured, same box
-    // (profiles/r03_epilogue_ab.txt): without them 2^20 x 4 in flight ran 23.9 instead of 24.7 ms per proof on 0.8 instead of
-    // 1.5 host cores -- but 2^18 x 8 in flight 10.8 instead of 8.5 ms.  Both epilogues are therefore SCHEDULES
-    // (SCHED_PIPELINE checks the three events, SCHED_PIPELINE_SYNC synchronises) and the choice between them is measured
-    // per class like the rest; a one-stream proof has nothing to synchronise.
-    if (sched == SCHED_PIPELINE_SYNC) {
-      ARK_CHECK_HIP(hipStreamSynchronize(sS));
-      ARK_CHECK_HIP(hipStreamSynchronize(sW));
-    } else if (!one_stream) {
+    t_tail = since_enter();
+  }
+
+  // sharded prove: this rank's five XYZZ sums (960 B for BLS12-381) go back to HBM, ONE ncclAllGather on the reduction stream,
+  // then the O(world) additions and the O(1) tail on the host -- on every rank
+  void gather_and_combine(const XYZZ<Fq> h1[4], const XYZZ<Fq2>& h2) {
+    hipStream_t sR = on(plan.reduce);
+    uint8_t* mine = land + parts.bytes;
+    memcpy(mine, h1, 4 * sizeof(XYZZ<Fq>));
+    memcpy(mine + 4 * sizeof(XYZZ<Fq>), &h2, sizeof(h2));
+    cm->gather.ensure(SUMS_BYTES * (size_t)(cm->world + 1));
+    uint8_t* d_mine = cm->gather.as<uint8_t>() + SUMS_BYTES * (size_t)cm->world;
+    ARK_CHECK_HIP(hipMemcpyAsync(d_mine, mine, SUMS_BYTES, hipMemcpyHostToDevice, sR));
+    ARK_CHECK_NCCL(ncclAllGather(d_mine, cm->gather.p, SUMS_BYTES, ncclUint8, cm->comm, sR));
+    uint8_t* all = mine + SUMS_BYTES;
+    ARK_CHECK_HIP(hipMemcpyAsync(all, cm->gather.p, SUMS_BYTES * (size_t)cm->world, hipMemcpyDeviceToHost, sR));
+    ARK_CHECK_HIP(hipEventRecord(ev[E_END], sR));
+    wait_event_polite(ev[E_END], plan.spin);
+    combine_partials_host<Curve>(all, (uint64_t)cm->world, r_canon, s_canon, out);
+  }
+
+  // Every stream has drained into the reduction stream through the event chain: E_END completes only after the last event of W
+  // (E_H), S (E_SORT2, or E_HT with the tails of H aside) and the accumulation stream (E_ACC_DONE0 + 4); nothing else is queued
+  // on them.  The prover used to call hipStreamSynchronize on the feeder streams here.  That is NOT free: HIP streams share a
+  // handful of hardware queues, and a synchronise on an idle stream of this proof waits -- spinning -- for the other proofs'
+  // kernels in the same queue: 22 and 82 ms in two of six traced 2^20 proofs with four in flight (profiles/r03_host_cpu.txt).
+  // Measured, same box (profiles/r03_epilogue_ab.txt): without them 2^20 x 4 in flight ran 23.9 instead of 24.7 ms per proof on
+  // 0.8 instead of 1.5 host cores -- but 2^18 x 8 in flight 10.8 instead of 8.5 ms.  Both epilogues are therefore SCHEDULES
+  // (SCHED_PIPELINE checks the three events, SCHED_PIPELINE_SYNC synchronises) and the choice between them is measured per class
+  // like the rest; a one-stream proof has nothing to synchronise.
+  void leave_streams() {
+    if (plan.epilogue == EPILOGUE_SYNC) {
+      ARK_CHECK_HIP(hipStreamSynchronize(on(plan.sort_z)));
+      ARK_CHECK_HIP(hipStreamSynchronize(on(plan.wm)));
+    } else if (plan.epilogue == EPILOGUE_CHECK_EVENTS) {
       for (hipEvent_t last : {ev[E_ACC_DONE0 + 4], h_tails_aside ? ev[E_HT] : ev[E_SORT2], ev[E_H]}) {
         const hipError_t q = hipEventQuery(last);
-        if (q == hipErrorNotReady) wait_event_polite(last, spin);
+        if (q == hipErrorNotReady) wait_event_polite(last, plan.spin);
         else if (q != hipSuccess) ARK_CHECK_HIP(q);
       }
     }
-    if (exploring) {
-      explore_guard.armed = false;
-      const int now_in_flight = inflight.c.load();
-      if (!concurrent && now_in_flight > 1) {
-        SchedTuner::of(ctx->device).unstart(tune_key, sched);
-      } else {
-        // in flight: the proof's wall time over the number of proofs that shared the device with it (mean of the counts at its
-        // start and at its end) -- an estimate of the time per proof that does not reward a phase for running while the
-        // caller's batch ramps down (run G: six in flight, a phase at the end of a batch read 107 ms of latency against
-        // 129 ms and was latched; the timed region then ran 7 % slower)
-        const double share = concurrent ? 0.5 * (double)(inflight.mine + now_in_flight) : 1.0;
-        SchedTuner::of(ctx->device).report(tune_key, concurrent, sched, since(t_enter) / (share < 1.0 ? 1.0 : share), pol.sched_explore,
-                                           static_sched);
-      }
+  }
+
+  void report_to_tuner() {
+    if (!explore.armed) return;
+    explore.armed = false;
+    const int now_in_flight = inflight.c.load();
+    if (!concurrent && now_in_flight > 1) {
+      SchedTuner::of(ctx->device).unstart(explore.key, sched);      // a polluted "alone" sample: measured again
+      return;
     }
+    // in flight: the proof's wall time over the number of proofs that shared the device with it (mean of the counts at its
+    // start and at its end) -- an estimate of the time per proof that does not reward a phase for running while the
+    // caller's batch ramps down (run G: six in flight, a phase at the end of a batch read 107 ms of latency against
+    // 129 ms and was latched; the timed region then ran 7 % slower)
+    const double share = concurrent ? 0.5 * (double)(inflight.mine + now_in_flight) : 1.0;
+    SchedTuner::of(ctx->device).report(explore.key, concurrent, sched, since_enter() / (share < 1.0 ? 1.0 : share), pol.sched_explore,
+                                       static_sched);
+  }
+
+  // phases overlap across streams: the entries are elapsed times of the respective stream segments
+  void record_timings() {
     auto el = [&](hipEvent_t a, hipEvent_t b) {
       float ms = 0;
       (void)hipEventElapsedTime(&ms, a, b);
       return ms;
     };
-    // phases overlap across streams: the entries are elapsed times of the respective stream segments
-    if (trace_host)
+    if (pol.trace_host)
       fprintf(stderr, "[ark355] prove host wall: all work queued %.2f ms, GPU drained %.2f ms, host tail done %.2f ms, "
                       "epilogue %.2f ms; GPU span %.2f ms\n",
-              t_launched, t_synced, t_tail, since(t_enter), el(ev[E_START], ev[E_END]));
+              t_launched, t_synced, t_tail, since_enter(), el(ev[E_START], ev[E_END]));
     ctx->timings.total_ms = el(ev[E_START], ev[E_END]);
     ctx->timings.h2d_ms = el(ev[E_START], ev[E_Z]);
     ctx->timings.witness_map_ms = el(ev[E_Z], ev[E_H]);
@@ -965,17 +997,43 @@ static void prove_run(ark355_ctx* ctx, ProverScratch& sc, PkDev& pk, const R1csD
     ctx->acc_ms = acc_ms;
     ctx->acc_launches = 5;
     ctx->acc_points = pts;
-    if (check_sat) {
-      unsigned long long fb;
-      memcpy(&fb, land_sat, 8);
-      if (fb != ~0ull) {
-        if (out) memset(out, 0, sizeof(*out));
-        char msg[160];
-        snprintf(msg, sizeof(msg), "constraint %llu is not satisfied by the assignment (policy CHECK_SATISFIED; the first of them)", fb);
-        throw HipError{ARK355_E_UNSATISFIABLE, msg};
-      }
-    }
   }
+
+  // policy CHECK_SATISFIED: the verdict came with the proof's last copy
+  void check_verdict() {
+    if (!plan.check_sat) return;
+    unsigned long long fb;
+    memcpy(&fb, land_sat, 8);
+    if (fb == ~0ull) return;
+    if (out) memset(out, 0, sizeof(*out));
+    char msg[160];
+    snprintf(msg, sizeof(msg), "constraint %llu is not satisfied by the assignment (policy CHECK_SATISFIED; the first of them)", fb);
+    throw HipError{ARK355_E_UNSATISFIABLE, msg};
+  }
+};
+
+// z_src: host or device pointer to m Fr (Montgomery); z_on_device selects the copy kind.
+template <class Curve>
+static void prove_run(ark355_ctx* ctx, ProverScratch& sc, PkDev& pk, const R1csDev& r1, const void* z_src,
+                      bool z_on_device, const uint8_t r_canon[32], const uint8_t s_canon[32], ark355_proof_raw* out,
+                      uint8_t* partials_out = nullptr, CommDev* cm = nullptr, int shard_mode = 0) {
+  ARK_REQUIRE(pk.curve == Curve::ID && r1.curve == Curve::ID, ARK355_EINVAL, "curve mismatch");
+  ARK_REQUIRE(pk.ell == r1.ell && pk.w == r1.w && pk.N == r1.N, ARK355_EINVAL,
+              "proving key and R1CS dimensions differ");
+  // first proof of a whole key: coefficient path or evaluation basis, for the life of the key (pk_bind)
+  const bool h_eval = pk_bind<Curve>(ctx, pk, r1);
+  ProveRun<Curve> p{ctx, sc, pk, r1, z_src, z_on_device, r_canon, s_canon, out, partials_out, cm, shard_mode, h_eval};
+  p.pick_schedule();
+  p.check_shard_plans();
+  p.queue_inputs();
+  p.queue_witness_map();
+  p.queue_sorts();
+  p.queue_msms();
+  p.finish();
+  p.leave_streams();
+  p.report_to_tuner();
+  p.record_timings();
+  p.check_verdict();
 }
 
 }  // namespace ark355

@@ -1104,7 +1104,7 @@ static Msm28Slot<P, COORDS>* msm_slots28(MsmBuckets& b, int which) {
 // format (PrecompTable::packed), which picks the accumulation kernel
 template <class F>
 static void msm_accumulate_phase(ark355_ctx* ctx, const MsmSort& s, MsmBuckets& b, const void* d_rows, bool packed,
-                                 hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+                                 hipStream_t stream, int acc_threads, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
   const MsmPlan& p = s.plan;
   if (!b.prepared) msm_prepare_phase<F>(ctx->policy, s, b, stream);      // stand-alone MSMs: same stream
   b.prepared = false;
@@ -1114,10 +1114,10 @@ static void msm_accumulate_phase(ark355_ctx* ctx, const MsmSort& s, MsmBuckets& 
   // four SIMDs at once and gives its slots back only when its slowest wave is done; with 64 lanes every SIMD refills by itself.
   // Measured, same box, interleaved (runs T, V): a LONE one-stream 2^20 proof 24.4-24.6 -> 23.8 ms device-resident with 64; four
   // proofs in flight 21.8-22.0 ms either way; the five-stream pipeline of a sharded proof's rank 15.9-16.0 -> 16.4-16.5 ms, i.e.
-  // worse (its feeder kernels then compete with four times as many workgroups for the dispatcher).  So the CALL says what it
-  // wants (ark355_ctx::acc_threads_hint: prove_run asks for 64 for a proof alone on one stream) and policy ACC_THREADS = 64 / 128 /
-  // 256 overrides it (0, the default: the hint, else 256).
-  const int acc_want = ctx->policy.acc_threads ? ctx->policy.acc_threads : ctx->acc_threads_hint;
+  // worse (its feeder kernels then compete with four times as many workgroups for the dispatcher).  So the CALLER says what it
+  // wants (acc_threads: ProvePlan asks for 64 for a proof alone on one stream; 0: 256) and policy ACC_THREADS = 64 / 128 / 256
+  // overrides it.
+  const int acc_want = ctx->policy.acc_threads ? ctx->policy.acc_threads : acc_threads;
   const uint32_t acc_t = (acc_want == 64 || acc_want == 128) ? (uint32_t)acc_want : MSM_THREADS;
   const uint32_t* keys = s.sorted_keys.as<uint32_t>();
   const uint32_t* vals = s.sorted_vals.as<uint32_t>();

@@ -6,15 +6,17 @@
 // ark355_prove_batch inherit the parent's policy at every call.
 //
 // Three groups:
-//   per proof      SCHED, SCHED_EXPLORE, WAIT_SPIN, WAIT_ADAPT, STREAM_PRIO, BATCH_TAILS, SIDE_G2_TAILS,
-//                  SIDE_WM, SIDE_H_TAILS, TRACE_HOST (+ the legacy spellings SERIAL and EPILOGUE_SYNC, which map onto SCHED);
+//   per proof      SCHED, SCHED_EXPLORE, WAIT_SPIN, WAIT_ADAPT, STREAM_PRIO, BATCH_TAILS, SIDE_G2_TAILS, SIDE_G1_TAILS,
+//                  SIDE_WM, SIDE_H_TAILS, TRACE_HOST (+ the legacy spellings SERIAL and EPILOGUE_SYNC, which map onto
+//                  SCHED); what they decide for one proof is computed in one place, prove_plan.h;
 //                  sharded proofs: DWM_LOOPBACK, RCCL_SELF (window / bucket-ring combining is the `mode` argument of
 //                  ark355_prove_sharded, not a policy)
 //   per key load   MSM_C, MSM_C_H, PACK_ROWS, TABLE_STRIDE, HBM_BUDGET_MB, SHARD_DIST_WM
 //                  (read when a key / base set is loaded through the context: the tables are built for them)
 //   per call       MSM_SEG, ACC_THREADS, NTT_RMAX, NTT_DIRECT_MAX, NTT_NOFUSE (A/B and test knobs of the kernels'
-//                  host drivers), CHECK_SATISFIED, H_EVAL (read at the first proof of a key), PAIRING_DEVICE, PAIRING_DEVICE_MIN (where the Miller loops of ark355_multi_pairing
-//                  and ark355_verify_batch run), PAIRING_EACH_MIN (the same for ark355_pairing_groups and ark355_verify_each)
+//                  host drivers), CHECK_SATISFIED, H_EVAL (read at the first proof of a key), PAIRING_DEVICE,
+//                  PAIRING_DEVICE_MIN (where the Miller loops of ark355_multi_pairing and ark355_verify_batch run),
+//                  PAIRING_EACH_MIN (the same for ark355_pairing_groups and ark355_verify_each)
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -63,8 +65,8 @@ struct TunePolicy {
   int32_t shard_dist_wm = 1;      // key shards: h_query in the layout of the distributed witness map when the world size allows it
   // ---- per call
   int32_t msm_seg = 0;            // entries per accumulation lane (0: msm_seg_len)
-  int32_t acc_threads = 0;        // workgroup size of the accumulation kernels without LDS: 64 / 128 / 256; 0: the call's own choice (a proof alone
-                                  // on one stream: 64, everything else: 256; msm_accumulate_phase)
+  int32_t acc_threads = 0;        // workgroup size of the accumulation kernels without LDS: 64 / 128 / 256; 0: the caller's own choice (a proof alone
+                                  // on one stream: 64, everything else: 256; ProvePlan::acc_threads)
   int32_t ntt_rmax = 0;           // 0: NTT_RMAX_LOG
   int32_t ntt_direct_max = -1;    // -1: NTT_DIRECT_MAX_LOG
   int32_t ntt_nofuse = 0;

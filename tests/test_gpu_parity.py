@@ -238,13 +238,19 @@ def test_prove_with_window_17_negating_high_scalars(gpu_lib, gpu_ctx, gpu_policy
     pc.prove_case(gpu_lib, gpu_ctx, C, A, B, Cm, z, ell, rs=((C.r - 3, 12345),))
 
 
-@pytest.mark.parametrize("batch,side", [(1, 1), (1, 0), (0, 0), (1, 2)], ids=["batched+side", "batched", "per-msm", "batched+side+g1-aside"])
-@pytest.mark.parametrize("circuit", ["mulchain", "dummy"])
+_TAIL_VARIANTS = {"batched+side": (1, 1), "batched": (1, 0), "per-msm": (0, 0), "batched+side+g1-aside": (1, 2)}
+
+
+@pytest.mark.parametrize("circuit,batch,side",
+                         [pytest.param(c, *v, id="%s-%s" % (c, k)) for c in ("mulchain", "dummy") for k, v in _TAIL_VARIANTS.items()]
+                         + [pytest.param("mulchain", 1, -1, id="mulchain-batched+side+wm-inline")])
 def test_one_stream_tail_variants(gpu_lib, gpu_ctx, gpu_policy, circuit, batch, side):
     """A one-stream proof: the four G1 tails as one launch per step (policy BATCH_TAILS) and -- the proof being alone on the
     device -- the G2 tails on a side stream underneath the G1 accumulations (SIDE_G2_TAILS), against the per-MSM tails of
-    rounds 1-3; uniform scalars and the all-equal DummyCircuit (heavy buckets).  Proof bytes == oracle every way."""
+    rounds 1-3; uniform scalars and the all-equal DummyCircuit (heavy buckets).  side = -1: the defaults, but the witness map and the
+    sort of h in front of the accumulations on the proof's own stream (SIDE_WM = 0).  Proof bytes == oracle every way."""
     gpu_policy.setenv("ARK355_SCHED", "0")
+    gpu_policy.setenv("ARK355_SIDE_WM", "0" if side == -1 else "1")
     gpu_policy.setenv("ARK355_BATCH_TAILS", str(batch))
     gpu_policy.setenv("ARK355_SIDE_G2_TAILS", "1" if side else "0")
     gpu_policy.setenv("ARK355_SIDE_G1_TAILS", "1" if side == 2 else "0")     # (round 6) A, B1, L' tails aside as a batch of three
