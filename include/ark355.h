@@ -36,6 +36,7 @@ typedef struct ark355_ctx ark355_ctx;
 typedef struct ark355_pk ark355_pk;
 typedef struct ark355_r1cs ark355_r1cs;
 typedef struct ark355_gr1cs ark355_gr1cs;
+typedef struct ark355_bases ark355_bases;     /* resident MSM bases: ark355_bases_load */
 
 enum { ARK355_BLS12_381 = 0, ARK355_BN254 = 1 };
 
@@ -130,6 +131,27 @@ int32_t ark355_diag_mad_rate(ark355_ctx* ctx, float target_ms, float* tmad_per_s
  * (cycles delta) / (ticks delta) x 100 MHz is the region's mean gfx clock; bench.py reports the median over the slots and
  * `gfx_cycles_per_constraint` with it. */
 int32_t ark355_diag_clocks(ark355_ctx* ctx, uint64_t* pairs, uint32_t capacity, uint32_t* count);
+/* Diagnostic: the SORT stage of an MSM on its own -- signed window digits, bucket histogram, exclusive scan, placement --
+ * exactly as every MSM and proof runs it (the library's own msm_sort_plan / msm_sort_run on the context's stream and scratch),
+ * with everything it leaves on the device copied back.  bases == NULL: the plan of a one-shot MSM of n terms (no window tables,
+ * every window its own bucket set); a handle: the plan of that handle's window tables (n <= its rows, same curve).  scalars: n
+ * host scalars of 32 bytes, canonical, or Montgomery images with scalars_mont != 0.
+ *   plan[0] window bits c, [1] windows per scalar, [2] window stride, [3] bucket sets, [4] buckets in all (sets x 2^(c-1)),
+ *   [5] 1 when scalars above (r - 1) / 2 are replaced by r - k with flipped signs, [6] table rows per window block (the handle's
+ *   rows; 0 without tables), [7] 1 when the one-pass counting sort ran (more first-level bins than the two-level sort keeps in LDS);
+ *   *total = number of non-zero digits;
+ *   counts / offsets: per bucket its entries and their exclusive prefix sum (bucket_capacity >= plan[4] words each);
+ *   sorted_keys / sorted_vals: *total entries grouped by bucket (entry_capacity >= *total words each): key = set * 2^(c-1) +
+ *   digit - 1 with window w in set w % stride, value = (w / stride) * plan[6] + scalar index, bit 31 = subtract.  The order
+ *   inside a bucket is unspecified.
+ * Each of the two array pairs may be NULL (both of a pair): a call with all four NULL returns the plan and *total, so that the
+ * caller can size its buffers.  ARK355_EINVAL: a NULL context, plan or total (before any HIP call), a capacity below what is
+ * needed (plan and *total are written all the same), a handle of another curve, more scalars than the handle has rows. */
+#define ARK355_SORT_PLAN_WORDS 8
+int32_t ark355_diag_msm_sort(ark355_ctx* ctx, int32_t curve, const ark355_bases* bases, const uint8_t* scalars, uint64_t n,
+                             int32_t scalars_mont, uint32_t plan[ARK355_SORT_PLAN_WORDS], uint32_t* counts, uint32_t* offsets,
+                             uint64_t bucket_capacity, uint32_t* sorted_keys, uint32_t* sorted_vals, uint64_t entry_capacity,
+                             uint32_t* total);
 
 /* Page-locked host memory for assignments / key vectors handed to the entry points below: H2D copies from pinned
  * memory run at PCIe rate (~55 GB/s) and truly asynchronously; pageable memory is staged by the runtime at a fraction
@@ -396,7 +418,6 @@ int32_t ark355_msm_g2(ark355_ctx* ctx, int32_t curve, const uint8_t* bases, cons
                       uint64_t n, uint8_t* out_affine);
 
 /* device-resident MSM: bases are uploaded once into a handle, scalars live in HBM */
-typedef struct ark355_bases ark355_bases;
 int32_t ark355_bases_load(ark355_ctx* ctx, int32_t curve, int32_t group /*1|2*/, const uint8_t* bases,
                           uint64_t n, ark355_bases** out);
 void ark355_bases_free(ark355_bases* b);

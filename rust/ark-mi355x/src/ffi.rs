@@ -60,6 +60,8 @@ pub const ARK355_GR1CS_MAX_FACTORS: u32 = 1024;
 pub const ARK355_GR1CS_MAX_PREDICATES: u32 = 1024;
 pub const ARK355_GR1CS_MAX_ROWS: u64 = 4294967295;
 pub const ARK355_PAIRING_GROUP_MAX: u32 = 64;
+/// words of the `plan` array of `ark355_diag_msm_sort`
+pub const ARK355_SORT_PLAN_WORDS: usize = 8;
 
 #[repr(C)]
 pub struct ark355_pk_desc {
@@ -171,6 +173,23 @@ extern "C" {
     pub fn ark355_diag_dispatch(ctx: *mut ark355_ctx, launches: u32, spin_us: u32, gap_us: *mut f32, lanes: *mut u32) -> i32;
     pub fn ark355_diag_mad_rate(ctx: *mut ark355_ctx, target_ms: f32, tmad_per_s: *mut f32, elapsed_ms: *mut f32) -> i32;
     pub fn ark355_diag_clocks(ctx: *mut ark355_ctx, pairs: *mut u64, capacity: u32, count: *mut u32) -> i32;
+    /// Diagnostic: the sort stage of an MSM on its own (digits, histogram, scan, placement), copied back to the host.
+    pub fn ark355_diag_msm_sort(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        bases: *const ark355_bases,
+        scalars: *const u8,
+        n: u64,
+        scalars_mont: i32,
+        plan: *mut u32,
+        counts: *mut u32,
+        offsets: *mut u32,
+        bucket_capacity: u64,
+        sorted_keys: *mut u32,
+        sorted_vals: *mut u32,
+        entry_capacity: u64,
+        total: *mut u32,
+    ) -> i32;
 
     pub fn ark355_host_alloc(bytes: u64, out: *mut *mut c_void) -> i32;
     pub fn ark355_host_free(p: *mut c_void);

@@ -31,6 +31,7 @@ GR1CS_MAX_TERMS = 256
 GR1CS_MAX_FACTORS = 1024
 GR1CS_MAX_PREDICATES = 1024
 GR1CS_MAX_ROWS = 4294967295
+SORT_PLAN_WORDS = 8
 
 _ERR_NAMES = {
     EINVAL: "EINVAL", ENOMEM: "ENOMEM", EHIP: "EHIP", ERCCL: "ERCCL", ENODEV: "ENODEV",
@@ -58,7 +59,7 @@ SYMBOLS = [
     "ark355_vk_process", "ark355_pvk_free", "ark355_pvk_info", "ark355_pvk_alpha_beta", "ark355_pvk_pairings",
     "ark355_verify_each_pvk", "ark355_verify_batch_pvk",
     "ark355_ctx_set_policy", "ark355_ctx_get_policy", "ark355_sched_info", "ark355_sched_reset", "ark355_diag_streams", "ark355_diag_dispatch",
-    "ark355_diag_mad_rate", "ark355_diag_clocks",
+    "ark355_diag_mad_rate", "ark355_diag_clocks", "ark355_diag_msm_sort",
 ]
 
 SCHED_NAMES = {-1: "auto", 0: "one_stream", 1: "pipeline", 2: "pipeline_sync", 3: "one_stream_spin"}
@@ -227,6 +228,7 @@ class Lib:
         d.ark355_diag_dispatch.argtypes = [vp, u32, u32, P(C.c_float), P(u32)]
         d.ark355_diag_mad_rate.argtypes = [vp, C.c_float, P(C.c_float), P(C.c_float)]
         d.ark355_diag_clocks.argtypes = [vp, P(u64), u32, P(u32)]
+        d.ark355_diag_msm_sort.argtypes = [vp, i32, vp, vp, u64, i32, P(u32 * SORT_PLAN_WORDS), vp, vp, u64, vp, vp, u64, P(u32)]
         d.ark355_get_timings.argtypes = [vp, P(Timings)]
         d.ark355_get_kernel_stats.argtypes = [vp, P(C.c_float), P(u64), P(u64)]
         for name in SYMBOLS:
@@ -292,6 +294,31 @@ class Lib:
         cnt = C.c_uint32(0)
         self.check(ctx, self.dll.ark355_diag_clocks(ctx, buf, cap, C.byref(cnt)))
         return {i: (int(buf[2 * i]), int(buf[2 * i + 1])) for i in range(int(cnt.value)) if buf[2 * i + 1]}
+
+    def diag_msm_sort(self, ctx, curve, scalars, n, mont=0, bases=None, arrays=True):
+        """ark355_diag_msm_sort: the sort stage of an MSM over `n` host scalars (32 bytes each; Montgomery images with mont=1),
+        planned without tables (bases=None) or for the window tables of a bases_load handle.  Returns the plan, `total` and --
+        unless arrays=False -- counts / offsets (one word per bucket) and sorted_keys / sorted_vals (total words) as numpy
+        arrays.  Two calls: the first, without arrays, sizes the buffers of the second."""
+        sp, keep = _buf(scalars)
+        plan = (C.c_uint32 * SORT_PLAN_WORDS)()
+        total = C.c_uint32(0)
+        self.check(ctx, self.dll.ark355_diag_msm_sort(ctx, curve, bases, sp, n, int(mont), C.byref(plan), None, None, 0, None, None, 0,
+                                                      C.byref(total)))
+        names = ("c", "windows", "wstride", "key_windows", "total_buckets", "negate_high", "row_stride", "one_pass")
+        out = dict(zip(names, (int(v) for v in plan)))
+        out["total"] = int(total.value)
+        if not arrays:
+            return out
+        nb, ne = out["total_buckets"], out["total"]
+        counts, offsets = np.empty(nb, dtype=np.uint32), np.empty(nb, dtype=np.uint32)
+        keys, vals = np.empty(max(ne, 1), dtype=np.uint32), np.empty(max(ne, 1), dtype=np.uint32)
+        plan2 = (C.c_uint32 * SORT_PLAN_WORDS)()
+        self.check(ctx, self.dll.ark355_diag_msm_sort(ctx, curve, bases, sp, n, int(mont), C.byref(plan2), counts.ctypes.data, offsets.ctypes.data,
+                                                      nb, keys.ctypes.data, vals.ctypes.data, ne, C.byref(total)))
+        assert list(plan2) == list(plan) and int(total.value) == ne
+        out.update(counts=counts, offsets=offsets, sorted_keys=keys[:ne], sorted_vals=vals[:ne])
+        return out
 
     @staticmethod
     def diag_clocks_delta(c0, c1):

@@ -341,6 +341,49 @@ struct Api {
     else msm_generic<Fq2>(ctx, g, b.tab.table.p, b.tab.packed, d_scalars, n, mont, out, want_affine, &b.tab);
   }
 
+  // ark355_diag_msm_sort: the sort stage of an MSM on its own -- the scalars go up, msm_sort_plan / msm_sort_run (the very
+  // functions every MSM and proof calls) run on the context's stream over its scratch, and everything the sort leaves on the
+  // device comes back.  b == nullptr: the plan of a one-shot MSM.  plan and *total are written before a capacity is refused.
+  static void diag_msm_sort(ark355_ctx* ctx, GenericScratch& g, const BasesDev* b, const uint8_t* scalars, uint64_t n, int mont,
+                            uint32_t* plan, uint32_t* counts, uint32_t* offsets, uint64_t bucket_capacity, uint32_t* sorted_keys,
+                            uint32_t* sorted_vals, uint64_t entry_capacity, uint32_t* total) {
+    hipStream_t st = ctx->stream;
+    if (b) ARK_REQUIRE(b->curve == Curve::ID, ARK355_EINVAL, "sort diagnostic: the base set belongs to another curve");
+    ARK_REQUIRE((counts == nullptr) == (offsets == nullptr) && (sorted_keys == nullptr) == (sorted_vals == nullptr), ARK355_EINVAL,
+                "sort diagnostic: counts / offsets and sorted_keys / sorted_vals come in pairs");
+    const PrecompTable* tab = b ? &b->tab : nullptr;
+    g.b.ensure(n * sizeof(Fr));
+    if (n) ARK_CHECK_HIP(hipMemcpyAsync(g.b.p, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, st));
+    msm_sort_plan<Fr>(ctx, g.sort, n, st, tab);
+    msm_sort_run<Fr>(ctx, g.sort, g.b.p, n, mont, st, tab);
+    const MsmPlan& p = g.sort.plan;
+    uint32_t tot = 0;
+    ARK_CHECK_HIP(hipMemcpyAsync(&tot, g.sort.total.p, 4, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+    plan[0] = p.c;
+    plan[1] = p.windows;
+    plan[2] = p.wstride;
+    plan[3] = p.key_windows;
+    plan[4] = p.total_buckets;
+    plan[5] = p.negate_high ? 1u : 0u;
+    plan[6] = tab ? (uint32_t)tab->n : 0u;
+    plan[7] = msm_sort_one_pass(p) ? 1u : 0u;
+    *total = tot;
+    ARK_REQUIRE((uint64_t)tot <= (uint64_t)p.windows * n, ARK355_EINVAL, "sort diagnostic: more entries than digits");
+    if (counts) {
+      ARK_REQUIRE(bucket_capacity >= p.total_buckets, ARK355_EINVAL, "sort diagnostic: bucket_capacity below the plan's buckets");
+      ARK_CHECK_HIP(hipMemcpy(counts, g.sort.counts.p, (size_t)p.total_buckets * 4, hipMemcpyDeviceToHost));
+      ARK_CHECK_HIP(hipMemcpy(offsets, g.sort.offsets.p, (size_t)p.total_buckets * 4, hipMemcpyDeviceToHost));
+    }
+    if (sorted_keys) {
+      ARK_REQUIRE(entry_capacity >= tot, ARK355_EINVAL, "sort diagnostic: entry_capacity below the number of entries");
+      if (tot) {
+        ARK_CHECK_HIP(hipMemcpy(sorted_keys, g.sort.sorted_keys.p, (size_t)tot * 4, hipMemcpyDeviceToHost));
+        ARK_CHECK_HIP(hipMemcpy(sorted_vals, g.sort.sorted_vals.p, (size_t)tot * 4, hipMemcpyDeviceToHost));
+      }
+    }
+  }
+
   template <class F>
   static void xyzz_sum_t(ark355_ctx* ctx, GenericScratch& g, const uint8_t* partials, uint64_t count, uint8_t* out) {
     hipStream_t st = ctx->stream;

@@ -266,6 +266,17 @@ int32_t ark355_diag_clocks(ark355_ctx* ctx, uint64_t* pairs, uint32_t capacity, 
     *count = DIAG_CLOCK_SLOTS;
   });
 }
+int32_t ark355_diag_msm_sort(ark355_ctx* ctx, int32_t curve, const ark355_bases* bases, const uint8_t* scalars, uint64_t n,
+                             int32_t scalars_mont, uint32_t plan[ARK355_SORT_PLAN_WORDS], uint32_t* counts, uint32_t* offsets,
+                             uint64_t bucket_capacity, uint32_t* sorted_keys, uint32_t* sorted_vals, uint64_t entry_capacity,
+                             uint32_t* total) {
+  if (!ctx || !plan || !total || (n && !scalars) || (bases && !bases->d)) return ARK355_EINVAL;
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(curve, A::diag_msm_sort(ctx, ex.generic, bases ? bases->d : nullptr, scalars, n, scalars_mont, plan, counts, offsets,
+                                           bucket_capacity, sorted_keys, sorted_vals, entry_capacity, total));
+  });
+}
 int32_t ark355_sched_reset(const ark355_ctx* ctx) {
   if (!ctx) return ARK355_EINVAL;
   SchedTuner::of(ctx->device).reset();

@@ -442,7 +442,10 @@ msm_scatter_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict
 // The order of entries inside a bucket is unspecified (as before); nothing downstream depends on it.
 constexpr uint32_t SORT_LO_BITS = 8;
 constexpr uint32_t SORT_LO = 1u << SORT_LO_BITS;
-constexpr uint32_t SORT_MAX_BINS = 4096;       // LDS counters of level 1
+#ifndef ARK_SORT_MAX_BINS
+#define ARK_SORT_MAX_BINS 4096u   // tests shrink it so that small bucket counts take the one-pass sort
+#endif
+constexpr uint32_t SORT_MAX_BINS = ARK_SORT_MAX_BINS;       // LDS counters of level 1
 constexpr uint32_t SORT_SPT = 4;               // scalars per thread in level 1
 constexpr uint32_t SORT_HI_THREADS = 1024;     // level-1 workgroup: 4096 scalars, [bin][workgroup] table stays small
 constexpr uint32_t SORT_EPT = 16;              // entries per thread in level 2
@@ -940,6 +943,9 @@ struct MsmSort {
   DevBuf keys, vals, counts, offsets, cursor, sorted_keys, sorted_vals, total, hist, hist_scanned, scan_aux;
 };
 
+// more first-level bins than the two-level sort keeps in LDS: the one-pass counting sort of round 1
+static inline bool msm_sort_one_pass(const MsmPlan& p) { return (p.total_buckets + SORT_LO - 1) / SORT_LO > SORT_MAX_BINS; }
+
 // Plan one sort (window size, buffer sizes) and clear its counters -- through `fb` when the caller batches the fills of
 // a whole proof (prove_run), on `stream` otherwise.  msm_sort_run queues the kernels.
 template <class Fr>
@@ -956,7 +962,7 @@ static void msm_sort_plan(ark355_ctx* ctx, MsmSort& s, uint64_t n, hipStream_t s
   ARK_REQUIRE(entries < (1ull << 31), ARK355_EINVAL, "MSM entry count must be < 2^31");
   // two-level sort: level 1 writes (key, value) PAIRS into `keys` (one 8-byte store per entry instead of two 4-byte stores into
   // two arrays: round 6); the one-pass fallback keeps separate arrays
-  const bool two_level = (p.total_buckets + SORT_LO - 1) / SORT_LO <= SORT_MAX_BINS;
+  const bool two_level = !msm_sort_one_pass(p);
   s.keys.ensure(entries * (two_level ? 8 : 4));
   if (!two_level) s.vals.ensure(entries * 4);
   s.sorted_keys.ensure(entries * 4 + 16);
@@ -985,7 +991,7 @@ static void msm_sort_run(ark355_ctx* ctx, MsmSort& s, const void* d_scalars, uin
   const uint64_t entries = (uint64_t)p.windows * n;
   const uint32_t bins = (p.total_buckets + SORT_LO - 1) / SORT_LO;
   // the one-pass counting sort of round 1 when level 1 would not fit LDS
-  if (bins > SORT_MAX_BINS) {
+  if (msm_sort_one_pass(p)) {
     const uint32_t grid_n = (uint32_t)((n + MSM_THREADS - 1) / MSM_THREADS);
     ARK_LAUNCH((msm_digits_kernel<Fr>), dim3(grid_n), dim3(MSM_THREADS), 0, stream, (const Fr*)d_scalars, (uint32_t)n,
                mont, p.c, p.windows, msm_digit_flags(p), stride, s.keys.as<uint32_t>(), s.vals.as<uint32_t>(),

@@ -41,7 +41,7 @@ def build(force=False, extra_flags=(), tag=""):
 
 def _build_locked(out, extra_flags, tag):
     objs = []
-    flags = list(extra_flags) + ["-O2", "-std=c++17", "-fPIC", "-DARK_EMUL", "-DARK_MSM_HEAVY_SPAN=2", "-DARK_MSM_HEAVY_GRID=3u", "-I", HERE, "-I", CSRC, "-w"]
+    flags = list(extra_flags) + ["-O2", "-std=c++17", "-fPIC", "-DARK_EMUL", "-DARK_MSM_HEAVY_SPAN=2", "-DARK_MSM_HEAVY_GRID=3u", "-DARK_SORT_MAX_BINS=256u", "-I", HERE, "-I", CSRC, "-w"]
 
     def cc(src):
         obj = os.path.join(HERE, os.path.basename(src) + (".%s" % tag if tag else "") + ".emul.o")

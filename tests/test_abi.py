@@ -68,7 +68,12 @@ def test_host_only_entry_points_reject_bad_arguments(built_lib):
     c, w, s, b = C.c_uint32(7), C.c_uint32(7), C.c_uint32(7), C.c_uint64(7)
     assert lib.dll.ark355_pk_table_info(None, C.byref(c), C.byref(w), C.byref(s), C.byref(b)) == EINVAL
     assert lib.dll.ark355_pk_dims(None, None, None, None) == EINVAL
-    from snark_amd._binding import ProofRaw
+    from snark_amd._binding import ProofRaw, SORT_PLAN_WORDS
+    # the sort diagnostic without a context: refused before any HIP call, nothing written
+    plan, total, sc = (C.c_uint32 * SORT_PLAN_WORDS)(*([7] * SORT_PLAN_WORDS)), C.c_uint32(7), (C.c_uint8 * 64)()
+    assert lib.dll.ark355_diag_msm_sort(None, snark_amd.BLS12_381, None, sc, 2, 0, C.byref(plan), None, None, 0, None, None, 0,
+                                        C.byref(total)) == EINVAL
+    assert list(plan) == [7] * SORT_PLAN_WORDS and total.value == 7
     buf = (C.c_uint8 * 512)()
     raw = ProofRaw()
     out = C.byref(raw)
