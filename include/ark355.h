@@ -271,10 +271,11 @@ int32_t ark355_prove_sharded_dev(ark355_ctx* ctx, ark355_comm* comm, const ark35
  * SWFlags (little-endian, flags in the last byte); compressed != 0 selects the compressed form.  `validate`:
  *   ARK355_VALIDATE_FULL (1)   everything ark-serialize's Validate::Yes checks: reduced coordinates, the curve equation
  *                              (uncompressed form; compressed points are on the curve by construction) AND membership in
- *                              the prime-order subgroup ([r]P = O: BLS12-381 G1/G2, BN254 G2) -- use it for anything that
+ *                              the prime-order subgroup (BLS12-381 G1/G2, BN254 G2; the endomorphism tests described at
+ *                              ark355_points_check, equivalent to [r]P = O) -- use it for anything that
  *                              comes from an untrusted party (proofs: a small-order component vanishes in the pairing, so
  *                              without the test one proof has many accepted encodings);
- *   ARK355_VALIDATE_CURVE (2)  the same without the subgroup test (a 255-bit scalar multiplication per point): the
+ *   ARK355_VALIDATE_CURVE (2)  the same without the subgroup test (a 64- to 128-bit scalar multiplication per point): the
  *                              explicit opt-out for key material from a trusted source;
  *   ARK355_VALIDATE_NONE (0)   Validate::No.
  * Flag combinations upstream rejects in every mode are rejected in every mode here: BLS12-381 sort bit without the
@@ -539,6 +540,30 @@ int32_t ark355_verify_each_pvk(ark355_ctx* ctx, const ark355_pvk* pvk, const ark
 /* ark355_verify_batch with the key taken from the handle (its points were checked at process time): the same verdict. */
 int32_t ark355_verify_batch_pvk(ark355_ctx* ctx, const ark355_pvk* pvk, const ark355_proof_raw* proofs,
                                 const uint8_t* public_inputs, const uint8_t* rho, uint64_t count, int32_t* ok);
+
+/* ---- proofs as wire bytes (Proof: CanonicalDeserialize, snark/src/lib.rs:32) -----------------------------------------------
+ * A verifier receives proofs as ark-serialize bytes.  These entries decode them on the device, one lane per point, and a bad
+ * or malleated encoding costs exactly its own proof: it is reported per proof, never as an error of the call.  The subgroup
+ * test of ARK355_VALIDATE_FULL is the endomorphism test ark-bls12-381 / ark-bn254 use upstream (phi(P) = -[x^2]P on
+ * BLS12-381 G1, psi(P) = [x]P on its G2, psi(P) = [6x^2]P on BN254 G2), equivalent to [r]P = O for points on the curve.
+ * ARK355_EINVAL is for arguments only: a NULL pointer with a non-zero count, an unknown validate or method,
+ * 3 * count >= 2^32, a handle of another device (ark355_last_error names the argument). */
+/* ark-ec is_on_curve + is_in_correct_subgroup_assuming_on_curve for n raw affine images, one lane per point:
+ * status[i] = 0, WIRE_NOT_ON_CURVE (2) or WIRE_NOT_IN_SUBGROUP (4); infinity is 0.  method 0: [r]P, 1: the endomorphism tests. */
+int32_t ark355_points_check(ark355_ctx* ctx, int32_t curve, int32_t group, const uint8_t* raw, uint64_t n, int32_t method,
+                            uint8_t* status);
+/* count proofs (a || b || c each, the layout of ark355_proof_from_bytes) decoded on the device.  status[j] = 0, or
+ * (k << 4) | wire status of the FIRST failing point in the order a (k=1), b (2), c (3), the wire status being 1 coordinate not
+ * reduced, 2 not on the curve, 3 bad flag bits, 4 not in the subgroup; out[j] is all zero where status[j] != 0. */
+int32_t ark355_proofs_from_bytes(ark355_ctx* ctx, int32_t curve, const uint8_t* in, uint64_t count, int32_t compressed,
+                                 int32_t validate, ark355_proof_raw* out, uint8_t* status);
+/* Proof::deserialize_with_mode + SNARK::verify_with_processed_vk per proof, without the proofs visiting the host as points:
+ * ok[j] = 1 iff proof j decodes under `validate` AND verifies; status (may be NULL) as above.  public_inputs, count == 0,
+ * num_instance == 1 and the route policy exactly as for ark355_verify_each_pvk (the host route decodes on host threads and
+ * gives the same ok and status). */
+int32_t ark355_verify_each_bytes(ark355_ctx* ctx, const ark355_pvk* pvk, const uint8_t* proofs, uint64_t count,
+                                 int32_t compressed, int32_t validate, const uint8_t* public_inputs, uint8_t* ok,
+                                 uint8_t* status);
 
 /* The scalars of the Groth16 generator (circuit_specific_setup, snark/src/lib.rs:43-46; upstream
  * generate_parameters_with_qap) from the R1CS matrices in CSR and the five trapdoor elements tau, alpha, beta, gamma,

@@ -506,6 +506,40 @@ extern "C" {
         ok: *mut i32,
     ) -> i32;
 
+    /// curve + subgroup status of n raw affine images (method 0: `[r]P`, 1: the endomorphism tests)
+    pub fn ark355_points_check(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        group: i32,
+        raw: *const u8,
+        n: u64,
+        method: i32,
+        status: *mut u8,
+    ) -> i32;
+    /// `count` proofs decoded on the device; one status byte per proof, a bad proof is not an error of the call
+    pub fn ark355_proofs_from_bytes(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        input: *const u8,
+        count: u64,
+        compressed: i32,
+        validate: i32,
+        out: *mut ark355_proof_raw,
+        status: *mut u8,
+    ) -> i32;
+    /// `Proof::deserialize_with_mode` + `SNARK::verify_with_processed_vk` per proof from wire bytes
+    pub fn ark355_verify_each_bytes(
+        ctx: *mut ark355_ctx,
+        pvk: *const ark355_pvk,
+        proofs: *const u8,
+        count: u64,
+        compressed: i32,
+        validate: i32,
+        public_inputs: *const u8,
+        ok: *mut u8,
+        status: *mut u8,
+    ) -> i32;
+
     pub fn ark355_setup_scalars(
         curve: i32,
         n_constraints: u64,

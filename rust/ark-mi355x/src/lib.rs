@@ -416,6 +416,50 @@ where
         Ok(out)
     }
 
+    /// `Proof::deserialize_with_mode` + `SNARK::verify_with_processed_vk` per proof (`ark355_verify_each_bytes`): `proofs` holds
+    /// `public_inputs.len()` serialized proofs back to back, decoded on the device under `validate`
+    /// (`ffi::ARK355_VALIDATE_FULL` for anything untrusted).  Returns `(ok, status)` per proof: a bad or malleated encoding costs
+    /// its own proof a `false` and a non-zero status, never the call.  Every list of public inputs must have `num_instance - 1`
+    /// elements.
+    pub fn verify_each_bytes(
+        pvk: &DevicePvk<E>,
+        public_inputs: &[Vec<E::ScalarField>],
+        proofs: &[u8],
+        compressed: bool,
+        validate: i32,
+    ) -> Result<(Vec<bool>, Vec<u8>), Mi355xError> {
+        let (ell, count) = (pvk.num_instance, public_inputs.len());
+        if public_inputs.iter().any(|x| x.len() + 1 != ell) {
+            return Err(Mi355xError::InvalidArgument("verify_each_bytes: num_instance - 1 public inputs per proof".into()));
+        }
+        let mut sizes = [0u32; 4];
+        let _ = unsafe { ffi::ark355_sizes(E::CURVE_ID, sizes.as_mut_ptr()) };
+        let fq = sizes[1] as usize;
+        let per_proof = if compressed { 4 * fq } else { 8 * fq };
+        if proofs.len() != count * per_proof {
+            return Err(Mi355xError::InvalidArgument("verify_each_bytes: the byte block does not hold one proof per input list".into()));
+        }
+        let xs: Vec<E::ScalarField> = public_inputs.iter().flatten().copied().collect();
+        let image = marshal::scalars_image(&xs);
+        let (mut ok, mut status) = (vec![0u8; count], vec![0u8; count]);
+        cache::with_ctx(|ctx| {
+            cache::check(ctx, unsafe {
+                ffi::ark355_verify_each_bytes(
+                    ctx,
+                    pvk.handle,
+                    proofs.as_ptr(),
+                    count as u64,
+                    compressed as i32,
+                    validate,
+                    if xs.is_empty() { core::ptr::null() } else { image.as_ptr() },
+                    ok.as_mut_ptr(),
+                    status.as_mut_ptr(),
+                )
+            })
+        })?;
+        Ok((ok.iter().map(|&v| v == 1).collect(), status))
+    }
+
     /// Assignments already synthesised (each `instance || witness`): up to `inflight` proofs share the GPU.
     pub fn prove_assignments<R: RngCore + CryptoRng>(
         res: &cache::Resident,

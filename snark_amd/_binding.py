@@ -58,6 +58,7 @@ SYMBOLS = [
     "ark355_setup_scalars", "ark355_setup", "ark355_verify_batch", "ark355_multi_pairing", "ark355_pairing_groups", "ark355_verify_each",
     "ark355_vk_process", "ark355_pvk_free", "ark355_pvk_info", "ark355_pvk_alpha_beta", "ark355_pvk_pairings",
     "ark355_verify_each_pvk", "ark355_verify_batch_pvk",
+    "ark355_points_check", "ark355_proofs_from_bytes", "ark355_verify_each_bytes",
     "ark355_ctx_set_policy", "ark355_ctx_get_policy", "ark355_sched_info", "ark355_sched_reset", "ark355_diag_streams", "ark355_diag_dispatch",
     "ark355_diag_mad_rate", "ark355_diag_clocks", "ark355_diag_msm_sort",
 ]
@@ -219,6 +220,9 @@ class Lib:
         d.ark355_pvk_alpha_beta.argtypes = [vp, vp]
         d.ark355_pvk_pairings.argtypes = [vp, vp, i32, vp, u64, vp, vp]
         d.ark355_verify_each_pvk.argtypes = [vp, vp, vp, vp, u64, vp]
+        d.ark355_points_check.argtypes = [vp, i32, i32, vp, u64, i32, vp]
+        d.ark355_proofs_from_bytes.argtypes = [vp, i32, vp, u64, i32, i32, vp, vp]
+        d.ark355_verify_each_bytes.argtypes = [vp, vp, vp, u64, i32, i32, vp, vp, vp]
         d.ark355_verify_batch_pvk.argtypes = [vp, vp, vp, vp, vp, u64, P(i32)]
         d.ark355_ctx_set_policy.argtypes = [vp, C.c_char_p, i64]
         d.ark355_ctx_get_policy.argtypes = [vp, C.c_char_p, P(i64)]
@@ -839,6 +843,38 @@ class Lib:
         ok = np.zeros(max(1, len(proofs)), dtype=np.uint8)
         self.check(ctx, self.dll.ark355_verify_each_pvk(ctx, pvk, arr, ib, len(proofs), ok.ctypes.data_as(C.c_void_p)))
         return [bool(v) for v in ok[:len(proofs)]]
+
+    # ---- proofs as wire bytes (include/ark355.h "proofs as wire bytes") ---------------------------------------------------
+    def points_check(self, ctx, curve, group, raw: bytes, n, method=1):
+        """ark355_points_check: curve + subgroup status of n raw affine images (method 0: [r]P, 1: the endomorphism tests).
+        Returns a list of int (0, 2 not on the curve, 4 not in the subgroup)."""
+        st = np.zeros(max(1, n), dtype=np.uint8)
+        rb, k = _buf(raw if n else None)
+        self.check(ctx, self.dll.ark355_points_check(ctx, curve, group, rb, n, int(method), st.ctypes.data_as(C.c_void_p)))
+        return [int(v) for v in st[:n]]
+
+    def proofs_from_bytes(self, ctx, curve, data: bytes, count, sizes, compressed=True, validate=1):
+        """ark355_proofs_from_bytes: `count` proofs (a || b || c each) decoded on the device.
+        Returns ([(a, b, c) raw images], [status]); the images of a proof with a non-zero status are all zero."""
+        arr = (ProofRaw * max(1, count))()
+        st = np.zeros(max(1, count), dtype=np.uint8)
+        db, k = _buf(data if count else None)
+        self.check(ctx, self.dll.ark355_proofs_from_bytes(ctx, curve, db, count, int(bool(compressed)), int(validate), arr,
+                                                          st.ctypes.data_as(C.c_void_p)))
+        out = [(bytes(arr[j].a)[:sizes["g1"]], bytes(arr[j].b)[:sizes["g2"]], bytes(arr[j].c)[:sizes["g1"]]) for j in range(count)]
+        return out, [int(v) for v in st[:count]]
+
+    def verify_each_bytes(self, ctx, pvk, data: bytes, count, public_inputs: bytes, compressed=True, validate=1, want_status=True):
+        """ark355_verify_each_bytes: `count` serialized proofs against a processed key.  Returns (list of bool, list of int
+        statuses or None with want_status=False)."""
+        ok = np.zeros(max(1, count), dtype=np.uint8)
+        st = np.zeros(max(1, count), dtype=np.uint8)
+        db, k = _buf(data if count else None)
+        ib, k1 = _buf(public_inputs if len(public_inputs) else None)
+        self.check(ctx, self.dll.ark355_verify_each_bytes(ctx, pvk, db, count, int(bool(compressed)), int(validate), ib,
+                                                          ok.ctypes.data_as(C.c_void_p),
+                                                          st.ctypes.data_as(C.c_void_p) if want_status else None))
+        return [bool(v) for v in ok[:count]], ([int(v) for v in st[:count]] if want_status else None)
 
     def verify_batch_pvk(self, ctx, pvk, proofs, public_inputs: bytes, rho=None) -> bool:
         """ark355_verify_batch_pvk: verify_batch against a processed key."""

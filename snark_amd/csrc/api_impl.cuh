@@ -778,6 +778,18 @@ struct Api {
                               const uint8_t* inputs, uint64_t count, uint8_t* ok) {
     Verify<Curve>{ctx, g.pair, g.c}.verify_each_pvk(pvk, proofs, inputs, count, ok);
   }
+  static void verify_each_bytes(ark355_ctx* ctx, GenericScratch& g, const PvkDev& pvk, const uint8_t* proofs, uint64_t count,
+                                bool compressed, int validate, const uint8_t* inputs, uint8_t* ok, uint8_t* status) {
+    Verify<Curve>{ctx, g.pair, g.c}.verify_each_bytes(pvk, proofs, count, compressed, validate, inputs, ok, status);
+  }
+  static void proofs_from_bytes(ark355_ctx* ctx, GenericScratch& g, const uint8_t* in, uint64_t count, bool compressed, int validate,
+                                ark355_proof_raw* out, uint8_t* status) {
+    Verify<Curve>{ctx, g.pair, g.c}.proofs_from_bytes(in, count, compressed, validate, out, status);
+  }
+  static void points_check(ark355_ctx* ctx, GenericScratch& g, int group, const uint8_t* raw, uint64_t n, int method,
+                           uint8_t* status) {
+    Verify<Curve>{ctx, g.pair, g.c}.points_check(group, raw, n, method, status);
+  }
   static bool verify_batch_pvk(ark355_ctx* ctx, GenericScratch& g, const PvkDev& pvk, const ark355_proof_raw* proofs,
                                const uint8_t* inputs, const uint8_t* rho, uint64_t count) {
     return Verify<Curve>{ctx, g.pair, g.c}.verify_batch_pvk(

@@ -879,6 +879,50 @@ int32_t ark355_verify_each_pvk(ark355_ctx* ctx, const ark355_pvk* pvk, const ark
   });
 }
 
+int32_t ark355_verify_each_bytes(ark355_ctx* ctx, const ark355_pvk* pvk, const uint8_t* proofs, uint64_t count, int32_t compressed,
+                                 int32_t validate, const uint8_t* public_inputs, uint8_t* ok, uint8_t* status) {
+  if (!ctx) return ARK355_EINVAL;
+  return guarded(ctx, [&] {
+    ARK_REQUIRE(pvk && pvk->d, ARK355_EINVAL, "ark355_verify_each_bytes: pvk is NULL");
+    ARK_REQUIRE(count == 0 || proofs, ARK355_EINVAL, "ark355_verify_each_bytes: proofs is NULL");
+    ARK_REQUIRE(count == 0 || ok, ARK355_EINVAL, "ark355_verify_each_bytes: ok is NULL");
+    ARK_REQUIRE(validate >= 0 && validate <= 2, ARK355_EINVAL, "ark355_verify_each_bytes: unknown validate");
+    ARK_REQUIRE(count <= 0xFFFFFFFFull / 3, ARK355_EINVAL, "ark355_verify_each_bytes: count: 3 * count must stay below 2^32");
+    if (count) memset(ok, 0, count);
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(pvk->d->curve,
+                   A::verify_each_bytes(ctx, ex.generic, *pvk->d, proofs, count, compressed != 0, validate, public_inputs, ok, status));
+  });
+}
+
+int32_t ark355_proofs_from_bytes(ark355_ctx* ctx, int32_t curve, const uint8_t* in, uint64_t count, int32_t compressed,
+                                 int32_t validate, ark355_proof_raw* out, uint8_t* status) {
+  if (!ctx) return ARK355_EINVAL;
+  return guarded(ctx, [&] {
+    ARK_REQUIRE(count == 0 || in, ARK355_EINVAL, "ark355_proofs_from_bytes: in is NULL");
+    ARK_REQUIRE(count == 0 || out, ARK355_EINVAL, "ark355_proofs_from_bytes: out is NULL");
+    ARK_REQUIRE(count == 0 || status, ARK355_EINVAL, "ark355_proofs_from_bytes: status is NULL");
+    ARK_REQUIRE(validate >= 0 && validate <= 2, ARK355_EINVAL, "ark355_proofs_from_bytes: unknown validate");
+    ARK_REQUIRE(count <= 0xFFFFFFFFull / 3, ARK355_EINVAL, "ark355_proofs_from_bytes: count: 3 * count must stay below 2^32");
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(curve, A::proofs_from_bytes(ctx, ex.generic, in, count, compressed != 0, validate, out, status));
+  });
+}
+
+int32_t ark355_points_check(ark355_ctx* ctx, int32_t curve, int32_t group, const uint8_t* raw, uint64_t n, int32_t method,
+                            uint8_t* status) {
+  if (!ctx) return ARK355_EINVAL;
+  return guarded(ctx, [&] {
+    ARK_REQUIRE(group == 1 || group == 2, ARK355_EINVAL, "ark355_points_check: group must be 1 or 2");
+    ARK_REQUIRE(method == 0 || method == 1, ARK355_EINVAL, "ark355_points_check: unknown method");
+    ARK_REQUIRE(n == 0 || raw, ARK355_EINVAL, "ark355_points_check: raw is NULL");
+    ARK_REQUIRE(n == 0 || status, ARK355_EINVAL, "ark355_points_check: status is NULL");
+    ARK_REQUIRE(n <= 0xFFFFFFFFull, ARK355_EINVAL, "ark355_points_check: n must stay below 2^32");
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(curve, A::points_check(ctx, ex.generic, group, raw, n, method, status));
+  });
+}
+
 int32_t ark355_verify_batch_pvk(ark355_ctx* ctx, const ark355_pvk* pvk, const ark355_proof_raw* proofs, const uint8_t* public_inputs,
                                 const uint8_t* rho, uint64_t count, int32_t* ok) {
   if (!ctx || !pvk || !pvk->d || !proofs || !ok || (pvk->d->ell > 1 && !public_inputs)) return ARK355_EINVAL;

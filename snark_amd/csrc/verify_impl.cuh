@@ -18,6 +18,7 @@ struct PairingScratch {
   DevBuf pmill, pfe, pgt, pverd;                  // per-group pairings: Miller values of a chunk, program + constants, GT values, verdicts
   DevBuf pabc, pprod, pflags;                     // ark355_verify_each: gamma_abc, the terms of the prepared inputs, per-point flags
   DevBuf pkmill;                                  // the *_pvk entries: Miller values of a chunk, three members per proof
+  DevBuf pbytes, ppst, pstatus;                   // the *_bytes entries: the wire bytes, the status of every point, of every proof
 };
 
 // ark355_pvk: what SNARK::process_vk computes once per key.  Immutable after ark355_vk_process; the device buffers belong to
@@ -648,6 +649,62 @@ struct Verify {
     trace("pvk_pairings", dev, n, t1 - t0, 0.0, now_ms() - t1, 0.0);
   }
 
+  // The device route of ark355_verify_each_pvk and ark355_verify_each_bytes from the staged proofs on (s.pg1 = A_j, C_j with
+  // room for 4 count points, s.pg2 = B_j): curve flags, prepared inputs, the pairs against gamma and delta, the chunked Miller
+  // stage, one final exponentiation per proof.  d_pst: the per-point statuses of proof_decode_kernel (NULL: the proofs came as
+  // points); a proof that failed to decode is marked bad like one off its curve, and s.pstatus receives the per-proof statuses.
+  void each_pvk_staged(const PvkDev& pvk, const uint8_t* inputs, uint64_t count, const uint8_t* d_pst, uint8_t* ok) {
+    hipStream_t st = ctx->stream;
+    const uint32_t m = (uint32_t)(pvk.ell - 1);
+    const Gt target = pvk_target(pvk);
+    s.pflags.ensure(4 * count);
+    G1* d_ac = s.pg1.as<G1>();
+    G2* d_b = s.pg2.as<G2>();
+    G1* d_nacc = d_ac + 2 * count;
+    G1* d_negc = d_ac + 3 * count;
+    uint8_t* d_flags = s.pflags.as<uint8_t>();
+    const G1* d_abc = pvk.abc.as<G1>();
+    ARK_LAUNCH((on_curve_flags_kernel<Curve>), dim3((uint32_t)((3 * count + 127) / 128)), dim3(128), 0, st, (const G1*)d_ac,
+               2 * count, (const G2*)d_b, count, d_flags);
+    ARK_CHECK_LAUNCH();
+    if (d_pst) {
+      s.pstatus.ensure(count);
+      ARK_LAUNCH((proof_status_kernel<Curve>), dim3((uint32_t)((count + 127) / 128)), dim3(128), 0, st, d_pst, count, s.pstatus.as<uint8_t>(),
+                 d_flags);
+      ARK_CHECK_LAUNCH();
+    }
+    if (m) {
+      s.psc.ensure(count * m * sizeof(Fr));
+      s.pprod.ensure(count * m * sizeof(XYZZ<Fq>));
+      ARK_CHECK_HIP(hipMemcpyAsync(s.psc.p, inputs, count * m * sizeof(Fr), hipMemcpyHostToDevice, st));
+      ARK_LAUNCH((prepared_input_terms_kernel<Curve>), dim3((uint32_t)((count * m + 127) / 128)), dim3(128), 0, st, d_abc,
+                 (const Fr*)s.psc.as<Fr>(), count, m, s.pprod.as<XYZZ<Fq>>());
+      ARK_CHECK_LAUNCH();
+    }
+    ARK_LAUNCH((verify_each_key_pairs_kernel<Curve>), dim3((uint32_t)((count + 127) / 128)), dim3(128), 0, st, d_abc,
+               (const XYZZ<Fq>*)s.pprod.as<XYZZ<Fq>>(), m, (const G1*)d_ac, (const uint8_t*)d_flags, count, d_nacc, d_negc,
+               d_flags + 3 * count);
+    ARK_CHECK_LAUNCH();
+    const FeDev fe = fe_upload(target);
+    const typename PD::Consts k = dev_consts();
+    s.pverd.ensure(count);
+    const uint32_t* lg = pvk_lines(pvk, 1);
+    const uint32_t* ld = pvk_lines(pvk, 2);
+    miller_chunks<true>(d_ac, d_b, count, PVK_EACH_CHUNK, [&](uint64_t off, uint32_t n, uint32_t stride) {
+      // the group layout of the chunk: proof j of it at 3 j .. 3 j + 2 of a row of 3 * stride
+      const uint32_t row = 3 * stride, blocks = (n + PAIR_LANES - 1) / PAIR_LANES;
+      s.pkmill.ensure((size_t)PD::W12 * row * sizeof(uint32_t));
+      ARK_LAUNCH((miller_spread_kernel<Curve>), dim3((n + 255) / 256), dim3(256), 0, st, (const uint32_t*)s.pmill.as<uint32_t>(),
+                 stride, n, row, 3u, s.pkmill.as<uint32_t>());
+      ARK_CHECK_LAUNCH();
+      ARK_LAUNCH((pairing_accumulate_key_kernel<Curve>), dim3(2 * blocks), dim3(PAIR_LANES), 0, st, (const G1*)d_nacc + off, n, lg,
+                 (const G1*)d_negc + off, n, ld, blocks, row, 3u, 1u, 2u, k, s.pkmill.as<uint32_t>());
+      ARK_CHECK_LAUNCH();
+      fe_launch(fe, s.pkmill.as<uint32_t>(), row, off, n, 3, d_flags + 3 * count, false);
+    });
+    fe_download(count, nullptr, ok);
+  }
+
   // SNARK::verify_with_processed_vk for every proof on its own: verify_each without the per-key work.  Device route: pass A
   // and the per-pair pass B over the count pairs (A_j, B_j) only; the 2 count pairs (-acc_j, gamma), (-C_j, delta) go through
   // pairing_accumulate_key_kernel against the handle's lines; one final exponentiation per proof over its three Miller values.
@@ -657,59 +714,132 @@ struct Verify {
     if (count == 0) return;
     ARK_REQUIRE(ell == 1 || inputs, ARK355_EINVAL, "public_inputs is NULL");
     ARK_REQUIRE(count <= 0xFFFFFFFFull / 3, ARK355_EINVAL, "3 * count must stay below 2^32");
-    const uint32_t m = (uint32_t)(ell - 1);
-    const Gt target = pvk_target(pvk);
     const double t0 = now_ms();
     const bool dev = on_device(ctx->policy.pairing_each_min, count);
     if (dev) {
-      hipStream_t st = ctx->stream;
       // behind the staged proofs: s.pg1 the -acc_j and the -C_j
       const StagedProofs staged = stage_proofs(proofs, count, 4 * count, count);
-      s.pflags.ensure(4 * count);
-      G1* d_ac = s.pg1.as<G1>();
-      G2* d_b = s.pg2.as<G2>();
-      G1* d_nacc = d_ac + 2 * count;
-      G1* d_negc = d_ac + 3 * count;
-      uint8_t* d_flags = s.pflags.as<uint8_t>();
-      const G1* d_abc = pvk.abc.as<G1>();
-      ARK_LAUNCH((on_curve_flags_kernel<Curve>), dim3((uint32_t)((3 * count + 127) / 128)), dim3(128), 0, st, (const G1*)d_ac,
-                 2 * count, (const G2*)d_b, count, d_flags);
-      ARK_CHECK_LAUNCH();
-      if (m) {
-        s.psc.ensure(count * m * sizeof(Fr));
-        s.pprod.ensure(count * m * sizeof(XYZZ<Fq>));
-        ARK_CHECK_HIP(hipMemcpyAsync(s.psc.p, inputs, count * m * sizeof(Fr), hipMemcpyHostToDevice, st));
-        ARK_LAUNCH((prepared_input_terms_kernel<Curve>), dim3((uint32_t)((count * m + 127) / 128)), dim3(128), 0, st, d_abc,
-                   (const Fr*)s.psc.as<Fr>(), count, m, s.pprod.as<XYZZ<Fq>>());
-        ARK_CHECK_LAUNCH();
-      }
-      ARK_LAUNCH((verify_each_key_pairs_kernel<Curve>), dim3((uint32_t)((count + 127) / 128)), dim3(128), 0, st, d_abc,
-                 (const XYZZ<Fq>*)s.pprod.as<XYZZ<Fq>>(), m, (const G1*)d_ac, (const uint8_t*)d_flags, count, d_nacc, d_negc,
-                 d_flags + 3 * count);
-      ARK_CHECK_LAUNCH();
-      const FeDev fe = fe_upload(target);
-      const typename PD::Consts k = dev_consts();
-      s.pverd.ensure(count);
-      const uint32_t* lg = pvk_lines(pvk, 1);
-      const uint32_t* ld = pvk_lines(pvk, 2);
-      miller_chunks<true>(d_ac, d_b, count, PVK_EACH_CHUNK, [&](uint64_t off, uint32_t n, uint32_t stride) {
-        // the group layout of the chunk: proof j of it at 3 j .. 3 j + 2 of a row of 3 * stride
-        const uint32_t row = 3 * stride, blocks = (n + PAIR_LANES - 1) / PAIR_LANES;
-        s.pkmill.ensure((size_t)PD::W12 * row * sizeof(uint32_t));
-        ARK_LAUNCH((miller_spread_kernel<Curve>), dim3((n + 255) / 256), dim3(256), 0, st, (const uint32_t*)s.pmill.as<uint32_t>(),
-                   stride, n, row, 3u, s.pkmill.as<uint32_t>());
-        ARK_CHECK_LAUNCH();
-        ARK_LAUNCH((pairing_accumulate_key_kernel<Curve>), dim3(2 * blocks), dim3(PAIR_LANES), 0, st, (const G1*)d_nacc + off, n, lg,
-                   (const G1*)d_negc + off, n, ld, blocks, row, 3u, 1u, 2u, k, s.pkmill.as<uint32_t>());
-        ARK_CHECK_LAUNCH();
-        fe_launch(fe, s.pkmill.as<uint32_t>(), row, off, n, 3, d_flags + 3 * count, false);
-      });
-      fe_download(count, nullptr, ok);
+      each_pvk_staged(pvk, inputs, count, nullptr, ok);
     } else {
-      each_host(reinterpret_cast<const G1*>(pvk.abc_host.data()), m, pvk_point(pvk, 1), pvk_point(pvk, 2), target, proofs, inputs,
-                count, ok);
+      each_host(reinterpret_cast<const G1*>(pvk.abc_host.data()), (uint32_t)(ell - 1), pvk_point(pvk, 1), pvk_point(pvk, 2),
+                pvk_target(pvk), proofs, inputs, count, ok);
     }
     trace("verify_each_pvk", dev, 3 * count, 0.0, 0.0, now_ms() - t0, 0.0);
+  }
+
+  // ---- proofs as wire bytes (Proof: CanonicalDeserialize, snark/src/lib.rs:32) ---------------------------------------------
+  // The arguments of the three entries are checked once, in capi.hip (ARK355_EINVAL names the argument).
+  static size_t proof_size(bool compressed) { return 2 * W::g1_size(compressed) + W::g2_size(compressed); }
+  // upload + proof_decode_kernel: s.pg1 / s.pg2 staged as stage_proofs leaves them (room for cap1 G1 points), s.ppst the
+  // per-point statuses.  Nothing is synchronised: `in` must stay alive until the caller has.
+  void decode_proofs_dev(const uint8_t* in, uint64_t count, bool compressed, int validate, uint64_t cap1) {
+    hipStream_t st = ctx->stream;
+    s.pbytes.ensure(count * proof_size(compressed));
+    s.pg1.ensure(cap1 * sizeof(G1));
+    s.pg2.ensure(count * sizeof(G2));
+    s.ppst.ensure(3 * count);
+    ARK_CHECK_HIP(hipMemcpyAsync(s.pbytes.p, in, count * proof_size(compressed), hipMemcpyHostToDevice, st));
+    const uint32_t blocks1 = (uint32_t)((2 * count + 127) / 128), blocks2 = (uint32_t)((count + 127) / 128);
+    ARK_LAUNCH((proof_decode_kernel<Curve>), dim3(blocks1 + blocks2), dim3(128), 0, st, (const uint8_t*)s.pbytes.as<uint8_t>(), count,
+               compressed ? 1 : 0, validate, blocks1, s.pg1.as<G1>(), s.pg2.as<G2>(), s.ppst.as<uint8_t>());
+    ARK_CHECK_LAUNCH();
+  }
+  // one proof on the host, the same verdict as the kernels': (k << 4) | status of the first failing point, out zero then
+  static uint8_t decode_proof_host(const uint8_t* in, bool compressed, int validate, ark355_proof_raw* out) {
+    const size_t s1 = W::g1_size(compressed), s2 = W::g2_size(compressed);
+    G1 a = G1::inf(), c = G1::inf();
+    G2 b = G2::inf();
+    uint8_t st = 0;                                    // the first failing point decides: nothing behind it is decoded
+    if (const int sa = W::g1_decode(in, compressed, validate, &a)) st = (uint8_t)(0x10 | sa);
+    else if (const int sb = W::g2_decode(in + s1, compressed, validate, &b)) st = (uint8_t)(0x20 | sb);
+    else if (const int sc = W::g1_decode(in + s1 + s2, compressed, validate, &c)) st = (uint8_t)(0x30 | sc);
+    memset(out, 0, sizeof(*out));
+    if (st == 0) {
+      memcpy(out->a, &a, sizeof(a));
+      memcpy(out->b, &b, sizeof(b));
+      memcpy(out->c, &c, sizeof(c));
+    }
+    return st;
+  }
+
+  // `count` proofs decoded on the device: the raw images and one status per proof; a bad proof is no error of the call
+  void proofs_from_bytes(const uint8_t* in, uint64_t count, bool compressed, int validate, ark355_proof_raw* out, uint8_t* status) {
+    if (count == 0) return;
+    hipStream_t st = ctx->stream;
+    decode_proofs_dev(in, count, compressed, validate, 2 * count);
+    s.pstatus.ensure(count);
+    ARK_LAUNCH((proof_status_kernel<Curve>), dim3((uint32_t)((count + 127) / 128)), dim3(128), 0, st, (const uint8_t*)s.ppst.as<uint8_t>(),
+               count, s.pstatus.as<uint8_t>(), (uint8_t*)nullptr);
+    ARK_CHECK_LAUNCH();
+    std::vector<G1> ac(2 * count);
+    std::vector<G2> bs(count);
+    ARK_CHECK_HIP(hipMemcpyAsync(ac.data(), s.pg1.p, 2 * count * sizeof(G1), hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipMemcpyAsync(bs.data(), s.pg2.p, count * sizeof(G2), hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipMemcpyAsync(status, s.pstatus.p, count, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+    memset(out, 0, count * sizeof(*out));
+    for (uint64_t j = 0; j < count; j++) {
+      if (status[j]) continue;
+      memcpy(out[j].a, &ac[j], sizeof(G1));
+      memcpy(out[j].b, &bs[j], sizeof(G2));
+      memcpy(out[j].c, &ac[count + j], sizeof(G1));
+    }
+  }
+
+  // Proof::deserialize_with_mode + verify_with_processed_vk per proof.  Device route: the bytes are decoded where the
+  // verifier reads its points (proof_decode_kernel), then the stages of ark355_verify_each_pvk; host route: decode_proof_host
+  // and each_host on host threads.  Both give the same ok and status.
+  void verify_each_bytes(const PvkDev& pvk, const uint8_t* in, uint64_t count, bool compressed, int validate, const uint8_t* inputs,
+                         uint8_t* ok, uint8_t* status) {
+    pvk_usable(pvk);
+    if (count == 0) return;
+    ARK_REQUIRE(pvk.ell == 1 || inputs, ARK355_EINVAL, "public_inputs is NULL");
+    const double t0 = now_ms();
+    double t1 = t0;
+    const bool dev = on_device(ctx->policy.pairing_each_min, count);
+    if (dev) {
+      decode_proofs_dev(in, count, compressed, validate, 4 * count);
+      if (ctx->policy.trace_host) {                       // the decode stage alone, for the trace only
+        ARK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        t1 = now_ms();
+      }
+      each_pvk_staged(pvk, inputs, count, s.ppst.as<uint8_t>(), ok);
+      if (status) {
+        ARK_CHECK_HIP(hipMemcpyAsync(status, s.pstatus.p, count, hipMemcpyDeviceToHost, ctx->stream));
+        ARK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+      }
+    } else {
+      std::vector<ark355_proof_raw> proofs(count);
+      std::vector<uint8_t> stv(count);
+      const size_t sp = proof_size(compressed);
+      host_each(count, [&](uint64_t j) { stv[j] = decode_proof_host(in + j * sp, compressed, validate, &proofs[j]); });
+      t1 = now_ms();
+      each_host(reinterpret_cast<const G1*>(pvk.abc_host.data()), (uint32_t)(pvk.ell - 1), pvk_point(pvk, 1), pvk_point(pvk, 2),
+                pvk_target(pvk), proofs.data(), inputs, count, ok);
+      for (uint64_t j = 0; j < count; j++)
+        if (stv[j]) ok[j] = 0;
+      if (status) memcpy(status, stv.data(), count);
+    }
+    trace("verify_each_bytes", dev, 3 * count, t1 - t0, 0.0, now_ms() - t1, 0.0);
+  }
+
+  // is_on_curve + is_in_correct_subgroup_assuming_on_curve of n raw images, always on the device (the two subgroup tests are
+  // compared where they run)
+  void points_check(int group, const uint8_t* raw, uint64_t n, int method, uint8_t* status) {
+    if (n == 0) return;
+    hipStream_t st = ctx->stream;
+    const size_t bytes = n * (group == 1 ? sizeof(G1) : sizeof(G2));
+    s.pbytes.ensure(bytes);
+    s.ppst.ensure(n);
+    ARK_CHECK_HIP(hipMemcpyAsync(s.pbytes.p, raw, bytes, hipMemcpyHostToDevice, st));
+    const dim3 grid((uint32_t)((n + 127) / 128));
+    if (group == 1)
+      ARK_LAUNCH((points_check_kernel<Curve, 1>), grid, dim3(128), 0, st, (const void*)s.pbytes.p, n, method, s.ppst.as<uint8_t>());
+    else
+      ARK_LAUNCH((points_check_kernel<Curve, 2>), grid, dim3(128), 0, st, (const void*)s.pbytes.p, n, method, s.ppst.as<uint8_t>());
+    ARK_CHECK_LAUNCH();
+    ARK_CHECK_HIP(hipMemcpyAsync(status, s.ppst.p, n, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
   }
 
   // ark355_verify_batch over the handle's copies of the key (unchecked, as ark355_verify_batch leaves the key unchecked)

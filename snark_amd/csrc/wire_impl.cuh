@@ -13,6 +13,7 @@
 //              bit7 "y is negative" (y > -y), bit6 infinity.
 // "y > -y" compares canonical integers; in Fq2 the c1 components decide first.
 #pragma once
+#include <type_traits>
 #include "common.h"
 #include "curve.cuh"
 
@@ -35,12 +36,84 @@ struct Wire {
 
   // [r] P == O: membership in the prime-order subgroup (`is_in_correct_subgroup_assuming_on_curve` upstream).  Points of
   // small order pair to 1, so a proof carrying one would still verify: many encodings per proof for callers that key
-  // on proof bytes.
+  // on proof bytes.  The slow reference of in_subgroup_fast below, reachable through ark355_points_check(method = 0).
   template <class F>
   ARK_HD static bool in_subgroup(const Affine<F>& p) {
     uint32_t r[Fr::N];
     for (int i = 0; i < Fr::N; i++) r[i] = Fr::Params::mod(i);
     return xyzz_mul_scalar(XYZZ<F>::from_affine(p), r, Fr::N).is_inf();
+  }
+  // ---- the same membership through an endomorphism (what ark-bls12-381 / ark-bn254 do upstream) ------------------------
+  // Each test is EQUIVALENT to [r]P == O for P on its curve, P != O (the decoders return before infinity gets here):
+  //   BLS12-381 G1: phi(P) == -[x^2]P, phi(x, y) = (beta x, y).  phi^2 + phi + 1 = 0 on all of E, so acceptance gives
+  //                 (x^4 - x^2 + 1) P = O, and x^4 - x^2 + 1 = r; on the subgroup phi acts as -x^2 (gen_params.py picks beta so).
+  //   BLS12-381 G2: psi(P) == [x]P = -[|x|]P.  psi^2 - t psi + q = 0 with t = x + 1, and gcd(x^2 - t x + q, #E'(F_q2)) = r.
+  //   BN254 G2:     psi(P) == [6x^2]P.  gcd((6x^2)^2 - t 6x^2 + q, r (2q - r)) = r with t = 6x^2 + 1.
+  // psi(x, y) = (conj(x) psi_x, conj(y) psi_y) (curve_params.h).  The multipliers are constants, so the branch of the ladder
+  // is the same in every lane.  The ladder is xyzz_mul_scalar over the affine point, exactly what [r]P runs, with a 64- to
+  // 128-bit multiplier; the comparison with the image is an out-of-line function of its own, so the image and its constants
+  // hold stack only after the ladder's frames are gone and the kernels' frames are those of the [r]P build.
+  static constexpr uint64_t BLS_X = 0xd201000000010000ull;                                            // |x|: 64 bits, weight 6
+  static constexpr uint64_t BLS_X2_HI = 0xac45a4010001a402ull, BLS_X2_LO = 0x0000000100000000ull;     // x^2: 128 bits, weight 17
+  static constexpr uint64_t BN_6X2_HI = 0x6f4d8248eeb859fbull, BN_6X2_LO = 0xf83e9682e87cfd46ull;     // 6 x^2: 127 bits, weight 70
+
+  // [hi * 2^64 + lo] p
+  template <class F>
+  ARK_HD static XYZZ<F> mul_const(const Affine<F>& p, uint64_t hi, uint64_t lo) {
+    const uint32_t k[4] = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+    return xyzz_mul_scalar(XYZZ<F>::from_affine(p), k, 4);
+  }
+  // projective r against the affine image (x, y), no inversion; r at infinity is a mismatch (the image is finite)
+  template <class F>
+  ARK_HD static bool same_point(const XYZZ<F>& r, const F& x, const F& y) {
+    if (r.is_inf()) return false;
+    return r.x == F::mul_ni(x, r.zz) && r.y == F::mul_ni(y, r.zzz);
+  }
+  // m == -phi(p), phi(x, y) = (beta x, y)
+  ARK_HD_NOINLINE static bool is_neg_phi(const XYZZ<Fq>& m, const Affine<Fq>& p) {
+    if constexpr (BLS) {
+      Fq beta;
+      for (int i = 0; i < Fq::N; i++) beta.l[i] = K::endo_beta(i);
+      return same_point(m, Fq::mul_ni(beta, p.x), Fq::neg(p.y));
+    } else {
+      return true;
+    }
+  }
+  // m == psi(p) (BN254) / m == -psi(p) (BLS12-381: x < 0)
+  ARK_HD_NOINLINE static bool is_psi(const XYZZ<Fq2>& m, const Affine<Fq2>& p) {
+    Fq2 kx, ky;
+    for (int i = 0; i < Fq::N; i++) {
+      kx.c0.l[i] = K::psi_x_c0(i);
+      kx.c1.l[i] = K::psi_x_c1(i);
+      ky.c0.l[i] = K::psi_y_c0(i);
+      ky.c1.l[i] = K::psi_y_c1(i);
+    }
+    const Fq2 ix = Fq2::mul_ni(Fq2{p.x.c0, Fq::neg(p.x.c1)}, kx), iy = Fq2::mul_ni(Fq2{p.y.c0, Fq::neg(p.y.c1)}, ky);
+    return same_point(m, ix, BLS ? Fq2::neg(iy) : iy);
+  }
+  ARK_HD static bool in_subgroup_fast(const Affine<Fq>& p) {
+    if constexpr (BLS) return is_neg_phi(mul_const(p, BLS_X2_HI, BLS_X2_LO), p);
+    else return true;                                         // cofactor 1
+  }
+  ARK_HD static bool in_subgroup_fast(const Affine<Fq2>& p) {
+    return is_psi(BLS ? mul_const(p, 0, BLS_X) : mul_const(p, BN_6X2_HI, BN_6X2_LO), p);
+  }
+  // the checks of ark355_points_check for one raw image
+  template <class F>
+  ARK_HD static int point_status(const Affine<F>& p, int method) {
+    if (p.is_inf()) return WIRE_OK;
+    if (!(F::sqr_ni(p.y) == curve_rhs(p.x))) return WIRE_NOT_ON_CURVE;
+    if (std::is_same<F, Fq>::value && !G1_HAS_COFACTOR) return WIRE_OK;      // cofactor 1
+    return (method == 0 ? in_subgroup(p) : in_subgroup_fast(p)) ? WIRE_OK : WIRE_NOT_IN_SUBGROUP;
+  }
+  // ARK_WIRE_SUBGROUP_RP: a measuring build whose decoders keep the [r]P test (tools/pairing_bench.py --from-bytes)
+  template <class F>
+  ARK_HD static bool decoder_in_subgroup(const Affine<F>& p) {
+#ifdef ARK_WIRE_SUBGROUP_RP
+    return in_subgroup(p);
+#else
+    return in_subgroup_fast(p);
+#endif
   }
   // every payload bit of an encoding whose infinity flag is set must be zero (flag bits masked)
   ARK_HD static bool payload_is_zero(const uint8_t* in, size_t size) {
@@ -232,7 +305,7 @@ struct Wire {
       if (validate && !(Fq::sqr_ni(y) == curve_rhs(x))) return WIRE_NOT_ON_CURVE;
     }
     *out = Affine<Fq>{x, y};
-    if (G1_HAS_COFACTOR && validate == WIRE_VALIDATE_FULL && !in_subgroup(*out)) return WIRE_NOT_IN_SUBGROUP;
+    if (G1_HAS_COFACTOR && validate == WIRE_VALIDATE_FULL && !decoder_in_subgroup(*out)) return WIRE_NOT_IN_SUBGROUP;
     return WIRE_OK;
   }
 
@@ -273,7 +346,7 @@ struct Wire {
       if (validate && !(Fq2::sqr_ni(y) == curve_rhs(x))) return WIRE_NOT_ON_CURVE;
     }
     *out = Affine<Fq2>{x, y};
-    if (validate == WIRE_VALIDATE_FULL && !in_subgroup(*out)) return WIRE_NOT_IN_SUBGROUP;
+    if (validate == WIRE_VALIDATE_FULL && !decoder_in_subgroup(*out)) return WIRE_NOT_IN_SUBGROUP;
     return WIRE_OK;
   }
 
@@ -348,6 +421,62 @@ wire_decode_kernel(const uint8_t* __restrict__ in, uint64_t n, int compressed, i
       cur = prev;
     }
   }
+}
+
+// `count` proofs (a || b || c each) straight into the staged layout of the per-proof verifier, one lane per point:
+// g1[j] = A_j, g1[count + j] = C_j, g2[j] = B_j, and pst in the same order (A_0.., C_0.., then B_0..) the wire status of each
+// point.  The first blocks1 = ceil(2 count / 128) workgroups decode the G1 points, the rest the G2 points, so no wave mixes
+// the two fields.  A point that fails is stored as infinity: the stages behind never see an unchecked coordinate.
+template <class Curve>
+__global__ void __launch_bounds__(128)
+proof_decode_kernel(const uint8_t* __restrict__ in, uint64_t count, int compressed, int validate, uint32_t blocks1,
+                    Affine<typename Curve::Fq>* __restrict__ g1, Affine<typename Curve::Fq2>* __restrict__ g2,
+                    uint8_t* __restrict__ pst) {
+  using W = Wire<Curve>;
+  const bool comp = compressed != 0;
+  const size_t s1 = W::g1_size(comp), s2 = W::g2_size(comp), sp = 2 * s1 + s2;
+  if (blockIdx.x < blocks1) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * count) return;
+    const uint8_t* src = i < count ? in + i * sp : in + (i - count) * sp + s1 + s2;
+    Affine<typename Curve::Fq> p = Affine<typename Curve::Fq>::inf();
+    const int st = W::g1_decode(src, comp, validate, &p);
+    g1[i] = st == WIRE_OK ? p : Affine<typename Curve::Fq>::inf();
+    pst[i] = (uint8_t)st;
+  } else {
+    const uint64_t j = (uint64_t)(blockIdx.x - blocks1) * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    Affine<typename Curve::Fq2> p = Affine<typename Curve::Fq2>::inf();
+    const int st = W::g2_decode(in + j * sp + s1, comp, validate, &p);
+    g2[j] = st == WIRE_OK ? p : Affine<typename Curve::Fq2>::inf();
+    pst[2 * count + j] = (uint8_t)st;
+  }
+}
+
+// one lane per proof: status[j] = 0 or (k << 4) | wire status of the first failing point in the order a (k = 1), b (2), c (3),
+// from the per-point statuses proof_decode_kernel left; bad (may be NULL): bad[j] |= 1 where the proof failed to decode
+template <class Curve>
+__global__ void __launch_bounds__(128)
+proof_status_kernel(const uint8_t* __restrict__ pst, uint64_t count, uint8_t* __restrict__ status, uint8_t* __restrict__ bad) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  const uint8_t a = pst[j], c = pst[count + j], b = pst[2 * count + j];
+  const uint8_t st = a ? (uint8_t)(0x10 | a) : b ? (uint8_t)(0x20 | b) : c ? (uint8_t)(0x30 | c) : (uint8_t)0;
+  status[j] = st;
+  if (bad && st) bad[j] |= 1;
+}
+
+// ark-ec is_on_curve + is_in_correct_subgroup_assuming_on_curve of n raw affine images, one lane per point; method 0 is
+// [r]P, 1 the endomorphism tests -- both live, so that they can be compared where they run
+template <class Curve, int GROUP>
+__global__ void __launch_bounds__(128)
+points_check_kernel(const void* __restrict__ raw, uint64_t n, int method, uint8_t* __restrict__ status) {
+  using W = Wire<Curve>;
+  using F = std::conditional_t<GROUP == 1, typename Curve::Fq, typename Curve::Fq2>;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Affine<F> p = reinterpret_cast<const Affine<F>*>(raw)[i];
+  status[i] = (uint8_t)W::point_status(p, method);
 }
 
 template <class Curve, int GROUP>

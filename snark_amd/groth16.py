@@ -432,6 +432,42 @@ class Groth16:
             out[j] = ok
         return out
 
+    def verify_each_bytes(self, vk: VerifyingKey, public_inputs, proof_bytes, compressed=True, validate=1):
+        """`ark355_verify_each_bytes`: `Proof::deserialize_with_mode` + `SNARK::verify_with_processed_vk` for every serialized
+        proof of ONE verifying key -> (oks, statuses).  `proof_bytes` is a list of encoded proofs (a || b || c each) or one block
+        of them; `validate` is 1 (full: curve and subgroup, the default), 2 (curve only) or 0.  A bad or malleated encoding
+        costs its own proof a False and a non-zero status, (k << 4) | wire status of the first failing point (k = 1 a, 2 b,
+        3 c); it never fails the call.  A wrong input length gives False (status 0) for that proof.  Uses the handle
+        `process_vk` attached and processes the key first if none is."""
+        cv = self.curve
+        comp = bool(compressed)
+        size = 2 * self.lib.point_size(cv.curve_id, 1, comp) + self.lib.point_size(cv.curve_id, 2, comp)
+        if isinstance(proof_bytes, (bytes, bytearray, memoryview)):
+            block = bytes(proof_bytes)
+            if len(block) % size:
+                raise ValueError("proof_bytes is not a whole number of %d-byte proofs" % size)
+            blobs = [block[k:k + size] for k in range(0, len(block), size)]
+        else:
+            blobs = [bytes(b) for b in proof_bytes]
+            if any(len(b) != size for b in blobs):
+                raise ValueError("every encoded proof has %d bytes in this form" % size)
+        if len(public_inputs) != len(blobs):
+            raise ValueError("verify_each_bytes needs one list of public inputs per proof")
+        ell = len(vk.gamma_abc_g1) // self.sizes["g1"]
+        good = [j for j, x in enumerate(public_inputs) if len(x) + 1 == ell]
+        oks, statuses = [False] * len(blobs), [0] * len(blobs)
+        if not good:
+            return oks, statuses
+        h = self._cached(self.process_vk(vk), "_ark355_pvk")
+        xs = b"".join(cv.fr_mont(v) for j in good for v in public_inputs[j])
+        try:
+            got, st = self.lib.verify_each_bytes(self.ctx, h, b"".join(blobs[j] for j in good), len(good), xs, comp, int(validate))
+        except Ark355Error as e:
+            raise SynthesisError(str(e)) from e
+        for j, ok, s in zip(good, got, st):
+            oks[j], statuses[j] = ok, s
+        return oks, statuses
+
     def verify_batch(self, vk: VerifyingKey, public_inputs, proofs, rng=None) -> bool:
         """`ark355_verify_batch`: all proofs of ONE verifying key checked with a random linear combination (count + 3
         Miller loops, one final exponentiation).  `rng` yields the 128-bit coefficients; required for more than one proof."""

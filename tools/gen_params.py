@@ -40,6 +40,40 @@ BN254 = _Curve(
              4082367875863433681332203403145435568316851327593401208105741076214120093531)))
 
 
+def _f2mul(a, b, q):
+    return ((a[0] * b[0] - a[1] * b[1]) % q, (a[0] * b[1] + a[1] * b[0]) % q)
+
+
+def _f2pow(a, e, q):
+    r = (1, 0)
+    for bit in bin(e)[2:]:
+        r = _f2mul(r, r, q)
+        if bit == "1":
+            r = _f2mul(r, a, q)
+    return r
+
+
+def endo_consts(curve):
+    """Constants of the endomorphism subgroup tests (Wire::in_subgroup_fast), canonical integers.
+    psi(x, y) = (conj(x) * psi_x, conj(y) * psi_y) is the untwist-Frobenius-twist map of the twist: the factors are
+    xi^((q-1)/3), xi^((q-1)/2) on the D-type twist of BN254 (xi = 9 + u) and their inverses on the M-type twist of BLS12-381
+    (xi = 1 + u).  BLS12-381 G1 adds beta, the primitive cube root of unity of F_q with phi(G) = -[x^2] G for
+    phi(x, y) = (beta x, y): it is 2^((q-1)/3), the other root fails on the generator."""
+    q = curve.q
+    bn = curve.name == "bn254"
+    xi = (9, 1) if bn else (1, 1)
+    px, py = _f2pow(xi, (q - 1) // 3, q), _f2pow(xi, (q - 1) // 2, q)
+    if not bn:
+        inv = lambda a: (a[0] * pow(a[0] * a[0] + a[1] * a[1], -1, q) % q, -a[1] * pow(a[0] * a[0] + a[1] * a[1], -1, q) % q)
+        px, py = inv(px), inv(py)
+    out = [("psi_x_c0", px[0]), ("psi_x_c1", px[1]), ("psi_y_c0", py[0]), ("psi_y_c1", py[1])]
+    if not bn:
+        beta = pow(2, (q - 1) // 3, q)
+        assert beta != 1 and pow(beta, 3, q) == 1 and hex(beta).startswith("0x5f19672fdf76")
+        out.append(("endo_beta", beta))
+    return out
+
+
 def limbs32(v, n):
     return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(n)]
 
@@ -99,7 +133,8 @@ def curve_block(tag, curve):
     for fn, val in (("g1_b", b1), ("g2_b_c0", b2[0]), ("g2_b_c1", b2[1]),
                     ("g1_gen_x", curve.g1_gen[0] * Rq % q), ("g1_gen_y", curve.g1_gen[1] * Rq % q),
                     ("g2_gen_x0", curve.g2_gen[0][0] * Rq % q), ("g2_gen_x1", curve.g2_gen[0][1] * Rq % q),
-                    ("g2_gen_y0", curve.g2_gen[1][0] * Rq % q), ("g2_gen_y1", curve.g2_gen[1][1] * Rq % q)):
+                    ("g2_gen_y0", curve.g2_gen[1][0] * Rq % q), ("g2_gen_y1", curve.g2_gen[1][1] * Rq % q),
+                    *[(fn, val * Rq % q) for fn, val in endo_consts(curve)]):
         s.append("  ARK_HD static constexpr uint32_t %s(int i) {" % fn)
         s.append("    constexpr uint32_t v[%d] = %s;" % (nq, arr(val, nq)))
         s.append("    return v[i];")

@@ -26,10 +26,20 @@ free), at 1 proof on the host route and 256 .. 16384 proofs on the device route.
 (min .. max) of the yardstick's readings: the processed entry does strictly less work, so it must not be slower than the
 yardstick by more than that spread.
 
+--from-bytes measures proofs arriving as ark-serialize bytes (compressed, VALIDATE_FULL; 4096 and 65536 proofs): the path
+without the bytes entries -- a host loop of `ark355_proof_from_bytes`, then `ark355_verify_each_pvk`, run up to --host-max
+proofs -- beside `ark355_verify_each_bytes`, and the decode stage alone (`ark355_proofs_from_bytes`).  --lib PATH runs the
+same legs on another build of the library: one built with -DARK_WIRE_SUBGROUP_RP (tools/build_variant.sh) keeps the `[r]P`
+subgroup test in its decoders, so its host loop is the loop as it was before the endomorphism tests and its decode stage
+states their gain apart from the gain of decoding on the device.
+
 One child process per curve, each under its own `timeout`.  Dev tool; run on an MI355X:
   python tools/pairing_bench.py [--reps 5] [--out profiles/pairing_bench.txt]
   python tools/pairing_bench.py --each [--reps 5] [--out profiles/pairing_each_bench.txt]
   python tools/pairing_bench.py --pvk [--reps 5] [--out profiles/pvk_bench.txt]
+  python tools/pairing_bench.py --from-bytes [--lib variants/lib_rp.so] [--out profiles/verify_bytes_bench.txt]
+  rocprofv3 --kernel-trace --output-format csv -- python tools/pairing_bench.py --from-bytes --child bls12_381 --host-max 0
+                                      (proof_decode_kernel alone: the stage's figure includes the copies; add --lib for the [r]P build)
   rocprofv3 --kernel-trace --stats --output-format csv -- python tools/pairing_bench.py --one-verify-each 4096
                                       (one BLS12-381 verify_each, for profiles/pairing_each_kernel_stats.csv)
   rocprofv3 --kernel-trace --stats --output-format csv -- python tools/pairing_bench.py --one-verify 4096
@@ -266,6 +276,88 @@ def child_pvk(curve_name, reps, sizes):
     print("", flush=True)
 
 
+def child_bytes(curve_name, reps, sizes, host_max, lib_path):
+    """Proofs from wire bytes (compressed, VALIDATE_FULL): the path without the bytes entries -- a host loop of
+    ark355_proof_from_bytes, then ark355_verify_each_pvk -- beside ark355_verify_each_bytes, and the decode stage alone
+    (ark355_proofs_from_bytes: upload, decode kernel, download).  --lib names another build of the library, e.g. one made with
+    -DARK_WIRE_SUBGROUP_RP, whose decoders keep the [r]P subgroup test: its loop is the loop of the commit before the bytes
+    entries, its decode kernel states the gain of the endomorphism tests apart from the gain of moving to the device."""
+    import ctypes
+    import snark_amd
+    import pairing_cases as P
+    from oracle.fields import BLS12_381, BN254
+    from snark_amd._binding import Lib, ProofRaw
+    C = {"bls12_381": BLS12_381, "bn254": BN254}[curve_name]
+    lib = Lib(lib_path) if lib_path else snark_amd.lib()
+    ctx = lib.ctx_create(0)
+    lib.ctx_set_policy(ctx, "PAIRING_DEVICE", 1)
+    vk, proofs, inputs, _, _ = P.oracle_batch(C, 8)
+    pvk = lib.vk_process(ctx, C.curve_id, vk)
+    sz = lib.sizes(C.curve_id)
+    wires = [lib.proof_to_bytes(C.curve_id, *p, True) for p in proofs]
+    psize = len(wires[0])
+    rows = []
+    for n in sizes:
+        blob = b"".join(wires[j % 8] for j in range(n))
+        xs = b"".join(inputs[j % 8] for j in range(n))
+        buf = (ctypes.c_uint8 * len(blob)).from_buffer_copy(blob)
+        xbuf = (ctypes.c_uint8 * len(xs)).from_buffer_copy(xs)
+        arr = (ProofRaw * n)()
+        ok = (ctypes.c_uint8 * n)()
+        base = ctypes.addressof(buf)
+        t = {"loop": [], "loop_pvk": [], "bytes": [], "decode": []}
+
+        def parent_path():
+            t0 = time.perf_counter()
+            for j in range(n):
+                rc = lib.dll.ark355_proof_from_bytes(C.curve_id, base + j * psize, psize, 1, 1, ctypes.byref(arr[j]))
+                assert rc == 0
+            t1 = time.perf_counter()
+            assert lib.dll.ark355_verify_each_pvk(ctx, pvk, arr, xbuf, n, ok) == 0
+            t2 = time.perf_counter()
+            assert bytes(ok) == bytes([1]) * n
+            return (t1 - t0) * 1e3, (t2 - t0) * 1e3
+
+        def new_entry():
+            t0 = time.perf_counter()
+            got = lib.verify_each_bytes(ctx, pvk, blob, n, xs, True, 1)
+            dt = (time.perf_counter() - t0) * 1e3
+            assert got == ([True] * n, [0] * n)
+            return dt
+
+        def decode_stage():
+            t0 = time.perf_counter()
+            _, st = lib.proofs_from_bytes(ctx, C.curve_id, blob, n, sz, True, 1)
+            dt = (time.perf_counter() - t0) * 1e3
+            assert st == [0] * n
+            return dt
+
+        new_entry()
+        decode_stage()                                  # warm-up: buffers allocated, code objects loaded
+        for rep in range(reps):
+            if n <= host_max and rep < 2:               # seconds per run: two runs state its spread
+                a, b = parent_path()
+                t["loop"].append(a)
+                t["loop_pvk"].append(b)
+            t["bytes"].append(new_entry())
+            t["decode"].append(decode_stage())
+        rows.append((n, t))
+    lib.pvk_free(pvk)
+    lib.ctx_destroy(ctx)
+    print("curve %s, library %s: ms per call over %d interleaved runs (host clock), compressed proofs, VALIDATE_FULL"
+          % (C.name, lib_path or "as built", reps))
+    print("%7s | %14s %14s | %17s %19s | %17s | %8s"
+          % ("proofs", "host loop", "loop + each_pvk", "verify_each_bytes", "(min .. max)", "proofs_from_bytes", "speed-up"))
+    nan = float("nan")
+    for n, t in rows:
+        lp = statistics.median(t["loop"]) if t["loop"] else nan
+        lv = statistics.median(t["loop_pvk"]) if t["loop_pvk"] else nan
+        vb = statistics.median(t["bytes"])
+        print("%7d | %14.3f %14.3f | %17.3f %19s | %17.3f | %8.2f"
+              % (n, lp, lv, vb, "(%.3f .. %.3f)" % (min(t["bytes"]), max(t["bytes"])), statistics.median(t["decode"]), lv / vb))
+    print("", flush=True)
+
+
 def one_verify_each(count):
     """one ark355_verify_each of `count` BLS12-381 proofs on the device route, in this process (for a kernel trace)"""
     import snark_amd
@@ -315,6 +407,9 @@ def main():
     ap.add_argument("--host-max", type=int, default=1024, help="--each: largest n the host route is run at")
     ap.add_argument("--one-verify-each", type=int, default=0, metavar="COUNT")
     ap.add_argument("--pvk", action="store_true", help="verify_each against verify_each_pvk and vk_process")
+    ap.add_argument("--from-bytes", action="store_true",
+                    help="proofs as wire bytes: proof_from_bytes loop + verify_each_pvk against verify_each_bytes, and the decode stage")
+    ap.add_argument("--lib", default=None, help="--from-bytes: another build of the library (path of the shared object)")
     a = ap.parse_args()
     if a.one_verify:
         return one_verify(a.one_verify)
@@ -324,9 +419,15 @@ def main():
         a.sizes = ",".join(str(s) for s in EACH_SIZES)
     if a.pvk and a.sizes == ",".join(str(s) for s in SIZES):
         a.sizes = ",".join(str(s) for s in PVK_SIZES)
+    if a.from_bytes and a.sizes == ",".join(str(s) for s in SIZES):
+        a.sizes = "4096,65536"
+        if a.host_max == 1024:
+            a.host_max = 4096
     sizes = [int(s) for s in a.sizes.split(",")]
     if a.child:
-        if a.pvk:
+        if a.from_bytes:
+            child_bytes(a.child, a.reps, sizes, a.host_max, a.lib)
+        elif a.pvk:
             child_pvk(a.child, a.reps, sizes)
         elif a.each:
             child_each(a.child, a.reps, sizes, a.host_max)
@@ -342,6 +443,8 @@ def main():
             cmd += ["--each", "--host-max", str(a.host_max)]
         if a.pvk:
             cmd += ["--pvk"]
+        if a.from_bytes:
+            cmd += ["--from-bytes", "--host-max", str(a.host_max)] + (["--lib", a.lib] if a.lib else [])
         r = subprocess.run(cmd, capture_output=True, text=True)
         print(r.stdout, end="", flush=True)
         text.append(r.stdout)
@@ -352,7 +455,9 @@ def main():
     if a.out and rc == 0:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
-            if a.pvk:
+            if a.from_bytes:
+                f.write("pairing_bench --from-bytes: proofs from wire bytes, one process per curve\n\n")
+            elif a.pvk:
                 f.write("pairing_bench --pvk: ark355_verify_each against ark355_verify_each_pvk on one handle, one process per curve\n\n")
             else:
                 f.write("pairing_bench%s: host route (PAIRING_DEVICE=0) against device route (PAIRING_DEVICE=1), one process per curve\n\n"
