@@ -76,11 +76,12 @@ static inline ProvePlan prove_plan(const TunePolicy& pol, const ProveCase& k) {
   p.one_stream = k.sched == SCHED_ONE_STREAM || k.sched == SCHED_ONE_STREAM_SPIN;
   p.spin = pol.wait_spin != 0 || k.sched == SCHED_ONE_STREAM_SPIN;
   p.plain = !k.comm && !k.partials;
-  p.check_sat = pol.check_satisfied != 0 && p.plain && k.shard_count <= 1;
   // (the bucket ring interleaves its own send / receive steps with the MSMs and therefore keeps the replicated map; without a
   // communicator only the timing diagnostic DWM_LOOPBACK runs the distributed map)
   p.ring = k.comm && k.ring;
   p.dist_wm = k.h_dist && (k.comm ? !k.ring : pol.dwm_loopback != 0);
+  // (the check is a by-product of the replicated witness map: the distributed one neither allocates nor clears its verdict)
+  p.check_sat = pol.check_satisfied != 0 && p.plain && k.shard_count <= 1 && !p.dist_wm;
   p.side_wm = p.one_stream && !k.concurrent && p.plain && pol.side_wm != 0;
   p.batch_tails = p.one_stream && !k.comm && pol.batch_tails != 0;
   // with other proofs in flight everything stays on the one stream (a second stream per proof is exactly what the one-stream

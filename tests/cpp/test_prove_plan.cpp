@@ -84,7 +84,10 @@ static void check_rules(const TunePolicy& pol, const ProveCase& k) {
   IMPLIES(k.comm && k.h_dist && !k.ring, p.dist_wm);
   // CHECK_SATISFIED: plain proofs of a whole key only
   IMPLIES(p.check_sat, p.plain && k.shard_count <= 1 && pol.check_satisfied != 0);
-  IMPLIES(pol.check_satisfied != 0 && p.plain && k.shard_count <= 1, p.check_sat);
+  IMPLIES(pol.check_satisfied != 0 && p.plain && k.shard_count <= 1 && !p.dist_wm, p.check_sat);
+  // ... and only with the replicated witness map, whose by-product the verdict is: a whole key in the layout of the distributed
+  // map under DWM_LOOPBACK never runs it, and prove_run would copy a verdict nobody allocated
+  IMPLIES(p.check_sat, !p.dist_wm);
   // one wave per workgroup only for a proof alone on one stream
   CHECK(p.acc_threads == ((one && !k.concurrent) ? 64 : 256));
   CHECK(p.spin == (pol.wait_spin != 0 || k.sched == SCHED_ONE_STREAM_SPIN));
