@@ -36,6 +36,7 @@ typedef struct ark355_ctx ark355_ctx;
 typedef struct ark355_pk ark355_pk;
 typedef struct ark355_r1cs ark355_r1cs;
 typedef struct ark355_gr1cs ark355_gr1cs;
+typedef struct ark355_sr1cs ark355_sr1cs;     /* a resident R1CS rewritten as Square R1CS: ark355_sr1cs_from_r1cs */
 typedef struct ark355_bases ark355_bases;     /* resident MSM bases: ark355_bases_load */
 
 enum { ARK355_BLS12_381 = 0, ARK355_BN254 = 1 };
@@ -402,6 +403,45 @@ int32_t ark355_gr1cs_eval(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predi
  * (ark355_last_error names its label) -- a proof that drops constraints is not obtainable through this path -- and when the
  * label "R1CS" is absent or not the polynomial x0 x1 - x2 of arity 3. */
 int32_t ark355_gr1cs_r1cs(ark355_ctx* ctx, const ark355_gr1cs* g, ark355_r1cs** out);
+
+/* ---- Square R1CS: Sr1csAdapter on the device (relations/src/sr1cs/mod.rs:124-265) -----------------------------------------
+ * The adapter behind the GM17-style provers (Polymath, Garuda, Pari): n rows <A_i,z><B_i,z> = <C_i,z> become 2n + P rows of the
+ * predicate "SR1CS" (x0^2 - x1, arity 2):
+ *     row 2i       M0 = A_i + B_i,   M1 = 4 C_i + s_i          s_i: the square variable of row i, (<A_i,z> - <B_i,z>)^2
+ *     row 2i + 1   M0 = A_i - B_i,   M1 = s_i
+ *     row 2n+k-1   M0 = v_k - x_k,   M1 empty                  one per public variable p_k (ascending) that occurs in A, B or C
+ * over renumbered variables: every old column that occurs, public or witness, becomes a witness allocated at its first
+ * occurrence (rows ascending; A, then B, then C; entries in stored order; a zero coefficient counts), the square variable of a
+ * row follows the row's new variables, and the publics that occur become the inputs 1 .. P.  A public that never occurs gets
+ * no input (mod.rs:177-181, :253-262).  num_instance' = 1 + P, num_witness' = U + n with U the old columns that occur.
+ * The system is built on the device from the resident CSR arrays (snark_amd/csrc/sr1cs_impl.cuh): no matrix visits the host.
+ * Entry order within a row and the merging of repeated columns are unspecified, as for ark355_r1cs_load. */
+/* r1cs_to_sr1cs / r1cs_to_sr1cs_with_assignment (mod.rs:124-183, :191-265: the same matrices).  The handle owns copies of what
+ * it needs: `r1cs` may be freed afterwards.  ARK355_EINVAL (with a message) for a NULL argument, a handle of another curve or
+ * device, 1 + P + U + n >= 2^31 variables, 2 (nnz A + nnz B) + 2 P or nnz C + 2 n above ARK355_GR1CS_MAX_ROWS, a row of 2^30
+ * entries or more.  n = 0 is legal: no rows, num_instance' = 1. */
+int32_t ark355_sr1cs_from_r1cs(ark355_ctx* ctx, const ark355_r1cs* r1cs, ark355_sr1cs** out);
+void ark355_sr1cs_free(ark355_sr1cs* s);
+/* the resident system, borrowed: valid until ark355_sr1cs_free, never passed to ark355_gr1cs_free.  One predicate, index 0,
+ * label "SR1CS" (predicate/polynomial_constraint.rs): every ark355_gr1cs_* entry works on it, ark355_gr1cs_r1cs refuses it. */
+const ark355_gr1cs* ark355_sr1cs_system(const ark355_sr1cs* s);
+/* num_instance', num_witness', 2n + P, the non-zeros of M0 and M1; any pointer may be NULL */
+int32_t ark355_sr1cs_dims(const ark355_sr1cs* s, uint64_t* num_instance, uint64_t* num_witness, uint64_t* num_constraints,
+                          uint64_t nnz[2]);
+/* the two BTreeMaps of the adapter (mod.rs:129-130), per old column: num_instance + num_witness entries each, either may be NULL.
+ * witness_col[j]: the column of its witness copy (0 for column 0, -1 when j never occurs); instance_col[j]: its new input k
+ * for j = p_k, -1 otherwise */
+int32_t ark355_sr1cs_var_map(ark355_ctx* ctx, const ark355_sr1cs* s, int64_t* witness_col, int64_t* instance_col);
+/* to_matrices()["SR1CS"][which] (which = 0 | 1) in the CSR convention of ark355_r1cs_load: row_ptr 2n + P + 1, col and coeff
+ * (Montgomery Fr) nnz[which] entries; ARK355_EINVAL when entry_capacity (entries col and coeff can hold) is below that */
+int32_t ark355_sr1cs_matrix(ark355_ctx* ctx, const ark355_sr1cs* s, int32_t which, uint64_t* row_ptr, uint32_t* col,
+                            uint8_t* coeff, uint64_t entry_capacity);
+/* the assignment of r1cs_to_sr1cs_with_assignment (mod.rs:199-262): z (num_instance + num_witness Fr, Montgomery) -> z_out
+ * (num_instance' + num_witness' Fr), every element written.  Two launches: the squares (<A_i,z> - <B_i,z>)^2 of
+ * evaluate_constraint (mod.rs:24-56, :238) and the scatter of the copies.  ARK355_E_ASSIGNMENT_MISSING if
+ * z_len < num_instance + num_witness.  The _dev variant reads and writes device memory and returns when z_out is complete. */
+int32_t ark355_sr1cs_assignment(ark355_ctx* ctx, const ark355_sr1cs* s, const uint8_t* z, uint64_t z_len, uint8_t* z_out);
+int32_t ark355_sr1cs_assignment_dev(ark355_ctx* ctx, const ark355_sr1cs* s, const void* d_z, uint64_t z_len, void* d_z_out);
 
 /* in-place radix-2 NTT over Fr, natural order in and out (ark-poly Radix2EvaluationDomain
  * fft / ifft / coset_fft / coset_ifft).  Errors with ARK355_E_POLY_DEGREE_TOO_LARGE past the

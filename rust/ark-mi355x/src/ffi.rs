@@ -21,6 +21,10 @@ pub struct ark355_gr1cs {
     _p: [u8; 0],
 }
 #[repr(C)]
+pub struct ark355_sr1cs {
+    _p: [u8; 0],
+}
+#[repr(C)]
 pub struct ark355_comm {
     _p: [u8; 0],
 }
@@ -380,6 +384,29 @@ extern "C" {
     pub fn ark355_gr1cs_mat_vec(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, predicate: u32, z: *const u8, z_len: u64, out: *mut u8) -> i32;
     pub fn ark355_gr1cs_eval(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, predicate: u32, z: *const u8, z_len: u64, out: *mut u8) -> i32;
     pub fn ark355_gr1cs_r1cs(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, out: *mut *mut ark355_r1cs) -> i32;
+
+    pub fn ark355_sr1cs_from_r1cs(ctx: *mut ark355_ctx, r1cs: *const ark355_r1cs, out: *mut *mut ark355_sr1cs) -> i32;
+    pub fn ark355_sr1cs_free(s: *mut ark355_sr1cs);
+    pub fn ark355_sr1cs_system(s: *const ark355_sr1cs) -> *const ark355_gr1cs;
+    pub fn ark355_sr1cs_dims(
+        s: *const ark355_sr1cs,
+        num_instance: *mut u64,
+        num_witness: *mut u64,
+        num_constraints: *mut u64,
+        nnz: *mut u64,
+    ) -> i32;
+    pub fn ark355_sr1cs_var_map(ctx: *mut ark355_ctx, s: *const ark355_sr1cs, witness_col: *mut i64, instance_col: *mut i64) -> i32;
+    pub fn ark355_sr1cs_matrix(
+        ctx: *mut ark355_ctx,
+        s: *const ark355_sr1cs,
+        which: i32,
+        row_ptr: *mut u64,
+        col: *mut u32,
+        coeff: *mut u8,
+        entry_capacity: u64,
+    ) -> i32;
+    pub fn ark355_sr1cs_assignment(ctx: *mut ark355_ctx, s: *const ark355_sr1cs, z: *const u8, z_len: u64, z_out: *mut u8) -> i32;
+    pub fn ark355_sr1cs_assignment_dev(ctx: *mut ark355_ctx, s: *const ark355_sr1cs, d_z: *const c_void, z_len: u64, d_z_out: *mut c_void) -> i32;
 
     pub fn ark355_ntt_fr(ctx: *mut ark355_ctx, curve: i32, data: *mut u8, log_n: u32, inverse: i32, coset: i32) -> i32;
     pub fn ark355_ntt_fr_dev(

@@ -47,7 +47,9 @@ SYMBOLS = [
     "ark355_r1cs_domain_size", "ark355_prove", "ark355_prove_dev", "ark355_witness_map", "ark355_witness_map_dist_sim",
     "ark355_is_satisfied", "ark355_r1cs_mat_vec",
     "ark355_gr1cs_load", "ark355_gr1cs_free", "ark355_gr1cs_num_constraints", "ark355_gr1cs_which_is_unsatisfied",
-    "ark355_gr1cs_mat_vec", "ark355_gr1cs_eval", "ark355_gr1cs_r1cs", "ark355_ntt_fr", "ark355_ntt_fr_dev",
+    "ark355_gr1cs_mat_vec", "ark355_gr1cs_eval", "ark355_gr1cs_r1cs",
+    "ark355_sr1cs_from_r1cs", "ark355_sr1cs_free", "ark355_sr1cs_system", "ark355_sr1cs_dims", "ark355_sr1cs_var_map",
+    "ark355_sr1cs_matrix", "ark355_sr1cs_assignment", "ark355_sr1cs_assignment_dev", "ark355_ntt_fr", "ark355_ntt_fr_dev",
     "ark355_msm_g1", "ark355_msm_g2", "ark355_bases_load", "ark355_bases_free", "ark355_msm_dev",
     "ark355_msm_dev_partial", "ark355_xyzz_sum", "ark355_fixed_base_mul", "ark355_get_timings",
     "ark355_get_kernel_stats", "ark355_pk_load_shard", "ark355_partial_size", "ark355_prove_shard",
@@ -172,6 +174,16 @@ class Lib:
         d.ark355_gr1cs_mat_vec.argtypes = [vp, vp, u32, vp, u64, vp]
         d.ark355_gr1cs_eval.argtypes = [vp, vp, u32, vp, u64, vp]
         d.ark355_gr1cs_r1cs.argtypes = [vp, vp, P(vp)]
+        d.ark355_sr1cs_from_r1cs.argtypes = [vp, vp, P(vp)]
+        d.ark355_sr1cs_free.argtypes = [vp]
+        d.ark355_sr1cs_free.restype = None
+        d.ark355_sr1cs_system.argtypes = [vp]
+        d.ark355_sr1cs_system.restype = vp
+        d.ark355_sr1cs_dims.argtypes = [vp, P(u64), P(u64), P(u64), P(u64 * 2)]
+        d.ark355_sr1cs_var_map.argtypes = [vp, vp, vp, vp]
+        d.ark355_sr1cs_matrix.argtypes = [vp, vp, i32, vp, vp, vp, u64]
+        d.ark355_sr1cs_assignment.argtypes = [vp, vp, vp, u64, vp]
+        d.ark355_sr1cs_assignment_dev.argtypes = [vp, vp, vp, u64, vp]
         d.ark355_ntt_fr.argtypes = [vp, i32, vp, u32, i32, i32]
         d.ark355_ntt_fr_dev.argtypes = [vp, i32, vp, vp, u32, i32, i32, vp]
         d.ark355_msm_g1.argtypes = [vp, i32, vp, vp, u64, vp]
@@ -651,6 +663,53 @@ class Lib:
         h = C.c_void_p()
         self.check(ctx, self.dll.ark355_gr1cs_r1cs(ctx, g, C.byref(h)))
         return h
+
+    # ---- Square R1CS: Sr1csAdapter on the device (include/ark355.h "Square R1CS") -----------------------------------
+    def sr1cs_from_r1cs(self, ctx, r1cs):
+        """an ark355_sr1cs handle from a resident R1CS (freed with sr1cs_free; the r1cs handle may be freed first)"""
+        h = C.c_void_p()
+        self.check(ctx, self.dll.ark355_sr1cs_from_r1cs(ctx, r1cs, C.byref(h)))
+        return h
+
+    def sr1cs_free(self, s):
+        self.dll.ark355_sr1cs_free(s)
+
+    def sr1cs_system(self, s):
+        """the borrowed ark355_gr1cs handle of the resident system (never passed to gr1cs_free)"""
+        return C.c_void_p(self.dll.ark355_sr1cs_system(s))
+
+    def sr1cs_dims(self, s):
+        """(num_instance', num_witness', rows, (nnz M0, nnz M1))"""
+        ell, w, n, nnz = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * 2)()
+        self.check(None, self.dll.ark355_sr1cs_dims(s, C.byref(ell), C.byref(w), C.byref(n), C.byref(nnz)))
+        return ell.value, w.value, n.value, (nnz[0], nnz[1])
+
+    def sr1cs_var_map(self, ctx, s, m):
+        """(witness_col, instance_col): int64 arrays over the m old columns (-1: none)"""
+        wit, inst = np.zeros(max(1, m), dtype=np.int64), np.zeros(max(1, m), dtype=np.int64)
+        self.check(ctx, self.dll.ark355_sr1cs_var_map(ctx, s, wit.ctypes.data_as(C.c_void_p), inst.ctypes.data_as(C.c_void_p)))
+        return wit[:m], inst[:m]
+
+    def sr1cs_matrix(self, ctx, s, which, rows, nnz, fr_size, entry_capacity=None):
+        """(row_ptr u64[rows + 1], col u32[nnz], coeff bytes) of matrix `which`"""
+        rp = np.zeros(rows + 1, dtype=np.uint64)
+        col = np.zeros(max(1, nnz), dtype=np.uint32)
+        cf = np.zeros(max(1, nnz * fr_size), dtype=np.uint8)
+        cap = nnz if entry_capacity is None else entry_capacity
+        self.check(ctx, self.dll.ark355_sr1cs_matrix(ctx, s, which, rp.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
+                                                     cf.ctypes.data_as(C.c_void_p), cap))
+        return rp, col[:nnz], cf.tobytes()[:nnz * fr_size]
+
+    def sr1cs_assignment(self, ctx, s, z, z_len, m_out, fr_size):
+        """z (Montgomery bytes) -> z' (m_out Fr, Montgomery bytes)"""
+        out = np.zeros(max(1, m_out * fr_size), dtype=np.uint8)
+        zb, k = _buf(z)
+        self.check(ctx, self.dll.ark355_sr1cs_assignment(ctx, s, zb, z_len, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:m_out * fr_size]
+
+    def sr1cs_assignment_dev(self, ctx, s, d_z, z_len, d_z_out):
+        """device pointers (ints): z -> z'; returns when z' is complete"""
+        self.check(ctx, self.dll.ark355_sr1cs_assignment_dev(ctx, s, C.c_void_p(d_z), z_len, C.c_void_p(d_z_out)))
 
     def ntt(self, ctx, curve, data: bytes, log_n, inverse=False, coset=False):
         a = np.frombuffer(bytearray(data), dtype=np.uint8)

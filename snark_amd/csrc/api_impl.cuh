@@ -6,6 +6,7 @@
 #include "common.h"
 #include "groth16_impl.cuh"
 #include "gr1cs_impl.cuh"
+#include "sr1cs_impl.cuh"
 #include "setup_impl.cuh"
 #include "wire_impl.cuh"
 #include "verify_impl.cuh"
@@ -224,6 +225,17 @@ struct Api {
     ARK_CHECK_HIP(hipStreamSynchronize(st));
   }
   static R1csDev* gr1cs_r1cs(ark355_ctx* ctx, const Gr1csDev& g) { return gr1cs_to_r1cs<Curve>(g, ctx->stream); }
+
+  // ---- Square R1CS (sr1cs_impl.cuh) ------------------------------------------------------------------------------
+  static Sr1csDev* sr1cs_from_r1cs(ark355_ctx* ctx, const R1csDev& r1) { return sr1cs_build<Curve>(r1, ctx->device, ctx->stream); }
+  static void sr1cs_matrix(ark355_ctx* ctx, GenericScratch& gs, const Sr1csDev& s, int which, uint64_t* row_ptr, uint32_t* col,
+                           uint8_t* coeff) {
+    ark355::sr1cs_matrix<Curve>(s, which, row_ptr, col, coeff, gs.a, ctx->stream);
+  }
+  static void sr1cs_assignment(ark355_ctx* ctx, ProverScratch& sc, GenericScratch& gs, const Sr1csDev& s, const void* z, void* z_out,
+                               bool on_dev) {
+    ark355::sr1cs_assignment<Curve>(s, z, z_out, on_dev, sc.zx, gs.a, ctx->stream);
+  }
 
   static void ntt_host(ark355_ctx* ctx, GenericScratch& g, uint8_t* data, uint32_t log_n, bool inverse, bool coset) {
     hipStream_t st = ctx->stream;

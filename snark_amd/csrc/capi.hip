@@ -24,6 +24,10 @@ struct ark355_r1cs {
 struct ark355_gr1cs {
   Gr1csDev* d;
 };
+struct ark355_sr1cs {
+  Sr1csDev* d;
+  ark355_gr1cs view;     // borrows d->sys: handed out by ark355_sr1cs_system, never freed on its own
+};
 struct ark355_bases {
   BasesDev* d;
 };
@@ -318,6 +322,7 @@ int32_t ark355_r1cs_load(ark355_ctx* ctx, int32_t curve, uint64_t n, uint64_t el
   return guarded(ctx, [&] {
     R1csDev* d = nullptr;
     CURVE_DISPATCH(curve, d = A::r1cs_load(n, ell, w, row_ptr, col, coeff));
+    d->device = ctx->device;
     *out = new ark355_r1cs{d};
   });
 }
@@ -601,8 +606,93 @@ int32_t ark355_gr1cs_r1cs(ark355_ctx* ctx, const ark355_gr1cs* g, ark355_r1cs** 
   return guarded(ctx, [&] {
     R1csDev* d = nullptr;
     CURVE_DISPATCH(g->d->curve, d = A::gr1cs_r1cs(ctx, *g->d));
+    d->device = ctx->device;
     *out = new ark355_r1cs{d};
   });
+}
+
+// ---- Square R1CS (sr1cs_impl.cuh) ----------------------------------------------------------------------------------------
+static int32_t refuse(ark355_ctx* ctx, const char* msg, int32_t code = ARK355_EINVAL) {
+  if (ctx) ctx->last_error = msg;
+  return code;
+}
+
+int32_t ark355_sr1cs_from_r1cs(ark355_ctx* ctx, const ark355_r1cs* r1cs, ark355_sr1cs** out) {
+  if (!ctx) return ARK355_EINVAL;
+  if (!out) return refuse(ctx, "ark355_sr1cs_from_r1cs: out is NULL");
+  *out = nullptr;
+  if (!r1cs || !r1cs->d) return refuse(ctx, "ark355_sr1cs_from_r1cs: r1cs is NULL");
+  if (r1cs->d->device >= 0 && r1cs->d->device != ctx->device)
+    return refuse(ctx, "ark355_sr1cs_from_r1cs: the r1cs handle lives on another device than the context");
+  return guarded(ctx, [&] {
+    Sr1csDev* d = nullptr;
+    CURVE_DISPATCH(r1cs->d->curve, d = A::sr1cs_from_r1cs(ctx, *r1cs->d));
+    *out = new ark355_sr1cs{d, ark355_gr1cs{&d->sys}};
+  });
+}
+void ark355_sr1cs_free(ark355_sr1cs* s) {
+  if (!s) return;
+  delete s->d;
+  delete s;
+}
+const ark355_gr1cs* ark355_sr1cs_system(const ark355_sr1cs* s) { return s ? &s->view : nullptr; }
+
+int32_t ark355_sr1cs_dims(const ark355_sr1cs* s, uint64_t* num_instance, uint64_t* num_witness, uint64_t* num_constraints,
+                          uint64_t nnz[2]) {
+  if (!s) return ARK355_EINVAL;
+  const Gr1csDev& g = s->d->sys;
+  if (num_instance) *num_instance = g.ell;
+  if (num_witness) *num_witness = g.w;
+  if (num_constraints) *num_constraints = g.total;
+  if (nnz) {
+    nnz[0] = g.preds[0].nnz[0];
+    nnz[1] = g.preds[0].nnz[1];
+  }
+  return ARK355_OK;
+}
+
+// the handle was built through a context of the same device
+static int32_t sr1cs_handle_check(ark355_ctx* ctx, const ark355_sr1cs* s, const char* null_msg) {
+  if (!s) return refuse(ctx, null_msg);
+  if (s->d->device != ctx->device) return refuse(ctx, "the sr1cs handle lives on another device than the context");
+  return ARK355_OK;
+}
+
+int32_t ark355_sr1cs_var_map(ark355_ctx* ctx, const ark355_sr1cs* s, int64_t* witness_col, int64_t* instance_col) {
+  if (!ctx) return ARK355_EINVAL;
+  if (int32_t rc = sr1cs_handle_check(ctx, s, "ark355_sr1cs_var_map: the sr1cs handle is NULL")) return rc;
+  return guarded(ctx, [&] { sr1cs_var_map(*s->d, witness_col, instance_col, ctx->stream); });
+}
+
+int32_t ark355_sr1cs_matrix(ark355_ctx* ctx, const ark355_sr1cs* s, int32_t which, uint64_t* row_ptr, uint32_t* col, uint8_t* coeff,
+                            uint64_t entry_capacity) {
+  if (!ctx) return ARK355_EINVAL;
+  if (int32_t rc = sr1cs_handle_check(ctx, s, "ark355_sr1cs_matrix: the sr1cs handle is NULL")) return rc;
+  if (which < 0 || which > 1) return refuse(ctx, "ark355_sr1cs_matrix: which must be 0 or 1");
+  if (!row_ptr || !col || !coeff) return refuse(ctx, "ark355_sr1cs_matrix: row_ptr / col / coeff is NULL");
+  if (entry_capacity < s->d->sys.preds[0].nnz[which])
+    return refuse(ctx, "ark355_sr1cs_matrix: entry_capacity below the matrix's non-zeros (ark355_sr1cs_dims)");
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(s->d->curve, A::sr1cs_matrix(ctx, ex.generic, *s->d, which, row_ptr, col, coeff));
+  });
+}
+
+static int32_t sr1cs_assignment_common(ark355_ctx* ctx, const ark355_sr1cs* s, const void* z, uint64_t z_len, void* z_out, bool on_dev) {
+  if (!ctx) return ARK355_EINVAL;
+  if (int32_t rc = sr1cs_handle_check(ctx, s, "ark355_sr1cs_assignment: the sr1cs handle is NULL")) return rc;
+  if (!z || !z_out) return refuse(ctx, "ark355_sr1cs_assignment: z / z_out is NULL");
+  if (z_len < s->d->m) return refuse(ctx, "assignment shorter than num_instance + num_witness", ARK355_E_ASSIGNMENT_MISSING);
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(s->d->curve, A::sr1cs_assignment(ctx, ex.prover, ex.generic, *s->d, z, z_out, on_dev));
+  });
+}
+int32_t ark355_sr1cs_assignment(ark355_ctx* ctx, const ark355_sr1cs* s, const uint8_t* z, uint64_t z_len, uint8_t* z_out) {
+  return sr1cs_assignment_common(ctx, s, z, z_len, z_out, false);
+}
+int32_t ark355_sr1cs_assignment_dev(ark355_ctx* ctx, const ark355_sr1cs* s, const void* d_z, uint64_t z_len, void* d_z_out) {
+  return sr1cs_assignment_common(ctx, s, d_z, z_len, d_z_out, true);
 }
 
 int32_t ark355_ntt_fr(ark355_ctx* ctx, int32_t curve, uint8_t* data, uint32_t log_n, int32_t inverse, int32_t coset) {

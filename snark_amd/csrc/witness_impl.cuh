@@ -27,6 +27,7 @@ static inline uint64_t r1cs_next_uid() {
 struct R1csDev {
   uint64_t uid = r1cs_next_uid();      // identity of this handle for the life of the process (a key bound to it: groth16_impl.cuh)
   int curve = 0;
+  int device = -1;                     // the device of the context that loaded it (capi.hip); -1: not recorded
   uint64_t n = 0, ell = 0, w = 0, m = 0, N = 0;
   uint32_t log_n = 0;
   uint64_t nnz[3] = {0, 0, 0};

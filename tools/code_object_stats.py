@@ -49,6 +49,8 @@ KERNELS = [
     (r"pairing_product_kernelINS_7BnCurve", "bn254.pairing_product"),
     (r"pairing_key_lines_kernelINS_7BnCurve", "bn254.pairing_key_lines"),
     (r"pairing_accumulate_key_kernelINS_7BnCurve", "bn254.pairing_accumulate_key"),
+    (r"sr1cs_assign_kernelINS_2FpINS_11BlsFrParams", "bls12_381.sr1cs_assign"),
+    (r"sr1cs_assign_kernelINS_2FpINS_10BnFrParams", "bn254.sr1cs_assign"),
 ]
 
 
