@@ -504,6 +504,12 @@ class ConstraintSystem {
     return z;
   }
 
+  // what finalize() consumes, as the reference stores it: the flat LC map, the interner's pool and argument_lcs column-wise
+  // (ark355_gr1cs_from_lcs takes these memory images as they are)
+  const LcMap<F>& lcs() const { return lc_map; }
+  const FieldInterner<F>& interner() const { return field_interner; }
+  const std::vector<std::vector<Variable>>& r1cs_arguments() const { return r1cs_args; }
+
   size_t num_instance_variables = 1;
   size_t num_witness_variables = 0;
   size_t num_linear_combinations = 1;

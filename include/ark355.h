@@ -90,6 +90,8 @@ int32_t ark355_sizes(int32_t curve, uint32_t what[4]);
  *                 PAIRING_DEVICE (0 host threads, 1 device, -1 [default] device from PAIRING_DEVICE_MIN pairs on) and
  *                 PAIRING_DEVICE_MIN: where the Miller loops of ark355_multi_pairing and ark355_verify_batch run;
  *                 PAIRING_EACH_MIN: the "from ... on" of ark355_pairing_groups and ark355_verify_each, in groups / proofs.
+ *                 LCS_ROW_LDS_MAX (ark355_gr1cs_from_lcs: the longest expanded LC whose sort-and-merge runs in LDS, 1 .. 1024
+ *                 [default 1024, what the workgroup's 8 KiB of keys hold]; longer ones take the path that works at any length).
  * ARK355_EINVAL for an unknown name.  ark355_prove_batch runs its worker contexts under the caller's policy.
  * (No counterpart in the reference: ark-groth16 has no runtime knobs; rayon's thread count is its only one.) */
 int32_t ark355_ctx_set_policy(ark355_ctx* ctx, const char* name, int64_t value);
@@ -403,6 +405,78 @@ int32_t ark355_gr1cs_eval(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predi
  * (ark355_last_error names its label) -- a proof that drops constraints is not obtainable through this path -- and when the
  * label "R1CS" is absent or not the polynomial x0 x1 - x2 of arity 3. */
 int32_t ark355_gr1cs_r1cs(ark355_ctx* ctx, const ark355_gr1cs* g, ark355_r1cs** out);
+
+/* to_matrices() of any resident system (constraint_system.rs:768-774), the read-back of what the entries below and
+ * ark355_sr1cs_from_r1cs build on the device.  ark355_gr1cs_dims: any pointer may be NULL.  ark355_gr1cs_pred_dims: nnz takes
+ * `arity` entries, any pointer may be NULL; ARK355_EINVAL for a predicate index out of range.  ark355_gr1cs_matrix: matrix `which`
+ * (< arity) of predicate `predicate` in the CSR convention of ark355_r1cs_load: row_ptr n_constraints + 1 entries, col and coeff
+ * (Montgomery Fr) at least entry_capacity >= nnz[which] entries. */
+int32_t ark355_gr1cs_dims(const ark355_gr1cs* g, uint64_t* num_instance, uint64_t* num_witness, uint32_t* n_preds);
+int32_t ark355_gr1cs_pred_dims(const ark355_gr1cs* g, uint32_t predicate, uint32_t* arity, uint64_t* n_constraints, uint64_t* nnz);
+int32_t ark355_gr1cs_matrix(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, uint32_t which, uint64_t* row_ptr,
+                            uint32_t* col, uint8_t* coeff, uint64_t entry_capacity);
+
+/* ---- finalize() on the device: inline the LC map, outline instances (snark_amd/csrc/lcmap_impl.cuh) -------------------------
+ * ConstraintSystem::finalize() + to_matrices() (constraint_system.rs:691-804, :826-863; instance_outliner.rs) from the memory
+ * images ark-relations keeps before finalize: LcMap's three flat arrays (lc_map.rs:51-56), Variable as a packed u64
+ * (utils/variable.rs:4-14: tag in the top 3 bits, payload in the low 61) and InternedField indices into the interner's pool
+ * (field_interner.rs:24-69).  All host arrays are copied during the call.
+ *
+ * Column of a variable: One -> 0; Instance(i) -> i (i < num_instance; Instance(0) is legal and is column 0); Witness(j) ->
+ * num_instance + j.  expand(Zero) = 0, expand(v) = 1 * col(v), expand(Lc(k)) = sum over the entries (c, v) of LC k of
+ * pool[c] * expand(v); LC k may reference only LCs of a smaller index (constraint_system.rs:735).  Row i of matrix t of a
+ * predicate is expand(args[t][i]); the argument may be a bare variable, Zero or an LC (get_lc, :777-788).
+ * Every row is stored in CANONICAL FORM: columns strictly ascending, repeated columns merged, entries whose merged coefficient
+ * is zero dropped; a row that cancels is empty; a coefficient equal to one carries pool index 0.  The reference compacts only
+ * when some LC uses another (:722-725) and otherwise keeps stored order and repeats: it agrees with this entry as linear forms.
+ *
+ * outline = 1 (outline_r1cs, the label "R1CS", arity 3) or 2 (outline_sr1cs, "SR1CS", arity 2): when that label is absent from
+ * preds nothing happens, as in finalize (:698-704).  A present label of another arity is ARK355_EINVAL -- the reference would
+ * remap the map and then drop the ArityMismatch of the appended rows; this entry refuses instead.  Otherwise, with ell =
+ * num_instance and w = num_witness: num_witness' = w + ell; INSIDE THE LC MAP ONLY One and Instance(0) become Witness(w) and
+ * Instance(i) becomes Witness(w + i) -- a bare variable passed directly as a predicate argument is not remapped (the reference
+ * rewrites lc_map only, and new_lc_add_helper hands a single-term coefficient-one LC back as the variable itself, :472-499;
+ * the quirk is kept) -- and ell rows are appended to the target: R1CS row 0: A = B = col(ell + w), C = col 0; row i: A =
+ * col(ell + w), B = col(ell + w + i), C = col i; SR1CS row i: M0 = col i - col(ell + w + i), M1 empty.  The matching assignment
+ * is z || 1 || z[1 .. ell).
+ *
+ * ARK355_EINVAL, with a message that names the array and the first offending index and never a fault (every index is checked
+ * by a device pass before a kernel follows it): a NULL where a count is non-zero; lc_offsets[0] != 0 or a decreasing offset; a
+ * tag above 4; an instance index >= num_instance, a witness index >= num_witness, an LC index >= n_lcs; an LC entry that
+ * references an LC of an index >= its own; a coefficient index >= n_pool; n_pool < 2, pool[0] != 1 or pool[1] != -1; duplicate
+ * labels; what ark355_gr1cs_load refuses about a polynomial; a matrix above ARK355_GR1CS_MAX_ROWS non-zeros.  ARK355_ENOMEM when
+ * an intermediate does not fit the device or 32-bit indices.  n_lcs = 0, predicates without rows and num_instance = 1 are legal.
+ * Policy LCS_ROW_LDS_MAX (per call): the longest expanded LC that is sorted in LDS; longer ones take the any-length path.
+ * The result is an ordinary handle: ark355_gr1cs_free, every ark355_gr1cs_* entry, ark355_gr1cs_r1cs -> ark355_sr1cs_from_r1cs. */
+#define ARK355_VAR_ZERO 0
+#define ARK355_VAR_ONE 1
+#define ARK355_VAR_INSTANCE 2
+#define ARK355_VAR_WITNESS 3
+#define ARK355_VAR_LC 4
+typedef struct {                  /* PredicateConstraintSystem before to_matrices (predicate/mod.rs:81-94)                */
+  const char* label;
+  uint32_t arity;
+  uint64_t n_constraints;
+  uint32_t n_terms;               /* the polynomial, as in ark355_predicate_desc                                          */
+  const uint8_t* term_coeff;
+  const uint32_t* term_ptr;
+  const uint32_t* term_var;
+  const uint32_t* term_exp;
+  const uint64_t* const* args;    /* arity arrays of n_constraints Variables: argument_lcs, column-wise                    */
+} ark355_predicate_lcs_desc;
+typedef struct {
+  uint64_t num_instance;
+  uint64_t num_witness;
+  uint64_t n_lcs;                 /* LcMap: lc_offsets has n_lcs + 1 entries, lc_offsets[0] == 0, non-decreasing          */
+  const uint64_t* lc_offsets;
+  const uint64_t* lc_vars;        /* lc_offsets[n_lcs] Variables                                                          */
+  const uint32_t* lc_coeffs;      /* ... and their indices into pool                                                      */
+  uint64_t n_pool;                /* FieldInterner::vec, Montgomery Fr: n_pool >= 2, pool[0] == 1, pool[1] == -1          */
+  const uint8_t* pool;
+  int32_t outline;                /* 0 none, 1 outline_r1cs, 2 outline_sr1cs                                              */
+} ark355_lc_system_desc;
+int32_t ark355_gr1cs_from_lcs(ark355_ctx* ctx, int32_t curve, const ark355_lc_system_desc* system,
+                              const ark355_predicate_lcs_desc* preds, uint32_t n_preds, ark355_gr1cs** out);
 
 /* ---- Square R1CS: Sr1csAdapter on the device (relations/src/sr1cs/mod.rs:124-265) -----------------------------------------
  * The adapter behind the GM17-style provers (Polymath, Garuda, Pari): n rows <A_i,z><B_i,z> = <C_i,z> become 2n + P rows of the

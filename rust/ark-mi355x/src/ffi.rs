@@ -63,6 +63,12 @@ pub const ARK355_GR1CS_MAX_TERMS: u32 = 256;
 pub const ARK355_GR1CS_MAX_FACTORS: u32 = 1024;
 pub const ARK355_GR1CS_MAX_PREDICATES: u32 = 1024;
 pub const ARK355_GR1CS_MAX_ROWS: u64 = 4294967295;
+/// tags of a packed `Variable` (top 3 bits; payload in the low 61): `ark355_gr1cs_from_lcs`
+pub const ARK355_VAR_ZERO: u64 = 0;
+pub const ARK355_VAR_ONE: u64 = 1;
+pub const ARK355_VAR_INSTANCE: u64 = 2;
+pub const ARK355_VAR_WITNESS: u64 = 3;
+pub const ARK355_VAR_LC: u64 = 4;
 pub const ARK355_PAIRING_GROUP_MAX: u32 = 64;
 /// words of the `plan` array of `ark355_diag_msm_sort`
 pub const ARK355_SORT_PLAN_WORDS: usize = 8;
@@ -99,6 +105,36 @@ pub struct ark355_predicate_desc {
     pub row_ptr: *const *const u64,
     pub col: *const *const u32,
     pub coeff: *const *const u8,
+}
+
+/// One predicate of `ark355_gr1cs_from_lcs`: the polynomial as in `ark355_predicate_desc` and `argument_lcs`, column-wise
+/// (`arity` arrays of `n_constraints` packed Variables).
+#[repr(C)]
+pub struct ark355_predicate_lcs_desc {
+    pub label: *const c_char,
+    pub arity: u32,
+    pub n_constraints: u64,
+    pub n_terms: u32,
+    pub term_coeff: *const u8,
+    pub term_ptr: *const u32,
+    pub term_var: *const u32,
+    pub term_exp: *const u32,
+    pub args: *const *const u64,
+}
+
+/// A constraint system before `finalize()`: the three flat arrays of `LcMap` and the interner's pool (Montgomery Fr;
+/// entries 0 and 1 are 1 and -1).  `outline`: 0 none, 1 `outline_r1cs`, 2 `outline_sr1cs`.
+#[repr(C)]
+pub struct ark355_lc_system_desc {
+    pub num_instance: u64,
+    pub num_witness: u64,
+    pub n_lcs: u64,
+    pub lc_offsets: *const u64,
+    pub lc_vars: *const u64,
+    pub lc_coeffs: *const u32,
+    pub n_pool: u64,
+    pub pool: *const u8,
+    pub outline: i32,
 }
 
 #[repr(C)]
@@ -384,6 +420,26 @@ extern "C" {
     pub fn ark355_gr1cs_mat_vec(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, predicate: u32, z: *const u8, z_len: u64, out: *mut u8) -> i32;
     pub fn ark355_gr1cs_eval(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, predicate: u32, z: *const u8, z_len: u64, out: *mut u8) -> i32;
     pub fn ark355_gr1cs_r1cs(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, out: *mut *mut ark355_r1cs) -> i32;
+    pub fn ark355_gr1cs_dims(g: *const ark355_gr1cs, num_instance: *mut u64, num_witness: *mut u64, n_preds: *mut u32) -> i32;
+    pub fn ark355_gr1cs_pred_dims(g: *const ark355_gr1cs, predicate: u32, arity: *mut u32, n_constraints: *mut u64, nnz: *mut u64) -> i32;
+    pub fn ark355_gr1cs_matrix(
+        ctx: *mut ark355_ctx,
+        g: *const ark355_gr1cs,
+        predicate: u32,
+        which: u32,
+        row_ptr: *mut u64,
+        col: *mut u32,
+        coeff: *mut u8,
+        entry_capacity: u64,
+    ) -> i32;
+    pub fn ark355_gr1cs_from_lcs(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        system: *const ark355_lc_system_desc,
+        preds: *const ark355_predicate_lcs_desc,
+        n_preds: u32,
+        out: *mut *mut ark355_gr1cs,
+    ) -> i32;
 
     pub fn ark355_sr1cs_from_r1cs(ctx: *mut ark355_ctx, r1cs: *const ark355_r1cs, out: *mut *mut ark355_sr1cs) -> i32;
     pub fn ark355_sr1cs_free(s: *mut ark355_sr1cs);

@@ -48,6 +48,7 @@ SYMBOLS = [
     "ark355_is_satisfied", "ark355_r1cs_mat_vec",
     "ark355_gr1cs_load", "ark355_gr1cs_free", "ark355_gr1cs_num_constraints", "ark355_gr1cs_which_is_unsatisfied",
     "ark355_gr1cs_mat_vec", "ark355_gr1cs_eval", "ark355_gr1cs_r1cs",
+    "ark355_gr1cs_dims", "ark355_gr1cs_pred_dims", "ark355_gr1cs_matrix", "ark355_gr1cs_from_lcs",
     "ark355_sr1cs_from_r1cs", "ark355_sr1cs_free", "ark355_sr1cs_system", "ark355_sr1cs_dims", "ark355_sr1cs_var_map",
     "ark355_sr1cs_matrix", "ark355_sr1cs_assignment", "ark355_sr1cs_assignment_dev", "ark355_ntt_fr", "ark355_ntt_fr_dev",
     "ark355_msm_g1", "ark355_msm_g2", "ark355_bases_load", "ark355_bases_free", "ark355_msm_dev",
@@ -94,6 +95,22 @@ class PredicateDesc(C.Structure):
                 ("term_coeff", C.c_void_p), ("term_ptr", C.c_void_p), ("term_var", C.c_void_p), ("term_exp", C.c_void_p),
                 ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("coeff", C.c_void_p)]
 
+
+class PredicateLcsDesc(C.Structure):
+    _fields_ = [("label", C.c_char_p), ("arity", C.c_uint32), ("n_constraints", C.c_uint64), ("n_terms", C.c_uint32),
+                ("term_coeff", C.c_void_p), ("term_ptr", C.c_void_p), ("term_var", C.c_void_p), ("term_exp", C.c_void_p),
+                ("args", C.c_void_p)]
+
+
+class LcSystemDesc(C.Structure):
+    _fields_ = [("num_instance", C.c_uint64), ("num_witness", C.c_uint64), ("n_lcs", C.c_uint64), ("lc_offsets", C.c_void_p),
+                ("lc_vars", C.c_void_p), ("lc_coeffs", C.c_void_p), ("n_pool", C.c_uint64), ("pool", C.c_void_p),
+                ("outline", C.c_int32)]
+
+
+# tags of a packed Variable (utils/variable.rs:4-14): tag << 61 | payload
+VAR_ZERO, VAR_ONE, VAR_INSTANCE, VAR_WITNESS, VAR_LC = 0, 1, 2, 3, 4
+VAR_TAG_SHIFT = 61
 
 SETUP_OUT_FIELDS = ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1", "a_query",
                     "b_g1_query", "b_g2_query", "h_query", "l_query", "u", "v", "w")
@@ -174,6 +191,10 @@ class Lib:
         d.ark355_gr1cs_mat_vec.argtypes = [vp, vp, u32, vp, u64, vp]
         d.ark355_gr1cs_eval.argtypes = [vp, vp, u32, vp, u64, vp]
         d.ark355_gr1cs_r1cs.argtypes = [vp, vp, P(vp)]
+        d.ark355_gr1cs_dims.argtypes = [vp, P(u64), P(u64), P(u32)]
+        d.ark355_gr1cs_pred_dims.argtypes = [vp, u32, P(u32), P(u64), vp]
+        d.ark355_gr1cs_matrix.argtypes = [vp, vp, u32, u32, vp, vp, vp, u64]
+        d.ark355_gr1cs_from_lcs.argtypes = [vp, i32, P(LcSystemDesc), P(PredicateLcsDesc), u32, P(vp)]
         d.ark355_sr1cs_from_r1cs.argtypes = [vp, vp, P(vp)]
         d.ark355_sr1cs_free.argtypes = [vp]
         d.ark355_sr1cs_free.restype = None
@@ -662,6 +683,74 @@ class Lib:
         """an ark355_r1cs handle from the predicate labelled "R1CS" (refused when another predicate has a row)"""
         h = C.c_void_p()
         self.check(ctx, self.dll.ark355_gr1cs_r1cs(ctx, g, C.byref(h)))
+        return h
+
+    def gr1cs_dims(self, g):
+        """(num_instance, num_witness, n_preds) of a resident system"""
+        ell, w, n = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        self.check(None, self.dll.ark355_gr1cs_dims(g, C.byref(ell), C.byref(w), C.byref(n)))
+        return ell.value, w.value, n.value
+
+    def gr1cs_pred_dims(self, g, predicate):
+        """(arity, n_constraints, (nnz of each matrix)) of one predicate (caller's index)"""
+        arity, n = C.c_uint32(0), C.c_uint64(0)
+        self.check(None, self.dll.ark355_gr1cs_pred_dims(g, predicate, C.byref(arity), C.byref(n), None))
+        nnz = (C.c_uint64 * max(1, arity.value))()
+        self.check(None, self.dll.ark355_gr1cs_pred_dims(g, predicate, None, None, C.addressof(nnz)))
+        return arity.value, n.value, tuple(nnz[k] for k in range(arity.value))
+
+    def gr1cs_matrix(self, ctx, g, predicate, which, rows, nnz, fr_size, entry_capacity=None):
+        """(row_ptr u64[rows + 1], col u32[nnz], coeff bytes) of matrix `which` of one predicate: to_matrices() of a resident system"""
+        rp = np.zeros(rows + 1, dtype=np.uint64)
+        col = np.zeros(max(1, nnz), dtype=np.uint32)
+        cf = np.zeros(max(1, nnz * fr_size), dtype=np.uint8)
+        cap = nnz if entry_capacity is None else entry_capacity
+        self.check(ctx, self.dll.ark355_gr1cs_matrix(ctx, g, predicate, which, rp.ctypes.data_as(C.c_void_p),
+                                                     col.ctypes.data_as(C.c_void_p), cf.ctypes.data_as(C.c_void_p), cap))
+        return rp, col[:nnz], cf.tobytes()[:nnz * fr_size]
+
+    # ---- finalize() on the device (include/ark355.h "finalize() on the device") -------------------------------------
+    def gr1cs_from_lcs(self, ctx, curve, ell, w, lc_offsets, lc_vars, lc_coeffs, pool, preds, outline=0, n_lcs=None, n_pool=None, n_preds=None):
+        """lc_offsets u64[n_lcs + 1], lc_vars u64[], lc_coeffs u32[], pool = Montgomery Fr bytes; preds: a list of (label,
+        arity, n_constraints, term_coeff bytes, term_ptr u32[], term_var u32[], term_exp u32[], args) with args = arity u64
+        arrays of packed Variables.  Any array may be None to hand the library a NULL pointer; n_lcs / n_pool / n_preds
+        override the counts the arrays imply."""
+        keep = []
+
+        def ptr(a, dtype):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.size == 0:
+                a = np.zeros(1, dtype)               # a valid pointer for an empty array (never read)
+            keep.append(a)
+            return a.ctypes.data
+
+        sysd = LcSystemDesc()
+        sysd.num_instance, sysd.num_witness, sysd.outline = ell, w, outline
+        sysd.n_lcs = n_lcs if n_lcs is not None else (len(lc_offsets) - 1 if lc_offsets is not None else 0)
+        sysd.lc_offsets, sysd.lc_vars, sysd.lc_coeffs = ptr(lc_offsets, np.uint64), ptr(lc_vars, np.uint64), ptr(lc_coeffs, np.uint32)
+        sysd.n_pool = n_pool if n_pool is not None else (len(pool) // 32 if pool is not None else 0)
+        sysd.pool = ptr(np.frombuffer(pool, dtype=np.uint8), np.uint8) if pool is not None else None
+        descs = None
+        if preds is not None:
+            descs = (PredicateLcsDesc * max(1, len(preds)))()
+            for d, (label, arity, n, term_coeff, term_ptr, term_var, term_exp, args) in zip(descs, preds):
+                d.label = label.encode("utf-8") if label is not None else None
+                d.arity, d.n_constraints = arity, n
+                d.n_terms = (len(term_ptr) - 1) if term_ptr is not None else (len(term_coeff) // 32 if term_coeff is not None else 0)
+                d.term_coeff = ptr(np.frombuffer(term_coeff, dtype=np.uint8), np.uint8) if term_coeff is not None else None
+                d.term_ptr, d.term_var, d.term_exp = ptr(term_ptr, np.uint32), ptr(term_var, np.uint32), ptr(term_exp, np.uint32)
+                if args is not None:
+                    ap = (C.c_void_p * max(1, len(args)))()
+                    for i, a in enumerate(args):
+                        ap[i] = ptr(a, np.uint64)
+                    keep.append(ap)
+                    d.args = C.addressof(ap)
+        h = C.c_void_p()
+        if n_preds is None:
+            n_preds = len(preds) if preds is not None else 0
+        self.check(ctx, self.dll.ark355_gr1cs_from_lcs(ctx, curve, C.byref(sysd), descs, n_preds, C.byref(h)))
         return h
 
     # ---- Square R1CS: Sr1csAdapter on the device (include/ark355.h "Square R1CS") -----------------------------------

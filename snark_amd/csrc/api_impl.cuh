@@ -7,6 +7,7 @@
 #include "groth16_impl.cuh"
 #include "gr1cs_impl.cuh"
 #include "sr1cs_impl.cuh"
+#include "lcmap_impl.cuh"
 #include "setup_impl.cuh"
 #include "wire_impl.cuh"
 #include "verify_impl.cuh"
@@ -225,6 +226,16 @@ struct Api {
     ARK_CHECK_HIP(hipStreamSynchronize(st));
   }
   static R1csDev* gr1cs_r1cs(ark355_ctx* ctx, const Gr1csDev& g) { return gr1cs_to_r1cs<Curve>(g, ctx->stream); }
+
+  static void gr1cs_matrix(ark355_ctx* ctx, GenericScratch& gs, const Gr1csDev& g, uint32_t p, uint32_t which, uint64_t* row_ptr,
+                           uint32_t* col, uint8_t* coeff) {
+    ark355::gr1cs_matrix<Curve>(g, g.preds[p], which, row_ptr, col, coeff, gs.a, ctx->stream);
+  }
+  // ---- finalize() on the device (lcmap_impl.cuh) -----------------------------------------------------------------
+  static Gr1csDev* gr1cs_from_lcs(ark355_ctx* ctx, const ark355_lc_system_desc& s, const ark355_predicate_lcs_desc* preds,
+                                  uint32_t n_preds) {
+    return lcs_finalize<Curve>(s, preds, n_preds, (uint32_t)std::max(ctx->policy.lcs_row_lds_max, 1), ctx->stream);
+  }
 
   // ---- Square R1CS (sr1cs_impl.cuh) ------------------------------------------------------------------------------
   static Sr1csDev* sr1cs_from_r1cs(ark355_ctx* ctx, const R1csDev& r1) { return sr1cs_build<Curve>(r1, ctx->device, ctx->stream); }

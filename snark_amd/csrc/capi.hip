@@ -611,11 +611,58 @@ int32_t ark355_gr1cs_r1cs(ark355_ctx* ctx, const ark355_gr1cs* g, ark355_r1cs** 
   });
 }
 
-// ---- Square R1CS (sr1cs_impl.cuh) ----------------------------------------------------------------------------------------
 static int32_t refuse(ark355_ctx* ctx, const char* msg, int32_t code = ARK355_EINVAL) {
   if (ctx) ctx->last_error = msg;
   return code;
 }
+
+int32_t ark355_gr1cs_dims(const ark355_gr1cs* g, uint64_t* num_instance, uint64_t* num_witness, uint32_t* n_preds) {
+  if (!g || !g->d) return ARK355_EINVAL;
+  if (num_instance) *num_instance = g->d->ell;
+  if (num_witness) *num_witness = g->d->w;
+  if (n_preds) *n_preds = (uint32_t)g->d->preds.size();
+  return ARK355_OK;
+}
+int32_t ark355_gr1cs_pred_dims(const ark355_gr1cs* g, uint32_t predicate, uint32_t* arity, uint64_t* n_constraints, uint64_t* nnz) {
+  if (!g || !g->d || predicate >= g->d->preds.size()) return ARK355_EINVAL;
+  const Gr1csPred& P = g->d->preds[predicate];
+  if (arity) *arity = P.arity;
+  if (n_constraints) *n_constraints = P.n;
+  if (nnz)
+    for (uint32_t k = 0; k < P.arity; k++) nnz[k] = P.nnz[k];
+  return ARK355_OK;
+}
+int32_t ark355_gr1cs_matrix(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, uint32_t which, uint64_t* row_ptr,
+                            uint32_t* col, uint8_t* coeff, uint64_t entry_capacity) {
+  if (!ctx) return ARK355_EINVAL;
+  if (!g || !g->d) return refuse(ctx, "ark355_gr1cs_matrix: the gr1cs handle is NULL");
+  if (predicate >= g->d->preds.size()) return refuse(ctx, "ark355_gr1cs_matrix: predicate index out of range");
+  const Gr1csPred& P = g->d->preds[predicate];
+  if (which >= P.arity) return refuse(ctx, "ark355_gr1cs_matrix: which must be below the predicate's arity");
+  if (!row_ptr || !col || !coeff) return refuse(ctx, "ark355_gr1cs_matrix: row_ptr / col / coeff is NULL");
+  if (entry_capacity < P.nnz[which])
+    return refuse(ctx, "ark355_gr1cs_matrix: entry_capacity below the matrix's non-zeros (ark355_gr1cs_pred_dims)");
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(g->d->curve, A::gr1cs_matrix(ctx, ex.generic, *g->d, predicate, which, row_ptr, col, coeff));
+  });
+}
+
+// ---- finalize() on the device (lcmap_impl.cuh) ------------------------------------------------------------------------------
+int32_t ark355_gr1cs_from_lcs(ark355_ctx* ctx, int32_t curve, const ark355_lc_system_desc* system,
+                              const ark355_predicate_lcs_desc* preds, uint32_t n_preds, ark355_gr1cs** out) {
+  if (!ctx) return ARK355_EINVAL;
+  if (!out) return refuse(ctx, "ark355_gr1cs_from_lcs: out is NULL");
+  *out = nullptr;
+  if (!system) return refuse(ctx, "ark355_gr1cs_from_lcs: system is NULL");
+  return guarded(ctx, [&] {
+    Gr1csDev* d = nullptr;
+    CURVE_DISPATCH(curve, d = A::gr1cs_from_lcs(ctx, *system, preds, n_preds));
+    *out = new ark355_gr1cs{d};
+  });
+}
+
+// ---- Square R1CS (sr1cs_impl.cuh) ----------------------------------------------------------------------------------------
 
 int32_t ark355_sr1cs_from_r1cs(ark355_ctx* ctx, const ark355_r1cs* r1cs, ark355_sr1cs** out) {
   if (!ctx) return ARK355_EINVAL;

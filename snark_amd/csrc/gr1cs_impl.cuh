@@ -177,6 +177,55 @@ static bool gr1cs_is_r1cs_polynomial(const ark355_predicate_desc& d) {
   return nonzero == 2;
 }
 
+// what ark355_gr1cs_load and ark355_gr1cs_from_lcs refuse about the head and the polynomial of a predicate
+static inline void gr1cs_validate_polynomial(const std::string& who, uint32_t arity, uint64_t n_constraints, uint32_t n_terms,
+                                             const uint8_t* term_coeff, const uint32_t* term_ptr, const uint32_t* term_var,
+                                             const uint32_t* term_exp) {
+  ARK_REQUIRE(arity >= 1, ARK355_EINVAL, who + "arity 0");
+  ARK_REQUIRE(arity <= ARK355_GR1CS_MAX_ARITY, ARK355_EINVAL, who + "arity above ARK355_GR1CS_MAX_ARITY");
+  ARK_REQUIRE(n_terms <= ARK355_GR1CS_MAX_TERMS, ARK355_EINVAL, who + "more terms than ARK355_GR1CS_MAX_TERMS");
+  ARK_REQUIRE(n_constraints <= ARK355_GR1CS_MAX_ROWS, ARK355_EINVAL, who + "more rows than ARK355_GR1CS_MAX_ROWS");
+  ARK_REQUIRE(n_terms == 0 || (term_ptr && term_coeff), ARK355_EINVAL, who + "term_ptr / term_coeff is NULL");
+  ARK_REQUIRE(n_terms == 0 || term_ptr[0] == 0, ARK355_EINVAL, who + "term_ptr must start at 0");
+  for (uint32_t k = 0; k < n_terms; k++) {
+    ARK_REQUIRE(term_ptr[k + 1] >= term_ptr[k], ARK355_EINVAL, who + "term_ptr must be non-decreasing");
+    ARK_REQUIRE(term_ptr[k + 1] <= ARK355_GR1CS_MAX_FACTORS, ARK355_EINVAL, who + "more factors than ARK355_GR1CS_MAX_FACTORS");
+  }
+  const uint32_t n_factors = n_terms ? term_ptr[n_terms] : 0;
+  ARK_REQUIRE(n_factors == 0 || (term_var && term_exp), ARK355_EINVAL, who + "term_var / term_exp is NULL");
+  for (uint32_t j = 0; j < n_factors; j++)
+    ARK_REQUIRE(term_var[j] < arity, ARK355_EINVAL, who + "term_var names a variable >= arity");
+}
+
+// the polynomial as the program gr1cs_pred_kernel reads; its coefficients are interned into `pool`
+template <class Fr>
+static std::vector<uint32_t> gr1cs_program(FrInterner<Fr>& pool, uint32_t n_terms, const uint8_t* term_coeff, const uint32_t* term_ptr,
+                                           const uint32_t* term_var, const uint32_t* term_exp) {
+  std::vector<uint32_t> prog;
+  prog.push_back(n_terms);
+  for (uint32_t k = 0; k < n_terms; k++) {
+    prog.push_back(pool.intern(term_coeff + (size_t)k * sizeof(Fr)));
+    prog.push_back(term_ptr[k + 1] - term_ptr[k]);
+    for (uint32_t j = term_ptr[k]; j < term_ptr[k + 1]; j++) {
+      prog.push_back(term_var[j]);
+      prog.push_back(term_exp[j]);
+    }
+  }
+  return prog;
+}
+
+// the labels in byte-wise lexicographic order, as BTreeMap<String, _> iterates: order[rank] = the caller's index
+static inline std::vector<uint32_t> gr1cs_label_order(const std::vector<const char*>& labels) {
+  std::vector<uint32_t> order(labels.size());
+  for (uint32_t p = 0; p < order.size(); p++) order[p] = p;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    const size_t la = strlen(labels[a]), lb = strlen(labels[b]);
+    const int c = memcmp(labels[a], labels[b], la < lb ? la : lb);
+    return c != 0 ? c < 0 : la < lb;
+  });
+  return order;
+}
+
 template <class Curve>
 static Gr1csDev* gr1cs_upload(uint64_t ell, uint64_t w, const ark355_predicate_desc* preds, uint32_t n_preds) {
   using Fr = typename Curve::Fr;
@@ -194,21 +243,7 @@ static Gr1csDev* gr1cs_upload(uint64_t ell, uint64_t w, const ark355_predicate_d
     const ark355_predicate_desc& d = preds[p];
     ARK_REQUIRE(d.label, ARK355_EINVAL, "predicate " + std::to_string(p) + ": label is NULL");
     const std::string who = "predicate \"" + std::string(d.label) + "\": ";
-    ARK_REQUIRE(d.arity >= 1, ARK355_EINVAL, who + "arity 0");
-    ARK_REQUIRE(d.arity <= ARK355_GR1CS_MAX_ARITY, ARK355_EINVAL, who + "arity above ARK355_GR1CS_MAX_ARITY");
-    ARK_REQUIRE(d.n_terms <= ARK355_GR1CS_MAX_TERMS, ARK355_EINVAL, who + "more terms than ARK355_GR1CS_MAX_TERMS");
-    ARK_REQUIRE(d.n_constraints <= ARK355_GR1CS_MAX_ROWS, ARK355_EINVAL, who + "more rows than ARK355_GR1CS_MAX_ROWS");
-    ARK_REQUIRE(d.n_terms == 0 || (d.term_ptr && d.term_coeff), ARK355_EINVAL, who + "term_ptr / term_coeff is NULL");
-    ARK_REQUIRE(d.n_terms == 0 || d.term_ptr[0] == 0, ARK355_EINVAL, who + "term_ptr must start at 0");
-    for (uint32_t k = 0; k < d.n_terms; k++) {
-      ARK_REQUIRE(d.term_ptr[k + 1] >= d.term_ptr[k], ARK355_EINVAL, who + "term_ptr must be non-decreasing");
-      ARK_REQUIRE(d.term_ptr[k + 1] <= ARK355_GR1CS_MAX_FACTORS, ARK355_EINVAL,
-                  who + "more factors than ARK355_GR1CS_MAX_FACTORS");
-    }
-    const uint32_t n_factors = d.n_terms ? d.term_ptr[d.n_terms] : 0;
-    ARK_REQUIRE(n_factors == 0 || (d.term_var && d.term_exp), ARK355_EINVAL, who + "term_var / term_exp is NULL");
-    for (uint32_t j = 0; j < n_factors; j++)
-      ARK_REQUIRE(d.term_var[j] < d.arity, ARK355_EINVAL, who + "term_var names a variable >= arity");
+    gr1cs_validate_polynomial(who, d.arity, d.n_constraints, d.n_terms, d.term_coeff, d.term_ptr, d.term_var, d.term_exp);
     ARK_REQUIRE(d.row_ptr && d.col && d.coeff, ARK355_EINVAL, who + "row_ptr / col / coeff is NULL");
     for (uint32_t k = 0; k < d.arity; k++) {
       const std::string mat = who + "matrix " + std::to_string(k) + ": ";
@@ -227,13 +262,9 @@ static Gr1csDev* gr1cs_upload(uint64_t ell, uint64_t w, const ark355_predicate_d
       ARK_REQUIRE(strcmp(preds[q].label, d.label) != 0, ARK355_EINVAL, who + "duplicate label");
   }
   // ---- ranks of the labels: byte-wise lexicographic, as BTreeMap<String, _> iterates -----------------------------------
-  std::vector<uint32_t> order(n_preds);
-  for (uint32_t p = 0; p < n_preds; p++) order[p] = p;
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    const size_t la = strlen(preds[a].label), lb = strlen(preds[b].label);
-    const int c = memcmp(preds[a].label, preds[b].label, la < lb ? la : lb);
-    return c != 0 ? c < 0 : la < lb;
-  });
+  std::vector<const char*> labels(n_preds);
+  for (uint32_t p = 0; p < n_preds; p++) labels[p] = preds[p].label;
+  const std::vector<uint32_t> order = gr1cs_label_order(labels);
   // ---- upload ------------------------------------------------------------------------------------------------------------
   FrInterner<Fr> pool;
   g->preds.resize(n_preds);
@@ -246,16 +277,7 @@ static Gr1csDev* gr1cs_upload(uint64_t ell, uint64_t w, const ark355_predicate_d
     P.n = d.n_constraints;
     P.r1cs_shape = gr1cs_is_r1cs_polynomial<Fr>(d);
     g->total += P.n;
-    std::vector<uint32_t> prog;
-    prog.push_back(d.n_terms);
-    for (uint32_t k = 0; k < d.n_terms; k++) {
-      prog.push_back(pool.intern(d.term_coeff + (size_t)k * sizeof(Fr)));
-      prog.push_back(d.term_ptr[k + 1] - d.term_ptr[k]);
-      for (uint32_t j = d.term_ptr[k]; j < d.term_ptr[k + 1]; j++) {
-        prog.push_back(d.term_var[j]);
-        prog.push_back(d.term_exp[j]);
-      }
-    }
+    const std::vector<uint32_t> prog = gr1cs_program<Fr>(pool, d.n_terms, d.term_coeff, d.term_ptr, d.term_var, d.term_exp);
     P.prog.alloc(prog.size() * 4);
     ARK_CHECK_HIP(hipMemcpy(P.prog.p, prog.data(), prog.size() * 4, hipMemcpyHostToDevice));
     P.nnz.resize(d.arity);
@@ -364,6 +386,36 @@ static R1csDev* gr1cs_to_r1cs(const Gr1csDev& g, hipStream_t stream) {
   r1cs_upload_zinv<Curve>(r.get());
   ARK_CHECK_HIP(hipStreamSynchronize(stream));
   return r.release();
+}
+
+// the coefficients of one matrix as field elements
+template <class Fr>
+__global__ void __launch_bounds__(256)
+gr1cs_coeff_kernel(const uint32_t* __restrict__ ci, const Fr* __restrict__ pool, uint64_t nnz, Fr* __restrict__ out) {
+  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nnz) return;
+  out[e] = pool[ci[e]];
+}
+
+// to_matrices() of a resident system (constraint_system.rs:768-774): matrix `which` of one predicate in the CSR convention of
+// ark355_r1cs_load; tmp: grow-only scratch for the gathered coefficients
+template <class Curve>
+static void gr1cs_matrix(const Gr1csDev& g, const Gr1csPred& Q, uint32_t which, uint64_t* row_ptr, uint32_t* col, uint8_t* coeff,
+                         DevBuf& tmp, hipStream_t st) {
+  using Fr = typename Curve::Fr;
+  const uint64_t nnz = Q.nnz[which];
+  std::vector<uint32_t> rp(Q.n + 1);
+  ARK_CHECK_HIP(hipMemcpyAsync(rp.data(), Q.row_ptr[which].p, (Q.n + 1) * 4, hipMemcpyDeviceToHost, st));
+  if (nnz) {
+    tmp.ensure(nnz * sizeof(Fr));
+    ARK_LAUNCH((gr1cs_coeff_kernel<Fr>), dim3((uint32_t)((nnz + 255) / 256)), dim3(256), 0, st,
+               (const uint32_t*)Q.cidx[which].as<uint32_t>(), (const Fr*)g.pool.as<Fr>(), nnz, tmp.as<Fr>());
+    ARK_CHECK_LAUNCH();
+    ARK_CHECK_HIP(hipMemcpyAsync(col, Q.col[which].p, nnz * 4, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipMemcpyAsync(coeff, tmp.p, nnz * sizeof(Fr), hipMemcpyDeviceToHost, st));
+  }
+  ARK_CHECK_HIP(hipStreamSynchronize(st));
+  for (uint64_t i = 0; i <= Q.n; i++) row_ptr[i] = rp[i];
 }
 
 }  // namespace ark355

@@ -16,7 +16,8 @@
 //   per call       MSM_SEG, ACC_THREADS, NTT_RMAX, NTT_DIRECT_MAX, NTT_NOFUSE (A/B and test knobs of the kernels'
 //                  host drivers), CHECK_SATISFIED, H_EVAL (read at the first proof of a key), PAIRING_DEVICE,
 //                  PAIRING_DEVICE_MIN (where the Miller loops of ark355_multi_pairing and ark355_verify_batch run),
-//                  PAIRING_EACH_MIN (the same for ark355_pairing_groups and ark355_verify_each)
+//                  PAIRING_EACH_MIN (the same for ark355_pairing_groups and ark355_verify_each), LCS_ROW_LDS_MAX (the longest
+//                  expanded LC that ark355_gr1cs_from_lcs sorts in LDS)
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -83,6 +84,9 @@ struct TunePolicy {
                                   // count from which the device route wins by 10 % at that count and every larger one, on the slower curve
   int32_t pairing_each_min = 256; // the same rule for ark355_pairing_groups and ark355_verify_each, counted in groups / proofs: the host route
                                   // pays one final exponentiation per group there (an estimate until its table is measured)
+  int32_t lcs_row_lds_max = 1024; // ark355_gr1cs_from_lcs (lcmap_impl.cuh): an expanded LC of at most this many entries is sorted and merged in the
+                                  // LDS of a 64-lane workgroup, a longer one by the any-length path on keys in global memory; clamped to 1 ..
+                                  // LCS_LDS_KEYS = 1024, the keys 8 KiB hold.  Tests lower it to reach the long path at small shapes.
 
   struct Field {
     const char* name;
@@ -131,6 +135,7 @@ inline const TunePolicy::Field* TunePolicy::fields(int* count) {
       ARK_POLICY_FIELD32("PAIRING_DEVICE", pairing_device),
       ARK_POLICY_FIELD32("PAIRING_DEVICE_MIN", pairing_device_min),
       ARK_POLICY_FIELD32("PAIRING_EACH_MIN", pairing_each_min),
+      ARK_POLICY_FIELD32("LCS_ROW_LDS_MAX", lcs_row_lds_max),
   };
   *count = (int)(sizeof(tab) / sizeof(tab[0]));
   return tab;

@@ -200,15 +200,6 @@ sr1cs_pool_kernel(const Fr* __restrict__ pool, uint32_t c, Fr* __restrict__ out)
   out[2 * c + i] = Fr::dbl(Fr::dbl(v));
 }
 
-// the coefficients of one matrix as field elements (ark355_sr1cs_matrix)
-template <class Fr>
-__global__ void __launch_bounds__(256)
-sr1cs_coeff_kernel(const uint32_t* __restrict__ ci, const Fr* __restrict__ pool, uint64_t nnz, Fr* __restrict__ out) {
-  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= nnz) return;
-  out[e] = pool[ci[e]];
-}
-
 // z'[s_i] = (<A_i,z> - <B_i,z>)^2: evaluate_constraint twice (mod.rs:24-56, :214-238)
 template <class Fr>
 __global__ void __launch_bounds__(256)
@@ -416,22 +407,8 @@ static inline void sr1cs_var_map(const Sr1csDev& s, int64_t* witness_col, int64_
 // matrix `which` in the CSR convention of ark355_r1cs_load; tmp: grow-only scratch for the gathered coefficients
 template <class Curve>
 static void sr1cs_matrix(const Sr1csDev& s, int which, uint64_t* row_ptr, uint32_t* col, uint8_t* coeff, DevBuf& tmp, hipStream_t st) {
-  using Fr = typename Curve::Fr;
   ARK_REQUIRE(s.curve == Curve::ID, ARK355_EINVAL, "ark355_sr1cs_matrix: the handle belongs to another curve");
-  const Gr1csPred& Q = s.sys.preds[0];
-  const uint64_t nnz = Q.nnz[which];
-  std::vector<uint32_t> rp(Q.n + 1);
-  ARK_CHECK_HIP(hipMemcpyAsync(rp.data(), Q.row_ptr[which].p, (Q.n + 1) * 4, hipMemcpyDeviceToHost, st));
-  if (nnz) {
-    tmp.ensure(nnz * sizeof(Fr));
-    ARK_LAUNCH((sr1cs_coeff_kernel<Fr>), dim3(sr1cs_grid(nnz)), dim3(256), 0, st, (const uint32_t*)Q.cidx[which].as<uint32_t>(),
-               (const Fr*)s.sys.pool.as<Fr>(), nnz, tmp.as<Fr>());
-    ARK_CHECK_LAUNCH();
-    ARK_CHECK_HIP(hipMemcpyAsync(col, Q.col[which].p, nnz * 4, hipMemcpyDeviceToHost, st));
-    ARK_CHECK_HIP(hipMemcpyAsync(coeff, tmp.p, nnz * sizeof(Fr), hipMemcpyDeviceToHost, st));
-  }
-  ARK_CHECK_HIP(hipStreamSynchronize(st));
-  for (uint64_t i = 0; i <= Q.n; i++) row_ptr[i] = rp[i];
+  gr1cs_matrix<Curve>(s.sys, s.sys.preds[0], (uint32_t)which, row_ptr, col, coeff, tmp, st);
 }
 
 }  // namespace ark355

@@ -79,6 +79,24 @@ class GR1CS:
                                    [b for _, b, _ in csr], [c for _, _, c in csr]))
         return GR1CS(curve, ell, w, preds)
 
+    @staticmethod
+    def from_handle(curve, lib, ctx, handle, predicates) -> "GR1CS":
+        """A ``GR1CS`` over a system that is already resident (``LcSystem.finalize``): predicates = [(label, terms)] in the order
+        the handle was built with; dimensions and row counts are read from the handle (``ark355_gr1cs_dims`` / ``_pred_dims``).
+        ``free()`` frees the handle."""
+        curve = CURVES[curve] if not isinstance(curve, Curve) else curve
+        ell, w, n_preds = lib.gr1cs_dims(handle)
+        if n_preds != len(predicates):
+            raise ValueError("the handle holds %d predicates, %d were named" % (n_preds, len(predicates)))
+        preds = []
+        for i, (label, terms) in enumerate(predicates):
+            arity, n, _ = lib.gr1cs_pred_dims(handle, i)
+            preds.append(Predicate(label, arity, [(c, list(f)) for c, f in terms], n, [], [], []))
+        g = GR1CS(curve, ell, w, preds)
+        g.lib, g.ctx, g.handle = lib, ctx, handle
+        g._index = {p.label: i for i, p in enumerate(preds)}
+        return g
+
     # ---- device ---------------------------------------------------------------------------------------------------
     def load(self, lib, ctx) -> "GR1CS":
         self.free()
@@ -144,6 +162,14 @@ class GR1CS:
         i = self._index[label]
         zb, n = self._z(z)
         return self.lib.gr1cs_eval(self.ctx, self.handle, i, zb, n, self.predicates[i].n, 32)
+
+    def matrices(self, label: str) -> List[Tuple[np.ndarray, np.ndarray, bytes]]:
+        """``to_matrices()[label]`` of the resident system: its arity matrices as (row_ptr u64, col u32, coeff Montgomery bytes),
+        the shape ``Lib.r1cs_load`` takes, read back from the device (``ark355_gr1cs_matrix``)"""
+        self._need()
+        i = self._index[label]
+        arity, n, nnz = self.lib.gr1cs_pred_dims(self.handle, i)
+        return [self.lib.gr1cs_matrix(self.ctx, self.handle, i, k, n, nnz[k], 32) for k in range(arity)]
 
     def r1cs_handle(self):
         """An ``ark355_r1cs`` handle (for ``Lib.prove``; the caller frees it with ``ark355_r1cs_free``) from the predicate

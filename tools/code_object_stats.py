@@ -51,6 +51,12 @@ KERNELS = [
     (r"pairing_accumulate_key_kernelINS_7BnCurve", "bn254.pairing_accumulate_key"),
     (r"sr1cs_assign_kernelINS_2FpINS_11BlsFrParams", "bls12_381.sr1cs_assign"),
     (r"sr1cs_assign_kernelINS_2FpINS_10BnFrParams", "bn254.sr1cs_assign"),
+    (r"lcs_expand_kernelINS_2FpINS_11BlsFrParams", "bls12_381.lcs_expand"),
+    (r"lcs_expand_kernelINS_2FpINS_10BnFrParams", "bn254.lcs_expand"),
+    (r"lcs_compact_lds_kernelINS_2FpINS_11BlsFrParams", "bls12_381.lcs_compact_lds"),
+    (r"lcs_compact_lds_kernelINS_2FpINS_10BnFrParams", "bn254.lcs_compact_lds"),
+    (r"lcs_compact_long_kernelINS_2FpINS_11BlsFrParams", "bls12_381.lcs_compact_long"),
+    (r"lcs_compact_long_kernelINS_2FpINS_10BnFrParams", "bn254.lcs_compact_long"),
 ]
 
 
