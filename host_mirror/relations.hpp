@@ -497,6 +497,24 @@ class ConstraintSystem {
   }
   bool is_satisfied() const { return which_is_unsatisfied().empty(); }
 
+  // What ark355_gr1cs_quotient_dims reports for this system's "R1CS" predicate once it is resident (x0 x1 - x2: degree 2, so
+  // D = 1 and h_len = N): log_n = 0 selects the smallest power of two >= max(n, 2); h_len = 0 when 2^log_n is below the row
+  // count, which the entry refuses.  The two-adicity of F bounds log_domain on the device; it is not known here.
+  struct QuotientDims {
+    uint64_t degree;
+    uint32_t log_domain, log_ext;
+    uint64_t h_len;
+  };
+  QuotientDims quotient_dims(uint32_t log_n = 0) const {
+    QuotientDims q{2, log_n, 0, 0};
+    if (log_n == 0) {
+      q.log_domain = 1;
+      while ((uint64_t(1) << q.log_domain) < num_r1cs_constraints) q.log_domain++;
+    }
+    if (q.log_domain < 64 && (uint64_t(1) << q.log_domain) >= num_r1cs_constraints) q.h_len = uint64_t(1) << q.log_domain;
+    return q;
+  }
+
   // the prover's view (:193-206)
   std::vector<F> full_assignment() const {
     std::vector<F> z = instance_assignment;
@@ -593,6 +611,7 @@ class ConstraintSystemRef {
   void finalize() const { borrow().finalize(); }
   bool is_satisfied() const { return borrow().is_satisfied(); }
   std::string which_is_unsatisfied() const { return borrow().which_is_unsatisfied(); }
+  typename ConstraintSystem<F>::QuotientDims quotient_dims(uint32_t log_n = 0) const { return borrow().quotient_dims(log_n); }
   std::map<std::string, std::vector<Matrix<F>>> to_matrices() const { return borrow().to_matrices(); }
   size_t num_constraints() const { return borrow().num_constraints(); }
   size_t num_instance_variables() const { return borrow().num_instance_variables; }

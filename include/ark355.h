@@ -517,6 +517,47 @@ int32_t ark355_sr1cs_matrix(ark355_ctx* ctx, const ark355_sr1cs* s, int32_t whic
 int32_t ark355_sr1cs_assignment(ark355_ctx* ctx, const ark355_sr1cs* s, const uint8_t* z, uint64_t z_len, uint8_t* z_out);
 int32_t ark355_sr1cs_assignment_dev(ark355_ctx* ctx, const ark355_sr1cs* s, const void* d_z, uint64_t z_len, void* d_z_out);
 
+/* ---- Quotient polynomial of any predicate (snark_amd/csrc/quotient_impl.cuh) -------------------------------------------------
+ * The step between the assignment of a resident system and the MSMs of a prover over it: for predicate `predicate` (the CALLER's
+ * index, as in ark355_gr1cs_eval) with polynomial P of arity t over the matrices M_0 .. M_{t-1} of n rows
+ * (predicate/polynomial_constraint.rs; for the system of ark355_sr1cs_system P = x0^2 - x1, sr1cs/mod.rs), on ANY handle -- from
+ * ark355_gr1cs_load, from ark355_gr1cs_from_lcs, or the borrowed one of ark355_sr1cs_system:
+ *     h(X) = P(m_0(X), .., m_{t-1}(X)) / (X^N - 1).
+ * Domain: N = 2^log_domain.  log_n = 0 selects the smallest power of two >= max(n, 2); otherwise log_domain = log_n, and
+ *   2^log_n < n is ARK355_EINVAL.  m_k interpolates M_k z over H_N = {w_N^i}; rows n .. N-1 are zero rows: every m_k is 0 there.
+ *   A NON-ZERO CONSTANT TERM of P therefore makes the padded rows unsatisfied unless N = n.
+ * degree: d, the total degree of P as written: the maximum over its terms of the sum of the term's exponents, summed in 64 bits
+ *   (an exponent is any uint32_t).  A term whose coefficient is zero still counts; x^0 contributes 0; a term without factors has
+ *   degree 0, as has a polynomial without terms.
+ * Extension: D = 1 for d <= 2, otherwise the smallest power of two >= d - 1; log_ext = log2(D); h_len = D * N.
+ * Output: h_out = h_len Fr, Montgomery, fully reduced: the coefficients (h_out[j] that of X^j) of the unique polynomial of
+ *   degree < D N that agrees with P(m_0(X), .., m_{t-1}(X)) / (X^N - 1) on the coset g H_{DN} = {g w_{DN}^i}, g the generator of
+ *   Fr's multiplicative group that every coset transform of this library uses (ark355_ntt_fr with coset = 1) and
+ *   w_{DN} the 2^(log_domain + log_ext)-th root of unity of ark355_ntt_fr.
+ *   For an assignment that satisfies all N rows (the padded ones included) this is the exact quotient: its degree is at most
+ *   (d - 1) N - d and every coefficient above that is zero.  For any other assignment the output is still the value the sentence
+ *   above defines -- the promise ark355_witness_map makes for a b - c -- and proves nothing.
+ * n = 0 is legal: N = 2, every m_k = 0, h is the constant P(0, .., 0) divided by X^N - 1 on the coset and interpolated.
+ * Errors (each leaves a message for ark355_last_error when a context was passed; all are detected before any allocation or
+ * launch): ARK355_E_POLY_DEGREE_TOO_LARGE when log_domain or log_domain + log_ext exceeds the two-adicity of Fr (32 for
+ * BLS12-381, 28 for BN254); ARK355_EINVAL for a NULL pointer, a predicate index out of range, 2^log_n < n, or a handle built
+ * through a context of another device; ARK355_E_ASSIGNMENT_MISSING if z_len < num_instance + num_witness.  ARK355_ENOMEM when
+ * the scratch does not fit the device: 2 t vectors of D N Fr (grow-only, owned by the context) plus the D constants
+ * (g^N w_D^s - 1)^-1.
+ * ark355_gr1cs_quotient_dims runs no HIP call and needs no context; any out pointer may be NULL.  degree, log_domain and
+ * log_ext are written whenever the handle and the index are valid -- a refusal reports the 64-bit degree it refused -- and
+ * h_len is 0 unless the return value is ARK355_OK.  Its refusals are the ones ark355_gr1cs_quotient makes about the same
+ * (g, predicate, log_n), with the same codes.
+ * ark355_gr1cs_quotient reads z (num_instance + num_witness Fr, Montgomery) and writes h_out in host memory.  The _dev variant
+ * reads d_z and writes d_h_out (h_len Fr) in device memory; like ark355_sr1cs_assignment_dev it works on the context's stream
+ * and returns when d_h_out is complete, so its output may feed ark355_msm_dev (scalars_mont = 1) directly. */
+int32_t ark355_gr1cs_quotient_dims(const ark355_gr1cs* g, uint32_t predicate, uint32_t log_n, uint64_t* degree,
+                                   uint32_t* log_domain, uint32_t* log_ext, uint64_t* h_len);
+int32_t ark355_gr1cs_quotient(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t* z, uint64_t z_len,
+                              uint32_t log_n, uint8_t* h_out);
+int32_t ark355_gr1cs_quotient_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* d_z, uint64_t z_len,
+                                  uint32_t log_n, void* d_h_out);
+
 /* in-place radix-2 NTT over Fr, natural order in and out (ark-poly Radix2EvaluationDomain
  * fft / ifft / coset_fft / coset_ifft).  Errors with ARK355_E_POLY_DEGREE_TOO_LARGE past the
  * field's two-adicity. */

@@ -463,6 +463,27 @@ extern "C" {
     ) -> i32;
     pub fn ark355_sr1cs_assignment(ctx: *mut ark355_ctx, s: *const ark355_sr1cs, z: *const u8, z_len: u64, z_out: *mut u8) -> i32;
     pub fn ark355_sr1cs_assignment_dev(ctx: *mut ark355_ctx, s: *const ark355_sr1cs, d_z: *const c_void, z_len: u64, d_z_out: *mut c_void) -> i32;
+    /// quotient of predicate `predicate` over N = 2^log_domain (`log_n` = 0: the smallest power of two >= max(n, 2)); see
+    /// include/ark355.h for the definition of degree, D = 2^log_ext and h_len = D * N.  No HIP call; any out pointer may be null.
+    pub fn ark355_gr1cs_quotient_dims(
+        g: *const ark355_gr1cs,
+        predicate: u32,
+        log_n: u32,
+        degree: *mut u64,
+        log_domain: *mut u32,
+        log_ext: *mut u32,
+        h_len: *mut u64,
+    ) -> i32;
+    pub fn ark355_gr1cs_quotient(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, predicate: u32, z: *const u8, z_len: u64, log_n: u32, h_out: *mut u8) -> i32;
+    pub fn ark355_gr1cs_quotient_dev(
+        ctx: *mut ark355_ctx,
+        g: *const ark355_gr1cs,
+        predicate: u32,
+        d_z: *const c_void,
+        z_len: u64,
+        log_n: u32,
+        d_h_out: *mut c_void,
+    ) -> i32;
 
     pub fn ark355_ntt_fr(ctx: *mut ark355_ctx, curve: i32, data: *mut u8, log_n: u32, inverse: i32, coset: i32) -> i32;
     pub fn ark355_ntt_fr_dev(

@@ -50,7 +50,8 @@ SYMBOLS = [
     "ark355_gr1cs_mat_vec", "ark355_gr1cs_eval", "ark355_gr1cs_r1cs",
     "ark355_gr1cs_dims", "ark355_gr1cs_pred_dims", "ark355_gr1cs_matrix", "ark355_gr1cs_from_lcs",
     "ark355_sr1cs_from_r1cs", "ark355_sr1cs_free", "ark355_sr1cs_system", "ark355_sr1cs_dims", "ark355_sr1cs_var_map",
-    "ark355_sr1cs_matrix", "ark355_sr1cs_assignment", "ark355_sr1cs_assignment_dev", "ark355_ntt_fr", "ark355_ntt_fr_dev",
+    "ark355_sr1cs_matrix", "ark355_sr1cs_assignment", "ark355_sr1cs_assignment_dev",
+    "ark355_gr1cs_quotient_dims", "ark355_gr1cs_quotient", "ark355_gr1cs_quotient_dev", "ark355_ntt_fr", "ark355_ntt_fr_dev",
     "ark355_msm_g1", "ark355_msm_g2", "ark355_bases_load", "ark355_bases_free", "ark355_msm_dev",
     "ark355_msm_dev_partial", "ark355_xyzz_sum", "ark355_fixed_base_mul", "ark355_get_timings",
     "ark355_get_kernel_stats", "ark355_pk_load_shard", "ark355_partial_size", "ark355_prove_shard",
@@ -205,6 +206,9 @@ class Lib:
         d.ark355_sr1cs_matrix.argtypes = [vp, vp, i32, vp, vp, vp, u64]
         d.ark355_sr1cs_assignment.argtypes = [vp, vp, vp, u64, vp]
         d.ark355_sr1cs_assignment_dev.argtypes = [vp, vp, vp, u64, vp]
+        d.ark355_gr1cs_quotient_dims.argtypes = [vp, u32, u32, P(u64), P(u32), P(u32), P(u64)]
+        d.ark355_gr1cs_quotient.argtypes = [vp, vp, u32, vp, u64, u32, vp]
+        d.ark355_gr1cs_quotient_dev.argtypes = [vp, vp, u32, vp, u64, u32, vp]
         d.ark355_ntt_fr.argtypes = [vp, i32, vp, u32, i32, i32]
         d.ark355_ntt_fr_dev.argtypes = [vp, i32, vp, vp, u32, i32, i32, vp]
         d.ark355_msm_g1.argtypes = [vp, i32, vp, vp, u64, vp]
@@ -678,6 +682,23 @@ class Lib:
         zb, k = _buf(z)
         self.check(ctx, self.dll.ark355_gr1cs_eval(ctx, g, predicate, zb, z_len, out.ctypes.data_as(C.c_void_p)))
         return out.tobytes()[:n * fr_size]
+
+    def gr1cs_quotient_dims(self, g, predicate, log_n=0):
+        """(degree, log_domain, log_ext, h_len) of the quotient of one predicate (no device work)"""
+        deg, ld, le, hl = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        self.check(None, self.dll.ark355_gr1cs_quotient_dims(g, predicate, log_n, C.byref(deg), C.byref(ld), C.byref(le), C.byref(hl)))
+        return deg.value, ld.value, le.value, hl.value
+
+    def gr1cs_quotient(self, ctx, g, predicate, z, z_len, log_n, h_len, fr_size):
+        """h = P(m_0, .., m_{t-1}) / (X^N - 1): h_len coefficients, Montgomery"""
+        out = np.zeros(max(1, h_len * fr_size), dtype=np.uint8)
+        zb, k = _buf(z)
+        self.check(ctx, self.dll.ark355_gr1cs_quotient(ctx, g, predicate, zb, z_len, log_n, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:h_len * fr_size]
+
+    def gr1cs_quotient_dev(self, ctx, g, predicate, d_z, z_len, log_n, d_h_out):
+        """the same on device pointers (ints): d_h_out takes h_len Fr; returns when it is complete"""
+        self.check(ctx, self.dll.ark355_gr1cs_quotient_dev(ctx, g, predicate, C.c_void_p(d_z), z_len, log_n, C.c_void_p(d_h_out)))
 
     def gr1cs_r1cs(self, ctx, g):
         """an ark355_r1cs handle from the predicate labelled "R1CS" (refused when another predicate has a row)"""

@@ -7,6 +7,7 @@
 #include "groth16_impl.cuh"
 #include "gr1cs_impl.cuh"
 #include "sr1cs_impl.cuh"
+#include "quotient_impl.cuh"
 #include "lcmap_impl.cuh"
 #include "setup_impl.cuh"
 #include "wire_impl.cuh"
@@ -246,6 +247,20 @@ struct Api {
   static void sr1cs_assignment(ark355_ctx* ctx, ProverScratch& sc, GenericScratch& gs, const Sr1csDev& s, const void* z, void* z_out,
                                bool on_dev) {
     ark355::sr1cs_assignment<Curve>(s, z, z_out, on_dev, sc.zx, gs.a, ctx->stream);
+  }
+
+  // ---- quotient of a predicate (quotient_impl.cuh) -----------------------------------------------------------------
+  static int32_t gr1cs_quotient_dims(const Gr1csPred& P, uint32_t log_n, QuotientDims* q, std::string* why) {
+    return quotient_dims(P, log_n, (uint32_t)Fr::Params::TWO_ADICITY, q, why);
+  }
+  // z and h_out both on the host or both on the device; returns when h_out is complete
+  static void gr1cs_quotient(ark355_ctx* ctx, ProverScratch& sc, QuotientScratch& qs, const Gr1csDev& g, uint32_t p,
+                             const QuotientDims& q, const void* z, bool on_dev, void* h_out) {
+    hipStream_t st = ctx->stream;
+    const void* d_z = on_dev ? z : gr1cs_stage_z(ctx, sc, g, (const uint8_t*)z);
+    void* d_h = quotient_run<Curve>(ctx, g, g.preds[p], q, d_z, qs, st);
+    ARK_CHECK_HIP(hipMemcpyAsync(h_out, d_h, q.h_len * sizeof(Fr), on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
   }
 
   static void ntt_host(ark355_ctx* ctx, GenericScratch& g, uint8_t* data, uint32_t log_n, bool inverse, bool coset) {

@@ -42,6 +42,7 @@ namespace {
 struct CtxExtra {
   ProverScratch prover;
   GenericScratch generic;
+  QuotientScratch quotient;
   std::vector<ark355_ctx*> lanes;     // child contexts of ark355_prove_batch (same device, private streams/scratch)
   ~CtxExtra();
 };
@@ -103,7 +104,7 @@ int32_t guarded(ark355_ctx* ctx, Fn&& fn, bool locked = false) {
 
 extern "C" {
 
-uint32_t ark355_version(void) { return (0u << 16) | 3u; }
+uint32_t ark355_version(void) { return (0u << 16) | 4u; }
 
 int32_t ark355_sizes(int32_t curve, uint32_t what[4]) {
   return guarded(nullptr, [&] { CURVE_DISPATCH(curve, A::sizes(what)); });
@@ -551,6 +552,7 @@ int32_t ark355_gr1cs_load(ark355_ctx* ctx, int32_t curve, uint64_t ell, uint64_t
   return guarded(ctx, [&] {
     Gr1csDev* d = nullptr;
     CURVE_DISPATCH(curve, d = A::gr1cs_load(ell, w, preds, n_preds));
+    d->device = ctx->device;
     *out = new ark355_gr1cs{d};
   });
 }
@@ -658,6 +660,7 @@ int32_t ark355_gr1cs_from_lcs(ark355_ctx* ctx, int32_t curve, const ark355_lc_sy
   return guarded(ctx, [&] {
     Gr1csDev* d = nullptr;
     CURVE_DISPATCH(curve, d = A::gr1cs_from_lcs(ctx, *system, preds, n_preds));
+    d->device = ctx->device;
     *out = new ark355_gr1cs{d};
   });
 }
@@ -740,6 +743,61 @@ int32_t ark355_sr1cs_assignment(ark355_ctx* ctx, const ark355_sr1cs* s, const ui
 }
 int32_t ark355_sr1cs_assignment_dev(ark355_ctx* ctx, const ark355_sr1cs* s, const void* d_z, uint64_t z_len, void* d_z_out) {
   return sr1cs_assignment_common(ctx, s, d_z, z_len, d_z_out, true);
+}
+
+// ---- quotient of a predicate (quotient_impl.cuh) -------------------------------------------------------------------------
+
+// the dimensions of one call, or the code that refuses them; *why is set with every refusal
+static int32_t quotient_dims_common(const ark355_gr1cs* g, uint32_t predicate, uint32_t log_n, QuotientDims* q, std::string* why) {
+  if (!g || !g->d) {
+    *why = "the gr1cs handle is NULL";
+    return ARK355_EINVAL;
+  }
+  if (predicate >= g->d->preds.size()) {
+    *why = "predicate index out of range";
+    return ARK355_EINVAL;
+  }
+  int32_t rc = ARK355_EINVAL;
+  const int32_t caught = guarded(nullptr, [&] {
+    CURVE_DISPATCH(g->d->curve, rc = A::gr1cs_quotient_dims(g->d->preds[predicate], log_n, q, why));
+  });
+  return caught != ARK355_OK ? caught : rc;
+}
+
+int32_t ark355_gr1cs_quotient_dims(const ark355_gr1cs* g, uint32_t predicate, uint32_t log_n, uint64_t* degree,
+                                   uint32_t* log_domain, uint32_t* log_ext, uint64_t* h_len) {
+  QuotientDims q;
+  std::string why;
+  const int32_t rc = quotient_dims_common(g, predicate, log_n, &q, &why);
+  if (degree) *degree = q.degree;
+  if (log_domain) *log_domain = q.log_domain;
+  if (log_ext) *log_ext = q.log_ext;
+  if (h_len) *h_len = q.h_len;
+  return rc;
+}
+
+static int32_t quotient_common(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* z, uint64_t z_len,
+                               uint32_t log_n, void* h_out, bool on_dev) {
+  if (!ctx) return ARK355_EINVAL;
+  QuotientDims q;
+  std::string why;
+  if (const int32_t rc = quotient_dims_common(g, predicate, log_n, &q, &why)) return refuse(ctx, ("ark355_gr1cs_quotient: " + why).c_str(), rc);
+  if (!z || !h_out) return refuse(ctx, "ark355_gr1cs_quotient: z / h_out is NULL");
+  if (g->d->device >= 0 && g->d->device != ctx->device)
+    return refuse(ctx, "ark355_gr1cs_quotient: the gr1cs handle lives on another device than the context");
+  if (z_len < g->d->m) return refuse(ctx, "assignment shorter than num_instance + num_witness", ARK355_E_ASSIGNMENT_MISSING);
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(g->d->curve, A::gr1cs_quotient(ctx, ex.prover, ex.quotient, *g->d, predicate, q, z, on_dev, h_out));
+  });
+}
+int32_t ark355_gr1cs_quotient(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t* z, uint64_t z_len,
+                              uint32_t log_n, uint8_t* h_out) {
+  return quotient_common(ctx, g, predicate, z, z_len, log_n, h_out, false);
+}
+int32_t ark355_gr1cs_quotient_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* d_z, uint64_t z_len,
+                                  uint32_t log_n, void* d_h_out) {
+  return quotient_common(ctx, g, predicate, d_z, z_len, log_n, d_h_out, true);
 }
 
 int32_t ark355_ntt_fr(ark355_ctx* ctx, int32_t curve, uint8_t* data, uint32_t log_n, int32_t inverse, int32_t coset) {

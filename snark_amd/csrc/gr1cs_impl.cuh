@@ -41,6 +41,7 @@ struct Gr1csPred {
   uint32_t rank = 0;             // position of the label in byte-wise lexicographic order
   uint64_t n = 0;
   bool r1cs_shape = false;       // arity 3 and the polynomial is x0 x1 - x2
+  uint64_t degree = 0;           // total degree of the polynomial as written (gr1cs_program_degree): quotient_impl.cuh
   std::vector<uint64_t> nnz;
   std::vector<DevBuf> row_ptr, col, cidx;
   DevBuf mats;                   // arity x Gr1csMat
@@ -49,6 +50,7 @@ struct Gr1csPred {
 
 struct Gr1csDev {
   int curve = 0;
+  int device = -1;                         // the device of the context that built it (capi.hip); -1: not recorded
   uint64_t ell = 0, w = 0, m = 0, total = 0;
   std::vector<Gr1csPred> preds;            // in the caller's order
   DevBuf pool;                             // interned coefficients of all matrices and polynomials; pool[0] == 1
@@ -214,6 +216,21 @@ static std::vector<uint32_t> gr1cs_program(FrInterner<Fr>& pool, uint32_t n_term
   return prog;
 }
 
+// total degree of a program: the maximum over its terms of the sum of the exponents, in 64 bits (an exponent is any uint32_t);
+// a term counts whatever its coefficient, x^0 contributes 0
+static inline uint64_t gr1cs_program_degree(const std::vector<uint32_t>& prog) {
+  uint64_t degree = 0;
+  size_t pc = 1;
+  for (uint32_t t = 0; t < prog[0]; t++) {
+    const uint32_t n_factors = prog[pc + 1];
+    pc += 2;
+    uint64_t sum = 0;
+    for (uint32_t f = 0; f < n_factors; f++, pc += 2) sum += prog[pc + 1];
+    degree = std::max(degree, sum);
+  }
+  return degree;
+}
+
 // the labels in byte-wise lexicographic order, as BTreeMap<String, _> iterates: order[rank] = the caller's index
 static inline std::vector<uint32_t> gr1cs_label_order(const std::vector<const char*>& labels) {
   std::vector<uint32_t> order(labels.size());
@@ -278,6 +295,7 @@ static Gr1csDev* gr1cs_upload(uint64_t ell, uint64_t w, const ark355_predicate_d
     P.r1cs_shape = gr1cs_is_r1cs_polynomial<Fr>(d);
     g->total += P.n;
     const std::vector<uint32_t> prog = gr1cs_program<Fr>(pool, d.n_terms, d.term_coeff, d.term_ptr, d.term_var, d.term_exp);
+    P.degree = gr1cs_program_degree(prog);
     P.prog.alloc(prog.size() * 4);
     ARK_CHECK_HIP(hipMemcpy(P.prog.p, prog.data(), prog.size() * 4, hipMemcpyHostToDevice));
     P.nnz.resize(d.arity);

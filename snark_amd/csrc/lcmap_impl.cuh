@@ -630,6 +630,7 @@ static Gr1csDev* lcs_finalize(const ark355_lc_system_desc& s, const ark355_predi
     poly.term_var = d.term_var;
     poly.term_exp = d.term_exp;
     P.r1cs_shape = gr1cs_is_r1cs_polynomial<Fr>(poly);
+    P.degree = gr1cs_program_degree(progs[p]);
     P.prog.alloc(progs[p].size() * 4);
     ARK_CHECK_HIP(hipMemcpyAsync(P.prog.p, progs[p].data(), progs[p].size() * 4, hipMemcpyHostToDevice, st));
     P.nnz.assign(d.arity, 0);

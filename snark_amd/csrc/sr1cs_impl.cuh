@@ -300,6 +300,7 @@ static Sr1csDev* sr1cs_build(const R1csDev& r, int device, hipStream_t st) {
   // ---- the system -------------------------------------------------------------------------------------------------------
   Gr1csDev& g = s->sys;
   g.curve = Curve::ID;
+  g.device = device;
   g.ell = 1 + P;
   g.w = U + n;
   g.m = g.ell + g.w;
@@ -311,6 +312,7 @@ static Sr1csDev* sr1cs_build(const R1csDev& r, int device, hipStream_t st) {
   Q.rank = 0;
   Q.n = rows;
   Q.r1cs_shape = false;
+  Q.degree = 2;
   Q.nnz = {nnz0, nnz1};
   Q.row_ptr.resize(2);
   Q.col.resize(2);

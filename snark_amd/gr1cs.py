@@ -163,6 +163,29 @@ class GR1CS:
         zb, n = self._z(z)
         return self.lib.gr1cs_eval(self.ctx, self.handle, i, zb, n, self.predicates[i].n, 32)
 
+    def quotient_dims(self, label: str, log_n: int = 0) -> Tuple[int, int, int, int]:
+        """(degree, log_domain, log_ext, h_len) of ``quotient(label, .., log_n)``: the total degree of the polynomial, the
+        evaluation domain N = 2^log_domain (``log_n = 0``: the smallest power of two >= max(n, 2)), the extension D = 2^log_ext
+        (1 up to degree 2, else next_pow2(degree - 1)) and h_len = D * N.  No device work."""
+        self._need()
+        return self.lib.gr1cs_quotient_dims(self.handle, self._index[label], log_n)
+
+    def quotient(self, label: str, z, log_n: int = 0) -> bytes:
+        """h = P(m_0, .., m_{t-1}) / (X^N - 1) of `label`: h_len Montgomery Fr, the coefficients of the polynomial of degree
+        < D N that agrees with the quotient on the coset g H_{DN} (``ark355_gr1cs_quotient``); exact for an assignment that
+        satisfies all N rows, the zero rows past n included"""
+        self._need()
+        i = self._index[label]
+        h_len = self.lib.gr1cs_quotient_dims(self.handle, i, log_n)[3]
+        zb, n = self._z(z)
+        return self.lib.gr1cs_quotient(self.ctx, self.handle, i, zb, n, log_n, h_len, 32)
+
+    def quotient_dev(self, label: str, d_z: int, z_len: int, d_h: int, log_n: int = 0):
+        """the same on device pointers: reads z_len Fr at d_z, writes h_len Fr (``quotient_dims``) at d_h and returns when they
+        are complete -- ready for ``ark355_msm_dev`` over Montgomery scalars"""
+        self._need()
+        self.lib.gr1cs_quotient_dev(self.ctx, self.handle, self._index[label], d_z, z_len, log_n, d_h)
+
     def matrices(self, label: str) -> List[Tuple[np.ndarray, np.ndarray, bytes]]:
         """``to_matrices()[label]`` of the resident system: its arity matrices as (row_ptr u64, col u32, coeff Montgomery bytes),
         the shape ``Lib.r1cs_load`` takes, read back from the device (``ark355_gr1cs_matrix``)"""
