@@ -119,7 +119,14 @@ int32_t ark355_ctx_create(int32_t device_id, ark355_ctx** out) {
   ark355_ctx* ctx = new (std::nothrow) ark355_ctx();
   if (!ctx) return ARK355_ENOMEM;
   ctx->device = device_id;
-  ctx->policy = TunePolicy::from_env();       // the ONLY place the environment is read (policy.h)
+  bool poison_in_env = false;
+  ctx->policy = TunePolicy::from_env(&poison_in_env);       // the ONLY place the policy's environment is read (policy.h)
+  // POISON_ALLOC is process-wide: the environment sets the one copy at the FIRST context that finds the variable (later contexts must
+  // not undo an ark355_ctx_set_policy made in between); every context reports the copy's value
+  static std::atomic<bool> poison_env_applied{false};
+  if (poison_in_env && !poison_env_applied.exchange(true))
+    poison_alloc_byte().store(poison_alloc_clamp(ctx->policy.poison_alloc), std::memory_order_relaxed);
+  ctx->policy.poison_alloc = poison_alloc_byte().load(std::memory_order_relaxed);
   if (hipSetDevice(device_id) != hipSuccess || hipStreamCreate(&ctx->stream) != hipSuccess) {
     delete ctx;
     return ARK355_EHIP;
@@ -160,23 +167,13 @@ void ark355_ctx_destroy(ark355_ctx* ctx) {
 int32_t ark355_host_alloc(uint64_t bytes, void** out) {
   if (!out) return ARK355_EINVAL;
   *out = nullptr;
-  void* p = nullptr;
-#if defined(ARK_EMUL)
-  p = malloc(bytes ? bytes : 1);
+  void* p = pinned_alloc(bytes);
   if (!p) return ARK355_ENOMEM;
-#else
-  if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) return ARK355_ENOMEM;
-#endif
   *out = p;
   return ARK355_OK;
 }
 void ark355_host_free(void* p) {
-  if (!p) return;
-#if defined(ARK_EMUL)
-  free(p);
-#else
-  (void)hipHostFree(p);
-#endif
+  pinned_free(p);
 }
 
 const char* ark355_last_error(const ark355_ctx* ctx) { return ctx ? ctx->last_error.c_str() : "null context"; }
@@ -188,11 +185,16 @@ int32_t ark355_ctx_set_policy(ark355_ctx* ctx, const char* name, int64_t value) 
     ctx->last_error = std::string("unknown policy name: ") + name;
     return ARK355_EINVAL;
   }
+  if (strcmp(name, "POISON_ALLOC") == 0) {
+    ctx->policy.poison_alloc = poison_alloc_clamp(value);
+    poison_alloc_byte().store(ctx->policy.poison_alloc, std::memory_order_relaxed);
+  }
   return ARK355_OK;
 }
 int32_t ark355_ctx_get_policy(ark355_ctx* ctx, const char* name, int64_t* value) {
   if (!ctx || !name || !value) return ARK355_EINVAL;
   std::lock_guard<std::mutex> lk(ctx->mu);
+  if (strcmp(name, "POISON_ALLOC") == 0) ctx->policy.poison_alloc = poison_alloc_byte().load(std::memory_order_relaxed);   // process-wide
   return ctx->policy.get(name, value) == 0 ? ARK355_OK : ARK355_EINVAL;
 }
 int32_t ark355_sched_info(const ark355_ctx* ctx, const ark355_pk* pk, int32_t in_flight, ark355_sched_report* out) {

@@ -54,6 +54,36 @@ struct HipError {
     if (!(cond)) throw ::ark355::HipError{(code), std::string(msg)}; \
   } while (0)
 
+// Policy POISON_ALLOC (policy.h): the one process-wide copy.  -1: off; 0 .. 255: every allocation below is filled with that byte
+// before it is handed out.  Host code only; the proving path never reads it (its scratch is allocated once and grows only).
+inline std::atomic<int32_t>& poison_alloc_byte() {
+  static std::atomic<int32_t> v{-1};
+  return v;
+}
+inline int32_t poison_alloc_clamp(int64_t v) { return (v < 0 || v > 255) ? -1 : (int32_t)v; }
+
+// page-locked host allocation (the landing zones of a proof's copies, ark355_host_alloc); nullptr when the runtime refuses.
+// An emulator header that models pinned memory says so (EMU_HAS_HOST_MALLOC); against one that does not, pinned memory is malloc's.
+#if defined(ARK_EMUL) && !defined(EMU_HAS_HOST_MALLOC)
+inline void* pinned_alloc_raw(size_t n) { return malloc(n); }
+inline void pinned_free(void* p) { free(p); }
+#else
+inline void* pinned_alloc_raw(size_t n) {
+  void* p = nullptr;
+  return hipHostMalloc(&p, n, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+}
+inline void pinned_free(void* p) {
+  if (p) (void)hipHostFree(p);
+}
+#endif
+inline void* pinned_alloc(size_t n) {
+  if (n == 0) n = 1;
+  void* p = pinned_alloc_raw(n);
+  const int32_t pb = poison_alloc_byte().load(std::memory_order_relaxed);
+  if (p && pb >= 0) memset(p, pb, n);
+  return p;
+}
+
 // RAII device allocation
 struct DevBuf {
   void* p = nullptr;
@@ -83,6 +113,16 @@ struct DevBuf {
       throw HipError{ARK355_ENOMEM, "hipMalloc(" + std::to_string(n) + ") failed"};
     }
     bytes = n;
+    const int32_t pb = poison_alloc_byte().load(std::memory_order_relaxed);
+    if (pb >= 0) {
+      // synchronous on purpose: the caller may use the buffer on any stream, and a fill still in flight would hide what it is meant to show
+      hipError_t f = hipMemset(p, pb, n);
+      if (f == hipSuccess) f = hipDeviceSynchronize();
+      if (f != hipSuccess) {
+        release();
+        throw HipError{ARK355_EHIP, "POISON_ALLOC fill of " + std::to_string(n) + " bytes failed"};
+      }
+    }
   }
   // grow-only scratch
   void ensure(size_t n) {

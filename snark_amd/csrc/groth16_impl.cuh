@@ -205,51 +205,29 @@ struct ProverScratch {
   static constexpr size_t STAGE_BYTES = 1024;
   void* stage() {
     if (!h_stage) {
-#if defined(ARK_EMUL)
-      h_stage = malloc(STAGE_BYTES);
-      if (!h_stage) throw HipError{ARK355_ENOMEM, "host allocation failed"};
-#else
-      if (hipHostMalloc(&h_stage, STAGE_BYTES, hipHostMallocDefault) != hipSuccess) {
-        h_stage = nullptr;
-        throw HipError{ARK355_ENOMEM, "hipHostMalloc failed"};
-      }
-#endif
+      h_stage = pinned_alloc(STAGE_BYTES);
+      if (!h_stage) throw HipError{ARK355_ENOMEM, "hipHostMalloc failed"};
     }
     return h_stage;
   }
   void* pinned(size_t bytes) {
     if (bytes > h_pinned_bytes) {
       release_pinned();
-#if defined(ARK_EMUL)
-      h_pinned = malloc(bytes);
-      if (!h_pinned) throw HipError{ARK355_ENOMEM, "host allocation failed"};
-#else
-      if (hipHostMalloc(&h_pinned, bytes, hipHostMallocDefault) != hipSuccess) {
-        h_pinned = nullptr;
-        throw HipError{ARK355_ENOMEM, "hipHostMalloc failed"};
-      }
-#endif
+      h_pinned = pinned_alloc(bytes);
+      if (!h_pinned) throw HipError{ARK355_ENOMEM, "hipHostMalloc failed"};
       h_pinned_bytes = bytes;
     }
     return h_pinned;
   }
   void release_pinned() {
     if (!h_pinned) return;
-#if defined(ARK_EMUL)
-    free(h_pinned);
-#else
-    (void)hipHostFree(h_pinned);
-#endif
+    pinned_free(h_pinned);
     h_pinned = nullptr;
     h_pinned_bytes = 0;
   }
   void release_stage() {
     if (!h_stage) return;
-#if defined(ARK_EMUL)
-    free(h_stage);
-#else
-    (void)hipHostFree(h_stage);
-#endif
+    pinned_free(h_stage);
     h_stage = nullptr;
   }
 };

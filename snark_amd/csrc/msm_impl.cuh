@@ -1078,9 +1078,14 @@ static XYZZ<F> msm_parts_finish(const XYZZ<F>* parts, const MsmPlan& p) {
 template <class F>
 static void msm_prepare_phase(const TunePolicy& pol, const MsmSort& s, MsmBuckets& b, hipStream_t stream, FillBatch* fb = nullptr) {
   const MsmPlan& p = s.plan;
-  b.prepared = true;
+  // The two flags say what HAS been queued, so they are set last: an allocation below that throws must leave them false, or the next
+  // call on this bucket set would skip its sizing and clears and accumulate into buffers of the failed call's making.
+  b.prepared = false;
   b.heavy_cleared = false;
-  if (p.n == 0) return;
+  if (p.n == 0) {
+    b.prepared = true;
+    return;
+  }
   const size_t slot = msm_slot_bytes<F>();
   const uint64_t entries = (uint64_t)p.windows * p.n;
   b.seg_len = msm_seg_len(entries, is_fp2<F>::value, pol.msm_seg);
@@ -1098,6 +1103,7 @@ static void msm_prepare_phase(const TunePolicy& pol, const MsmSort& s, MsmBucket
   b.heavy_count.ensure(16);
   fill_bytes(fb, b.heavy_count.p, 0, 4, stream);
   b.heavy_cleared = true;
+  b.prepared = true;
 }
 
 // destination arrays of the 28-bit accumulation kernels: which = 0 buckets, 1 head, 2 tail

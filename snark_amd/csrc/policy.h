@@ -18,6 +18,9 @@
 //                  PAIRING_DEVICE_MIN (where the Miller loops of ark355_multi_pairing and ark355_verify_batch run),
 //                  PAIRING_EACH_MIN (the same for ark355_pairing_groups and ark355_verify_each), LCS_ROW_LDS_MAX (the longest
 //                  expanded LC that ark355_gr1cs_from_lcs sorts in LDS)
+//   process-wide   POISON_ALLOC: a TEST knob, not a tuning switch.  Device and pinned host buffers are allocated by objects that know no
+//                  context (DevBuf, common.h), so the value is mirrored into ONE atomic of the process (poison_alloc_byte): setting it
+//                  through any context, or through the environment of a context created later, changes it for every context.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -87,6 +90,12 @@ struct TunePolicy {
   int32_t lcs_row_lds_max = 1024; // ark355_gr1cs_from_lcs (lcmap_impl.cuh): an expanded LC of at most this many entries is sorted and merged in the
                                   // LDS of a 64-lane workgroup, a longer one by the any-length path on keys in global memory; clamped to 1 ..
                                   // LCS_LDS_KEYS = 1024, the keys 8 KiB hold.  Tests lower it to reach the long path at small shapes.
+  // ---- process-wide (test knob)
+  int32_t poison_alloc = -1;      // 0 .. 255: every device buffer (DevBuf::alloc) and pinned host buffer is filled with this byte, synchronously,
+                                  // before the allocator returns, so that no test passes because fresh memory happened to hold zeros; -1 (default)
+                                  // off: one relaxed load per allocation.  The field only reports the value: what acts is the process-wide mirror
+                                  // (common.h), written by ark355_ctx_set_policy and, ONCE per process, by ARK355_POISON_ALLOC at the first
+                                  // ark355_ctx_create that finds it: a later context does not undo what ark355_ctx_set_policy has set since.
 
   struct Field {
     const char* name;
@@ -98,7 +107,8 @@ struct TunePolicy {
   // 0 on success, -1 for an unknown name
   int set(const char* name, int64_t v);
   int get(const char* name, int64_t* v) const;
-  static TunePolicy from_env();
+  // poison_alloc_in_env: whether ARK355_POISON_ALLOC was present (the one policy whose value is process-wide, see poison_alloc)
+  static TunePolicy from_env(bool* poison_alloc_in_env = nullptr);
 };
 
 #define ARK_POLICY_FIELD32(n, f) {n, 0, offsetof(TunePolicy, f)}
@@ -136,6 +146,7 @@ inline const TunePolicy::Field* TunePolicy::fields(int* count) {
       ARK_POLICY_FIELD32("PAIRING_DEVICE_MIN", pairing_device_min),
       ARK_POLICY_FIELD32("PAIRING_EACH_MIN", pairing_each_min),
       ARK_POLICY_FIELD32("LCS_ROW_LDS_MAX", lcs_row_lds_max),
+      ARK_POLICY_FIELD32("POISON_ALLOC", poison_alloc),
   };
   *count = (int)(sizeof(tab) / sizeof(tab[0]));
   return tab;
@@ -177,8 +188,9 @@ inline int TunePolicy::get(const char* name, int64_t* v) const {
   return -1;
 }
 
-inline TunePolicy TunePolicy::from_env() {
+inline TunePolicy TunePolicy::from_env(bool* poison_alloc_in_env) {
   TunePolicy p;
+  if (poison_alloc_in_env) *poison_alloc_in_env = false;
   int n = 0;
   const Field* f = fields(&n);
   char var[64];
@@ -186,6 +198,7 @@ inline TunePolicy TunePolicy::from_env() {
     snprintf(var, sizeof(var), "ARK355_%s", f[i].name);
     if (const char* e = getenv(var)) {
       if (e[0]) p.set(f[i].name, strtoll(e, nullptr, 10));
+      if (e[0] && poison_alloc_in_env && strcmp(f[i].name, "POISON_ALLOC") == 0) *poison_alloc_in_env = true;
     }
   }
   // legacy spellings (rounds 1-3): ARK355_SERIAL=1|0, ARK355_EPILOGUE_SYNC=0|1

@@ -1,5 +1,7 @@
 // TEST INFRASTRUCTURE ONLY -- scheduler of the HIP emulator (see hip_emul.h).
 #include "hip_emul.h"
+#include <map>
+#include <mutex>
 
 namespace emu {
 dim3 g_threadIdx, g_blockIdx, g_blockDim, g_gridDim;
@@ -133,5 +135,107 @@ void launch(dim3 grid, dim3 block, size_t smem, const std::function<void()>& bod
         }
       }
   g_dyn_smem = nullptr;
+  mem_check();                           // a kernel that stored past a buffer fails the launch check that follows it
+}
+
+// ---- allocator (see hip_emul.h) ---------------------------------------------------------------------------------------
+// Layout of one block: [GUARD_FRONT bytes POISON_GUARD][body, n bytes][GUARD_BACK bytes POISON_GUARD]; the body is what the
+// caller sees.  The registry is locked: the ranks of a multi-GPU test are threads of one process.
+namespace {
+std::mutex g_mem_mu;
+std::map<char*, size_t> g_live;          // body -> size
+hipError_t g_pending = hipSuccess;
+char g_mem_msg[256] = "no guard-band error";
+
+// first byte of [p, p + n) that is not `v`, or n
+size_t first_not(const unsigned char* p, size_t n, unsigned char v) {
+  uint64_t w;
+  memset(&w, v, sizeof(w));
+  size_t i = 0;
+  for (; i + 8 <= n; i += 8) {
+    uint64_t x;
+    memcpy(&x, p + i, 8);
+    if (x != w) break;
+  }
+  for (; i < n; i++)
+    if (p[i] != v) return i;
+  return n;
+}
+
+// locked.  Reports the first damaged band only while no error is pending, repairs every damaged band.
+void check_block(char* body, size_t n) {
+  unsigned char* front = reinterpret_cast<unsigned char*>(body) - GUARD_FRONT;
+  unsigned char* back = reinterpret_cast<unsigned char*>(body) + n;
+  const size_t f = first_not(front, GUARD_FRONT, POISON_GUARD), b = first_not(back, GUARD_BACK, POISON_GUARD);
+  if (f == GUARD_FRONT && b == GUARD_BACK) return;
+  if (g_pending == hipSuccess) {
+    g_pending = hipErrorEmuGuardBand;
+    if (b != GUARD_BACK)
+      snprintf(g_mem_msg, sizeof(g_mem_msg), "emulator: guard band AFTER an allocation of %zu bytes damaged, first at byte %zu past its end",
+               n, b);
+    else {
+      size_t last = GUARD_FRONT;         // the damaged byte nearest to the body says how far before it the store went
+      while (last > 0 && front[last - 1] == POISON_GUARD) last--;
+      snprintf(g_mem_msg, sizeof(g_mem_msg), "emulator: guard band BEFORE an allocation of %zu bytes damaged, nearest at byte %zu before its start",
+               n, GUARD_FRONT - last + 1);
+    }
+  }
+  memset(front, POISON_GUARD, GUARD_FRONT);
+  memset(back, POISON_GUARD, GUARD_BACK);
+}
+}  // namespace
+
+hipError_t mem_alloc(void** p, size_t n) {
+  *p = nullptr;
+  if (n == 0) n = 1;
+  void* raw = nullptr;
+  if (n > SIZE_MAX - GUARD_FRONT - GUARD_BACK || posix_memalign(&raw, 256, GUARD_FRONT + n + GUARD_BACK) != 0) return hipErrorOutOfMemory;
+  char* body = static_cast<char*>(raw) + GUARD_FRONT;
+  memset(raw, POISON_GUARD, GUARD_FRONT);
+  memset(body, POISON_FRESH, n);
+  memset(body + n, POISON_GUARD, GUARD_BACK);
+  std::lock_guard<std::mutex> lk(g_mem_mu);
+  g_live[body] = n;
+  *p = body;
+  return hipSuccess;
+}
+
+hipError_t mem_free(void* p) {
+  if (!p) return hipSuccess;
+  std::lock_guard<std::mutex> lk(g_mem_mu);
+  auto it = g_live.find(static_cast<char*>(p));
+  if (it == g_live.end()) return hipErrorInvalidValue;          // not ours, or freed twice: left alone
+  check_block(it->first, it->second);
+  memset(it->first, POISON_FREED, it->second);
+  free(it->first - GUARD_FRONT);
+  g_live.erase(it);
+  return g_pending;                      // stays pending: the library's destructors ignore what hipFree returns
+}
+
+void mem_check() {
+  std::lock_guard<std::mutex> lk(g_mem_mu);
+  for (auto& kv : g_live) check_block(kv.first, kv.second);
+}
+
+hipError_t mem_report() {
+  mem_check();
+  std::lock_guard<std::mutex> lk(g_mem_mu);
+  const hipError_t e = g_pending;
+  g_pending = hipSuccess;
+  return e;
+}
+
+hipError_t mem_peek() {
+  mem_check();
+  std::lock_guard<std::mutex> lk(g_mem_mu);
+  return g_pending;
+}
+
+// the ranks of a multi-GPU test are threads: the caller gets its own copy, taken under the lock that guards the writer
+const char* mem_error_string() {
+  static thread_local char mine[sizeof(g_mem_msg)];
+  std::lock_guard<std::mutex> lk(g_mem_mu);
+  memcpy(mine, g_mem_msg, sizeof(mine));
+  return mine;
 }
 }  // namespace emu

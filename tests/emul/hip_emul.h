@@ -193,32 +193,56 @@ typedef EmuEvent* hipEvent_t;
 #define hipMemcpyDeviceToHost 2
 #define hipMemcpyDeviceToDevice 3
 #define hipMemcpyDefault 4
-static inline hipError_t hipMalloc(void** p, size_t n) {
-  *p = malloc(n ? n : 1);
-  return *p ? hipSuccess : hipErrorOutOfMemory;
-}
+#define hipErrorInvalidValue 1
+#define hipErrorEmuGuardBand 9001           // emulator only: something wrote into the guard band of an allocation
+#define hipHostMallocDefault 0u
+#define EMU_HAS_HOST_MALLOC 1             // hipHostMalloc / hipHostFree exist here: the library's pinned buffers go through them (common.h)
+
+// ---- allocator -------------------------------------------------------------------------------------------------------
+// Fresh memory is never zero here and never holds what a freed buffer held: a call that passes only because malloc handed
+// back zero pages, or because the previous owner of a block left plausible values, must not pass on the emulator.
+//   body    filled with POISON_FRESH when allocated, with POISON_FREED before it goes back to the heap
+//   bands   GUARD_FRONT bytes before and GUARD_BACK bytes after the body, filled with POISON_GUARD; every launch, copy, fill,
+//           synchronisation and hipFree walks the bands of the live allocations (emu::mem_check)
+// A damaged band never aborts: it becomes the pending error, which the next hipGetLastError / hipPeekAtLastError /
+// synchronisation / hipFree returns ONCE (the band is repaired, so that one stray store fails the call that made it and
+// not every later test of the process); hipGetErrorString(hipErrorEmuGuardBand) names the allocation's size and the side.
+namespace emu {
+constexpr unsigned char POISON_FRESH = 0xA5, POISON_GUARD = 0xC3, POISON_FREED = 0xDD;
+constexpr size_t GUARD_FRONT = 256, GUARD_BACK = 64;     // the front band also keeps the body at hipMalloc's 256-byte alignment
+hipError_t mem_alloc(void** p, size_t n);
+hipError_t mem_free(void* p);
+void mem_check();                 // walks every live band; damage becomes the pending error
+hipError_t mem_report();          // mem_check, then hands the pending error out and clears it
+hipError_t mem_peek();            // the same without clearing
+const char* mem_error_string();   // text of the last guard-band error (a copy that belongs to the calling thread)
+}  // namespace emu
+
+static inline hipError_t hipMalloc(void** p, size_t n) { return emu::mem_alloc(p, n); }
 template <class T>
 static inline hipError_t hipMalloc(T** p, size_t n) {
   return hipMalloc((void**)p, n);
 }
-static inline hipError_t hipFree(void* p) {
-  free(p);
-  return hipSuccess;
-}
+static inline hipError_t hipFree(void* p) { return emu::mem_free(p); }
+static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = hipHostMallocDefault) { return emu::mem_alloc(p, n); }
+static inline hipError_t hipHostFree(void* p) { return emu::mem_free(p); }
+// copies and fills are "launches" too: an overrun is caught at the copy that made it (a synchronous one reports it itself)
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, int) {
   memmove(d, s, n);
-  return hipSuccess;
+  return emu::mem_report();
 }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, int, hipStream_t) {
   memmove(d, s, n);
+  emu::mem_check();
   return hipSuccess;
 }
 static inline hipError_t hipMemset(void* d, int v, size_t n) {
   memset(d, v, n);
-  return hipSuccess;
+  return emu::mem_report();
 }
 static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) {
   memset(d, v, n);
+  emu::mem_check();
   return hipSuccess;
 }
 static inline hipError_t hipStreamCreate(hipStream_t* s) {
@@ -226,10 +250,10 @@ static inline hipError_t hipStreamCreate(hipStream_t* s) {
   return hipSuccess;
 }
 static inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
-static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
-static inline hipError_t hipGetLastError() { return hipSuccess; }
-static inline hipError_t hipPeekAtLastError() { return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t) { return emu::mem_report(); }
+static inline hipError_t hipDeviceSynchronize() { return emu::mem_report(); }
+static inline hipError_t hipGetLastError() { return emu::mem_report(); }
+static inline hipError_t hipPeekAtLastError() { return emu::mem_peek(); }
 static inline hipError_t hipSetDevice(int) { return hipSuccess; }
 static inline hipError_t hipGetDevice(int* d) {
   *d = 0;
@@ -239,7 +263,7 @@ static inline hipError_t hipGetDeviceCount(int* n) {
   *n = 1;
   return hipSuccess;
 }
-static inline const char* hipGetErrorString(hipError_t) { return "emu"; }
+static inline const char* hipGetErrorString(hipError_t e) { return e == hipErrorEmuGuardBand ? emu::mem_error_string() : "emu"; }
 static inline hipError_t hipEventCreate(hipEvent_t* e) {
   *e = new EmuEvent();
   return hipSuccess;
@@ -254,7 +278,7 @@ static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t = nullptr) {
   e->t = std::chrono::steady_clock::now();
   return hipSuccess;
 }
-static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+static inline hipError_t hipEventSynchronize(hipEvent_t) { return emu::mem_report(); }
 static inline hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
 #ifndef hipErrorNotReady
 #define hipErrorNotReady ((hipError_t)600)

@@ -41,6 +41,8 @@ INSTANCES = {
     "w0": _w0_instance,                                                      # ark355_r1cs_load accepts num_witness = 0
     "N2": _ell1_instance,
     "N4": lambda r: S.mulchain_direct(r, 2),
+    "mulchain70": lambda r: S.mulchain_direct(r, 70),                        # the sizes of the dirty-scratch sequence (dirty_cases.py)
+    "mulchain9": lambda r: S.mulchain_direct(r, 9),
 }
 WHOLE_KEY = ("mulchain13", "bench_lc20", "bench_lc100", "dummy16", "pow2_exact", "n1", "w0")
 
