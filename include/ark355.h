@@ -92,6 +92,8 @@ int32_t ark355_sizes(int32_t curve, uint32_t what[4]);
  *                 PAIRING_EACH_MIN: the "from ... on" of ark355_pairing_groups and ark355_verify_each, in groups / proofs.
  *                 LCS_ROW_LDS_MAX (ark355_gr1cs_from_lcs: the longest expanded LC whose sort-and-merge runs in LDS, 1 .. 1024
  *                 [default 1024, what the workgroup's 8 KiB of keys hold]; longer ones take the path that works at any length).
+ *                 COLS_LANE_MAX (ark355_gr1cs_mat_vec_t / ark355_gr1cs_columns_at: the longest column a single lane sums
+ *                 [default 64; <= 0 selects it]; longer ones are cut into chunks of 2048 entries, one workgroup each).
  * ARK355_EINVAL for an unknown name.  ark355_prove_batch runs its worker contexts under the caller's policy.
  * (No counterpart in the reference: ark-groth16 has no runtime knobs; rayon's thread count is its only one.) */
 int32_t ark355_ctx_set_policy(ark355_ctx* ctx, const char* name, int64_t value);
@@ -558,6 +560,42 @@ int32_t ark355_gr1cs_quotient(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t p
 int32_t ark355_gr1cs_quotient_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* d_z, uint64_t z_len,
                                   uint32_t log_n, void* d_h_out);
 
+/* ---- Column polynomials of any predicate at a point (snark_amd/csrc/columns_impl.cuh) ----------------------------------------
+ * The generator's half of a resident system, for ANY handle (ark355_gr1cs_load, ark355_sr1cs_system, ark355_gr1cs_from_lcs) and
+ * any predicate of it: the scalars of a key over the system are its column polynomials at the trapdoor point tau,
+ *     cols[k][j] = sum_i M_k[i][j] L_i(tau)        (k < t, j < m = num_instance + num_witness),
+ * what R1CSToQAP::instance_map_with_evaluation computes as a, b, c for R1CS (without its extra instance rows: a caller who wants
+ * them appends the rows e_j to M_0).  Fr values are Montgomery images of 32 bytes, tau is a canonical
+ * 32-byte little-endian integer (>= r: ARK355_EINVAL), `predicate` is the CALLER's index.  The _dev variants read and write
+ * device memory of the calling process, work on the context's stream and return when the output is complete, so that
+ * "matrices -> key scalars -> key points" (ark355_gr1cs_columns_at_dev -> ark355_fixed_base_mul_dev, scalars_mont = 1) stays on
+ * the device.  No matrix, and not the Lagrange vector, visits the host.
+ * Refusals, all made before any allocation or launch and all with a message in ark355_last_error; the context works after
+ * every one of them: ARK355_EINVAL for a NULL pointer, a predicate index out of range, tau >= r, 2^log_n < n, y_len < n, a
+ * handle built through a context of another device, t m + 1 >= 2^32 or the predicate's non-zeros summed over its t matrices
+ * >= 2^32; ARK355_E_POLY_DEGREE_TOO_LARGE for a domain beyond the two-adicity of Fr; ARK355_ENOMEM when the scratch does not
+ * fit (it is allocated before the first launch).  Policy COLS_LANE_MAX (per call) moves the threshold between the two gather
+ * paths and never the result. */
+
+/* evaluate_all_lagrange_coefficients: out[i] = L_i(tau) over H_N = {w_N^i}, N = 2^log_n, 0 <= log_n <= two-adicity of Fr
+ * (ARK355_E_POLY_DEGREE_TOO_LARGE beyond it).  tau inside the domain gives the indicator vector; N = 1 gives {1}. */
+int32_t ark355_lagrange_fr(ark355_ctx* ctx, int32_t curve, uint32_t log_n, const uint8_t tau[32], uint8_t* out);
+int32_t ark355_lagrange_fr_dev(ark355_ctx* ctx, int32_t curve, uint32_t log_n, const uint8_t tau[32], void* d_out);
+
+/* Transposed mat_vec_mul for the t matrices of one predicate: out = t x m Fr, matrix-major, m = num_instance + num_witness,
+ * out[k][j] = sum over the STORED entries (i, j, c) of M_k of c * y[i]  (repeated columns of a row each contribute, a stored
+ * zero contributes zero, a column without entries is zero).  y: n Fr (the predicate's rows); y_len < n is ARK355_EINVAL.
+ * Every one of the t m outputs is written.  n = 0 is legal: all zero. */
+int32_t ark355_gr1cs_mat_vec_t(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t* y, uint64_t y_len, uint8_t* out);
+int32_t ark355_gr1cs_mat_vec_t_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* d_y, uint64_t y_len, void* d_out);
+
+/* The column polynomials of predicate `predicate` at tau: out[k][j] = sum_i M_k[i][j] L_i(tau) = (M_k^T L(tau))_j, the
+ * generalisation of R1CSToQAP::instance_map_with_evaluation's a, b, c to any predicate.  Domain exactly as for
+ * ark355_gr1cs_quotient: log_n = 0 selects the smallest power of two >= max(n, 2), otherwise N = 2^log_n and 2^log_n < n is
+ * ARK355_EINVAL; rows n .. N-1 are zero rows.  The Lagrange vector never visits the host. */
+int32_t ark355_gr1cs_columns_at(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t tau[32], uint32_t log_n, uint8_t* out);
+int32_t ark355_gr1cs_columns_at_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t tau[32], uint32_t log_n, void* d_out);
+
 /* in-place radix-2 NTT over Fr, natural order in and out (ark-poly Radix2EvaluationDomain
  * fft / ifft / coset_fft / coset_ifft).  Errors with ARK355_E_POLY_DEGREE_TOO_LARGE past the
  * field's two-adicity. */
@@ -591,6 +629,10 @@ int32_t ark355_xyzz_sum(ark355_ctx* ctx, int32_t curve, int32_t group, const uin
  * circuit_specific_setup (snark/src/lib.rs:43-46) to build the query vectors */
 int32_t ark355_fixed_base_mul(ark355_ctx* ctx, int32_t curve, int32_t group, const uint8_t* base,
                               const uint8_t* scalars, uint64_t n, uint8_t* out_affine);
+/* ark355_fixed_base_mul with the scalars in device memory; scalars_mont != 0: Montgomery images, converted on the device
+ * (the convention of ark355_msm_dev).  Same output bytes as ark355_fixed_base_mul on the same values. */
+int32_t ark355_fixed_base_mul_dev(ark355_ctx* ctx, int32_t curve, int32_t group, const uint8_t* base, const void* d_scalars,
+                                  uint64_t n, int32_t scalars_mont, uint8_t* out_affine);
 
 /* ---- batch verification (SNARK::verify / verify_with_processed_vk, snark/src/lib.rs:59-80) ------
  * Checks `count` proofs of ONE verifying key at once with the random-linear-combination test

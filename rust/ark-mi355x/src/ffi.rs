@@ -485,6 +485,29 @@ extern "C" {
         d_h_out: *mut c_void,
     ) -> i32;
 
+    /// column polynomials of any predicate at a point (include/ark355.h): L_i(tau) over 2^log_n points, the transposed
+    /// products M_k^T y of one predicate, and the two composed; `_dev` variants read and write device memory.
+    pub fn ark355_lagrange_fr(ctx: *mut ark355_ctx, curve: i32, log_n: u32, tau: *const u8, out: *mut u8) -> i32;
+    pub fn ark355_lagrange_fr_dev(ctx: *mut ark355_ctx, curve: i32, log_n: u32, tau: *const u8, d_out: *mut c_void) -> i32;
+    pub fn ark355_gr1cs_mat_vec_t(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, predicate: u32, y: *const u8, y_len: u64, out: *mut u8) -> i32;
+    pub fn ark355_gr1cs_mat_vec_t_dev(
+        ctx: *mut ark355_ctx,
+        g: *const ark355_gr1cs,
+        predicate: u32,
+        d_y: *const c_void,
+        y_len: u64,
+        d_out: *mut c_void,
+    ) -> i32;
+    pub fn ark355_gr1cs_columns_at(ctx: *mut ark355_ctx, g: *const ark355_gr1cs, predicate: u32, tau: *const u8, log_n: u32, out: *mut u8) -> i32;
+    pub fn ark355_gr1cs_columns_at_dev(
+        ctx: *mut ark355_ctx,
+        g: *const ark355_gr1cs,
+        predicate: u32,
+        tau: *const u8,
+        log_n: u32,
+        d_out: *mut c_void,
+    ) -> i32;
+
     pub fn ark355_ntt_fr(ctx: *mut ark355_ctx, curve: i32, data: *mut u8, log_n: u32, inverse: i32, coset: i32) -> i32;
     pub fn ark355_ntt_fr_dev(
         ctx: *mut ark355_ctx,
@@ -527,6 +550,16 @@ extern "C" {
         base: *const u8,
         scalars: *const u8,
         n: u64,
+        out_affine: *mut u8,
+    ) -> i32;
+    pub fn ark355_fixed_base_mul_dev(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        group: i32,
+        base: *const u8,
+        d_scalars: *const c_void,
+        n: u64,
+        scalars_mont: i32,
         out_affine: *mut u8,
     ) -> i32;
 

@@ -51,9 +51,11 @@ SYMBOLS = [
     "ark355_gr1cs_dims", "ark355_gr1cs_pred_dims", "ark355_gr1cs_matrix", "ark355_gr1cs_from_lcs",
     "ark355_sr1cs_from_r1cs", "ark355_sr1cs_free", "ark355_sr1cs_system", "ark355_sr1cs_dims", "ark355_sr1cs_var_map",
     "ark355_sr1cs_matrix", "ark355_sr1cs_assignment", "ark355_sr1cs_assignment_dev",
-    "ark355_gr1cs_quotient_dims", "ark355_gr1cs_quotient", "ark355_gr1cs_quotient_dev", "ark355_ntt_fr", "ark355_ntt_fr_dev",
+    "ark355_gr1cs_quotient_dims", "ark355_gr1cs_quotient", "ark355_gr1cs_quotient_dev",
+    "ark355_lagrange_fr", "ark355_lagrange_fr_dev", "ark355_gr1cs_mat_vec_t", "ark355_gr1cs_mat_vec_t_dev",
+    "ark355_gr1cs_columns_at", "ark355_gr1cs_columns_at_dev", "ark355_ntt_fr", "ark355_ntt_fr_dev",
     "ark355_msm_g1", "ark355_msm_g2", "ark355_bases_load", "ark355_bases_free", "ark355_msm_dev",
-    "ark355_msm_dev_partial", "ark355_xyzz_sum", "ark355_fixed_base_mul", "ark355_get_timings",
+    "ark355_msm_dev_partial", "ark355_xyzz_sum", "ark355_fixed_base_mul", "ark355_fixed_base_mul_dev", "ark355_get_timings",
     "ark355_get_kernel_stats", "ark355_pk_load_shard", "ark355_partial_size", "ark355_prove_shard",
     "ark355_prove_combine", "ark355_prove_batch", "ark355_comm_unique_id", "ark355_comm_init", "ark355_comm_destroy",
     "ark355_prove_sharded", "ark355_prove_sharded_dev", "ark355_point_size", "ark355_pk_load_bytes", "ark355_pk_dims",
@@ -209,6 +211,12 @@ class Lib:
         d.ark355_gr1cs_quotient_dims.argtypes = [vp, u32, u32, P(u64), P(u32), P(u32), P(u64)]
         d.ark355_gr1cs_quotient.argtypes = [vp, vp, u32, vp, u64, u32, vp]
         d.ark355_gr1cs_quotient_dev.argtypes = [vp, vp, u32, vp, u64, u32, vp]
+        d.ark355_lagrange_fr.argtypes = [vp, i32, u32, vp, vp]
+        d.ark355_lagrange_fr_dev.argtypes = [vp, i32, u32, vp, vp]
+        d.ark355_gr1cs_mat_vec_t.argtypes = [vp, vp, u32, vp, u64, vp]
+        d.ark355_gr1cs_mat_vec_t_dev.argtypes = [vp, vp, u32, vp, u64, vp]
+        d.ark355_gr1cs_columns_at.argtypes = [vp, vp, u32, vp, u32, vp]
+        d.ark355_gr1cs_columns_at_dev.argtypes = [vp, vp, u32, vp, u32, vp]
         d.ark355_ntt_fr.argtypes = [vp, i32, vp, u32, i32, i32]
         d.ark355_ntt_fr_dev.argtypes = [vp, i32, vp, vp, u32, i32, i32, vp]
         d.ark355_msm_g1.argtypes = [vp, i32, vp, vp, u64, vp]
@@ -220,6 +228,7 @@ class Lib:
         d.ark355_msm_dev_partial.argtypes = [vp, vp, vp, u64, i32, vp]
         d.ark355_xyzz_sum.argtypes = [vp, i32, i32, vp, u64, vp]
         d.ark355_fixed_base_mul.argtypes = [vp, i32, i32, vp, vp, u64, vp]
+        d.ark355_fixed_base_mul_dev.argtypes = [vp, i32, i32, vp, vp, u64, i32, vp]
         d.ark355_pk_load_shard.argtypes = [vp, i32, P(PkDesc), u32, u32, P(vp)]
         d.ark355_partial_size.argtypes = [i32]
         d.ark355_partial_size.restype = u64
@@ -700,6 +709,39 @@ class Lib:
         """the same on device pointers (ints): d_h_out takes h_len Fr; returns when it is complete"""
         self.check(ctx, self.dll.ark355_gr1cs_quotient_dev(ctx, g, predicate, C.c_void_p(d_z), z_len, log_n, C.c_void_p(d_h_out)))
 
+    # ---- column polynomials of a predicate at a point (csrc/columns_impl.cuh) --------------------------------------
+    def lagrange_fr(self, ctx, curve, log_n, tau: bytes, fr_size=32):
+        """L_i(tau) for i < 2^log_n (tau: canonical 32 bytes, little-endian): 2^log_n Montgomery Fr"""
+        out = np.zeros((1 << log_n) * fr_size, dtype=np.uint8)
+        tb, k = _buf(tau)
+        self.check(ctx, self.dll.ark355_lagrange_fr(ctx, curve, log_n, tb, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()
+
+    def lagrange_fr_dev(self, ctx, curve, log_n, tau: bytes, d_out):
+        tb, k = _buf(tau)
+        self.check(ctx, self.dll.ark355_lagrange_fr_dev(ctx, curve, log_n, tb, C.c_void_p(d_out)))
+
+    def gr1cs_mat_vec_t(self, ctx, g, predicate, y, y_len, out_len, fr_size=32):
+        """M_k^T y of one predicate: out_len = arity * (num_instance + num_witness) Montgomery Fr, matrix-major"""
+        out = np.zeros(max(1, out_len * fr_size), dtype=np.uint8)
+        yb, k = _buf(y if len(y) else b"\0")
+        self.check(ctx, self.dll.ark355_gr1cs_mat_vec_t(ctx, g, predicate, yb, y_len, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:out_len * fr_size]
+
+    def gr1cs_mat_vec_t_dev(self, ctx, g, predicate, d_y, y_len, d_out):
+        self.check(ctx, self.dll.ark355_gr1cs_mat_vec_t_dev(ctx, g, predicate, C.c_void_p(d_y), y_len, C.c_void_p(d_out)))
+
+    def gr1cs_columns_at(self, ctx, g, predicate, tau: bytes, log_n, out_len, fr_size=32):
+        """the column polynomials of one predicate at tau: out_len = arity * (num_instance + num_witness) Montgomery Fr"""
+        out = np.zeros(max(1, out_len * fr_size), dtype=np.uint8)
+        tb, k = _buf(tau)
+        self.check(ctx, self.dll.ark355_gr1cs_columns_at(ctx, g, predicate, tb, log_n, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:out_len * fr_size]
+
+    def gr1cs_columns_at_dev(self, ctx, g, predicate, tau: bytes, log_n, d_out):
+        tb, k = _buf(tau)
+        self.check(ctx, self.dll.ark355_gr1cs_columns_at_dev(ctx, g, predicate, tb, log_n, C.c_void_p(d_out)))
+
     def gr1cs_r1cs(self, ctx, g):
         """an ark355_r1cs handle from the predicate labelled "R1CS" (refused when another predicate has a row)"""
         h = C.c_void_p()
@@ -857,6 +899,14 @@ class Lib:
         pb, k = _buf(partials if count else None)
         self.check(ctx, self.dll.ark355_xyzz_sum(ctx, curve, group, pb, count, out.ctypes.data_as(C.c_void_p)))
         return out.tobytes()
+
+    def fixed_base_mul_dev(self, ctx, curve, group, base: bytes, d_scalars, n, scalars_mont, point_size):
+        """ark355_fixed_base_mul over n scalars in device memory (d_scalars: int); scalars_mont: they are Montgomery images"""
+        out = np.zeros(max(1, n * point_size), dtype=np.uint8)
+        bb, k1 = _buf(base)
+        self.check(ctx, self.dll.ark355_fixed_base_mul_dev(ctx, curve, group, bb, C.c_void_p(d_scalars), n, 1 if scalars_mont else 0,
+                                                           out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:n * point_size]
 
     def fixed_base_mul(self, ctx, curve, group, base: bytes, scalars, n, point_size):
         out = np.zeros(max(1, n * point_size), dtype=np.uint8)

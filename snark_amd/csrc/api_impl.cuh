@@ -8,6 +8,7 @@
 #include "gr1cs_impl.cuh"
 #include "sr1cs_impl.cuh"
 #include "quotient_impl.cuh"
+#include "columns_impl.cuh"
 #include "lcmap_impl.cuh"
 #include "setup_impl.cuh"
 #include "wire_impl.cuh"
@@ -65,6 +66,17 @@ fixed_base_mul_kernel(const Affine<F>* __restrict__ table, const Fr* __restrict_
     if (d) xyzz_madd_ni(acc, table[w * FB_ROW + (d - 1)]);
   }
   out[i] = acc;
+}
+
+// canonical values of n Montgomery images (the device-scalar entry of the fixed-base multiplication)
+template <class Fr>
+__global__ void __launch_bounds__(256)
+fr_from_mont_kernel(const Fr* __restrict__ in, uint64_t n, Fr* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Fr one = Fr::zero();                     // the integer 1: x R * 1 / R = x.  Fr::from_mont calls the out-of-line multiplication,
+  one.l[0] = 1;                            // whose operands travel through 48 bytes of stack per lane; inlined there is none
+  out[i] = Fr::mul(in[i], one);
 }
 
 struct GenericScratch {
@@ -260,6 +272,58 @@ struct Api {
     const void* d_z = on_dev ? z : gr1cs_stage_z(ctx, sc, g, (const uint8_t*)z);
     void* d_h = quotient_run<Curve>(ctx, g, g.preds[p], q, d_z, qs, st);
     ARK_CHECK_HIP(hipMemcpyAsync(h_out, d_h, q.h_len * sizeof(Fr), on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+
+  // ---- column polynomials of a predicate at a point (columns_impl.cuh) ----------------------------------------------
+  static uint32_t two_adicity() { return (uint32_t)Fr::Params::TWO_ADICITY; }
+  // a canonical 32-byte little-endian integer below r -> its Montgomery image; false for a value >= r
+  static bool fr_from_canonical(const uint8_t* bytes, Fr* mont) {
+    Fr c;
+    memcpy(c.l, bytes, sizeof(Fr));
+    if (!fr_canonical(c)) return false;
+    *mont = Fr::to_mont(c);
+    return true;
+  }
+  static int32_t gr1cs_columns_dims(const Gr1csDev& g, const Gr1csPred& P, bool with_domain, uint32_t log_n, ColumnsDims* d,
+                                    std::string* why) {
+    return columns_dims(g, P, with_domain, log_n, two_adicity(), d, why);
+  }
+  // out[i] = L_i(tau) for i < 2^log_n, in host or in device memory; returns when out is complete
+  static void lagrange(ark355_ctx* ctx, ColumnsScratch& cs, uint32_t log_n, const Fr& tau, void* out, bool on_dev) {
+    hipStream_t st = ctx->stream;
+    const size_t bytes = sizeof(Fr) << log_n;
+    if (!on_dev) cs.lag.ensure(bytes);
+    void* d_L = on_dev ? out : cs.lag.p;
+    lagrange_run<Curve>(log_n, tau, d_L, st);
+    if (!on_dev) ARK_CHECK_HIP(hipMemcpyAsync(out, d_L, bytes, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+  // tau == nullptr: out = M_k^T y for the caller's y; otherwise y = (L_i(tau))_i over 2^d.log_domain points, computed into the
+  // scratch.  y and out both on the host or both on the device; every allocation happens before the first launch.
+  static void gr1cs_columns(ark355_ctx* ctx, ColumnsScratch& cs, const Gr1csDev& g, uint32_t p, const ColumnsDims& d, const void* y,
+                            const Fr* tau, bool on_dev, void* out) {
+    hipStream_t st = ctx->stream;
+    const Gr1csPred& P = g.preds[p];
+    const uint32_t lane_max = cols_lane_max(ctx->policy.cols_lane_max);
+    const size_t out_bytes = (size_t)d.cols * sizeof(Fr);
+    columns_reserve<Fr>(cs, d, lane_max);
+    if (tau && d.nnz) cs.lag.ensure(sizeof(Fr) << d.log_domain);
+    if (!on_dev) {
+      cs.out.ensure(out_bytes);
+      if (!tau && d.nnz) cs.y.ensure((size_t)d.n * sizeof(Fr));
+    }
+    const void* d_y = y;
+    if (tau) {
+      if (d.nnz) lagrange_run<Curve>(d.log_domain, *tau, cs.lag.p, st);
+      d_y = cs.lag.p;
+    } else if (!on_dev && d.nnz) {
+      ARK_CHECK_HIP(hipMemcpyAsync(cs.y.p, y, (size_t)d.n * sizeof(Fr), hipMemcpyHostToDevice, st));
+      d_y = cs.y.p;
+    }
+    void* d_out = on_dev ? out : cs.out.p;
+    columns_run<Curve>(g, P, d, d_y, d_out, cs, lane_max, st);
+    if (!on_dev && out_bytes) ARK_CHECK_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     ARK_CHECK_HIP(hipStreamSynchronize(st));
   }
 
@@ -475,22 +539,31 @@ struct Api {
   // a handful of scalars go without the table: building its 8 160 points would cost more than it saves
   static constexpr uint64_t FB_TABLE_MIN = 512;
 
+  // scalars: n canonical values on the host, or (on_dev) n values in device memory, Montgomery images when mont
   template <class F>
-  static void fixed_base_t(ark355_ctx* ctx, GenericScratch& g, const uint8_t* base, const uint8_t* scalars, uint64_t n,
-                           uint8_t* out) {
+  static void fixed_base_t(ark355_ctx* ctx, GenericScratch& g, const uint8_t* base, const void* scalars, uint64_t n,
+                           uint8_t* out, bool on_dev = false, bool mont = false) {
     hipStream_t st = ctx->stream;
     const uint32_t rows = FB_WINDOWS * FB_ROW;
     DevBuf d_base(sizeof(Affine<F>)), d_tx((size_t)rows * sizeof(XYZZ<F>)), d_ta((size_t)rows * sizeof(Affine<F>));
-    g.b.ensure(n * sizeof(Fr));
+    if (!on_dev || mont) g.b.ensure(n * sizeof(Fr));
     g.a.ensure((n ? n : 1) * sizeof(XYZZ<F>));
     g.c.ensure((n ? n : 1) * sizeof(Affine<F>));
     ARK_CHECK_HIP(hipMemcpyAsync(d_base.p, base, sizeof(Affine<F>), hipMemcpyHostToDevice, st));
     if (n) {
       ARK_REQUIRE(n < (1ull << 32), ARK355_EINVAL, "too many scalars");
-      ARK_CHECK_HIP(hipMemcpyAsync(g.b.p, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, st));
+      const Fr* d_k = g.b.as<Fr>();
+      if (!on_dev) {
+        ARK_CHECK_HIP(hipMemcpyAsync(g.b.p, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, st));
+      } else if (mont) {
+        ARK_LAUNCH((fr_from_mont_kernel<Fr>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, (const Fr*)scalars, n, g.b.as<Fr>());
+        ARK_CHECK_LAUNCH();
+      } else {
+        d_k = (const Fr*)scalars;
+      }
       const bool table = n >= FB_TABLE_MIN;
       if (table) fixed_base_table<F>(d_base.as<Affine<F>>(), d_tx.as<XYZZ<F>>(), d_ta.as<Affine<F>>(), st);
-      fixed_base_mul_dev<F>(d_base.as<Affine<F>>(), table ? d_ta.as<Affine<F>>() : nullptr, g.b.as<Fr>(), n, g.a.as<XYZZ<F>>(),
+      fixed_base_mul_dev<F>(d_base.as<Affine<F>>(), table ? d_ta.as<Affine<F>>() : nullptr, d_k, n, g.a.as<XYZZ<F>>(),
                             g.c.as<Affine<F>>(), st);
       ARK_CHECK_HIP(hipMemcpyAsync(out, g.c.p, n * sizeof(Affine<F>), hipMemcpyDeviceToHost, st));
     }
@@ -501,6 +574,11 @@ struct Api {
                          uint64_t n, uint8_t* out) {
     if (group == 1) fixed_base_t<Fq>(ctx, g, base, scalars, n, out);
     else fixed_base_t<Fq2>(ctx, g, base, scalars, n, out);
+  }
+  static void fixed_base_dev(ark355_ctx* ctx, GenericScratch& g, int group, const uint8_t* base, const void* d_scalars, uint64_t n,
+                             bool mont, uint8_t* out) {
+    if (group == 1) fixed_base_t<Fq>(ctx, g, base, d_scalars, n, out, true, mont);
+    else fixed_base_t<Fq2>(ctx, g, base, d_scalars, n, out, true, mont);
   }
 
   // ---- Groth16 generator scalars on the host (the library's own field code, std::thread) ------------------------------

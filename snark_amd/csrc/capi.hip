@@ -43,6 +43,7 @@ struct CtxExtra {
   ProverScratch prover;
   GenericScratch generic;
   QuotientScratch quotient;
+  ColumnsScratch columns;
   std::vector<ark355_ctx*> lanes;     // child contexts of ark355_prove_batch (same device, private streams/scratch)
   ~CtxExtra();
 };
@@ -802,6 +803,95 @@ int32_t ark355_gr1cs_quotient_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32
   return quotient_common(ctx, g, predicate, d_z, z_len, log_n, d_h_out, true);
 }
 
+// ---- column polynomials of a predicate at a point (columns_impl.cuh) -------------------------------------------------------
+
+// tau (canonical, below r) as the Montgomery image of curve `curve`; *why is set with every refusal.  No HIP call.
+static int32_t tau_common(int32_t curve, const uint8_t* tau, BlsCurve::Fr* bls, BnCurve::Fr* bn, std::string* why) {
+  bool ok = false;
+  const int32_t caught = guarded(nullptr, [&] {
+    if (curve == ARK355_BLS12_381) ok = Api<BlsCurve>::fr_from_canonical(tau, bls);
+    else if (curve == ARK355_BN254) ok = Api<BnCurve>::fr_from_canonical(tau, bn);
+    else throw HipError{ARK355_EINVAL, "unknown curve id"};
+  });
+  if (caught != ARK355_OK) {
+    *why = "unknown curve id";
+    return caught;
+  }
+  if (!ok) {
+    *why = "tau is not below r";
+    return ARK355_EINVAL;
+  }
+  return ARK355_OK;
+}
+
+static int32_t lagrange_common(ark355_ctx* ctx, int32_t curve, uint32_t log_n, const uint8_t* tau, void* out, bool on_dev) {
+  if (!ctx) return ARK355_EINVAL;
+  if (!tau || !out) return refuse(ctx, "ark355_lagrange_fr: tau / out is NULL");
+  BlsCurve::Fr t_bls;
+  BnCurve::Fr t_bn;
+  std::string why;
+  if (const int32_t rc = tau_common(curve, tau, &t_bls, &t_bn, &why)) return refuse(ctx, ("ark355_lagrange_fr: " + why).c_str(), rc);
+  const uint32_t two_adicity = curve == ARK355_BLS12_381 ? Api<BlsCurve>::two_adicity() : Api<BnCurve>::two_adicity();
+  if (log_n > two_adicity)
+    return refuse(ctx, "ark355_lagrange_fr: the evaluation domain exceeds the largest radix-2 domain of Fr", ARK355_E_POLY_DEGREE_TOO_LARGE);
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    if (curve == ARK355_BLS12_381) Api<BlsCurve>::lagrange(ctx, ex.columns, log_n, t_bls, out, on_dev);
+    else Api<BnCurve>::lagrange(ctx, ex.columns, log_n, t_bn, out, on_dev);
+  });
+}
+int32_t ark355_lagrange_fr(ark355_ctx* ctx, int32_t curve, uint32_t log_n, const uint8_t tau[32], uint8_t* out) {
+  return lagrange_common(ctx, curve, log_n, tau, out, false);
+}
+int32_t ark355_lagrange_fr_dev(ark355_ctx* ctx, int32_t curve, uint32_t log_n, const uint8_t tau[32], void* d_out) {
+  return lagrange_common(ctx, curve, log_n, tau, d_out, true);
+}
+
+// y != nullptr: the transposed products with the caller's y; tau != nullptr: with the Lagrange vector at tau
+static int32_t columns_common(ark355_ctx* ctx, const char* who, const ark355_gr1cs* g, uint32_t predicate, const void* y, uint64_t y_len,
+                              const uint8_t* tau, uint32_t log_n, void* out, bool on_dev, bool at) {
+  if (!ctx) return ARK355_EINVAL;
+  const std::string pre = std::string(who) + ": ";
+  if (!g || !g->d) return refuse(ctx, (pre + "the gr1cs handle is NULL").c_str());
+  if (!out || (at ? !tau : !y)) return refuse(ctx, (pre + (at ? "tau / out is NULL" : "y / out is NULL")).c_str());
+  if (predicate >= g->d->preds.size()) return refuse(ctx, (pre + "predicate index out of range").c_str());
+  if (g->d->device >= 0 && g->d->device != ctx->device)
+    return refuse(ctx, (pre + "the gr1cs handle lives on another device than the context").c_str());
+  const Gr1csPred& P = g->d->preds[predicate];
+  std::string why;
+  BlsCurve::Fr t_bls;
+  BnCurve::Fr t_bn;
+  if (at) {
+    if (const int32_t rc = tau_common(g->d->curve, tau, &t_bls, &t_bn, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  } else if (y_len < P.n) {
+    return refuse(ctx, (pre + "y is shorter than the predicate's row count").c_str());
+  }
+  ColumnsDims d;
+  int32_t rc = ARK355_EINVAL;
+  const int32_t caught = guarded(nullptr, [&] {
+    CURVE_DISPATCH(g->d->curve, rc = A::gr1cs_columns_dims(*g->d, P, at, log_n, &d, &why));
+  });
+  if (caught != ARK355_OK) return refuse(ctx, (pre + "unknown curve id").c_str(), caught);
+  if (rc != ARK355_OK) return refuse(ctx, (pre + why).c_str(), rc);
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    if (g->d->curve == ARK355_BLS12_381) Api<BlsCurve>::gr1cs_columns(ctx, ex.columns, *g->d, predicate, d, y, at ? &t_bls : nullptr, on_dev, out);
+    else Api<BnCurve>::gr1cs_columns(ctx, ex.columns, *g->d, predicate, d, y, at ? &t_bn : nullptr, on_dev, out);
+  });
+}
+int32_t ark355_gr1cs_mat_vec_t(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t* y, uint64_t y_len, uint8_t* out) {
+  return columns_common(ctx, "ark355_gr1cs_mat_vec_t", g, predicate, y, y_len, nullptr, 0, out, false, false);
+}
+int32_t ark355_gr1cs_mat_vec_t_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* d_y, uint64_t y_len, void* d_out) {
+  return columns_common(ctx, "ark355_gr1cs_mat_vec_t", g, predicate, d_y, y_len, nullptr, 0, d_out, true, false);
+}
+int32_t ark355_gr1cs_columns_at(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t tau[32], uint32_t log_n, uint8_t* out) {
+  return columns_common(ctx, "ark355_gr1cs_columns_at", g, predicate, nullptr, 0, tau, log_n, out, false, true);
+}
+int32_t ark355_gr1cs_columns_at_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t tau[32], uint32_t log_n, void* d_out) {
+  return columns_common(ctx, "ark355_gr1cs_columns_at", g, predicate, nullptr, 0, tau, log_n, d_out, true, true);
+}
+
 int32_t ark355_ntt_fr(ark355_ctx* ctx, int32_t curve, uint8_t* data, uint32_t log_n, int32_t inverse, int32_t coset) {
   if (!ctx || !data) return ARK355_EINVAL;
   if (log_n > 40) return ARK355_E_POLY_DEGREE_TOO_LARGE;
@@ -887,6 +977,16 @@ int32_t ark355_fixed_base_mul(ark355_ctx* ctx, int32_t curve, int32_t group, con
   return guarded(ctx, [&] {
     CtxExtra& ex = extra(ctx);
     CURVE_DISPATCH(curve, A::fixed_base(ctx, ex.generic, group, base, scalars, n, out_affine));
+  });
+}
+int32_t ark355_fixed_base_mul_dev(ark355_ctx* ctx, int32_t curve, int32_t group, const uint8_t* base, const void* d_scalars,
+                                  uint64_t n, int32_t scalars_mont, uint8_t* out_affine) {
+  if (!ctx) return ARK355_EINVAL;
+  if (!base || (n && (!d_scalars || !out_affine))) return refuse(ctx, "ark355_fixed_base_mul_dev: base / d_scalars / out_affine is NULL");
+  if (group != 1 && group != 2) return refuse(ctx, "ark355_fixed_base_mul_dev: group must be 1 or 2");
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(curve, A::fixed_base_dev(ctx, ex.generic, group, base, d_scalars, n, scalars_mont != 0, out_affine));
   });
 }
 

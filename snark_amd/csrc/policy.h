@@ -17,7 +17,8 @@
 //                  host drivers), CHECK_SATISFIED, H_EVAL (read at the first proof of a key), PAIRING_DEVICE,
 //                  PAIRING_DEVICE_MIN (where the Miller loops of ark355_multi_pairing and ark355_verify_batch run),
 //                  PAIRING_EACH_MIN (the same for ark355_pairing_groups and ark355_verify_each), LCS_ROW_LDS_MAX (the longest
-//                  expanded LC that ark355_gr1cs_from_lcs sorts in LDS)
+//                  expanded LC that ark355_gr1cs_from_lcs sorts in LDS), COLS_LANE_MAX (the longest column one lane of
+//                  ark355_gr1cs_mat_vec_t / ark355_gr1cs_columns_at sums)
 //   process-wide   POISON_ALLOC: a TEST knob, not a tuning switch.  Device and pinned host buffers are allocated by objects that know no
 //                  context (DevBuf, common.h), so the value is mirrored into ONE atomic of the process (poison_alloc_byte): setting it
 //                  through any context, or through the environment of a context created later, changes it for every context.
@@ -90,6 +91,11 @@ struct TunePolicy {
   int32_t lcs_row_lds_max = 1024; // ark355_gr1cs_from_lcs (lcmap_impl.cuh): an expanded LC of at most this many entries is sorted and merged in the
                                   // LDS of a 64-lane workgroup, a longer one by the any-length path on keys in global memory; clamped to 1 ..
                                   // LCS_LDS_KEYS = 1024, the keys 8 KiB hold.  Tests lower it to reach the long path at small shapes.
+  int32_t cols_lane_max = 64;     // ark355_gr1cs_mat_vec_t / ark355_gr1cs_columns_at (columns_impl.cuh): a column of at most this many stored
+                                  // entries is summed by one lane, a longer one in chunks of COLS_CHUNK = 2048 entries, one workgroup each.  64 is
+                                  // the generator's SETUP_LANE_COL: a lane's serial chain stays at 64 multiply-adds while the waves of a
+                                  // 2^20-row circuit's few hot columns spread over the device.  <= 0: the default; clamped to 2^20.  Tests lower
+                                  // it to reach the chunked path at small shapes.
   // ---- process-wide (test knob)
   int32_t poison_alloc = -1;      // 0 .. 255: every device buffer (DevBuf::alloc) and pinned host buffer is filled with this byte, synchronously,
                                   // before the allocator returns, so that no test passes because fresh memory happened to hold zeros; -1 (default)
@@ -146,6 +152,7 @@ inline const TunePolicy::Field* TunePolicy::fields(int* count) {
       ARK_POLICY_FIELD32("PAIRING_DEVICE_MIN", pairing_device_min),
       ARK_POLICY_FIELD32("PAIRING_EACH_MIN", pairing_each_min),
       ARK_POLICY_FIELD32("LCS_ROW_LDS_MAX", lcs_row_lds_max),
+      ARK_POLICY_FIELD32("COLS_LANE_MAX", cols_lane_max),
       ARK_POLICY_FIELD32("POISON_ALLOC", poison_alloc),
   };
   *count = (int)(sizeof(tab) / sizeof(tab[0]));

@@ -186,6 +186,35 @@ class GR1CS:
         self._need()
         self.lib.gr1cs_quotient_dev(self.ctx, self.handle, self._index[label], d_z, z_len, log_n, d_h)
 
+    def mat_vec_t(self, label: str, y) -> List[bytes]:
+        """M_k^T y for the matrices of `label` (``ark355_gr1cs_mat_vec_t``): arity byte strings of m = ell + w Montgomery Fr
+        each, column j the sum of c * y[i] over the stored entries (i, j, c).  y: n canonical ints or Montgomery bytes."""
+        self._need()
+        i = self._index[label]
+        yb, n = self._z(y)
+        out = self.lib.gr1cs_mat_vec_t(self.ctx, self.handle, i, yb, n, self.predicates[i].arity * self.m, 32)
+        return [out[k * self.m * 32:(k + 1) * self.m * 32] for k in range(self.predicates[i].arity)]
+
+    def mat_vec_t_dev(self, label: str, d_y: int, y_len: int, d_out: int):
+        """the same on device pointers: reads y_len >= n Fr at d_y, writes arity * m Fr at d_out, returns when complete"""
+        self._need()
+        self.lib.gr1cs_mat_vec_t_dev(self.ctx, self.handle, self._index[label], d_y, y_len, d_out)
+
+    def columns_at(self, label: str, tau: int, log_n: int = 0) -> List[bytes]:
+        """The column polynomials of `label` at tau (``ark355_gr1cs_columns_at``): arity byte strings of m Montgomery Fr,
+        column j of matrix k = sum_i M_k[i][j] L_i(tau) over N = 2^log_n points (``log_n = 0``: as ``quotient_dims``)."""
+        self._need()
+        i = self._index[label]
+        out = self.lib.gr1cs_columns_at(self.ctx, self.handle, i, int(tau).to_bytes(32, "little"), log_n,
+                                        self.predicates[i].arity * self.m, 32)
+        return [out[k * self.m * 32:(k + 1) * self.m * 32] for k in range(self.predicates[i].arity)]
+
+    def columns_at_dev(self, label: str, tau: int, d_out: int, log_n: int = 0):
+        """the same into device memory: arity * m Fr at d_out, complete on return -- ready for
+        ``Lib.fixed_base_mul_dev(.., scalars_mont=1)``"""
+        self._need()
+        self.lib.gr1cs_columns_at_dev(self.ctx, self.handle, self._index[label], int(tau).to_bytes(32, "little"), log_n, d_out)
+
     def matrices(self, label: str) -> List[Tuple[np.ndarray, np.ndarray, bytes]]:
         """``to_matrices()[label]`` of the resident system: its arity matrices as (row_ptr u64, col u32, coeff Montgomery bytes),
         the shape ``Lib.r1cs_load`` takes, read back from the device (``ark355_gr1cs_matrix``)"""

@@ -314,6 +314,28 @@ class Groth16:
         fb = self.lib.is_satisfied(self.ctx, self.load_r1cs(r1cs), z, len(z) // 32)
         return None if fb < 0 else fb
 
+    # ---- generator pieces for keys over any resident system (GR1CS.columns_at_dev feeds the second) ----------------
+    def lagrange(self, log_n: int, tau: int) -> bytes:
+        """``evaluate_all_lagrange_coefficients``: L_i(tau) for i < 2^log_n, Montgomery Fr (``ark355_lagrange_fr``)"""
+        return self.lib.lagrange_fr(self.ctx, self.curve.curve_id, log_n, int(tau).to_bytes(32, "little"))
+
+    def fixed_base_mul(self, group: int, scalars, base: Optional[bytes] = None) -> bytes:
+        """scalars[i] * base (default: the group's generator) as raw affine points; scalars: canonical ints or bytes"""
+        cv = self.curve
+        if not isinstance(scalars, (bytes, bytearray, np.ndarray)):
+            scalars = b"".join(cv.fr_canon(s) for s in scalars)
+        base = base or (cv.g1_gen_raw() if group == 1 else cv.g2_gen_raw())
+        return self.lib.fixed_base_mul(self.ctx, cv.curve_id, group, base, scalars, len(scalars) // 32,
+                                       self.sizes["g1"] if group == 1 else self.sizes["g2"])
+
+    def fixed_base_mul_dev(self, group: int, d_scalars: int, n: int, scalars_mont: bool = True, base: Optional[bytes] = None) -> bytes:
+        """the same over n scalars resident at device pointer d_scalars; ``scalars_mont``: Montgomery images, as
+        ``GR1CS.columns_at_dev`` and ``GR1CS.quotient_dev`` leave them (``ark355_fixed_base_mul_dev``)"""
+        cv = self.curve
+        base = base or (cv.g1_gen_raw() if group == 1 else cv.g2_gen_raw())
+        return self.lib.fixed_base_mul_dev(self.ctx, cv.curve_id, group, base, d_scalars, n, scalars_mont,
+                                           self.sizes["g1"] if group == 1 else self.sizes["g2"])
+
     # ---- closed form from a retained trapdoor (bench / tests: size-independent proof check) -----------------------
     def prove_closed_form(self, pk: ProvingKey, z_ints: Sequence[int], r: int, s: int) -> Proof:
         td = pk.trapdoor
