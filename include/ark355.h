@@ -94,6 +94,8 @@ int32_t ark355_sizes(int32_t curve, uint32_t what[4]);
  *                 [default 1024, what the workgroup's 8 KiB of keys hold]; longer ones take the path that works at any length).
  *                 COLS_LANE_MAX (ark355_gr1cs_mat_vec_t / ark355_gr1cs_columns_at: the longest column a single lane sums
  *                 [default 64; <= 0 selects it]; longer ones are cut into chunks of 2048 entries, one workgroup each).
+ *                 POLY_LANE_COEFFS (ark355_poly_eval_fr / ark355_poly_div_linear_fr: the consecutive coefficients a lane owns
+ *                 [default 8; <= 0 selects it; clamped to 1 .. 8]; a test knob, the outputs do not depend on it).
  * ARK355_EINVAL for an unknown name.  ark355_prove_batch runs its worker contexts under the caller's policy.
  * (No counterpart in the reference: ark-groth16 has no runtime knobs; rayon's thread count is its only one.) */
 int32_t ark355_ctx_set_policy(ark355_ctx* ctx, const char* name, int64_t value);
@@ -595,6 +597,50 @@ int32_t ark355_gr1cs_mat_vec_t_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint3
  * ARK355_EINVAL; rows n .. N-1 are zero rows.  The Lagrange vector never visits the host. */
 int32_t ark355_gr1cs_columns_at(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t tau[32], uint32_t log_n, uint8_t* out);
 int32_t ark355_gr1cs_columns_at_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t tau[32], uint32_t log_n, void* d_out);
+
+/* ---- Polynomial openings: evaluate, divide by X - x, combine (snark_amd/csrc/poly_impl.cuh) -----------------------------------
+ * What a KZG-style prover (Polymath, Pari, Garuda) does with a challenge x once it has committed: evaluate its polynomials at x
+ * (ark-poly DensePolynomial::evaluate), form the witness polynomial (p(X) - p(x)) / (X - x) (ark-poly-commit
+ * KZG10::compute_witness_polynomial) and fold several polynomials with powers of a second challenge (DensePolynomial's Add and
+ * Mul<F>), so that "assignment -> quotient -> commitments -> openings" stays on the device.  The reference tree holds only the
+ * traits and the relations and has no counterpart.
+ * Conventions: Fr values are Montgomery images of 32 bytes; outputs are fully reduced; x and the scalars are canonical 32-byte
+ * little-endian integers, a value >= r is ARK355_EINVAL.  `count` polynomials of `len` coefficients lie back to back:
+ * polynomial k at element k * len, coeffs[k][j] the coefficient of X^j.  The _dev variants read and write device memory of the
+ * calling process on the context's stream and return when the output is complete; x and the scalars stay host pointers.
+ * eval: out[k] = sum_j coeffs[k][j] x^j, count Fr.  len = 0 gives 0; x = 0 gives coeffs[k][0].
+ * div_linear: q_out has the layout of the input, count x len Fr, every element written:
+ *     q_out[k][j] = sum_{i > j} coeffs[k][i] x^(i-j-1) for j < len - 1,  q_out[k][len-1] = 0,  rem_out[k] = p_k(x),
+ *   the bytes ark355_poly_eval_fr returns, so that p_k(X) = q_k(X) (X - x) + rem_k holds coefficient by coefficient, for any p
+ *   and any x, a root or not.  A row of q_out feeds ark355_msm_dev (scalars_mont = 1) with the bases that committed p.
+ *   rem_out may be NULL: nothing beyond q_out is written then.  len = 0 writes only rem = 0; len = 1 gives q = {0}, rem = c_0.
+ *   In place is legal: q_out == coeffs exactly (every lane loads its coefficients before it stores its quotients and reads
+ *   no other lane's input).  Any other overlap of the two ranges, or of rem_out with either, is ARK355_EINVAL.
+ * lincomb: out[j] = sum_k scalars[k] * polys[k][j], len Fr; scalars: count x 32 bytes in HOST memory for both variants.
+ *   count = 0 writes zeros.  out == polys exactly (in place on polynomial 0) is legal; any other overlap is ARK355_EINVAL.
+ * count = 0 returns ARK355_OK and writes nothing, except for lincomb, which writes its len zeros.
+ * Refusals, all made before any allocation or launch, each with a message in ark355_last_error; the context works after every
+ * one of them: ARK355_EINVAL for a NULL pointer where something is to be read or written (x always; the scalars when
+ * count > 0; coefficients and outputs when they hold at least one element), an unknown curve, x or a scalar >= r,
+ * len >= 2^32, count * len >= 2^40 (every index is 64-bit; the bound only keeps byte counts far from overflow),
+ * count > ARK355_POLY_MAX_COUNT (all three entries), and the overlaps above.  ARK355_ENOMEM when the scratch does not fit: it
+ * is grow-only, owned by the context and reserved before the first launch -- 32 * count * (ceil(len / 2048) + ..) bytes of
+ * partial values for eval and div_linear, and for the host variants the staging of the polynomials.
+ * Policy POLY_LANE_COEFFS (per call; default 8; <= 0 selects it; clamped to 1 .. 8): the consecutive coefficients one lane
+ * owns, 256 times as many a workgroup.  It moves the borders of the decomposition and never a byte of any output. */
+#define ARK355_POLY_MAX_COUNT 1024
+int32_t ark355_poly_eval_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* coeffs, uint64_t len, uint64_t count, const uint8_t x[32],
+                            uint8_t* out);
+int32_t ark355_poly_eval_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_coeffs, uint64_t len, uint64_t count,
+                                const uint8_t x[32], void* d_out);
+int32_t ark355_poly_div_linear_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* coeffs, uint64_t len, uint64_t count,
+                                  const uint8_t x[32], uint8_t* q_out, uint8_t* rem_out);
+int32_t ark355_poly_div_linear_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_coeffs, uint64_t len, uint64_t count,
+                                      const uint8_t x[32], void* d_q_out, void* d_rem_out);
+int32_t ark355_poly_lincomb_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* polys, uint64_t len, uint64_t count,
+                               const uint8_t* scalars, uint8_t* out);
+int32_t ark355_poly_lincomb_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_polys, uint64_t len, uint64_t count,
+                                   const uint8_t* scalars, void* d_out);
 
 /* in-place radix-2 NTT over Fr, natural order in and out (ark-poly Radix2EvaluationDomain
  * fft / ifft / coset_fft / coset_ifft).  Errors with ARK355_E_POLY_DEGREE_TOO_LARGE past the

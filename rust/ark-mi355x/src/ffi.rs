@@ -70,6 +70,8 @@ pub const ARK355_VAR_INSTANCE: u64 = 2;
 pub const ARK355_VAR_WITNESS: u64 = 3;
 pub const ARK355_VAR_LC: u64 = 4;
 pub const ARK355_PAIRING_GROUP_MAX: u32 = 64;
+/// most polynomials one call of the `ark355_poly_*` entries takes
+pub const ARK355_POLY_MAX_COUNT: u32 = 1024;
 /// words of the `plan` array of `ark355_diag_msm_sort`
 pub const ARK355_SORT_PLAN_WORDS: usize = 8;
 
@@ -505,6 +507,57 @@ extern "C" {
         predicate: u32,
         tau: *const u8,
         log_n: u32,
+        d_out: *mut c_void,
+    ) -> i32;
+
+    // polynomial openings (snark_amd/csrc/poly_impl.cuh): evaluate, divide by X - x, combine; `count` polynomials of `len`
+    // Montgomery coefficients back to back, x and the scalars canonical 32-byte little-endian integers in host memory
+    pub fn ark355_poly_eval_fr(ctx: *mut ark355_ctx, curve: i32, coeffs: *const u8, len: u64, count: u64, x: *const u8, out: *mut u8) -> i32;
+    pub fn ark355_poly_eval_fr_dev(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        d_coeffs: *const c_void,
+        len: u64,
+        count: u64,
+        x: *const u8,
+        d_out: *mut c_void,
+    ) -> i32;
+    pub fn ark355_poly_div_linear_fr(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        coeffs: *const u8,
+        len: u64,
+        count: u64,
+        x: *const u8,
+        q_out: *mut u8,
+        rem_out: *mut u8,
+    ) -> i32;
+    pub fn ark355_poly_div_linear_fr_dev(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        d_coeffs: *const c_void,
+        len: u64,
+        count: u64,
+        x: *const u8,
+        d_q_out: *mut c_void,
+        d_rem_out: *mut c_void,
+    ) -> i32;
+    pub fn ark355_poly_lincomb_fr(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        polys: *const u8,
+        len: u64,
+        count: u64,
+        scalars: *const u8,
+        out: *mut u8,
+    ) -> i32;
+    pub fn ark355_poly_lincomb_fr_dev(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        d_polys: *const c_void,
+        len: u64,
+        count: u64,
+        scalars: *const u8,
         d_out: *mut c_void,
     ) -> i32;
 

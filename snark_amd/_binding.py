@@ -53,7 +53,9 @@ SYMBOLS = [
     "ark355_sr1cs_matrix", "ark355_sr1cs_assignment", "ark355_sr1cs_assignment_dev",
     "ark355_gr1cs_quotient_dims", "ark355_gr1cs_quotient", "ark355_gr1cs_quotient_dev",
     "ark355_lagrange_fr", "ark355_lagrange_fr_dev", "ark355_gr1cs_mat_vec_t", "ark355_gr1cs_mat_vec_t_dev",
-    "ark355_gr1cs_columns_at", "ark355_gr1cs_columns_at_dev", "ark355_ntt_fr", "ark355_ntt_fr_dev",
+    "ark355_gr1cs_columns_at", "ark355_gr1cs_columns_at_dev",
+    "ark355_poly_eval_fr", "ark355_poly_eval_fr_dev", "ark355_poly_div_linear_fr", "ark355_poly_div_linear_fr_dev",
+    "ark355_poly_lincomb_fr", "ark355_poly_lincomb_fr_dev", "ark355_ntt_fr", "ark355_ntt_fr_dev",
     "ark355_msm_g1", "ark355_msm_g2", "ark355_bases_load", "ark355_bases_free", "ark355_msm_dev",
     "ark355_msm_dev_partial", "ark355_xyzz_sum", "ark355_fixed_base_mul", "ark355_fixed_base_mul_dev", "ark355_get_timings",
     "ark355_get_kernel_stats", "ark355_pk_load_shard", "ark355_partial_size", "ark355_prove_shard",
@@ -217,6 +219,12 @@ class Lib:
         d.ark355_gr1cs_mat_vec_t_dev.argtypes = [vp, vp, u32, vp, u64, vp]
         d.ark355_gr1cs_columns_at.argtypes = [vp, vp, u32, vp, u32, vp]
         d.ark355_gr1cs_columns_at_dev.argtypes = [vp, vp, u32, vp, u32, vp]
+        d.ark355_poly_eval_fr.argtypes = [vp, i32, vp, u64, u64, vp, vp]
+        d.ark355_poly_eval_fr_dev.argtypes = [vp, i32, vp, u64, u64, vp, vp]
+        d.ark355_poly_div_linear_fr.argtypes = [vp, i32, vp, u64, u64, vp, vp, vp]
+        d.ark355_poly_div_linear_fr_dev.argtypes = [vp, i32, vp, u64, u64, vp, vp, vp]
+        d.ark355_poly_lincomb_fr.argtypes = [vp, i32, vp, u64, u64, vp, vp]
+        d.ark355_poly_lincomb_fr_dev.argtypes = [vp, i32, vp, u64, u64, vp, vp]
         d.ark355_ntt_fr.argtypes = [vp, i32, vp, u32, i32, i32]
         d.ark355_ntt_fr_dev.argtypes = [vp, i32, vp, vp, u32, i32, i32, vp]
         d.ark355_msm_g1.argtypes = [vp, i32, vp, vp, u64, vp]
@@ -741,6 +749,49 @@ class Lib:
     def gr1cs_columns_at_dev(self, ctx, g, predicate, tau: bytes, log_n, d_out):
         tb, k = _buf(tau)
         self.check(ctx, self.dll.ark355_gr1cs_columns_at_dev(ctx, g, predicate, tb, log_n, C.c_void_p(d_out)))
+
+    # ---- polynomial openings (csrc/poly_impl.cuh) --------------------------------------------------------------------
+    def poly_eval_fr(self, ctx, curve, coeffs, length, count, x: bytes, fr_size=32):
+        """p_k(x) for `count` polynomials of `length` Montgomery coefficients lying back to back (x: canonical 32 bytes,
+        little-endian): count Montgomery Fr"""
+        out = np.zeros(max(1, count * fr_size), dtype=np.uint8)
+        cb, k = _buf(coeffs if len(coeffs) else b"\0")
+        xb, kx = _buf(x)
+        self.check(ctx, self.dll.ark355_poly_eval_fr(ctx, curve, cb, length, count, xb, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:count * fr_size]
+
+    def poly_eval_fr_dev(self, ctx, curve, d_coeffs, length, count, x: bytes, d_out):
+        xb, kx = _buf(x)
+        self.check(ctx, self.dll.ark355_poly_eval_fr_dev(ctx, curve, C.c_void_p(d_coeffs), length, count, xb, C.c_void_p(d_out)))
+
+    def poly_div_linear_fr(self, ctx, curve, coeffs, length, count, x: bytes, want_rem=True, fr_size=32):
+        """(q, rem): q_k = (p_k - p_k(x)) / (X - x) in the layout of the input, rem_k = p_k(x) (None when want_rem is false)"""
+        q = np.zeros(max(1, count * length * fr_size), dtype=np.uint8)
+        rem = np.zeros(max(1, count * fr_size), dtype=np.uint8)
+        cb, k = _buf(coeffs if len(coeffs) else b"\0")
+        xb, kx = _buf(x)
+        self.check(ctx, self.dll.ark355_poly_div_linear_fr(ctx, curve, cb, length, count, xb, q.ctypes.data_as(C.c_void_p),
+                                                           rem.ctypes.data_as(C.c_void_p) if want_rem else None))
+        return q.tobytes()[:count * length * fr_size], (rem.tobytes()[:count * fr_size] if want_rem else None)
+
+    def poly_div_linear_fr_dev(self, ctx, curve, d_coeffs, length, count, x: bytes, d_q_out, d_rem_out=None):
+        """the same on device pointers (ints); d_q_out == d_coeffs divides in place; d_rem_out may be None"""
+        xb, kx = _buf(x)
+        self.check(ctx, self.dll.ark355_poly_div_linear_fr_dev(ctx, curve, C.c_void_p(d_coeffs), length, count, xb, C.c_void_p(d_q_out),
+                                                               C.c_void_p(d_rem_out) if d_rem_out else None))
+
+    def poly_lincomb_fr(self, ctx, curve, polys, length, count, scalars: bytes, fr_size=32):
+        """sum_k scalars[k] polys[k]: `length` Montgomery Fr (scalars: count canonical 32-byte integers)"""
+        out = np.zeros(max(1, length * fr_size), dtype=np.uint8)
+        pb, k = _buf(polys if len(polys) else b"\0")
+        sb, ks = _buf(scalars if len(scalars) else b"\0")
+        self.check(ctx, self.dll.ark355_poly_lincomb_fr(ctx, curve, pb, length, count, sb, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:length * fr_size]
+
+    def poly_lincomb_fr_dev(self, ctx, curve, d_polys, length, count, scalars: bytes, d_out):
+        """the same on device pointers (ints); the scalars stay host bytes; d_out == d_polys combines in place on polynomial 0"""
+        sb, ks = _buf(scalars if len(scalars) else b"\0")
+        self.check(ctx, self.dll.ark355_poly_lincomb_fr_dev(ctx, curve, C.c_void_p(d_polys), length, count, sb, C.c_void_p(d_out)))
 
     def gr1cs_r1cs(self, ctx, g):
         """an ark355_r1cs handle from the predicate labelled "R1CS" (refused when another predicate has a row)"""

@@ -9,6 +9,7 @@
 #include "sr1cs_impl.cuh"
 #include "quotient_impl.cuh"
 #include "columns_impl.cuh"
+#include "poly_impl.cuh"
 #include "lcmap_impl.cuh"
 #include "setup_impl.cuh"
 #include "wire_impl.cuh"
@@ -324,6 +325,73 @@ struct Api {
     void* d_out = on_dev ? out : cs.out.p;
     columns_run<Curve>(g, P, d, d_y, d_out, cs, lane_max, st);
     if (!on_dev && out_bytes) ARK_CHECK_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+
+  // ---- polynomial openings (poly_impl.cuh): the refusals are capi.hip's; every allocation happens before the first launch --
+  // out[k] = p_k(x); coeffs and out both on the host or both on the device; returns when out is complete
+  static void poly_eval(ark355_ctx* ctx, PolyScratch& ps, const void* coeffs, uint64_t len, uint64_t count, const Fr& x, void* out,
+                        bool on_dev) {
+    hipStream_t st = ctx->stream;
+    if (!count) return;
+    const PolyPlan plan = poly_plan(len, count, poly_lane_coeffs(ctx->policy.poly_lane_coeffs));
+    const size_t bytes = (size_t)count * len * sizeof(Fr), out_bytes = (size_t)count * sizeof(Fr);
+    poly_reserve<Fr>(ps, plan, count, false);
+    if (!on_dev) {
+      ps.in.ensure(bytes);
+      ps.small.ensure(out_bytes);
+      if (bytes) ARK_CHECK_HIP(hipMemcpyAsync(ps.in.p, coeffs, bytes, hipMemcpyHostToDevice, st));
+    }
+    void* d_out = on_dev ? out : ps.small.p;
+    poly_eval_run<Curve>(on_dev ? coeffs : ps.in.p, count, plan, x, d_out, ps, st);
+    if (!on_dev) ARK_CHECK_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+  // q[k] = (p_k - p_k(x)) / (X - x), rem[k] = p_k(x) (rem may be null); the host variant divides in place on its staging
+  static void poly_div_linear(ark355_ctx* ctx, PolyScratch& ps, const void* coeffs, uint64_t len, uint64_t count, const Fr& x,
+                              void* q, void* rem, bool on_dev) {
+    hipStream_t st = ctx->stream;
+    if (!count) return;
+    const PolyPlan plan = poly_plan(len, count, poly_lane_coeffs(ctx->policy.poly_lane_coeffs));
+    const size_t bytes = (size_t)count * len * sizeof(Fr), rem_bytes = (size_t)count * sizeof(Fr);
+    if (!len) {                                          // nothing to divide: only the remainder, zero, is written
+      if (!rem) return;
+      if (on_dev) {
+        ARK_CHECK_HIP(hipMemsetAsync(rem, 0, rem_bytes, st));
+        ARK_CHECK_HIP(hipStreamSynchronize(st));
+      } else {
+        memset(rem, 0, rem_bytes);
+      }
+      return;
+    }
+    poly_reserve<Fr>(ps, plan, count, !rem || !on_dev);
+    if (!on_dev) {
+      ps.in.ensure(bytes);
+      ARK_CHECK_HIP(hipMemcpyAsync(ps.in.p, coeffs, bytes, hipMemcpyHostToDevice, st));
+    }
+    void* d_q = on_dev ? q : ps.in.p;
+    void* d_rem = on_dev ? rem : ps.rem.p;
+    poly_div_run<Curve>(on_dev ? coeffs : ps.in.p, count, plan, x, d_q, d_rem, ps, st);
+    if (!on_dev) {
+      ARK_CHECK_HIP(hipMemcpyAsync(q, d_q, bytes, hipMemcpyDeviceToHost, st));
+      if (rem) ARK_CHECK_HIP(hipMemcpyAsync(rem, d_rem, rem_bytes, hipMemcpyDeviceToHost, st));
+    }
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+  // out = sum_k scalars[k] polys[k]; scalars: count Montgomery images on the host; the host variant combines in place on its staging
+  static void poly_lincomb(ark355_ctx* ctx, PolyScratch& ps, const void* polys, uint64_t len, uint64_t count, const Fr* scalars,
+                           void* out, bool on_dev) {
+    hipStream_t st = ctx->stream;
+    if (!len) return;
+    const size_t bytes = (size_t)count * len * sizeof(Fr), out_bytes = (size_t)len * sizeof(Fr);
+    ps.tab.ensure(std::max((size_t)count, (size_t)POLY_MAX_LEVELS * POLY_TAB_STRIDE) * sizeof(Fr));
+    if (!on_dev) {
+      ps.in.ensure(std::max(bytes, out_bytes));
+      if (bytes) ARK_CHECK_HIP(hipMemcpyAsync(ps.in.p, polys, bytes, hipMemcpyHostToDevice, st));
+    }
+    void* d_out = on_dev ? out : ps.in.p;
+    poly_lincomb_run<Curve>(on_dev ? polys : ps.in.p, len, count, scalars, d_out, ps, st);
+    if (!on_dev) ARK_CHECK_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     ARK_CHECK_HIP(hipStreamSynchronize(st));
   }
 

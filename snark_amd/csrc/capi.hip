@@ -44,6 +44,7 @@ struct CtxExtra {
   GenericScratch generic;
   QuotientScratch quotient;
   ColumnsScratch columns;
+  PolyScratch poly;
   std::vector<ark355_ctx*> lanes;     // child contexts of ark355_prove_batch (same device, private streams/scratch)
   ~CtxExtra();
 };
@@ -890,6 +891,136 @@ int32_t ark355_gr1cs_columns_at(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t
 }
 int32_t ark355_gr1cs_columns_at_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const uint8_t tau[32], uint32_t log_n, void* d_out) {
   return columns_common(ctx, "ark355_gr1cs_columns_at", g, predicate, nullptr, 0, tau, log_n, d_out, true, true);
+}
+
+// ---- polynomial openings (poly_impl.cuh) ---------------------------------------------------------------------------------------
+
+// a canonical scalar named `name` as the Montgomery image of curve `curve`; *why is set with every refusal.  No HIP call.
+static int32_t poly_scalar(int32_t curve, const uint8_t* v, const char* name, BlsCurve::Fr* bls, BnCurve::Fr* bn, std::string* why) {
+  const int32_t rc = tau_common(curve, v, bls, bn, why);
+  if (rc != ARK355_OK && *why == "tau is not below r") *why = std::string(name) + " is not below r";
+  return rc;
+}
+
+// whether [a, a + an) and [b, b + bn) share a byte
+static bool poly_overlap(const void* a, uint64_t an, const void* b, uint64_t bn) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return an && bn && x < y + bn && y < x + an;
+}
+
+// what eval, div_linear and lincomb refuse about (curve, len, count) alone
+static int32_t poly_shape(int32_t curve, uint64_t len, uint64_t count, std::string* why) {
+  if (curve != ARK355_BLS12_381 && curve != ARK355_BN254) {
+    *why = "unknown curve id";
+    return ARK355_EINVAL;
+  }
+  if (count > POLY_MAX_COUNT) {
+    *why = "count exceeds ARK355_POLY_MAX_COUNT";
+    return ARK355_EINVAL;
+  }
+  if (len >= (1ull << 32)) {
+    *why = "len must stay below 2^32";
+    return ARK355_EINVAL;
+  }
+  if (count * len >= POLY_MAX_ELEMS) {
+    *why = "count * len must stay below 2^40";
+    return ARK355_EINVAL;
+  }
+  return ARK355_OK;
+}
+
+static int32_t poly_eval_common(ark355_ctx* ctx, int32_t curve, const void* coeffs, uint64_t len, uint64_t count, const uint8_t* x,
+                                void* out, bool on_dev) {
+  if (!ctx) return ARK355_EINVAL;
+  const std::string pre = "ark355_poly_eval_fr: ";
+  std::string why;
+  if (const int32_t rc = poly_shape(curve, len, count, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if (!x || (count && !out) || (count * len && !coeffs)) return refuse(ctx, (pre + "coeffs / x / out is NULL").c_str());
+  BlsCurve::Fr x_bls;
+  BnCurve::Fr x_bn;
+  if (const int32_t rc = poly_scalar(curve, x, "x", &x_bls, &x_bn, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if (poly_overlap(coeffs, count * len * 32, out, count * 32)) return refuse(ctx, (pre + "out overlaps coeffs").c_str());
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    if (curve == ARK355_BLS12_381) Api<BlsCurve>::poly_eval(ctx, ex.poly, coeffs, len, count, x_bls, out, on_dev);
+    else Api<BnCurve>::poly_eval(ctx, ex.poly, coeffs, len, count, x_bn, out, on_dev);
+  });
+}
+int32_t ark355_poly_eval_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* coeffs, uint64_t len, uint64_t count, const uint8_t x[32],
+                            uint8_t* out) {
+  return poly_eval_common(ctx, curve, coeffs, len, count, x, out, false);
+}
+int32_t ark355_poly_eval_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_coeffs, uint64_t len, uint64_t count, const uint8_t x[32],
+                                void* d_out) {
+  return poly_eval_common(ctx, curve, d_coeffs, len, count, x, d_out, true);
+}
+
+static int32_t poly_div_common(ark355_ctx* ctx, int32_t curve, const void* coeffs, uint64_t len, uint64_t count, const uint8_t* x,
+                               void* q, void* rem, bool on_dev) {
+  if (!ctx) return ARK355_EINVAL;
+  const std::string pre = "ark355_poly_div_linear_fr: ";
+  std::string why;
+  if (const int32_t rc = poly_shape(curve, len, count, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  const uint64_t bytes = count * len * 32;
+  if (!x || (bytes && (!coeffs || !q))) return refuse(ctx, (pre + "coeffs / x / q_out is NULL").c_str());
+  BlsCurve::Fr x_bls;
+  BnCurve::Fr x_bn;
+  if (const int32_t rc = poly_scalar(curve, x, "x", &x_bls, &x_bn, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if (q != coeffs && poly_overlap(coeffs, bytes, q, bytes))
+    return refuse(ctx, (pre + "q_out overlaps coeffs without being equal to it").c_str());
+  if (rem && (poly_overlap(coeffs, bytes, rem, count * 32) || poly_overlap(q, bytes, rem, count * 32)))
+    return refuse(ctx, (pre + "rem_out overlaps coeffs or q_out").c_str());
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    if (curve == ARK355_BLS12_381) Api<BlsCurve>::poly_div_linear(ctx, ex.poly, coeffs, len, count, x_bls, q, rem, on_dev);
+    else Api<BnCurve>::poly_div_linear(ctx, ex.poly, coeffs, len, count, x_bn, q, rem, on_dev);
+  });
+}
+int32_t ark355_poly_div_linear_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* coeffs, uint64_t len, uint64_t count,
+                                  const uint8_t x[32], uint8_t* q_out, uint8_t* rem_out) {
+  return poly_div_common(ctx, curve, coeffs, len, count, x, q_out, rem_out, false);
+}
+int32_t ark355_poly_div_linear_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_coeffs, uint64_t len, uint64_t count,
+                                      const uint8_t x[32], void* d_q_out, void* d_rem_out) {
+  return poly_div_common(ctx, curve, d_coeffs, len, count, x, d_q_out, d_rem_out, true);
+}
+
+static int32_t poly_lincomb_common(ark355_ctx* ctx, int32_t curve, const void* polys, uint64_t len, uint64_t count,
+                                   const uint8_t* scalars, void* out, bool on_dev) {
+  if (!ctx) return ARK355_EINVAL;
+  const std::string pre = "ark355_poly_lincomb_fr: ";
+  std::string why;
+  if (const int32_t rc = poly_shape(curve, len, count, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if ((len && !out) || (count && !scalars) || (count * len && !polys)) return refuse(ctx, (pre + "polys / scalars / out is NULL").c_str());
+  std::vector<BlsCurve::Fr> s_bls;
+  std::vector<BnCurve::Fr> s_bn;
+  const int32_t caught = guarded(nullptr, [&] {
+    if (curve == ARK355_BLS12_381) s_bls.resize(count);
+    else s_bn.resize(count);
+  });
+  if (caught != ARK355_OK) return refuse(ctx, (pre + "host allocation failed").c_str(), caught);
+  for (uint64_t k = 0; k < count; k++) {
+    BlsCurve::Fr a;
+    BnCurve::Fr b;
+    if (const int32_t rc = poly_scalar(curve, scalars + 32 * k, "a scalar", &a, &b, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+    if (curve == ARK355_BLS12_381) s_bls[k] = a;
+    else s_bn[k] = b;
+  }
+  if (out != polys && poly_overlap(polys, count * len * 32, out, len * 32))
+    return refuse(ctx, (pre + "out overlaps polys without being equal to it").c_str());
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    if (curve == ARK355_BLS12_381) Api<BlsCurve>::poly_lincomb(ctx, ex.poly, polys, len, count, s_bls.data(), out, on_dev);
+    else Api<BnCurve>::poly_lincomb(ctx, ex.poly, polys, len, count, s_bn.data(), out, on_dev);
+  });
+}
+int32_t ark355_poly_lincomb_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* polys, uint64_t len, uint64_t count, const uint8_t* scalars,
+                               uint8_t* out) {
+  return poly_lincomb_common(ctx, curve, polys, len, count, scalars, out, false);
+}
+int32_t ark355_poly_lincomb_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_polys, uint64_t len, uint64_t count,
+                                   const uint8_t* scalars, void* d_out) {
+  return poly_lincomb_common(ctx, curve, d_polys, len, count, scalars, d_out, true);
 }
 
 int32_t ark355_ntt_fr(ark355_ctx* ctx, int32_t curve, uint8_t* data, uint32_t log_n, int32_t inverse, int32_t coset) {

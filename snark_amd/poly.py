@@ -1,0 +1,59 @@
+"""Polynomial openings on the device (``include/ark355.h`` "Polynomial openings", ``csrc/poly_impl.cuh``): what a KZG-style
+prover does with a challenge once it has committed -- evaluate (ark-poly ``DensePolynomial::evaluate``), divide by ``X - x``
+(ark-poly-commit ``KZG10::compute_witness_polynomial``) and combine (``DensePolynomial``'s ``Add`` / ``Mul<F>``).
+
+Polynomials are Montgomery Fr coefficients, 32 bytes each, ``count`` polynomials of ``length`` coefficients back to back;
+points and scalars are Python integers below r.  The ``_dev`` forms take device pointers (ints) of the calling process, e.g.
+``torch.Tensor.data_ptr()``, and return when the output is complete, so that ``GR1CS.quotient_dev`` -> ``Poly.eval_dev`` ->
+``Poly.div_linear_dev`` -> ``ark355_msm_dev`` never visits the host."""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Tuple
+
+from . import lib as _lib
+from .params import CURVES, Curve
+
+
+def _canon(v: int) -> bytes:
+    return int(v).to_bytes(32, "little")
+
+
+class Poly:
+    def __init__(self, curve="bls12_381", lib=None, ctx=None, device: int = 0):
+        """``lib`` / ``ctx`` are injectable so that tests drive this over the CPU emulator build, or share a context; by
+        default the HIP library is loaded and a context of its own is created (and destroyed by ``close``)."""
+        self.curve: Curve = CURVES[curve] if not isinstance(curve, Curve) else curve
+        self.lib = lib if lib is not None else _lib()
+        self._own_ctx = ctx is None
+        self.ctx = self.lib.ctx_create(device) if ctx is None else ctx
+
+    def close(self):
+        if self._own_ctx and self.ctx is not None:
+            self.lib.ctx_destroy(self.ctx)
+        self.ctx = None
+
+    # ---- host forms ------------------------------------------------------------------------------------------------
+    def eval(self, coeffs: bytes, length: int, x: int, count: int = 1) -> bytes:
+        """p_k(x) for k < count: count Montgomery Fr"""
+        return self.lib.poly_eval_fr(self.ctx, self.curve.curve_id, coeffs, length, count, _canon(x))
+
+    def div_linear(self, coeffs: bytes, length: int, x: int, count: int = 1, want_rem: bool = True) -> Tuple[bytes, Optional[bytes]]:
+        """(q, rem) with p_k(X) = q_k(X) (X - x) + rem_k; q in the layout of the input"""
+        return self.lib.poly_div_linear_fr(self.ctx, self.curve.curve_id, coeffs, length, count, _canon(x), want_rem)
+
+    def lincomb(self, polys: bytes, length: int, scalars: Sequence[int]) -> bytes:
+        """sum_k scalars[k] polys[k]: ``length`` Montgomery Fr"""
+        return self.lib.poly_lincomb_fr(self.ctx, self.curve.curve_id, polys, length, len(scalars), b"".join(_canon(s) for s in scalars))
+
+    # ---- device forms ----------------------------------------------------------------------------------------------
+    def eval_dev(self, d_coeffs: int, length: int, x: int, d_out: int, count: int = 1) -> None:
+        self.lib.poly_eval_fr_dev(self.ctx, self.curve.curve_id, d_coeffs, length, count, _canon(x), d_out)
+
+    def div_linear_dev(self, d_coeffs: int, length: int, x: int, d_q_out: int, d_rem_out: Optional[int] = None, count: int = 1) -> None:
+        """``d_q_out == d_coeffs`` divides in place; ``d_rem_out`` may be None"""
+        self.lib.poly_div_linear_fr_dev(self.ctx, self.curve.curve_id, d_coeffs, length, count, _canon(x), d_q_out, d_rem_out)
+
+    def lincomb_dev(self, d_polys: int, length: int, scalars: Sequence[int], d_out: int) -> None:
+        """``d_out == d_polys`` combines in place on polynomial 0"""
+        self.lib.poly_lincomb_fr_dev(self.ctx, self.curve.curve_id, d_polys, length, len(scalars), b"".join(_canon(s) for s in scalars),
+                                     d_out)
