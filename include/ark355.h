@@ -96,6 +96,8 @@ int32_t ark355_sizes(int32_t curve, uint32_t what[4]);
  *                 [default 64; <= 0 selects it]; longer ones are cut into chunks of 2048 entries, one workgroup each).
  *                 POLY_LANE_COEFFS (ark355_poly_eval_fr / ark355_poly_div_linear_fr: the consecutive coefficients a lane owns
  *                 [default 8; <= 0 selects it; clamped to 1 .. 8]; a test knob, the outputs do not depend on it).
+ *                 EVALS_LANE_POINTS (ark355_evals_eval_fr / ark355_evals_div_linear_fr: the consecutive domain points a lane owns
+ *                 [default 8; <= 0 selects it; clamped to 1 .. 8]; a test knob, the outputs do not depend on it).
  * ARK355_EINVAL for an unknown name.  ark355_prove_batch runs its worker contexts under the caller's policy.
  * (No counterpart in the reference: ark-groth16 has no runtime knobs; rayon's thread count is its only one.) */
 int32_t ark355_ctx_set_policy(ark355_ctx* ctx, const char* name, int64_t value);
@@ -641,6 +643,48 @@ int32_t ark355_poly_lincomb_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* po
                                const uint8_t* scalars, uint8_t* out);
 int32_t ark355_poly_lincomb_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_polys, uint64_t len, uint64_t count,
                                    const uint8_t* scalars, void* d_out);
+
+/* ---- Openings in the evaluation basis: evaluate and divide by X - x (snark_amd/csrc/evals_impl.cuh) ---------------------------
+ * The same two steps for a polynomial held as its values over a domain, as a prover with a Lagrange-basis key holds it
+ * (ark355_lagrange_fr_dev -> ark355_fixed_base_mul_dev build such a key; ark-poly Evaluations::interpolate + evaluate and
+ * KZG10::compute_witness_polynomial are the two-transform route this replaces).  No transform runs.
+ * N = 2^log_n, w the N-th root of unity of ark355_ntt_fr, s = 1 for coset = 0 and the coset generator of ark355_ntt_fr for
+ * coset != 0, a_i = s w^i.  `count` vectors of N Montgomery Fr lie back to back: evals[k][i] = p_k(a_i) for the unique p_k of degree
+ * < N.  x is a canonical 32-byte little-endian integer below r.  The _dev variants work on the context's stream and return when
+ * the output is complete; x stays a host pointer.
+ * eval: out[k] = p_k(x), count Fr: the bytes ark355_poly_eval_fr returns on the coefficients ark355_ntt_fr(inverse = 1, coset)
+ *   gives.  For x = a_j that is evals[k][j].
+ * div_linear: q_out[k][i] = q_k(a_i) for q_k(X) = (p_k(X) - p_k(x)) / (X - x), count x N Fr, every element written: byte for byte
+ *   ark355_ntt_fr(forward, coset) of the q_out of ark355_poly_div_linear_fr on the interpolated coefficients (q_k has degree
+ *   <= N - 2, so its N values are exact).  For a_i != x that is (evals[k][i] - y_k) / (a_i - x); at the one j with a_j = x, if any,
+ *   - sum_{i != j} q[k][i] w^(i-j).  rem_out[k] = p_k(x), the bytes of eval; rem_out may be NULL.  N = 1 gives q = {0}.
+ *   A row of q_out feeds ark355_msm_dev (scalars_mont = 1) with the Lagrange-basis bases that committed evals.
+ *   In place is legal: q_out == evals exactly.  Any other overlap of the two ranges, or of rem_out with either, is ARK355_EINVAL.
+ * count = 0 returns ARK355_OK and writes nothing.
+ * Refusals, all made before any allocation or launch, each with a message in ark355_last_error; the context works after every
+ * one of them: ARK355_EINVAL for a NULL pointer where something is to be read or written (x always; evals and the outputs when
+ * count > 0), an unknown curve, x >= r, count > ARK355_POLY_MAX_COUNT, count * N >= 2^40 and the overlaps above;
+ * ARK355_E_POLY_DEGREE_TOO_LARGE for log_n above the two-adicity of Fr (32 / 28).  ARK355_ENOMEM when the scratch does not fit:
+ * it is grow-only, owned by the context and reserved before the first launch -- 32 * count * (ceil(N / 2048) + ..) bytes of
+ * partial sums, 12 KiB of tables, and for the host variants the staging of the vectors.
+ * Policy EVALS_LANE_POINTS (per call; default 8; <= 0 selects it; clamped to 1 .. 8): the consecutive points one lane owns, 256
+ * times as many a workgroup; one field inversion serves a whole workgroup (2048 points at the default).  It never changes a byte
+ * of any output. */
+int32_t ark355_evals_eval_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* evals, uint32_t log_n, uint64_t count, int32_t coset,
+                             const uint8_t x[32], uint8_t* out);
+int32_t ark355_evals_eval_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_evals, uint32_t log_n, uint64_t count, int32_t coset,
+                                 const uint8_t x[32], void* d_out);
+int32_t ark355_evals_div_linear_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* evals, uint32_t log_n, uint64_t count, int32_t coset,
+                                   const uint8_t x[32], uint8_t* q_out, uint8_t* rem_out);
+int32_t ark355_evals_div_linear_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_evals, uint32_t log_n, uint64_t count,
+                                       int32_t coset, const uint8_t x[32], void* d_q_out, void* d_rem_out);
+/* The values of the argument polynomials m_0 .. m_{t-1} of predicate `predicate` over H_N in DEVICE memory: d_out[k][i] =
+ * (M_k z)_i for i < n and zero for n <= i < N, t x N Montgomery Fr, matrix-major -- what ark355_gr1cs_mat_vec returns to the host,
+ * padded to the domain, so that ark355_evals_eval_fr_dev / ark355_evals_div_linear_fr_dev open m_k without a transform.  The
+ * domain rule is that of ark355_gr1cs_quotient (log_n = 0: the smallest power of two >= max(n, 2)), and so are the refusals and
+ * their codes, except that ARK355_E_POLY_DEGREE_TOO_LARGE applies to the domain alone: the predicate's degree plays no part. */
+int32_t ark355_gr1cs_mat_vec_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* d_z, uint64_t z_len,
+                                 uint32_t log_n, void* d_out);
 
 /* in-place radix-2 NTT over Fr, natural order in and out (ark-poly Radix2EvaluationDomain
  * fft / ifft / coset_fft / coset_ifft).  Errors with ARK355_E_POLY_DEGREE_TOO_LARGE past the

@@ -561,6 +561,58 @@ extern "C" {
         d_out: *mut c_void,
     ) -> i32;
 
+    pub fn ark355_evals_eval_fr(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        evals: *const u8,
+        log_n: u32,
+        count: u64,
+        coset: i32,
+        x: *const u8,
+        out: *mut u8,
+    ) -> i32;
+    pub fn ark355_evals_eval_fr_dev(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        d_evals: *const c_void,
+        log_n: u32,
+        count: u64,
+        coset: i32,
+        x: *const u8,
+        d_out: *mut c_void,
+    ) -> i32;
+    pub fn ark355_evals_div_linear_fr(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        evals: *const u8,
+        log_n: u32,
+        count: u64,
+        coset: i32,
+        x: *const u8,
+        q_out: *mut u8,
+        rem_out: *mut u8,
+    ) -> i32;
+    pub fn ark355_evals_div_linear_fr_dev(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        d_evals: *const c_void,
+        log_n: u32,
+        count: u64,
+        coset: i32,
+        x: *const u8,
+        d_q_out: *mut c_void,
+        d_rem_out: *mut c_void,
+    ) -> i32;
+    pub fn ark355_gr1cs_mat_vec_dev(
+        ctx: *mut ark355_ctx,
+        g: *const ark355_gr1cs,
+        predicate: u32,
+        d_z: *const c_void,
+        z_len: u64,
+        log_n: u32,
+        d_out: *mut c_void,
+    ) -> i32;
+
     pub fn ark355_ntt_fr(ctx: *mut ark355_ctx, curve: i32, data: *mut u8, log_n: u32, inverse: i32, coset: i32) -> i32;
     pub fn ark355_ntt_fr_dev(
         ctx: *mut ark355_ctx,

@@ -55,7 +55,9 @@ SYMBOLS = [
     "ark355_lagrange_fr", "ark355_lagrange_fr_dev", "ark355_gr1cs_mat_vec_t", "ark355_gr1cs_mat_vec_t_dev",
     "ark355_gr1cs_columns_at", "ark355_gr1cs_columns_at_dev",
     "ark355_poly_eval_fr", "ark355_poly_eval_fr_dev", "ark355_poly_div_linear_fr", "ark355_poly_div_linear_fr_dev",
-    "ark355_poly_lincomb_fr", "ark355_poly_lincomb_fr_dev", "ark355_ntt_fr", "ark355_ntt_fr_dev",
+    "ark355_poly_lincomb_fr", "ark355_poly_lincomb_fr_dev",
+    "ark355_evals_eval_fr", "ark355_evals_eval_fr_dev", "ark355_evals_div_linear_fr", "ark355_evals_div_linear_fr_dev",
+    "ark355_gr1cs_mat_vec_dev", "ark355_ntt_fr", "ark355_ntt_fr_dev",
     "ark355_msm_g1", "ark355_msm_g2", "ark355_bases_load", "ark355_bases_free", "ark355_msm_dev",
     "ark355_msm_dev_partial", "ark355_xyzz_sum", "ark355_fixed_base_mul", "ark355_fixed_base_mul_dev", "ark355_get_timings",
     "ark355_get_kernel_stats", "ark355_pk_load_shard", "ark355_partial_size", "ark355_prove_shard",
@@ -225,6 +227,11 @@ class Lib:
         d.ark355_poly_div_linear_fr_dev.argtypes = [vp, i32, vp, u64, u64, vp, vp, vp]
         d.ark355_poly_lincomb_fr.argtypes = [vp, i32, vp, u64, u64, vp, vp]
         d.ark355_poly_lincomb_fr_dev.argtypes = [vp, i32, vp, u64, u64, vp, vp]
+        d.ark355_evals_eval_fr.argtypes = [vp, i32, vp, u32, u64, i32, vp, vp]
+        d.ark355_evals_eval_fr_dev.argtypes = [vp, i32, vp, u32, u64, i32, vp, vp]
+        d.ark355_evals_div_linear_fr.argtypes = [vp, i32, vp, u32, u64, i32, vp, vp, vp]
+        d.ark355_evals_div_linear_fr_dev.argtypes = [vp, i32, vp, u32, u64, i32, vp, vp, vp]
+        d.ark355_gr1cs_mat_vec_dev.argtypes = [vp, vp, u32, vp, u64, u32, vp]
         d.ark355_ntt_fr.argtypes = [vp, i32, vp, u32, i32, i32]
         d.ark355_ntt_fr_dev.argtypes = [vp, i32, vp, vp, u32, i32, i32, vp]
         d.ark355_msm_g1.argtypes = [vp, i32, vp, vp, u64, vp]
@@ -792,6 +799,42 @@ class Lib:
         """the same on device pointers (ints); the scalars stay host bytes; d_out == d_polys combines in place on polynomial 0"""
         sb, ks = _buf(scalars if len(scalars) else b"\0")
         self.check(ctx, self.dll.ark355_poly_lincomb_fr_dev(ctx, curve, C.c_void_p(d_polys), length, count, sb, C.c_void_p(d_out)))
+
+    # ---- openings in the evaluation basis (csrc/evals_impl.cuh) --------------------------------------------------------
+    def evals_eval_fr(self, ctx, curve, evals, log_n, count, coset, x: bytes, fr_size=32):
+        """p_k(x) for `count` polynomials held as their 2^log_n Montgomery values over the domain (coset != 0: over the coset of
+        ark355_ntt_fr), lying back to back (x: canonical 32 bytes, little-endian): count Montgomery Fr"""
+        out = np.zeros(max(1, count * fr_size), dtype=np.uint8)
+        eb, k = _buf(evals if len(evals) else b"\0")
+        xb, kx = _buf(x)
+        self.check(ctx, self.dll.ark355_evals_eval_fr(ctx, curve, eb, log_n, count, coset, xb, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:count * fr_size]
+
+    def evals_eval_fr_dev(self, ctx, curve, d_evals, log_n, count, coset, x: bytes, d_out):
+        xb, kx = _buf(x)
+        self.check(ctx, self.dll.ark355_evals_eval_fr_dev(ctx, curve, C.c_void_p(d_evals), log_n, count, coset, xb, C.c_void_p(d_out)))
+
+    def evals_div_linear_fr(self, ctx, curve, evals, log_n, count, coset, x: bytes, want_rem=True, fr_size=32):
+        """(q, rem): the values of q_k = (p_k - p_k(x)) / (X - x) over the same domain, in the layout of the input, and
+        rem_k = p_k(x) (None when want_rem is false)"""
+        size = (count << log_n) * fr_size
+        q = np.zeros(max(1, size), dtype=np.uint8)
+        rem = np.zeros(max(1, count * fr_size), dtype=np.uint8)
+        eb, k = _buf(evals if len(evals) else b"\0")
+        xb, kx = _buf(x)
+        self.check(ctx, self.dll.ark355_evals_div_linear_fr(ctx, curve, eb, log_n, count, coset, xb, q.ctypes.data_as(C.c_void_p),
+                                                            rem.ctypes.data_as(C.c_void_p) if want_rem else None))
+        return q.tobytes()[:size], (rem.tobytes()[:count * fr_size] if want_rem else None)
+
+    def evals_div_linear_fr_dev(self, ctx, curve, d_evals, log_n, count, coset, x: bytes, d_q_out, d_rem_out=None):
+        """the same on device pointers (ints); d_q_out == d_evals divides in place; d_rem_out may be None"""
+        xb, kx = _buf(x)
+        self.check(ctx, self.dll.ark355_evals_div_linear_fr_dev(ctx, curve, C.c_void_p(d_evals), log_n, count, coset, xb,
+                                                                C.c_void_p(d_q_out), C.c_void_p(d_rem_out) if d_rem_out else None))
+
+    def gr1cs_mat_vec_dev(self, ctx, g, predicate, d_z, z_len, log_n, d_out):
+        """the values of m_0 .. m_{t-1} over H_N on device pointers (ints): t x N Montgomery Fr, rows n .. N-1 zero"""
+        self.check(ctx, self.dll.ark355_gr1cs_mat_vec_dev(ctx, g, predicate, C.c_void_p(d_z), z_len, log_n, C.c_void_p(d_out)))
 
     def gr1cs_r1cs(self, ctx, g):
         """an ark355_r1cs handle from the predicate labelled "R1CS" (refused when another predicate has a row)"""

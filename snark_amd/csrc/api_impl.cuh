@@ -10,6 +10,7 @@
 #include "quotient_impl.cuh"
 #include "columns_impl.cuh"
 #include "poly_impl.cuh"
+#include "evals_impl.cuh"
 #include "lcmap_impl.cuh"
 #include "setup_impl.cuh"
 #include "wire_impl.cuh"
@@ -392,6 +393,63 @@ struct Api {
     void* d_out = on_dev ? out : ps.in.p;
     poly_lincomb_run<Curve>(on_dev ? polys : ps.in.p, len, count, scalars, d_out, ps, st);
     if (!on_dev) ARK_CHECK_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+
+  // ---- openings in the evaluation basis (evals_impl.cuh): the refusals are capi.hip's; every allocation happens before the first launch
+  // out[k] = p_k(x) from the values of p_k over the domain; evals and out both on the host or both on the device
+  static void evals_eval(ark355_ctx* ctx, EvalsScratch& es, const void* evals, uint32_t log_n, uint64_t count, bool coset, const Fr& x,
+                         void* out, bool on_dev) {
+    hipStream_t st = ctx->stream;
+    if (!count) return;
+    const EvalsPlan plan = evals_plan(log_n, count, evals_lane_points(ctx->policy.evals_lane_points));
+    const EvalsPoint<Fr> pt = evals_point<Fr>(log_n, coset, x);
+    const size_t bytes = (size_t)count * plan.N * sizeof(Fr), out_bytes = (size_t)count * sizeof(Fr);
+    evals_reserve<Fr>(es, plan, count, false);
+    if (!on_dev) {
+      es.in.ensure(bytes);
+      es.small.ensure(out_bytes);
+      ARK_CHECK_HIP(hipMemcpyAsync(es.in.p, evals, bytes, hipMemcpyHostToDevice, st));
+    }
+    if (!pt.inside) evals_upload_tables<Fr>(es, plan, pt, st);
+    void* d_out = on_dev ? out : es.small.p;
+    evals_eval_run<Curve>(on_dev ? evals : es.in.p, count, plan, pt, d_out, es, st);
+    if (!on_dev) ARK_CHECK_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+  // q[k][i] = q_k(a_i) for q_k = (p_k - p_k(x)) / (X - x), rem[k] = p_k(x) (rem may be null); the host variant divides in place on
+  // its staging
+  static void evals_div_linear(ark355_ctx* ctx, EvalsScratch& es, const void* evals, uint32_t log_n, uint64_t count, bool coset,
+                               const Fr& x, void* q, void* rem, bool on_dev) {
+    hipStream_t st = ctx->stream;
+    if (!count) return;
+    const EvalsPlan plan = evals_plan(log_n, count, evals_lane_points(ctx->policy.evals_lane_points));
+    const EvalsPoint<Fr> pt = evals_point<Fr>(log_n, coset, x);
+    const size_t bytes = (size_t)count * plan.N * sizeof(Fr), rem_bytes = (size_t)count * sizeof(Fr);
+    evals_reserve<Fr>(es, plan, count, !rem || !on_dev);
+    if (!on_dev) {
+      es.in.ensure(bytes);
+      ARK_CHECK_HIP(hipMemcpyAsync(es.in.p, evals, bytes, hipMemcpyHostToDevice, st));
+    }
+    evals_upload_tables<Fr>(es, plan, pt, st);
+    void* d_q = on_dev ? q : es.in.p;
+    void* d_rem = on_dev ? rem : es.rem.p;
+    evals_div_run<Curve>(on_dev ? evals : es.in.p, count, plan, pt, d_q, d_rem, es, st);
+    if (!on_dev) {
+      ARK_CHECK_HIP(hipMemcpyAsync(q, d_q, bytes, hipMemcpyDeviceToHost, st));
+      if (rem) ARK_CHECK_HIP(hipMemcpyAsync(rem, d_rem, rem_bytes, hipMemcpyDeviceToHost, st));
+    }
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+  // d_out[k][i] = (M_k z)_i for i < n and zero for n <= i < N = 2^q.log_domain: the values of m_k over H_N, matrix-major
+  static void gr1cs_mat_vec_dev(ark355_ctx* ctx, const Gr1csDev& g, uint32_t p, const QuotientDims& q, const void* d_z, void* d_out) {
+    hipStream_t st = ctx->stream;
+    const Gr1csPred& P = g.preds[p];
+    if (!P.arity) return;
+    const uint64_t N = 1ull << q.log_domain;
+    ARK_LAUNCH((gr1cs_spmv_padded_kernel<Fr>), dim3((uint32_t)((N + 255) / 256), P.arity), dim3(256), 0, st,
+               (const Gr1csMat*)P.mats.template as<Gr1csMat>(), (const Fr*)g.pool.template as<Fr>(), (const Fr*)d_z, P.n, N, N, (Fr*)d_out);
+    ARK_CHECK_LAUNCH();
     ARK_CHECK_HIP(hipStreamSynchronize(st));
   }
 

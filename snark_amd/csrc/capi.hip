@@ -45,6 +45,7 @@ struct CtxExtra {
   QuotientScratch quotient;
   ColumnsScratch columns;
   PolyScratch poly;
+  EvalsScratch evals;
   std::vector<ark355_ctx*> lanes;     // child contexts of ark355_prove_batch (same device, private streams/scratch)
   ~CtxExtra();
 };
@@ -1021,6 +1022,105 @@ int32_t ark355_poly_lincomb_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* po
 int32_t ark355_poly_lincomb_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_polys, uint64_t len, uint64_t count,
                                    const uint8_t* scalars, void* d_out) {
   return poly_lincomb_common(ctx, curve, d_polys, len, count, scalars, d_out, true);
+}
+
+// ---- openings in the evaluation basis (evals_impl.cuh) -----------------------------------------------------------------------
+
+// what eval and div_linear refuse about (curve, log_n, count) alone
+static int32_t evals_shape(int32_t curve, uint32_t log_n, uint64_t count, std::string* why) {
+  if (curve != ARK355_BLS12_381 && curve != ARK355_BN254) {
+    *why = "unknown curve id";
+    return ARK355_EINVAL;
+  }
+  if (count > POLY_MAX_COUNT) {
+    *why = "count exceeds ARK355_POLY_MAX_COUNT";
+    return ARK355_EINVAL;
+  }
+  const uint32_t two_adicity = curve == ARK355_BLS12_381 ? Api<BlsCurve>::two_adicity() : Api<BnCurve>::two_adicity();
+  if (log_n > two_adicity) {
+    *why = "the evaluation domain exceeds the largest radix-2 domain of Fr";
+    return ARK355_E_POLY_DEGREE_TOO_LARGE;
+  }
+  if ((count << log_n) >= POLY_MAX_ELEMS) {              // count <= 2^10, log_n <= 32: no overflow
+    *why = "count * 2^log_n must stay below 2^40";
+    return ARK355_EINVAL;
+  }
+  return ARK355_OK;
+}
+
+static int32_t evals_eval_common(ark355_ctx* ctx, int32_t curve, const void* evals, uint32_t log_n, uint64_t count, int32_t coset,
+                                 const uint8_t* x, void* out, bool on_dev) {
+  if (!ctx) return ARK355_EINVAL;
+  const std::string pre = "ark355_evals_eval_fr: ";
+  std::string why;
+  if (const int32_t rc = evals_shape(curve, log_n, count, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if (!x || (count && (!out || !evals))) return refuse(ctx, (pre + "evals / x / out is NULL").c_str());
+  BlsCurve::Fr x_bls;
+  BnCurve::Fr x_bn;
+  if (const int32_t rc = poly_scalar(curve, x, "x", &x_bls, &x_bn, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if (poly_overlap(evals, (count << log_n) * 32, out, count * 32)) return refuse(ctx, (pre + "out overlaps evals").c_str());
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    if (curve == ARK355_BLS12_381) Api<BlsCurve>::evals_eval(ctx, ex.evals, evals, log_n, count, coset != 0, x_bls, out, on_dev);
+    else Api<BnCurve>::evals_eval(ctx, ex.evals, evals, log_n, count, coset != 0, x_bn, out, on_dev);
+  });
+}
+int32_t ark355_evals_eval_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* evals, uint32_t log_n, uint64_t count, int32_t coset,
+                             const uint8_t x[32], uint8_t* out) {
+  return evals_eval_common(ctx, curve, evals, log_n, count, coset, x, out, false);
+}
+int32_t ark355_evals_eval_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_evals, uint32_t log_n, uint64_t count, int32_t coset,
+                                 const uint8_t x[32], void* d_out) {
+  return evals_eval_common(ctx, curve, d_evals, log_n, count, coset, x, d_out, true);
+}
+
+static int32_t evals_div_common(ark355_ctx* ctx, int32_t curve, const void* evals, uint32_t log_n, uint64_t count, int32_t coset,
+                                const uint8_t* x, void* q, void* rem, bool on_dev) {
+  if (!ctx) return ARK355_EINVAL;
+  const std::string pre = "ark355_evals_div_linear_fr: ";
+  std::string why;
+  if (const int32_t rc = evals_shape(curve, log_n, count, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  const uint64_t bytes = (count << log_n) * 32;
+  if (!x || (count && (!evals || !q))) return refuse(ctx, (pre + "evals / x / q_out is NULL").c_str());
+  BlsCurve::Fr x_bls;
+  BnCurve::Fr x_bn;
+  if (const int32_t rc = poly_scalar(curve, x, "x", &x_bls, &x_bn, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if (q != evals && poly_overlap(evals, bytes, q, bytes))
+    return refuse(ctx, (pre + "q_out overlaps evals without being equal to it").c_str());
+  if (rem && (poly_overlap(evals, bytes, rem, count * 32) || poly_overlap(q, bytes, rem, count * 32)))
+    return refuse(ctx, (pre + "rem_out overlaps evals or q_out").c_str());
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    if (curve == ARK355_BLS12_381) Api<BlsCurve>::evals_div_linear(ctx, ex.evals, evals, log_n, count, coset != 0, x_bls, q, rem, on_dev);
+    else Api<BnCurve>::evals_div_linear(ctx, ex.evals, evals, log_n, count, coset != 0, x_bn, q, rem, on_dev);
+  });
+}
+int32_t ark355_evals_div_linear_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* evals, uint32_t log_n, uint64_t count, int32_t coset,
+                                   const uint8_t x[32], uint8_t* q_out, uint8_t* rem_out) {
+  return evals_div_common(ctx, curve, evals, log_n, count, coset, x, q_out, rem_out, false);
+}
+int32_t ark355_evals_div_linear_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_evals, uint32_t log_n, uint64_t count,
+                                       int32_t coset, const uint8_t x[32], void* d_q_out, void* d_rem_out) {
+  return evals_div_common(ctx, curve, d_evals, log_n, count, coset, x, d_q_out, d_rem_out, true);
+}
+
+// the values of m_0 .. m_{t-1} over H_N in device memory: the refusals of ark355_gr1cs_quotient_dev about the same arguments, except
+// that the predicate's degree does not matter here
+int32_t ark355_gr1cs_mat_vec_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* d_z, uint64_t z_len,
+                                 uint32_t log_n, void* d_out) {
+  if (!ctx) return ARK355_EINVAL;
+  QuotientDims q;
+  std::string why;
+  int32_t rc = quotient_dims_common(g, predicate, log_n, &q, &why);
+  if (rc == ARK355_E_POLY_DEGREE_TOO_LARGE && q.log_domain <= (g->d->curve == ARK355_BLS12_381 ? Api<BlsCurve>::two_adicity()
+                                                                                                : Api<BnCurve>::two_adicity()))
+    rc = ARK355_OK;                                        // only the extended domain was too large: none is used here
+  if (rc) return refuse(ctx, ("ark355_gr1cs_mat_vec_dev: " + why).c_str(), rc);
+  if (!d_z || !d_out) return refuse(ctx, "ark355_gr1cs_mat_vec_dev: d_z / d_out is NULL");
+  if (g->d->device >= 0 && g->d->device != ctx->device)
+    return refuse(ctx, "ark355_gr1cs_mat_vec_dev: the gr1cs handle lives on another device than the context");
+  if (z_len < g->d->m) return refuse(ctx, "assignment shorter than num_instance + num_witness", ARK355_E_ASSIGNMENT_MISSING);
+  return guarded(ctx, [&] { CURVE_DISPATCH(g->d->curve, A::gr1cs_mat_vec_dev(ctx, *g->d, predicate, q, d_z, d_out)); });
 }
 
 int32_t ark355_ntt_fr(ark355_ctx* ctx, int32_t curve, uint8_t* data, uint32_t log_n, int32_t inverse, int32_t coset) {

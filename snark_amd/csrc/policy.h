@@ -19,7 +19,8 @@
 //                  PAIRING_EACH_MIN (the same for ark355_pairing_groups and ark355_verify_each), LCS_ROW_LDS_MAX (the longest
 //                  expanded LC that ark355_gr1cs_from_lcs sorts in LDS), COLS_LANE_MAX (the longest column one lane of
 //                  ark355_gr1cs_mat_vec_t / ark355_gr1cs_columns_at sums), POLY_LANE_COEFFS (the coefficients one lane of
-//                  ark355_poly_eval_fr / ark355_poly_div_linear_fr owns)
+//                  ark355_poly_eval_fr / ark355_poly_div_linear_fr owns), EVALS_LANE_POINTS (the domain points one lane of
+//                  ark355_evals_eval_fr / ark355_evals_div_linear_fr owns)
 //   process-wide   POISON_ALLOC: a TEST knob, not a tuning switch.  Device and pinned host buffers are allocated by objects that know no
 //                  context (DevBuf, common.h), so the value is mirrored into ONE atomic of the process (poison_alloc_byte): setting it
 //                  through any context, or through the environment of a context created later, changes it for every context.
@@ -100,6 +101,10 @@ struct TunePolicy {
   int32_t poly_lane_coeffs = 8;   // ark355_poly_eval_fr / ark355_poly_div_linear_fr (poly_impl.cuh): the consecutive coefficients a lane owns, and
                                   // so the chunk of a workgroup (256 times as many).  <= 0: the default; clamped to 1 .. 8.  Tests lower it to
                                   // reach the second and third level of the decomposition at small lengths; it never changes a byte of any output.
+  int32_t evals_lane_points = 8;  // ark355_evals_eval_fr / ark355_evals_div_linear_fr (evals_impl.cuh): the consecutive domain points a lane owns; a
+                                  // workgroup owns 256 times as many and shares one field inversion among all of them.  <= 0: the
+                                  // default; clamped to 1 .. 8.  Tests lower it to reach more workgroups and reduction levels at small domains; it
+                                  // never changes a byte of any output.
   // ---- process-wide (test knob)
   int32_t poison_alloc = -1;      // 0 .. 255: every device buffer (DevBuf::alloc) and pinned host buffer is filled with this byte, synchronously,
                                   // before the allocator returns, so that no test passes because fresh memory happened to hold zeros; -1 (default)
@@ -158,6 +163,7 @@ inline const TunePolicy::Field* TunePolicy::fields(int* count) {
       ARK_POLICY_FIELD32("LCS_ROW_LDS_MAX", lcs_row_lds_max),
       ARK_POLICY_FIELD32("COLS_LANE_MAX", cols_lane_max),
       ARK_POLICY_FIELD32("POLY_LANE_COEFFS", poly_lane_coeffs),
+      ARK_POLICY_FIELD32("EVALS_LANE_POINTS", evals_lane_points),
       ARK_POLICY_FIELD32("POISON_ALLOC", poison_alloc),
   };
   *count = (int)(sizeof(tab) / sizeof(tab[0]));

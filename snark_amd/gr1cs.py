@@ -186,6 +186,13 @@ class GR1CS:
         self._need()
         self.lib.gr1cs_quotient_dev(self.ctx, self.handle, self._index[label], d_z, z_len, log_n, d_h)
 
+    def mat_vec_dev(self, label: str, d_z: int, z_len: int, d_out: int, log_n: int = 0):
+        """the values of m_0 .. m_{t-1} of `label` over H_N on device pointers (``ark355_gr1cs_mat_vec_dev``): reads z_len Fr at
+        d_z, writes arity x N Fr at d_out, matrix-major, rows n .. N-1 zero (N = 2^log_domain of ``quotient_dims``) -- ready for
+        ``Evals.eval_dev`` / ``Evals.div_linear_dev``"""
+        self._need()
+        self.lib.gr1cs_mat_vec_dev(self.ctx, self.handle, self._index[label], d_z, z_len, log_n, d_out)
+
     def mat_vec_t(self, label: str, y) -> List[bytes]:
         """M_k^T y for the matrices of `label` (``ark355_gr1cs_mat_vec_t``): arity byte strings of m = ell + w Montgomery Fr
         each, column j the sum of c * y[i] over the stored entries (i, j, c).  y: n canonical ints or Montgomery bytes."""

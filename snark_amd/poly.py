@@ -57,3 +57,40 @@ class Poly:
         """``d_out == d_polys`` combines in place on polynomial 0"""
         self.lib.poly_lincomb_fr_dev(self.ctx, self.curve.curve_id, d_polys, length, len(scalars), b"".join(_canon(s) for s in scalars),
                                      d_out)
+
+
+class Evals:
+    """The same openings for polynomials held in the evaluation basis (``include/ark355.h`` "Openings in the evaluation basis",
+    ``csrc/evals_impl.cuh``): ``count`` vectors of ``2^log_n`` Montgomery values over the domain of ``ark355_ntt_fr`` (``coset``:
+    over its coset), back to back.  No transform runs: ``GR1CS.mat_vec_dev`` -> ``Evals.eval_dev`` -> ``Evals.div_linear_dev`` ->
+    ``ark355_msm_dev`` over a Lagrange-basis key never visits the host."""
+
+    def __init__(self, curve="bls12_381", lib=None, ctx=None, device: int = 0):
+        self.curve: Curve = CURVES[curve] if not isinstance(curve, Curve) else curve
+        self.lib = lib if lib is not None else _lib()
+        self._own_ctx = ctx is None
+        self.ctx = self.lib.ctx_create(device) if ctx is None else ctx
+
+    def close(self):
+        if self._own_ctx and self.ctx is not None:
+            self.lib.ctx_destroy(self.ctx)
+        self.ctx = None
+
+    # ---- host forms ------------------------------------------------------------------------------------------------
+    def eval(self, evals: bytes, log_n: int, x: int, count: int = 1, coset: bool = False) -> bytes:
+        """p_k(x) for k < count: count Montgomery Fr"""
+        return self.lib.evals_eval_fr(self.ctx, self.curve.curve_id, evals, log_n, count, int(coset), _canon(x))
+
+    def div_linear(self, evals: bytes, log_n: int, x: int, count: int = 1, coset: bool = False,
+                   want_rem: bool = True) -> Tuple[bytes, Optional[bytes]]:
+        """(q, rem): the values of (p_k - p_k(x)) / (X - x) over the same domain, and rem_k = p_k(x)"""
+        return self.lib.evals_div_linear_fr(self.ctx, self.curve.curve_id, evals, log_n, count, int(coset), _canon(x), want_rem)
+
+    # ---- device forms ----------------------------------------------------------------------------------------------
+    def eval_dev(self, d_evals: int, log_n: int, x: int, d_out: int, count: int = 1, coset: bool = False) -> None:
+        self.lib.evals_eval_fr_dev(self.ctx, self.curve.curve_id, d_evals, log_n, count, int(coset), _canon(x), d_out)
+
+    def div_linear_dev(self, d_evals: int, log_n: int, x: int, d_q_out: int, d_rem_out: Optional[int] = None, count: int = 1,
+                       coset: bool = False) -> None:
+        """``d_q_out == d_evals`` divides in place; ``d_rem_out`` may be None"""
+        self.lib.evals_div_linear_fr_dev(self.ctx, self.curve.curve_id, d_evals, log_n, count, int(coset), _canon(x), d_q_out, d_rem_out)
