@@ -98,6 +98,9 @@ int32_t ark355_sizes(int32_t curve, uint32_t what[4]);
  *                 [default 8; <= 0 selects it; clamped to 1 .. 8]; a test knob, the outputs do not depend on it).
  *                 EVALS_LANE_POINTS (ark355_evals_eval_fr / ark355_evals_div_linear_fr: the consecutive domain points a lane owns
  *                 [default 8; <= 0 selects it; clamped to 1 .. 8]; a test knob, the outputs do not depend on it).
+ *                 SUMCHECK_LANE_PAIRS (ark355_sumcheck_round: the consecutive output pairs a lane owns; ark355_mle_fix_fr /
+ *                 ark355_mle_eval_fr: the consecutive outputs a lane owns [default 1; <= 0 selects it; clamped to 1 .. 8]; the
+ *                 outputs do not depend on it).
  * ARK355_EINVAL for an unknown name.  ark355_prove_batch runs its worker contexts under the caller's policy.
  * (No counterpart in the reference: ark-groth16 has no runtime knobs; rayon's thread count is its only one.) */
 int32_t ark355_ctx_set_policy(ark355_ctx* ctx, const char* name, int64_t value);
@@ -685,6 +688,77 @@ int32_t ark355_evals_div_linear_fr_dev(ark355_ctx* ctx, int32_t curve, const voi
  * their codes, except that ARK355_E_POLY_DEGREE_TOO_LARGE applies to the domain alone: the predicate's degree plays no part. */
 int32_t ark355_gr1cs_mat_vec_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* d_z, uint64_t z_len,
                                  uint32_t log_n, void* d_out);
+
+/* ---- Multilinear extensions: the eq table, fixing variables, evaluation (snark_amd/csrc/mle_impl.cuh) ---------------------------
+ * The multilinear side of a prover (Spartan- or Garuda-style) over the same resident tables: ark-poly's
+ * DenseMultilinearExtension::evaluate and ::fix_variables, little-endian variable order.  v = num_vars, N = 2^v.  A table f holds N
+ * Montgomery Fr; index i = sum_j b_j 2^j; f~(x_0 .. x_{v-1}) = sum_i f[i] prod_j (b_j x_j + (1 - b_j)(1 - x_j)): variable 0 is the
+ * lowest index bit.  The t x N output of ark355_gr1cs_mat_vec_dev is t such tables.  Fixing variable 0 to r gives
+ * f'[i] = f[2i] + r (f[2i+1] - f[2i]), N / 2 entries; the old variable j + 1 becomes variable j.  A point is `num_vars` (fix: k)
+ * canonical 32-byte little-endian integers below r, back to back, always in HOST memory.  The _dev variants work on the context's
+ * stream and return when the output is complete.
+ * eq:   out[i] = prod_j (b_j point_j + (1 - b_j)(1 - point_j)), N Fr; num_vars = 0 writes {1}.  For a point in {0,1}^v it is the
+ *   indicator of that index.
+ * fix:  variables 0 .. k-1 of `count` back-to-back tables fixed to point[0 .. k): count x 2^(v-k) Fr, back to back, every element
+ *   written.  k = 0 copies.  In place is not offered (a lane's output index is another lane's input): any overlap of out with evals
+ *   is ARK355_EINVAL.
+ * eval: out[k] = f~_k(point), count Fr: the bytes fix gives with k = num_vars.
+ * count = 0 returns ARK355_OK and writes nothing.  Every output is fully reduced: the bytes do not depend on the route.
+ * Refusals, all made before any allocation or launch, each with a message in ark355_last_error; the context works after every one
+ * of them: ARK355_EINVAL for a NULL pointer where something is to be read or written, an unknown curve, a point coordinate >= r,
+ * count > ARK355_POLY_MAX_COUNT, num_vars > 40 (the two-adicity of Fr plays no part), count * N >= 2^40, k > num_vars and the
+ * overlap above.  ARK355_ENOMEM when the scratch does not fit: it is grow-only, owned by the context and reserved before the first
+ * launch -- 32 * count * (N / 2 + N / 4) bytes for the halvings of fix / eval, and for the host variants the staging of the tables.
+ * Policy SUMCHECK_LANE_PAIRS (below) also sets the consecutive outputs a lane of fix / eval owns; it never changes a byte. */
+int32_t ark355_mle_eq_fr(ark355_ctx* ctx, int32_t curve, uint32_t num_vars, const uint8_t* point, uint8_t* out);
+int32_t ark355_mle_eq_fr_dev(ark355_ctx* ctx, int32_t curve, uint32_t num_vars, const uint8_t* point, void* d_out);
+int32_t ark355_mle_fix_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* evals, uint32_t num_vars, uint64_t count, const uint8_t* point,
+                          uint32_t k, uint8_t* out);
+int32_t ark355_mle_fix_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_evals, uint32_t num_vars, uint64_t count,
+                              const uint8_t* point, uint32_t k, void* d_out);
+int32_t ark355_mle_eval_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* evals, uint32_t num_vars, uint64_t count, const uint8_t* point,
+                           uint8_t* out);
+int32_t ark355_mle_eval_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_evals, uint32_t num_vars, uint64_t count,
+                               const uint8_t* point, void* d_out);
+
+/* ---- Sum-check of a GR1CS predicate over resident tables (snark_amd/csrc/sumcheck_impl.cuh) ------------------------------------
+ * The prover's side of ark-linear-sumcheck's IPForMLSumcheck::prove_round for the claim
+ *     S = sum_{i < N} W[i] * P(T_0[i], .., T_{t-1}[i]),   N = 2^num_vars,
+ * P the polynomial of predicate `predicate` (the caller's index) of any resident handle, t its arity.
+ * d_tables: t x N Montgomery Fr in device memory, matrix-major -- what ark355_gr1cs_mat_vec_dev writes with 2^log_n = N, but any
+ *   data is legal.  d_weight: N Fr, or NULL for weight 1 everywhere; typically the output of ark355_mle_eq_fr_dev.
+ * d = the predicate's degree as written (the 64-bit quantity ark355_gr1cs_quotient_dims reports), D = d + (d_weight ? 1 : 0),
+ * points = D + 1 <= ARK355_SUMCHECK_MAX_POINTS.  A degree as written above the true degree only yields extra, still correct, points.
+ * After j challenges the state is the tables folded j times by the rule of ark355_mle_fix_fr: T^(j), W^(j) of 2^(v-j) entries.
+ * round: the message of round j + 1 (j = 0 .. v-1) is, for X = 0 .. D,
+ *     g[X] = sum_{i < 2^(v-j-1)} Wx * P(A_0, .., A_{t-1}),   A_k = T_k^(j)[2i] + X (T_k^(j)[2i+1] - T_k^(j)[2i]),
+ *   Wx formed likewise from W^(j), or 1: `points` Montgomery Fr at evals_out (host).  So g_1(0) + g_1(1) = S and
+ *   g_{j+1}(0) + g_{j+1}(1) = g_j(r_j).  Round 1 takes challenge = NULL; round j + 1 > 1 takes r_j (canonical, below r, host), folds
+ *   with it and then sums.  A call out of order -- NULL later, non-NULL first, a round after the v-th -- is ARK355_EINVAL and leaves
+ *   the state untouched, and so does a challenge >= r.
+ * finish: folds with r_v and returns T_0^(v)[0], .., T_{t-1}^(v)[0], W^(v)[0] (1 without a weight): t + 1 Fr at finals_out (host).
+ *   The verifier's last check is g_v(r_v) = W * P(T_0, .., T_{t-1}).  finals_out[k] is ark355_mle_eval_fr of table k at (r_1 .. r_v).
+ *   num_vars = 0: no round is legal and finish(NULL) returns the inputs' single entries.  finish before the v-th round is
+ *   ARK355_EINVAL; after finish only info and free are legal.
+ * Ownership: the handle borrows d_tables and d_weight read-only and never writes them; the borrow lasts until the call of round 2
+ *   returns (until finish when num_vars <= 1): after that the caller may free or overwrite them.  From round 2 on the handle works
+ *   in its own buffers of (t + 1)(N / 2 + N / 4) Fr; they and the partial-sum buffers are allocated in begin (ARK355_ENOMEM there),
+ *   no later call allocates, and the state lives in the handle, not in the context's scratch: any other entry may run on the same
+ *   context between two rounds.  The gr1cs handle must outlive the sumcheck handle (the polynomial stays resident there).  Every
+ *   round returns after one host wait: the next challenge depends on its message.
+ * Refusals at begin, each with a message, the context works after every one: ARK355_EINVAL for a NULL g, d_tables or out, a
+ *   predicate index out of range, a handle of another device, num_vars > 40, (t + 1) N >= 2^40, and points >
+ *   ARK355_SUMCHECK_MAX_POINTS (the message names the degree).  *out is NULL after a refusal.
+ * Policy SUMCHECK_LANE_PAIRS (per call; default 1; <= 0 selects it; clamped to 1 .. 8): the consecutive output pairs one lane of the
+ *   round kernel owns.  It moves borders and never changes a byte of any output. */
+#define ARK355_SUMCHECK_MAX_POINTS 32
+typedef struct ark355_sumcheck ark355_sumcheck;
+int32_t ark355_gr1cs_sumcheck_begin_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* d_tables,
+                                        const void* d_weight, uint32_t num_vars, ark355_sumcheck** out);
+int32_t ark355_sumcheck_info(const ark355_sumcheck* sc, uint32_t* num_vars, uint32_t* arity, uint32_t* points, uint32_t* rounds_done);
+int32_t ark355_sumcheck_round(ark355_ctx* ctx, ark355_sumcheck* sc, const uint8_t* challenge, uint8_t* evals_out);
+int32_t ark355_sumcheck_finish(ark355_ctx* ctx, ark355_sumcheck* sc, const uint8_t* challenge, uint8_t* finals_out);
+void ark355_sumcheck_free(ark355_sumcheck* sc);
 
 /* in-place radix-2 NTT over Fr, natural order in and out (ark-poly Radix2EvaluationDomain
  * fft / ifft / coset_fft / coset_ifft).  Errors with ARK355_E_POLY_DEGREE_TOO_LARGE past the

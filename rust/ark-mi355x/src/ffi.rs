@@ -36,6 +36,11 @@ pub struct ark355_bases {
 pub struct ark355_pvk {
     _p: [u8; 0],
 }
+/// one sum-check run over resident tables: `ark355_gr1cs_sumcheck_begin_dev`
+#[repr(C)]
+pub struct ark355_sumcheck {
+    _p: [u8; 0],
+}
 
 pub const ARK355_BLS12_381: i32 = 0;
 pub const ARK355_BN254: i32 = 1;
@@ -72,6 +77,8 @@ pub const ARK355_VAR_LC: u64 = 4;
 pub const ARK355_PAIRING_GROUP_MAX: u32 = 64;
 /// most polynomials one call of the `ark355_poly_*` entries takes
 pub const ARK355_POLY_MAX_COUNT: u32 = 1024;
+/// most evaluation points of one sum-check round: the predicate's degree as written, plus one with a weight, plus one
+pub const ARK355_SUMCHECK_MAX_POINTS: u32 = 32;
 /// words of the `plan` array of `ark355_diag_msm_sort`
 pub const ARK355_SORT_PLAN_WORDS: usize = 8;
 
@@ -612,6 +619,67 @@ extern "C" {
         log_n: u32,
         d_out: *mut c_void,
     ) -> i32;
+
+    pub fn ark355_mle_eq_fr(ctx: *mut ark355_ctx, curve: i32, num_vars: u32, point: *const u8, out: *mut u8) -> i32;
+    pub fn ark355_mle_eq_fr_dev(ctx: *mut ark355_ctx, curve: i32, num_vars: u32, point: *const u8, d_out: *mut c_void) -> i32;
+    pub fn ark355_mle_fix_fr(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        evals: *const u8,
+        num_vars: u32,
+        count: u64,
+        point: *const u8,
+        k: u32,
+        out: *mut u8,
+    ) -> i32;
+    pub fn ark355_mle_fix_fr_dev(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        d_evals: *const c_void,
+        num_vars: u32,
+        count: u64,
+        point: *const u8,
+        k: u32,
+        d_out: *mut c_void,
+    ) -> i32;
+    pub fn ark355_mle_eval_fr(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        evals: *const u8,
+        num_vars: u32,
+        count: u64,
+        point: *const u8,
+        out: *mut u8,
+    ) -> i32;
+    pub fn ark355_mle_eval_fr_dev(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        d_evals: *const c_void,
+        num_vars: u32,
+        count: u64,
+        point: *const u8,
+        d_out: *mut c_void,
+    ) -> i32;
+
+    pub fn ark355_gr1cs_sumcheck_begin_dev(
+        ctx: *mut ark355_ctx,
+        g: *const ark355_gr1cs,
+        predicate: u32,
+        d_tables: *const c_void,
+        d_weight: *const c_void,
+        num_vars: u32,
+        out: *mut *mut ark355_sumcheck,
+    ) -> i32;
+    pub fn ark355_sumcheck_info(
+        sc: *const ark355_sumcheck,
+        num_vars: *mut u32,
+        arity: *mut u32,
+        points: *mut u32,
+        rounds_done: *mut u32,
+    ) -> i32;
+    pub fn ark355_sumcheck_round(ctx: *mut ark355_ctx, sc: *mut ark355_sumcheck, challenge: *const u8, evals_out: *mut u8) -> i32;
+    pub fn ark355_sumcheck_finish(ctx: *mut ark355_ctx, sc: *mut ark355_sumcheck, challenge: *const u8, finals_out: *mut u8) -> i32;
+    pub fn ark355_sumcheck_free(sc: *mut ark355_sumcheck);
 
     pub fn ark355_ntt_fr(ctx: *mut ark355_ctx, curve: i32, data: *mut u8, log_n: u32, inverse: i32, coset: i32) -> i32;
     pub fn ark355_ntt_fr_dev(

@@ -36,4 +36,4 @@ CURVE_IDS = {"bls12_381": BLS12_381, "bn254": BN254}
 from .gr1cs import GR1CS  # noqa: E402,F401 -- every predicate of a constraint system on the device (snark_amd/gr1cs.py)
 from .sr1cs import SR1CS  # noqa: E402,F401 -- Sr1csAdapter on the device: a resident R1CS as Square R1CS (snark_amd/sr1cs.py)
 from .lcmap import LcSystem, outlined_assignment  # noqa: E402,F401 -- finalize() on the device: LC map -> resident GR1CS (snark_amd/lcmap.py)
-from .poly import Evals, Poly  # noqa: E402,F401 -- polynomial openings on the device: evaluate, divide by X - x, combine (snark_amd/poly.py)
+from .poly import Evals, Mle, Poly, Sumcheck  # noqa: E402,F401 -- polynomial openings on the device: evaluate, divide by X - x, combine; multilinear extensions and sum-check (snark_amd/poly.py)

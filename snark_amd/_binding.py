@@ -57,7 +57,10 @@ SYMBOLS = [
     "ark355_poly_eval_fr", "ark355_poly_eval_fr_dev", "ark355_poly_div_linear_fr", "ark355_poly_div_linear_fr_dev",
     "ark355_poly_lincomb_fr", "ark355_poly_lincomb_fr_dev",
     "ark355_evals_eval_fr", "ark355_evals_eval_fr_dev", "ark355_evals_div_linear_fr", "ark355_evals_div_linear_fr_dev",
-    "ark355_gr1cs_mat_vec_dev", "ark355_ntt_fr", "ark355_ntt_fr_dev",
+    "ark355_gr1cs_mat_vec_dev",
+    "ark355_mle_eq_fr", "ark355_mle_eq_fr_dev", "ark355_mle_fix_fr", "ark355_mle_fix_fr_dev", "ark355_mle_eval_fr", "ark355_mle_eval_fr_dev",
+    "ark355_gr1cs_sumcheck_begin_dev", "ark355_sumcheck_info", "ark355_sumcheck_round", "ark355_sumcheck_finish", "ark355_sumcheck_free",
+    "ark355_ntt_fr", "ark355_ntt_fr_dev",
     "ark355_msm_g1", "ark355_msm_g2", "ark355_bases_load", "ark355_bases_free", "ark355_msm_dev",
     "ark355_msm_dev_partial", "ark355_xyzz_sum", "ark355_fixed_base_mul", "ark355_fixed_base_mul_dev", "ark355_get_timings",
     "ark355_get_kernel_stats", "ark355_pk_load_shard", "ark355_partial_size", "ark355_prove_shard",
@@ -232,6 +235,18 @@ class Lib:
         d.ark355_evals_div_linear_fr.argtypes = [vp, i32, vp, u32, u64, i32, vp, vp, vp]
         d.ark355_evals_div_linear_fr_dev.argtypes = [vp, i32, vp, u32, u64, i32, vp, vp, vp]
         d.ark355_gr1cs_mat_vec_dev.argtypes = [vp, vp, u32, vp, u64, u32, vp]
+        d.ark355_mle_eq_fr.argtypes = [vp, i32, u32, vp, vp]
+        d.ark355_mle_eq_fr_dev.argtypes = [vp, i32, u32, vp, vp]
+        d.ark355_mle_fix_fr.argtypes = [vp, i32, vp, u32, u64, vp, u32, vp]
+        d.ark355_mle_fix_fr_dev.argtypes = [vp, i32, vp, u32, u64, vp, u32, vp]
+        d.ark355_mle_eval_fr.argtypes = [vp, i32, vp, u32, u64, vp, vp]
+        d.ark355_mle_eval_fr_dev.argtypes = [vp, i32, vp, u32, u64, vp, vp]
+        d.ark355_gr1cs_sumcheck_begin_dev.argtypes = [vp, vp, u32, vp, vp, u32, P(vp)]
+        d.ark355_sumcheck_info.argtypes = [vp, P(u32), P(u32), P(u32), P(u32)]
+        d.ark355_sumcheck_round.argtypes = [vp, vp, vp, vp]
+        d.ark355_sumcheck_finish.argtypes = [vp, vp, vp, vp]
+        d.ark355_sumcheck_free.argtypes = [vp]
+        d.ark355_sumcheck_free.restype = None
         d.ark355_ntt_fr.argtypes = [vp, i32, vp, u32, i32, i32]
         d.ark355_ntt_fr_dev.argtypes = [vp, i32, vp, vp, u32, i32, i32, vp]
         d.ark355_msm_g1.argtypes = [vp, i32, vp, vp, u64, vp]
@@ -835,6 +850,74 @@ class Lib:
     def gr1cs_mat_vec_dev(self, ctx, g, predicate, d_z, z_len, log_n, d_out):
         """the values of m_0 .. m_{t-1} over H_N on device pointers (ints): t x N Montgomery Fr, rows n .. N-1 zero"""
         self.check(ctx, self.dll.ark355_gr1cs_mat_vec_dev(ctx, g, predicate, C.c_void_p(d_z), z_len, log_n, C.c_void_p(d_out)))
+
+    # ---- multilinear extensions (csrc/mle_impl.cuh) -----------------------------------------------------------------------
+    def mle_eq_fr(self, ctx, curve, num_vars, point: bytes, fr_size=32):
+        """eq(point, i) for i < 2^num_vars (point: num_vars canonical 32-byte integers, little-endian): 2^num_vars Montgomery Fr"""
+        out = np.zeros(fr_size << num_vars, dtype=np.uint8)
+        pb, k = _buf(point if len(point) else b"\0")
+        self.check(ctx, self.dll.ark355_mle_eq_fr(ctx, curve, num_vars, pb, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()
+
+    def mle_eq_fr_dev(self, ctx, curve, num_vars, point: bytes, d_out):
+        pb, k = _buf(point if len(point) else b"\0")
+        self.check(ctx, self.dll.ark355_mle_eq_fr_dev(ctx, curve, num_vars, pb, C.c_void_p(d_out)))
+
+    def mle_fix_fr(self, ctx, curve, evals, num_vars, count, point: bytes, k, fr_size=32):
+        """variables 0 .. k-1 of `count` back-to-back tables of 2^num_vars Montgomery Fr fixed to point[0 .. k): count x 2^(num_vars-k)"""
+        size = (count << max(num_vars - k, 0)) * fr_size
+        out = np.zeros(max(1, size), dtype=np.uint8)
+        eb, ke = _buf(evals if len(evals) else b"\0")
+        pb, kp = _buf(point if len(point) else b"\0")
+        self.check(ctx, self.dll.ark355_mle_fix_fr(ctx, curve, eb, num_vars, count, pb, k, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:size]
+
+    def mle_fix_fr_dev(self, ctx, curve, d_evals, num_vars, count, point: bytes, k, d_out):
+        pb, kp = _buf(point if len(point) else b"\0")
+        self.check(ctx, self.dll.ark355_mle_fix_fr_dev(ctx, curve, C.c_void_p(d_evals), num_vars, count, pb, k, C.c_void_p(d_out)))
+
+    def mle_eval_fr(self, ctx, curve, evals, num_vars, count, point: bytes, fr_size=32):
+        """f~_k(point) for k < count: count Montgomery Fr"""
+        out = np.zeros(max(1, count * fr_size), dtype=np.uint8)
+        eb, ke = _buf(evals if len(evals) else b"\0")
+        pb, kp = _buf(point if len(point) else b"\0")
+        self.check(ctx, self.dll.ark355_mle_eval_fr(ctx, curve, eb, num_vars, count, pb, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:count * fr_size]
+
+    def mle_eval_fr_dev(self, ctx, curve, d_evals, num_vars, count, point: bytes, d_out):
+        pb, kp = _buf(point if len(point) else b"\0")
+        self.check(ctx, self.dll.ark355_mle_eval_fr_dev(ctx, curve, C.c_void_p(d_evals), num_vars, count, pb, C.c_void_p(d_out)))
+
+    # ---- sum-check of a predicate (csrc/sumcheck_impl.cuh) ------------------------------------------------------------------
+    def gr1cs_sumcheck_begin_dev(self, ctx, g, predicate, d_tables, d_weight, num_vars):
+        """a sumcheck handle over arity x 2^num_vars Fr at d_tables and 2^num_vars Fr at d_weight (None: weight 1), device pointers"""
+        h = C.c_void_p()
+        self.check(ctx, self.dll.ark355_gr1cs_sumcheck_begin_dev(ctx, g, predicate, C.c_void_p(d_tables) if d_tables else None,
+                                                                 C.c_void_p(d_weight) if d_weight else None, num_vars, C.byref(h)))
+        return h
+
+    def sumcheck_info(self, sc):
+        """(num_vars, arity, points, rounds_done)"""
+        v = [C.c_uint32(0) for _ in range(4)]
+        self.check(None, self.dll.ark355_sumcheck_info(sc, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def sumcheck_round(self, ctx, sc, challenge, points, fr_size=32):
+        """the message of the next round: `points` Montgomery Fr (challenge: None exactly in round 1, else canonical 32 bytes)"""
+        out = np.zeros(max(1, points * fr_size), dtype=np.uint8)
+        cb, k = _buf(challenge)
+        self.check(ctx, self.dll.ark355_sumcheck_round(ctx, sc, cb, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:points * fr_size]
+
+    def sumcheck_finish(self, ctx, sc, challenge, arity, fr_size=32):
+        """T_0, .., T_{t-1}, W at the point of the challenges: arity + 1 Montgomery Fr"""
+        out = np.zeros((arity + 1) * fr_size, dtype=np.uint8)
+        cb, k = _buf(challenge)
+        self.check(ctx, self.dll.ark355_sumcheck_finish(ctx, sc, cb, out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()
+
+    def sumcheck_free(self, sc):
+        self.dll.ark355_sumcheck_free(sc)
 
     def gr1cs_r1cs(self, ctx, g):
         """an ark355_r1cs handle from the predicate labelled "R1CS" (refused when another predicate has a row)"""

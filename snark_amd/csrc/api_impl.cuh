@@ -11,6 +11,8 @@
 #include "columns_impl.cuh"
 #include "poly_impl.cuh"
 #include "evals_impl.cuh"
+#include "mle_impl.cuh"
+#include "sumcheck_impl.cuh"
 #include "lcmap_impl.cuh"
 #include "setup_impl.cuh"
 #include "wire_impl.cuh"
@@ -451,6 +453,49 @@ struct Api {
                (const Gr1csMat*)P.mats.template as<Gr1csMat>(), (const Fr*)g.pool.template as<Fr>(), (const Fr*)d_z, P.n, N, N, (Fr*)d_out);
     ARK_CHECK_LAUNCH();
     ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+
+  // ---- multilinear extensions (mle_impl.cuh): the refusals are capi.hip's; every allocation happens before the first launch
+  // out[i] = eq(pt, i), 2^v Fr; pt: v Montgomery elements on the host
+  static void mle_eq(ark355_ctx* ctx, MleScratch& ms, uint32_t v, const Fr* pt, void* out, bool on_dev) {
+    hipStream_t st = ctx->stream;
+    const size_t bytes = sizeof(Fr) << v;
+    ms.pt.ensure((size_t)(2 * v + 2) * sizeof(Fr));
+    if (!on_dev) ms.out.ensure(bytes);
+    Fr* d_out = on_dev ? (Fr*)out : ms.out.template as<Fr>();
+    mle_eq_run<Fr>(v, pt, d_out, ms, st);
+    if (!on_dev) ARK_CHECK_HIP(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+  // variables 0 .. k-1 of `count` tables of 2^v fixed to pt[0 .. k): count x 2^(v-k) Fr; k = v is eval
+  static void mle_fix(ark355_ctx* ctx, MleScratch& ms, const void* evals, uint32_t v, uint64_t count, const Fr* pt, uint32_t k, void* out,
+                      bool on_dev) {
+    hipStream_t st = ctx->stream;
+    if (!count) return;
+    const size_t bytes = (size_t)(count << v) * sizeof(Fr), out_bytes = (size_t)(count << (v - k)) * sizeof(Fr);
+    mle_fix_reserve<Fr>(ms, v, count, k);
+    if (!on_dev) {
+      ms.in.ensure(bytes);
+      ms.out.ensure(out_bytes);
+      ARK_CHECK_HIP(hipMemcpyAsync(ms.in.p, evals, bytes, hipMemcpyHostToDevice, st));
+    }
+    Fr* d_out = on_dev ? (Fr*)out : ms.out.template as<Fr>();
+    mle_fix_run<Fr>(on_dev ? (const Fr*)evals : (const Fr*)ms.in.template as<Fr>(), v, count, pt, k, d_out, ms,
+                    sumcheck_lane_pairs(ctx->policy.sumcheck_lane_pairs), st);
+    if (!on_dev) ARK_CHECK_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    ARK_CHECK_HIP(hipStreamSynchronize(st));
+  }
+
+  // ---- sum-check of a predicate (sumcheck_impl.cuh): the order of the calls is checked by capi.hip
+  static SumcheckDev* sumcheck_begin(ark355_ctx* ctx, const Gr1csDev& g, uint32_t p, const void* d_tables, const void* d_weight,
+                                     uint32_t num_vars) {
+    return ark355::sumcheck_begin<Curve>(ctx->device, g, p, d_tables, d_weight, num_vars);
+  }
+  static void sumcheck_round(ark355_ctx* ctx, SumcheckDev& sc, const Fr& r, void* out) {
+    ark355::sumcheck_round<Curve>(sc, r, sumcheck_lane_pairs(ctx->policy.sumcheck_lane_pairs), out, ctx->stream);
+  }
+  static void sumcheck_finish(ark355_ctx* ctx, SumcheckDev& sc, const Fr& r, void* out) {
+    ark355::sumcheck_finish<Curve>(sc, r, out, ctx->stream);
   }
 
   static void ntt_host(ark355_ctx* ctx, GenericScratch& g, uint8_t* data, uint32_t log_n, bool inverse, bool coset) {

@@ -37,6 +37,9 @@ struct ark355_comm {
 struct ark355_pvk {
   PvkDev* d;
 };
+struct ark355_sumcheck {
+  SumcheckDev* d;
+};
 
 namespace {
 struct CtxExtra {
@@ -46,6 +49,7 @@ struct CtxExtra {
   ColumnsScratch columns;
   PolyScratch poly;
   EvalsScratch evals;
+  MleScratch mle;
   std::vector<ark355_ctx*> lanes;     // child contexts of ark355_prove_batch (same device, private streams/scratch)
   ~CtxExtra();
 };
@@ -1121,6 +1125,188 @@ int32_t ark355_gr1cs_mat_vec_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_
     return refuse(ctx, "ark355_gr1cs_mat_vec_dev: the gr1cs handle lives on another device than the context");
   if (z_len < g->d->m) return refuse(ctx, "assignment shorter than num_instance + num_witness", ARK355_E_ASSIGNMENT_MISSING);
   return guarded(ctx, [&] { CURVE_DISPATCH(g->d->curve, A::gr1cs_mat_vec_dev(ctx, *g->d, predicate, q, d_z, d_out)); });
+}
+
+// ---- multilinear extensions (mle_impl.cuh) ---------------------------------------------------------------------------------------
+
+// what eq, fix and eval refuse about (curve, num_vars, count) alone
+static int32_t mle_shape(int32_t curve, uint32_t num_vars, uint64_t count, std::string* why) {
+  if (curve != ARK355_BLS12_381 && curve != ARK355_BN254) {
+    *why = "unknown curve id";
+    return ARK355_EINVAL;
+  }
+  if (count > POLY_MAX_COUNT) {
+    *why = "count exceeds ARK355_POLY_MAX_COUNT";
+    return ARK355_EINVAL;
+  }
+  if (num_vars > MLE_MAX_VARS) {
+    *why = "num_vars must not exceed 40";
+    return ARK355_EINVAL;
+  }
+  if ((count << num_vars) >= POLY_MAX_ELEMS) {             // count <= 2^10, num_vars <= 40: no overflow
+    *why = "count * 2^num_vars must stay below 2^40";
+    return ARK355_EINVAL;
+  }
+  return ARK355_OK;
+}
+
+// `n` canonical scalars as Montgomery images of curve `curve` (one of the two vectors is filled); *why is set with every refusal
+static int32_t mle_point(int32_t curve, const uint8_t* point, uint32_t n, std::vector<BlsCurve::Fr>* bls, std::vector<BnCurve::Fr>* bn,
+                         std::string* why) {
+  bls->assign(curve == ARK355_BLS12_381 ? n : 0, BlsCurve::Fr::zero());
+  bn->assign(curve == ARK355_BN254 ? n : 0, BnCurve::Fr::zero());
+  for (uint32_t j = 0; j < n; j++) {
+    BlsCurve::Fr a;
+    BnCurve::Fr b;
+    const std::string name = "point[" + std::to_string(j) + "]";
+    if (const int32_t rc = poly_scalar(curve, point + 32 * (size_t)j, name.c_str(), &a, &b, why)) return rc;
+    if (curve == ARK355_BLS12_381) (*bls)[j] = a;
+    else (*bn)[j] = b;
+  }
+  return ARK355_OK;
+}
+
+static int32_t mle_eq_common(ark355_ctx* ctx, int32_t curve, uint32_t num_vars, const uint8_t* point, void* out, bool on_dev) {
+  if (!ctx) return ARK355_EINVAL;
+  const std::string pre = "ark355_mle_eq_fr: ";
+  std::string why;
+  if (const int32_t rc = mle_shape(curve, num_vars, 1, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if (!out || (num_vars && !point)) return refuse(ctx, (pre + "point / out is NULL").c_str());
+  std::vector<BlsCurve::Fr> p_bls;
+  std::vector<BnCurve::Fr> p_bn;
+  if (const int32_t rc = mle_point(curve, point, num_vars, &p_bls, &p_bn, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    if (curve == ARK355_BLS12_381) Api<BlsCurve>::mle_eq(ctx, ex.mle, num_vars, p_bls.data(), out, on_dev);
+    else Api<BnCurve>::mle_eq(ctx, ex.mle, num_vars, p_bn.data(), out, on_dev);
+  });
+}
+int32_t ark355_mle_eq_fr(ark355_ctx* ctx, int32_t curve, uint32_t num_vars, const uint8_t* point, uint8_t* out) {
+  return mle_eq_common(ctx, curve, num_vars, point, out, false);
+}
+int32_t ark355_mle_eq_fr_dev(ark355_ctx* ctx, int32_t curve, uint32_t num_vars, const uint8_t* point, void* d_out) {
+  return mle_eq_common(ctx, curve, num_vars, point, d_out, true);
+}
+
+// fix (k < 0: eval, every variable) on host or device pointers
+static int32_t mle_fix_common(ark355_ctx* ctx, const char* who, int32_t curve, const void* evals, uint32_t num_vars, uint64_t count,
+                              const uint8_t* point, int64_t k_or_all, void* out, bool on_dev) {
+  if (!ctx) return ARK355_EINVAL;
+  const std::string pre = std::string(who) + ": ";
+  std::string why;
+  if (const int32_t rc = mle_shape(curve, num_vars, count, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if (k_or_all > (int64_t)num_vars) return refuse(ctx, (pre + "k exceeds num_vars").c_str());
+  const uint32_t k = k_or_all < 0 ? num_vars : (uint32_t)k_or_all;
+  if ((k && !point) || (count && (!evals || !out))) return refuse(ctx, (pre + "evals / point / out is NULL").c_str());
+  std::vector<BlsCurve::Fr> p_bls;
+  std::vector<BnCurve::Fr> p_bn;
+  if (const int32_t rc = mle_point(curve, point, k, &p_bls, &p_bn, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if (poly_overlap(evals, (count << num_vars) * 32, out, (count << (num_vars - k)) * 32)) return refuse(ctx, (pre + "out overlaps evals").c_str());
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    if (curve == ARK355_BLS12_381) Api<BlsCurve>::mle_fix(ctx, ex.mle, evals, num_vars, count, p_bls.data(), k, out, on_dev);
+    else Api<BnCurve>::mle_fix(ctx, ex.mle, evals, num_vars, count, p_bn.data(), k, out, on_dev);
+  });
+}
+int32_t ark355_mle_fix_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* evals, uint32_t num_vars, uint64_t count, const uint8_t* point,
+                          uint32_t k, uint8_t* out) {
+  return mle_fix_common(ctx, "ark355_mle_fix_fr", curve, evals, num_vars, count, point, k, out, false);
+}
+int32_t ark355_mle_fix_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_evals, uint32_t num_vars, uint64_t count, const uint8_t* point,
+                              uint32_t k, void* d_out) {
+  return mle_fix_common(ctx, "ark355_mle_fix_fr", curve, d_evals, num_vars, count, point, k, d_out, true);
+}
+int32_t ark355_mle_eval_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* evals, uint32_t num_vars, uint64_t count, const uint8_t* point,
+                           uint8_t* out) {
+  return mle_fix_common(ctx, "ark355_mle_eval_fr", curve, evals, num_vars, count, point, -1, out, false);
+}
+int32_t ark355_mle_eval_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_evals, uint32_t num_vars, uint64_t count, const uint8_t* point,
+                               void* d_out) {
+  return mle_fix_common(ctx, "ark355_mle_eval_fr", curve, d_evals, num_vars, count, point, -1, d_out, true);
+}
+
+// ---- sum-check of a predicate (sumcheck_impl.cuh) -------------------------------------------------------------------------------
+
+int32_t ark355_gr1cs_sumcheck_begin_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* d_tables,
+                                        const void* d_weight, uint32_t num_vars, ark355_sumcheck** out) {
+  if (!ctx) return ARK355_EINVAL;
+  const char* pre = "ark355_gr1cs_sumcheck_begin_dev: ";
+  if (!out) return refuse(ctx, (std::string(pre) + "out is NULL").c_str());
+  *out = nullptr;
+  if (!g || !g->d) return refuse(ctx, (std::string(pre) + "the gr1cs handle is NULL").c_str());
+  if (!d_tables) return refuse(ctx, (std::string(pre) + "d_tables is NULL").c_str());
+  if (predicate >= g->d->preds.size()) return refuse(ctx, (std::string(pre) + "predicate index out of range").c_str());
+  if (g->d->device >= 0 && g->d->device != ctx->device)
+    return refuse(ctx, (std::string(pre) + "the gr1cs handle lives on another device than the context").c_str());
+  if (num_vars > MLE_MAX_VARS) return refuse(ctx, (std::string(pre) + "num_vars must not exceed 40").c_str());
+  if ((((uint64_t)g->d->preds[predicate].arity + 1) << num_vars) >= SUMCHECK_MAX_ELEMS)
+    return refuse(ctx, (std::string(pre) + "(arity + 1) * 2^num_vars must stay below 2^40").c_str());
+  return guarded(ctx, [&] {
+    SumcheckDev* d = nullptr;
+    CURVE_DISPATCH(g->d->curve, d = A::sumcheck_begin(ctx, *g->d, predicate, d_tables, d_weight, num_vars));
+    *out = new ark355_sumcheck{d};
+  });
+}
+
+int32_t ark355_sumcheck_info(const ark355_sumcheck* sc, uint32_t* num_vars, uint32_t* arity, uint32_t* points, uint32_t* rounds_done) {
+  if (!sc || !sc->d) return ARK355_EINVAL;
+  if (num_vars) *num_vars = sc->d->num_vars;
+  if (arity) *arity = sc->d->arity;
+  if (points) *points = sc->d->points;
+  if (rounds_done) *rounds_done = sc->d->rounds_done;
+  return ARK355_OK;
+}
+
+// what round and finish share: the handle, the device, the challenge (present exactly when `want`) as a Montgomery image
+static int32_t sumcheck_step_common(ark355_ctx* ctx, const char* pre, ark355_sumcheck* sc, const uint8_t* challenge, bool want, void* out,
+                                    BlsCurve::Fr* r_bls, BnCurve::Fr* r_bn) {
+  if (!sc || !sc->d) return refuse(ctx, (std::string(pre) + "the sumcheck handle is NULL").c_str());
+  if (!out) return refuse(ctx, (std::string(pre) + "the output is NULL").c_str());
+  if (sc->d->device != ctx->device) return refuse(ctx, (std::string(pre) + "the sumcheck handle lives on another device than the context").c_str());
+  if (sc->d->finished) return refuse(ctx, (std::string(pre) + "the run is finished: only ark355_sumcheck_info and ark355_sumcheck_free are legal").c_str());
+  if (want && !challenge) return refuse(ctx, (std::string(pre) + "call out of order: this call needs a challenge").c_str());
+  if (!want && challenge) return refuse(ctx, (std::string(pre) + "call out of order: this call takes no challenge (NULL)").c_str());
+  *r_bls = BlsCurve::Fr::zero();
+  *r_bn = BnCurve::Fr::zero();
+  if (want) {
+    std::string why;
+    if (const int32_t rc = poly_scalar(sc->d->curve, challenge, "challenge", r_bls, r_bn, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  }
+  return ARK355_OK;
+}
+
+int32_t ark355_sumcheck_round(ark355_ctx* ctx, ark355_sumcheck* sc, const uint8_t* challenge, uint8_t* evals_out) {
+  if (!ctx) return ARK355_EINVAL;
+  const char* pre = "ark355_sumcheck_round: ";
+  if (sc && sc->d && !sc->d->finished && sc->d->rounds_done >= sc->d->num_vars)
+    return refuse(ctx, (std::string(pre) + "call out of order: every round has run").c_str());
+  BlsCurve::Fr r_bls;
+  BnCurve::Fr r_bn;
+  if (const int32_t rc = sumcheck_step_common(ctx, pre, sc, challenge, sc && sc->d && sc->d->rounds_done > 0, evals_out, &r_bls, &r_bn)) return rc;
+  return guarded(ctx, [&] {
+    if (sc->d->curve == ARK355_BLS12_381) Api<BlsCurve>::sumcheck_round(ctx, *sc->d, r_bls, evals_out);
+    else Api<BnCurve>::sumcheck_round(ctx, *sc->d, r_bn, evals_out);
+  });
+}
+
+int32_t ark355_sumcheck_finish(ark355_ctx* ctx, ark355_sumcheck* sc, const uint8_t* challenge, uint8_t* finals_out) {
+  if (!ctx) return ARK355_EINVAL;
+  const char* pre = "ark355_sumcheck_finish: ";
+  if (sc && sc->d && !sc->d->finished && sc->d->rounds_done < sc->d->num_vars)
+    return refuse(ctx, (std::string(pre) + "call out of order: rounds are still to run").c_str());
+  BlsCurve::Fr r_bls;
+  BnCurve::Fr r_bn;
+  if (const int32_t rc = sumcheck_step_common(ctx, pre, sc, challenge, sc && sc->d && sc->d->num_vars > 0, finals_out, &r_bls, &r_bn)) return rc;
+  return guarded(ctx, [&] {
+    if (sc->d->curve == ARK355_BLS12_381) Api<BlsCurve>::sumcheck_finish(ctx, *sc->d, r_bls, finals_out);
+    else Api<BnCurve>::sumcheck_finish(ctx, *sc->d, r_bn, finals_out);
+  });
+}
+
+void ark355_sumcheck_free(ark355_sumcheck* sc) {
+  if (!sc) return;
+  delete sc->d;
+  delete sc;
 }
 
 int32_t ark355_ntt_fr(ark355_ctx* ctx, int32_t curve, uint8_t* data, uint32_t log_n, int32_t inverse, int32_t coset) {

@@ -20,7 +20,8 @@
 //                  expanded LC that ark355_gr1cs_from_lcs sorts in LDS), COLS_LANE_MAX (the longest column one lane of
 //                  ark355_gr1cs_mat_vec_t / ark355_gr1cs_columns_at sums), POLY_LANE_COEFFS (the coefficients one lane of
 //                  ark355_poly_eval_fr / ark355_poly_div_linear_fr owns), EVALS_LANE_POINTS (the domain points one lane of
-//                  ark355_evals_eval_fr / ark355_evals_div_linear_fr owns)
+//                  ark355_evals_eval_fr / ark355_evals_div_linear_fr owns), SUMCHECK_LANE_PAIRS (the output pairs one lane of
+//                  ark355_sumcheck_round owns, and the outputs one lane of ark355_mle_fix_fr / ark355_mle_eval_fr owns)
 //   process-wide   POISON_ALLOC: a TEST knob, not a tuning switch.  Device and pinned host buffers are allocated by objects that know no
 //                  context (DevBuf, common.h), so the value is mirrored into ONE atomic of the process (poison_alloc_byte): setting it
 //                  through any context, or through the environment of a context created later, changes it for every context.
@@ -105,8 +106,12 @@ struct TunePolicy {
                                   // workgroup owns 256 times as many and shares one field inversion among all of them.  <= 0: the
                                   // default; clamped to 1 .. 8.  Tests lower it to reach more workgroups and reduction levels at small domains; it
                                   // never changes a byte of any output.
+  int32_t sumcheck_lane_pairs = 1;// ark355_sumcheck_round (sumcheck_impl.cuh): the consecutive output pairs a lane of the round kernel owns, and the
+                                  // consecutive outputs a lane of ark355_mle_fix_fr / ark355_mle_eval_fr owns (mle_impl.cuh).  <= 0: the default;
+                                  // clamped to 1 .. 8.  Tests lower it to reach more workgroups and a second reduction level at small tables;
+                                  // it moves borders and never changes a byte of any output.
   // ---- process-wide (test knob)
-  int32_t poison_alloc = -1;      // 0 .. 255: every device buffer (DevBuf::alloc) and pinned host buffer is filled with this byte, synchronously,
+  int32_t poison_alloc = -1;     // 0 .. 255: every device buffer (DevBuf::alloc) and pinned host buffer is filled with this byte, synchronously,
                                   // before the allocator returns, so that no test passes because fresh memory happened to hold zeros; -1 (default)
                                   // off: one relaxed load per allocation.  The field only reports the value: what acts is the process-wide mirror
                                   // (common.h), written by ark355_ctx_set_policy and, ONCE per process, by ARK355_POISON_ALLOC at the first
@@ -164,6 +169,7 @@ inline const TunePolicy::Field* TunePolicy::fields(int* count) {
       ARK_POLICY_FIELD32("COLS_LANE_MAX", cols_lane_max),
       ARK_POLICY_FIELD32("POLY_LANE_COEFFS", poly_lane_coeffs),
       ARK_POLICY_FIELD32("EVALS_LANE_POINTS", evals_lane_points),
+      ARK_POLICY_FIELD32("SUMCHECK_LANE_PAIRS", sumcheck_lane_pairs),
       ARK_POLICY_FIELD32("POISON_ALLOC", poison_alloc),
   };
   *count = (int)(sizeof(tab) / sizeof(tab[0]));

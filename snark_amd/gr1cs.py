@@ -193,6 +193,16 @@ class GR1CS:
         self._need()
         self.lib.gr1cs_mat_vec_dev(self.ctx, self.handle, self._index[label], d_z, z_len, log_n, d_out)
 
+    def sumcheck_dev(self, label: str, d_tables: int, d_weight: Optional[int], num_vars: int):
+        """a ``Sumcheck`` (snark_amd/poly.py) of ``sum_i W[i] P(T_0[i], .., T_{t-1}[i])`` for the polynomial P of `label`
+        (``ark355_gr1cs_sumcheck_begin_dev``): d_tables holds arity x 2^num_vars Fr, matrix-major -- what ``mat_vec_dev`` writes --,
+        d_weight 2^num_vars Fr or None for weight 1.  Both are borrowed until the second round returns; this system must stay
+        loaded until the run is closed."""
+        from .poly import Sumcheck
+        self._need()
+        return Sumcheck(self.lib, self.ctx, self.lib.gr1cs_sumcheck_begin_dev(self.ctx, self.handle, self._index[label], d_tables, d_weight,
+                                                                              num_vars))
+
     def mat_vec_t(self, label: str, y) -> List[bytes]:
         """M_k^T y for the matrices of `label` (``ark355_gr1cs_mat_vec_t``): arity byte strings of m = ell + w Montgomery Fr
         each, column j the sum of c * y[i] over the stored entries (i, j, c).  y: n canonical ints or Montgomery bytes."""

@@ -94,3 +94,87 @@ class Evals:
                        coset: bool = False) -> None:
         """``d_q_out == d_evals`` divides in place; ``d_rem_out`` may be None"""
         self.lib.evals_div_linear_fr_dev(self.ctx, self.curve.curve_id, d_evals, log_n, count, int(coset), _canon(x), d_q_out, d_rem_out)
+
+
+class Mle:
+    """Multilinear extensions on the device (``include/ark355.h`` "Multilinear extensions", ``csrc/mle_impl.cuh``): tables of
+    ``2^num_vars`` Montgomery Fr over the Boolean hypercube, variable 0 the lowest index bit (ark-poly's
+    ``DenseMultilinearExtension``).  Points are sequences of Python integers below r and stay on the host; the ``_dev`` forms take
+    device pointers (ints) for the tables and the outputs: ``GR1CS.mat_vec_dev`` -> ``Mle.eq_dev`` -> ``GR1CS.sumcheck_dev`` ->
+    ``Mle.eval_dev`` never visits the host with a table."""
+
+    def __init__(self, curve="bls12_381", lib=None, ctx=None, device: int = 0):
+        self.curve: Curve = CURVES[curve] if not isinstance(curve, Curve) else curve
+        self.lib = lib if lib is not None else _lib()
+        self._own_ctx = ctx is None
+        self.ctx = self.lib.ctx_create(device) if ctx is None else ctx
+
+    def close(self):
+        if self._own_ctx and self.ctx is not None:
+            self.lib.ctx_destroy(self.ctx)
+        self.ctx = None
+
+    @staticmethod
+    def _point(point: Sequence[int]) -> bytes:
+        return b"".join(_canon(v) for v in point)
+
+    # ---- host forms ------------------------------------------------------------------------------------------------
+    def eq(self, point: Sequence[int]) -> bytes:
+        """eq(point, i) for i < 2^len(point): Montgomery Fr"""
+        return self.lib.mle_eq_fr(self.ctx, self.curve.curve_id, len(point), self._point(point))
+
+    def fix(self, evals: bytes, num_vars: int, point: Sequence[int], count: int = 1) -> bytes:
+        """variables 0 .. len(point)-1 of ``count`` tables fixed to ``point``: count x 2^(num_vars - len(point)) Montgomery Fr"""
+        return self.lib.mle_fix_fr(self.ctx, self.curve.curve_id, evals, num_vars, count, self._point(point), len(point))
+
+    def eval(self, evals: bytes, num_vars: int, point: Sequence[int], count: int = 1) -> bytes:
+        """f~_k(point) for k < count (``len(point) == num_vars``): count Montgomery Fr"""
+        assert len(point) == num_vars
+        return self.lib.mle_eval_fr(self.ctx, self.curve.curve_id, evals, num_vars, count, self._point(point))
+
+    # ---- device forms ----------------------------------------------------------------------------------------------
+    def eq_dev(self, point: Sequence[int], d_out: int) -> None:
+        self.lib.mle_eq_fr_dev(self.ctx, self.curve.curve_id, len(point), self._point(point), d_out)
+
+    def fix_dev(self, d_evals: int, num_vars: int, point: Sequence[int], d_out: int, count: int = 1) -> None:
+        """``d_out`` may not overlap ``d_evals``"""
+        self.lib.mle_fix_fr_dev(self.ctx, self.curve.curve_id, d_evals, num_vars, count, self._point(point), len(point), d_out)
+
+    def eval_dev(self, d_evals: int, num_vars: int, point: Sequence[int], d_out: int, count: int = 1) -> None:
+        assert len(point) == num_vars
+        self.lib.mle_eval_fr_dev(self.ctx, self.curve.curve_id, d_evals, num_vars, count, self._point(point), d_out)
+
+
+class Sumcheck:
+    """One sum-check run of a predicate over resident tables (``include/ark355.h`` "Sum-check of a GR1CS predicate",
+    ``csrc/sumcheck_impl.cuh``); made by ``GR1CS.sumcheck_dev``.  ``round(None)`` is round 1, ``round(r_j)`` every later one,
+    ``finish(r_v)`` returns the tables and the weight at the point of the challenges.  The caller's device memory is borrowed
+    until the second ``round`` returns; the GR1CS it came from must stay loaded until ``close``."""
+
+    def __init__(self, lib, ctx, handle):
+        self.lib, self.ctx, self.handle = lib, ctx, handle
+
+    def info(self) -> Tuple[int, int, int, int]:
+        """(num_vars, arity, points, rounds_done)"""
+        return self.lib.sumcheck_info(self.handle)
+
+    def round(self, challenge: Optional[int] = None) -> bytes:
+        """the next round's message g(0) .. g(D): ``points`` Montgomery Fr"""
+        points = self.info()[2]
+        return self.lib.sumcheck_round(self.ctx, self.handle, None if challenge is None else _canon(challenge), points)
+
+    def finish(self, challenge: Optional[int] = None) -> bytes:
+        """T_0 .. T_{t-1}, W at (r_1 .. r_v): arity + 1 Montgomery Fr (``challenge`` is None exactly when num_vars = 0)"""
+        arity = self.info()[1]
+        return self.lib.sumcheck_finish(self.ctx, self.handle, None if challenge is None else _canon(challenge), arity)
+
+    def close(self):
+        if self.handle is not None:
+            self.lib.sumcheck_free(self.handle)
+        self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

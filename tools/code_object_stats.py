@@ -57,6 +57,19 @@ KERNELS = [
     (r"lcs_compact_lds_kernelINS_2FpINS_10BnFrParams", "bn254.lcs_compact_lds"),
     (r"lcs_compact_long_kernelINS_2FpINS_11BlsFrParams", "bls12_381.lcs_compact_long"),
     (r"lcs_compact_long_kernelINS_2FpINS_10BnFrParams", "bn254.lcs_compact_long"),
+    # the round kernel of the sum-check: <FOLD, WEIGHT> = <1, 1> a later round with a weight, <0, 1> round 1, <1, 0> / <0, 0> without one
+    (r"sumcheck_round_kernelINS_2FpINS_11BlsFrParamsEEELb1ELb1E", "bls12_381.sumcheck_round_fold_weight"),
+    (r"sumcheck_round_kernelINS_2FpINS_11BlsFrParamsEEELb0ELb1E", "bls12_381.sumcheck_round_first_weight"),
+    (r"sumcheck_round_kernelINS_2FpINS_11BlsFrParamsEEELb1ELb0E", "bls12_381.sumcheck_round_fold"),
+    (r"sumcheck_round_kernelINS_2FpINS_11BlsFrParamsEEELb0ELb0E", "bls12_381.sumcheck_round_first"),
+    (r"sumcheck_round_kernelINS_2FpINS_10BnFrParamsEEELb1ELb1E", "bn254.sumcheck_round_fold_weight"),
+    (r"sumcheck_round_kernelINS_2FpINS_10BnFrParamsEEELb0ELb1E", "bn254.sumcheck_round_first_weight"),
+    (r"sumcheck_round_kernelINS_2FpINS_10BnFrParamsEEELb1ELb0E", "bn254.sumcheck_round_fold"),
+    (r"sumcheck_round_kernelINS_2FpINS_10BnFrParamsEEELb0ELb0E", "bn254.sumcheck_round_first"),
+    (r"mle_fold_kernelINS_2FpINS_11BlsFrParams", "bls12_381.mle_fold"),
+    (r"mle_fold_kernelINS_2FpINS_10BnFrParams", "bn254.mle_fold"),
+    (r"mle_eq_kernelINS_2FpINS_11BlsFrParamsEEELi3E", "bls12_381.mle_eq"),
+    (r"mle_eq_kernelINS_2FpINS_10BnFrParamsEEELi3E", "bn254.mle_eq"),
 ]
 
 
