@@ -164,6 +164,46 @@ int32_t ark355_diag_msm_sort(ark355_ctx* ctx, int32_t curve, const ark355_bases*
                              int32_t scalars_mont, uint32_t plan[ARK355_SORT_PLAN_WORDS], uint32_t* counts, uint32_t* offsets,
                              uint64_t bucket_capacity, uint32_t* sorted_keys, uint32_t* sorted_vals, uint64_t entry_capacity,
                              uint32_t* total);
+/* Diagnostic (a TEST entry): one field primitive of the library's arithmetic layers on operands the caller designed, one lane per
+ * element on the context's stream (workgroups of 256 lanes, any n up to ARK355_FIELD_OPS_MAX_N).  The kernels call the very functions
+ * the production kernels call, instantiated on the production parameter classes; nothing is converted, reduced or checked on the way
+ * in, so an operand must satisfy the documented precondition of the operation it is sent to (csrc/field.cuh, csrc/field28.cuh).
+ *   field   ARK355_FLD_*: the 32-bit-limb Montgomery fields Fq / Fr of both curves, their quadratic extensions Fq2, and the
+ *           radix-2^28 form of Fq the bucket kernels compute in (Fq28).
+ *   op      ARK355_FOP_*.  Fq / Fr: ADD SUB NEG DBL MUL (inlined multiplier) MUL_NI (out of line) SQR MUL2SUM (x0 x1 + x2 x3) MUL_SUB
+ *           (x0 x1 - x2 x3) INV TO_MONT FROM_MONT.  Fq2: ADD SUB NEG MUL MUL_NI SQR SQR_NI INV MUL_SUB.  Fq28: FROM_FP TO_FP
+ *           TO_FP_LT8 NORM CANON IS_ZERO (is_zero_mod_p) IS_ZERO_INL HINT (multiple_hint) ADD MUL SQR MUL2SUM MUL4SUM
+ *           (x0 x1 + x2 x3 + x4 x5 + x6 x7), COND_SUB + log2 K for K = 1, 2, 4, 8, 16, and the biased FOP28_SUB + 16 K + BETA
+ *           (x0 - x1 + K p) / FOP28_NEG + 16 K + BETA (K p - x0) for the (K, BETA) classes the bucket and tail kernels instantiate:
+ *           sub (3,1) (5,1) (6,1) (8,1) (11,1); neg (2,1) (3,1) (3,3) (4,2) (4,3) (5,1) (5,4) (6,1) (8,1).  (The Fq28 codes are
+ *           the ARK355_FOP28_* values.)
+ *   operands  operand_count host arrays of n elements each, raw little-endian 32-bit limb words: 12 (BLS12-381 Fq) or 8 words per
+ *           Fq / Fr element, twice that per Fq2 element (c0 then c1), 14 (BLS12-381) or 10 (BN254) words per Fq28 element --
+ *           FROM_FP takes Fq words.  operand_count must be the operation's arity (1, 2, 4 or 8).
+ *   result  n elements of the same layout (TO_FP / TO_FP_LT8: Fq words; IS_ZERO / IS_ZERO_INL / HINT: one word per element);
+ *           result_capacity = the words the buffer holds.
+ *   *flavour  written by the kernel itself: 1 when it was compiled with the inline-assembly multiplier of field.cuh (the device
+ *           build), 0 otherwise (the portable multiplier).
+ * ARK355_EINVAL, before any HIP call: a NULL context, operands, operand array, result or flavour; an unknown field or operation; a
+ * combination the library cannot instantiate (MUL2SUM / MUL_SUB on BLS12-381 Fr, whose modulus leaves one spare top bit where the
+ * dual-product chain needs two; an operation of another field type; a bias class no kernel uses); a wrong operand_count; n above the
+ * limit; a result_capacity below n elements. */
+#define ARK355_FIELD_OPS_MAX_N (1u << 24)
+enum {
+  ARK355_FLD_BLS_FQ = 0, ARK355_FLD_BLS_FR = 1, ARK355_FLD_BN_FQ = 2, ARK355_FLD_BN_FR = 3, ARK355_FLD_BLS_FQ2 = 4,
+  ARK355_FLD_BN_FQ2 = 5, ARK355_FLD_BLS_FQ28 = 6, ARK355_FLD_BN_FQ28 = 7
+};
+enum {
+  ARK355_FOP_ADD = 0, ARK355_FOP_SUB = 1, ARK355_FOP_NEG = 2, ARK355_FOP_DBL = 3, ARK355_FOP_MUL = 4, ARK355_FOP_MUL_NI = 5,
+  ARK355_FOP_SQR = 6, ARK355_FOP_MUL2SUM = 7, ARK355_FOP_MUL_SUB = 8, ARK355_FOP_INV = 9, ARK355_FOP_TO_MONT = 10,
+  ARK355_FOP_FROM_MONT = 11, ARK355_FOP_SQR_NI = 12,
+  ARK355_FOP28_FROM_FP = 32, ARK355_FOP28_TO_FP = 33, ARK355_FOP28_TO_FP_LT8 = 34, ARK355_FOP28_NORM = 35, ARK355_FOP28_CANON = 36,
+  ARK355_FOP28_IS_ZERO = 37, ARK355_FOP28_IS_ZERO_INL = 38, ARK355_FOP28_HINT = 39, ARK355_FOP28_ADD = 40, ARK355_FOP28_MUL = 41,
+  ARK355_FOP28_SQR = 42, ARK355_FOP28_MUL2SUM = 43, ARK355_FOP28_MUL4SUM = 44, ARK355_FOP28_COND_SUB = 48,
+  ARK355_FOP28_SUB = 256, ARK355_FOP28_NEG = 512
+};
+int32_t ark355_diag_field_ops(ark355_ctx* ctx, int32_t field, int32_t op, const uint32_t* const* operands, uint32_t operand_count,
+                              uint64_t n, uint32_t* result, uint64_t result_capacity, uint32_t* flavour);
 
 /* Page-locked host memory for assignments / key vectors handed to the entry points below: H2D copies from pinned
  * memory run at PCIe rate (~55 GB/s) and truly asynchronously; pageable memory is staged by the runtime at a fraction

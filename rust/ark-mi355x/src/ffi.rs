@@ -81,6 +81,48 @@ pub const ARK355_POLY_MAX_COUNT: u32 = 1024;
 pub const ARK355_SUMCHECK_MAX_POINTS: u32 = 32;
 /// words of the `plan` array of `ark355_diag_msm_sort`
 pub const ARK355_SORT_PLAN_WORDS: usize = 8;
+/// most elements one call of `ark355_diag_field_ops` takes
+pub const ARK355_FIELD_OPS_MAX_N: u64 = 1 << 24;
+/// fields of `ark355_diag_field_ops`
+pub const ARK355_FLD_BLS_FQ: i32 = 0;
+pub const ARK355_FLD_BLS_FR: i32 = 1;
+pub const ARK355_FLD_BN_FQ: i32 = 2;
+pub const ARK355_FLD_BN_FR: i32 = 3;
+pub const ARK355_FLD_BLS_FQ2: i32 = 4;
+pub const ARK355_FLD_BN_FQ2: i32 = 5;
+pub const ARK355_FLD_BLS_FQ28: i32 = 6;
+pub const ARK355_FLD_BN_FQ28: i32 = 7;
+/// operations of `ark355_diag_field_ops`: Fq / Fr / Fq2 ...
+pub const ARK355_FOP_ADD: i32 = 0;
+pub const ARK355_FOP_SUB: i32 = 1;
+pub const ARK355_FOP_NEG: i32 = 2;
+pub const ARK355_FOP_DBL: i32 = 3;
+pub const ARK355_FOP_MUL: i32 = 4;
+pub const ARK355_FOP_MUL_NI: i32 = 5;
+pub const ARK355_FOP_SQR: i32 = 6;
+pub const ARK355_FOP_MUL2SUM: i32 = 7;
+pub const ARK355_FOP_MUL_SUB: i32 = 8;
+pub const ARK355_FOP_INV: i32 = 9;
+pub const ARK355_FOP_TO_MONT: i32 = 10;
+pub const ARK355_FOP_FROM_MONT: i32 = 11;
+pub const ARK355_FOP_SQR_NI: i32 = 12;
+/// ... and the radix-2^28 form of Fq (COND_SUB + log2 K; SUB / NEG + 16 K + BETA)
+pub const ARK355_FOP28_FROM_FP: i32 = 32;
+pub const ARK355_FOP28_TO_FP: i32 = 33;
+pub const ARK355_FOP28_TO_FP_LT8: i32 = 34;
+pub const ARK355_FOP28_NORM: i32 = 35;
+pub const ARK355_FOP28_CANON: i32 = 36;
+pub const ARK355_FOP28_IS_ZERO: i32 = 37;
+pub const ARK355_FOP28_IS_ZERO_INL: i32 = 38;
+pub const ARK355_FOP28_HINT: i32 = 39;
+pub const ARK355_FOP28_ADD: i32 = 40;
+pub const ARK355_FOP28_MUL: i32 = 41;
+pub const ARK355_FOP28_SQR: i32 = 42;
+pub const ARK355_FOP28_MUL2SUM: i32 = 43;
+pub const ARK355_FOP28_MUL4SUM: i32 = 44;
+pub const ARK355_FOP28_COND_SUB: i32 = 48;
+pub const ARK355_FOP28_SUB: i32 = 256;
+pub const ARK355_FOP28_NEG: i32 = 512;
 
 #[repr(C)]
 pub struct ark355_pk_desc {
@@ -238,6 +280,19 @@ extern "C" {
         sorted_vals: *mut u32,
         entry_capacity: u64,
         total: *mut u32,
+    ) -> i32;
+    /// Diagnostic (test entry): one field primitive (`ARK355_FOP_*`) of field `ARK355_FLD_*` on `n` elements per operand
+    /// array of raw limb words, one lane per element; `*flavour` = 1 when the kernel ran the inline-assembly multiplier.
+    pub fn ark355_diag_field_ops(
+        ctx: *mut ark355_ctx,
+        field: i32,
+        op: i32,
+        operands: *const *const u32,
+        operand_count: u32,
+        n: u64,
+        result: *mut u32,
+        result_capacity: u64,
+        flavour: *mut u32,
     ) -> i32;
 
     pub fn ark355_host_alloc(bytes: u64, out: *mut *mut c_void) -> i32;

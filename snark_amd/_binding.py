@@ -32,6 +32,14 @@ GR1CS_MAX_FACTORS = 1024
 GR1CS_MAX_PREDICATES = 1024
 GR1CS_MAX_ROWS = 4294967295
 SORT_PLAN_WORDS = 8
+# ark355_diag_field_ops: fields and operation codes (ARK355_FLD_* / ARK355_FOP_* / ARK355_FOP28_* of include/ark355.h)
+FIELD_OPS_MAX_N = 1 << 24
+FLD = {"BlsFq": 0, "BlsFr": 1, "BnFq": 2, "BnFr": 3, "BlsFq2": 4, "BnFq2": 5, "BlsFq28": 6, "BnFq28": 7}
+FOP = {"add": 0, "sub": 1, "neg": 2, "dbl": 3, "mul": 4, "mul_ni": 5, "sqr": 6, "mul2sum": 7, "mul_sub": 8, "inv": 9,
+       "to_mont": 10, "from_mont": 11, "sqr_ni": 12}
+FOP28 = {"from_fp": 32, "to_fp": 33, "to_fp_lt8": 34, "norm": 35, "canon": 36, "is_zero_mod_p": 37, "is_zero_mod_p_inl": 38,
+         "multiple_hint": 39, "add": 40, "mul": 41, "sqr": 42, "mul2sum": 43, "mul4sum": 44, "cond_sub": 48, "sub": 0x100,
+         "neg": 0x200}
 
 _ERR_NAMES = {
     EINVAL: "EINVAL", ENOMEM: "ENOMEM", EHIP: "EHIP", ERCCL: "ERCCL", ENODEV: "ENODEV",
@@ -73,7 +81,7 @@ SYMBOLS = [
     "ark355_verify_each_pvk", "ark355_verify_batch_pvk",
     "ark355_points_check", "ark355_proofs_from_bytes", "ark355_verify_each_bytes",
     "ark355_ctx_set_policy", "ark355_ctx_get_policy", "ark355_sched_info", "ark355_sched_reset", "ark355_diag_streams", "ark355_diag_dispatch",
-    "ark355_diag_mad_rate", "ark355_diag_clocks", "ark355_diag_msm_sort",
+    "ark355_diag_mad_rate", "ark355_diag_clocks", "ark355_diag_msm_sort", "ark355_diag_field_ops",
 ]
 
 SCHED_NAMES = {-1: "auto", 0: "one_stream", 1: "pipeline", 2: "pipeline_sync", 3: "one_stream_spin"}
@@ -309,6 +317,7 @@ class Lib:
         d.ark355_diag_mad_rate.argtypes = [vp, C.c_float, P(C.c_float), P(C.c_float)]
         d.ark355_diag_clocks.argtypes = [vp, P(u64), u32, P(u32)]
         d.ark355_diag_msm_sort.argtypes = [vp, i32, vp, vp, u64, i32, P(u32 * SORT_PLAN_WORDS), vp, vp, u64, vp, vp, u64, P(u32)]
+        d.ark355_diag_field_ops.argtypes = [vp, i32, i32, P(vp), u32, u64, vp, u64, P(u32)]
         d.ark355_get_timings.argtypes = [vp, P(Timings)]
         d.ark355_get_kernel_stats.argtypes = [vp, P(C.c_float), P(u64), P(u64)]
         for name in SYMBOLS:
@@ -399,6 +408,18 @@ class Lib:
         assert list(plan2) == list(plan) and int(total.value) == ne
         out.update(counts=counts, offsets=offsets, sorted_keys=keys[:ne], sorted_vals=vals[:ne])
         return out
+
+    def diag_field_ops(self, ctx, field, op, operands, n, out_words):
+        """ark355_diag_field_ops: one field primitive (FOP_* / FOP28_*) of field FLD_* on `n` elements per operand, one lane per
+        element.  operands: numpy uint32 arrays of n x words raw limb words each; out_words: words per result element.  Returns
+        (result as an (n, out_words) uint32 array, flavour word: 1 when the kernel ran the inline-assembly multiplier)."""
+        ops = [np.ascontiguousarray(o, dtype=np.uint32) for o in operands]
+        ptrs = (C.c_void_p * max(len(ops), 1))(*[o.ctypes.data for o in ops])
+        res = np.zeros((max(n, 1), out_words), dtype=np.uint32)
+        flavour = C.c_uint32(0xFFFFFFFF)
+        self.check(ctx, self.dll.ark355_diag_field_ops(ctx, int(field), int(op), ptrs, len(ops), n, res.ctypes.data, n * out_words,
+                                                       C.byref(flavour)))
+        return res[:n], int(flavour.value)
 
     @staticmethod
     def diag_clocks_delta(c0, c1):

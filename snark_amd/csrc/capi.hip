@@ -7,6 +7,7 @@
 #include <new>
 #include <thread>
 #include "api_impl.cuh"
+#include "diag_field_impl.cuh"     // ark355_diag_field_ops: its kernels are compiled in this translation unit only
 
 namespace ark355 {
 extern template struct Api<BlsCurve>;
@@ -290,6 +291,25 @@ int32_t ark355_diag_msm_sort(ark355_ctx* ctx, int32_t curve, const ark355_bases*
     CURVE_DISPATCH(curve, A::diag_msm_sort(ctx, ex.generic, bases ? bases->d : nullptr, scalars, n, scalars_mont, plan, counts, offsets,
                                            bucket_capacity, sorted_keys, sorted_vals, entry_capacity, total));
   });
+}
+int32_t ark355_diag_field_ops(ark355_ctx* ctx, int32_t field, int32_t op, const uint32_t* const* operands, uint32_t operand_count,
+                              uint64_t n, uint32_t* result, uint64_t result_capacity, uint32_t* flavour) {
+  // every refusal below happens before any HIP call
+  if (!ctx || !operands || !result || !flavour) return ARK355_EINVAL;
+  FieldOpShape shape{};
+  if (!diag_field_op_shape(field, op, shape)) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->last_error = "field diagnostic: unknown field / operation, or a combination the library does not instantiate";
+    return ARK355_EINVAL;
+  }
+  if (operand_count != (uint32_t)shape.arity || n > ARK355_FIELD_OPS_MAX_N || result_capacity < n * (uint64_t)shape.out_words) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->last_error = "field diagnostic: operand count, element count or result capacity does not fit the operation";
+    return ARK355_EINVAL;
+  }
+  for (int j = 0; j < shape.arity; j++)
+    if (!operands[j]) return ARK355_EINVAL;
+  return guarded(ctx, [&] { diag_field_ops_run(ctx->stream, field, op, shape, operands, n, result, flavour); });
 }
 int32_t ark355_sched_reset(const ark355_ctx* ctx) {
   if (!ctx) return ARK355_EINVAL;

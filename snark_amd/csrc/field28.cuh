@@ -16,9 +16,13 @@
 //   since the Karatsuba level of round 5 is the default (mulsum -> mulsum_kara), whose EVERY limb is below 2^31: the
 //   level multiplies signed differences of limbs (v_mad_i64_i32), so a 2^32 limb against a 2^28 limb -- legal for the
 //   schoolbook pass -- is not.  Every caller in this library stays below 2^30.6; the emulator build traps on a limb
-//   >= 2^31 (ARK_F28_TRAP in mulsum_kara), the device build does not check.  They
-//   return an N value < 1.05 p as long as the product of the operand VALUES is < 2^10 p^2 -- far above anything
-//   the mixed addition produces.  Only the kernel boundary converts: window tables are converted to this form
+//   >= 2^31 (ARK_F28_TRAP in mulsum_kara), the device build does not check.  The limb bounds are not the whole
+//   contract: with V = sum_j a_j b_j over the operand VALUES the passes return the integer (V + m p) / R' < V / R' + p,
+//   normalised, its top limb stored in 32 bits -- so V / R' + p must stay below 2^(28 (N - 1) + 32) (14 all-ones limbs of
+//   2^30 against the same satisfy x + y <= 60 and do NOT), and the result is < 1.05 p as long as V < 0.05 p R':
+//   V < 125 p^2 on BLS12-381 (R' / p = 2519), V < 2^20 p^2 on BN254 -- the passes of the mixed additions stay below
+//   about 100 p^2.  (tests/fieldops_cases.py drives every function of this file on the device against these
+//   statements, through ark355_diag_field_ops.)  Only the kernel boundary converts: window tables are converted to this form
 //   once per key (from_fp), flushed bucket partials are converted back to the canonical 32-bit Montgomery form
 //   (to_fp), so nothing outside the accumulation kernels sees a non-canonical value and no output byte changes.
 #pragma once
@@ -74,8 +78,10 @@ struct Fp28 {
     return out;
   }
   // k*p in "borrow-friendly" form: every limb except the top one is raised by BETA*2^28 (the borrow is taken
-  // from the next limb), so that bias(i) - x.l[i] >= 0 for any x with limbs <= BETA*(2^28 - 1) and value
-  // < (k-1) p.  Same integer value k*p.
+  // from the next limb), so that bias(i) - x.l[i] >= 0 for any x whose limbs below the top one are <= BETA*(2^28 - 1)
+  // and whose top limb is <= (top limb of k p) - BETA.  A value < (k-1) p gives the latter on BLS12-381; on BN254,
+  // where the top limb of p is 3, a value < (k - (BETA + 1) / 3) p is enough -- the callers (sums of at most three
+  // products < 1.05 p under bias<5, 4>, one product under BETA = 1) stay well inside.  Same integer value k*p.
   ARK_HD static constexpr Limbs make_bias(uint32_t k, uint32_t beta) {
     Limbs d = make_kp(k);
     for (int i = 0; i < N; i++) {
@@ -139,7 +145,7 @@ struct Fp28 {
     }
     return r;
   }
-  // a - b + K p   (b: limbs <= BETA (2^28 - 1), value < (K - 1) p)
+  // a - b + K p   (b: b.l[i] <= bias<K, BETA>(i) for every i, see make_bias; a.l[i] + bias(i) - b.l[i] < 2^32)
   template <uint32_t K, uint32_t BETA>
   ARK_HD static Fp28 sub(const Fp28& a, const Fp28& b) {
     Fp28 r;
@@ -165,7 +171,8 @@ struct Fp28 {
     }
     return r;
   }
-  // carry propagation: limbs < 2^28 except the top one (which keeps whatever is left)
+  // carry propagation: limbs < 2^28 except the top one (which keeps whatever is left).  Input: limbs whose carry chain
+  // stays inside 32 bits (any limbs < 2^32 - 16), a value whose top limb then still fits
   ARK_HD static Fp28 norm(const Fp28& a) {
     Fp28 r;
     uint32_t c = 0;

@@ -3,7 +3,13 @@
 The Montgomery multiplier of csrc/field.cuh is an inline-assembly carry chain on the device and portable C++ everywhere else
 (emulator, host): only a GPU run executes the former.  What enters the multiplier is the Montgomery IMAGE x R mod p of a
 value, so the operands here are chosen by their image: all-zero / all-one limbs, single carries across every limb, the
-neighbourhood of the modulus.  Every expected value is computed in Python integers."""
+neighbourhood of the modulus.  Every expected value is computed in Python integers.
+
+What this module covers: `Fr::mul`, pattern times pattern, through ark355_r1cs_mat_vec / ark355_gr1cs_eval
+(diagonal_pairs_case), and `Fq` only as COORDINATES -- the x of points at or near a pattern (pattern_points_g1), which a group
+law subtracts before it multiplies.  It does not cover Fq pattern times pattern, the dual product mul2sum / mul_sub, add / sub /
+neg / reduce_once at their own edges, Fp2 or the radix-2^28 Fp28: those are pinned primitive by primitive in
+tests/fieldops_cases.py (ark355_diag_field_ops), which reuses montgomery_images below."""
 from __future__ import annotations
 
 import itertools

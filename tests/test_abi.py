@@ -74,6 +74,13 @@ def test_host_only_entry_points_reject_bad_arguments(built_lib):
     assert lib.dll.ark355_diag_msm_sort(None, snark_amd.BLS12_381, None, sc, 2, 0, C.byref(plan), None, None, 0, None, None, 0,
                                         C.byref(total)) == EINVAL
     assert list(plan) == [7] * SORT_PLAN_WORDS and total.value == 7
+    # the field diagnostic without a context: refused before any HIP call, nothing written (the other NULL arguments need a
+    # context: tests/fieldops_cases.py refusal_cases)
+    from snark_amd._binding import FLD, FOP
+    a, res, fl = (C.c_uint32 * 8)(), (C.c_uint32 * 8)(*([7] * 8)), C.c_uint32(7)
+    ops = (C.c_void_p * 2)(C.addressof(a), C.addressof(a))
+    assert lib.dll.ark355_diag_field_ops(None, FLD["BnFq"], FOP["add"], ops, 2, 1, res, 8, C.byref(fl)) == EINVAL
+    assert list(res) == [7] * 8 and fl.value == 7
     buf = (C.c_uint8 * 512)()
     raw = ProofRaw()
     out = C.byref(raw)
@@ -111,6 +118,18 @@ def test_kernel_statistics_are_read_from_the_built_library(built_lib):
     assert st["bn254.g1"]["hot_block"]["multiply_adds"] < g1["multiply_adds"]
     assert max(b["scratch_loads"] for b in (g1, st["bn254.g1"]["hot_block"])) == 0
     assert g2["lds"] >= 48 and g2["scratch_loads"] + g2["scratch_stores"] < 40, g2
+    # the test kernels of ark355_diag_field_ops: the inlined multipliers (their long branch-free runs) make no scratch access and
+    # the Fp28 kernels none at all; what the Fp / Fp2 kernels have is the by-reference operands of the out-of-line `_ni` bodies
+    # they call as the production kernels do (a few dozen accesses, none in a multiplier)
+    diag = ("diag.fp_bls_fq", "diag.fp_bls_fr", "diag.fp_bn_fq", "diag.fp_bn_fr", "diag.fp2_bls_fq2", "diag.fp2_bn_fq2",
+            "diag.fp28_bls_fq", "diag.fp28_bn_fq")
+    for key in diag:
+        assert key in st, (key, sorted(st))
+        hb = st[key]["hot_block"]
+        assert hb["multiply_adds"] > 200 and hb["scratch_loads"] == 0 and hb["scratch_stores"] == 0, (key, hb)
+        assert st[key]["scratch_loads"] + st[key]["scratch_stores"] < 64, (key, st[key])
+    for key in diag[-2:]:
+        assert st[key]["scratch_loads"] + st[key]["scratch_stores"] == 0, (key, st[key])
     side = os.path.splitext(built_lib)[0] + ".stats.json"
     if os.path.exists(side):
         assert json.load(open(side))["bls12_381.g1"]["hot_block"]["multiply_adds"] == g1["multiply_adds"]

@@ -70,6 +70,17 @@ KERNELS = [
     (r"mle_fold_kernelINS_2FpINS_10BnFrParams", "bn254.mle_fold"),
     (r"mle_eq_kernelINS_2FpINS_11BlsFrParamsEEELi3E", "bls12_381.mle_eq"),
     (r"mle_eq_kernelINS_2FpINS_10BnFrParamsEEELi3E", "bn254.mle_eq"),
+    # the test kernels of ark355_diag_field_ops: their long branch-free runs are the INLINED multipliers (no scratch access there,
+    # none at all in the Fp28 kernels); the 16 - 58 accesses of the Fp / Fp2 kernels are the by-reference operands (and, for the
+    # 24-word BLS12-381 Fq2, the returned value) of the out-of-line `_ni` bodies they call as the production kernels do
+    (r"diag_fp_kernelINS_2FpINS_11BlsFqParams", "diag.fp_bls_fq"),
+    (r"diag_fp_kernelINS_2FpINS_11BlsFrParams", "diag.fp_bls_fr"),
+    (r"diag_fp_kernelINS_2FpINS_10BnFqParams", "diag.fp_bn_fq"),
+    (r"diag_fp_kernelINS_2FpINS_10BnFrParams", "diag.fp_bn_fr"),
+    (r"diag_fp2_kernelINS_3Fp2INS_11BlsFqParams", "diag.fp2_bls_fq2"),
+    (r"diag_fp2_kernelINS_3Fp2INS_10BnFqParams", "diag.fp2_bn_fq2"),
+    (r"diag_fp28_kernelINS_4Fp28INS_11BlsFqParams", "diag.fp28_bls_fq"),
+    (r"diag_fp28_kernelINS_4Fp28INS_10BnFqParams", "diag.fp28_bn_fq"),
 ]
 
 
