@@ -830,7 +830,15 @@ int32_t ark355_xyzz_sum(ark355_ctx* ctx, int32_t curve, int32_t group, const uin
                         uint64_t count, uint8_t* out_affine);
 
 /* out[i] = scalars[i] * base (fixed base, canonical scalars) -> affine; used by
- * circuit_specific_setup (snark/src/lib.rs:43-46) to build the query vectors */
+ * circuit_specific_setup (snark/src/lib.rs:43-46) to build the query vectors.
+ * A scalar is read as a 256-bit little-endian integer k and need not be below r.  Fewer than 512 scalars are multiplied out by
+ * double-and-add over all 256 bits, 512 or more through a table of d 2^(8 w) base (w < 32, d < 256); both compute k * base in the
+ * group, which for a base in the subgroup of prime order r is (k mod r) * base: k = r and k = 2 r give the point at infinity
+ * (all zero), k = 2^256 - 1 gives ((2^256 - 1) mod r) * base.  On the table route such a k can bring the running sum to plus or
+ * minus the row of the last window (k = r, 2 r: minus; k = 2 d 2^248 - r with d = ceil(r / 2^248): plus); the mixed addition
+ * doubles or cancels there (tests/grouplaw_cases.py).  For a base outside that subgroup (G2 takes any point of the twist, BLS12-381
+ * G1 any point of the curve) the result is still k * base, which then depends on k itself and not only on k mod r.  A base at
+ * infinity gives infinity for every k. */
 int32_t ark355_fixed_base_mul(ark355_ctx* ctx, int32_t curve, int32_t group, const uint8_t* base,
                               const uint8_t* scalars, uint64_t n, uint8_t* out_affine);
 /* ark355_fixed_base_mul with the scalars in device memory; scalars_mont != 0: Montgomery images, converted on the device

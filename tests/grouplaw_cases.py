@@ -1,0 +1,690 @@
+"""The cold 32-bit XYZZ group law (snark_amd/csrc/curve.cuh: xyzz_add, xyzz_dbl, xyzz_madd_ni with xyzz_dbl_affine_ni, xyzz_mul_scalar,
+xyzz_to_affine; wave_reduce_sum / batch_to_affine_kernel of msm_impl.cuh) driven through equal, opposite and empty operands -- shared
+by the CPU-emulator tier (tests/test_emul_grouplaw.py) and the GPU tier (tests/test_gpu_grouplaw.py).
+
+Sums of random points never take the branches P + P, P + (-P), O + P, P + O, O + O, and never meet two equal points in different
+representations.  Here every point is m P for one seeded P = s G per (curve, group) and a small integer m, so every operand of every
+addition is known as an integer modulo r: the expected result is computed on integers first, each design asserts ON INTEGERS that it
+has the property it is named for (which additions double, cancel or meet an empty operand; which outputs are at infinity; which
+scalars collide with a table row), and only then is the library called.  The expected points come from the oracle alone
+(oracle.curves, oracle.c.cbase.fixed_base); nothing of the library stands on the expected side.
+
+  1  ark355_xyzz_sum over XYZZ operands built by hand, against an integer model of xyzz_sum_kernel's dealing
+  2  ark355_fixed_base_mul / _dev on both routes (double-and-add below 512 scalars, the 32 x 255 window table from 512 on)
+  3  ark355_hbasis_transform over structured inputs, against a model of the butterflies in the exponent
+  4  ark355_hbasis_gather with U_j = m_j P
+  5  ark355_verify_each / _pvk with prepared inputs that double, cancel, start and end at infinity"""
+from __future__ import annotations
+
+import random
+from collections import Counter
+
+import hbasis_cases as hc
+from helpers import r1cs_load_from_rows
+from oracle import serialize as Z, synthetic as S
+from oracle.c import cbase
+from oracle.curves import g1, g2
+from oracle.ntt import Domain
+
+CLASSES = ("generic", "double", "cancel", "left-empty", "right-empty", "both-empty")
+
+
+def classify(a, b, r):
+    """What xyzz_add / xyzz_madd take for a P + b P (P of prime order r)."""
+    a %= r
+    b %= r
+    if not a:
+        return "left-empty" if b else "both-empty"
+    if not b:
+        return "right-empty"
+    if a == b:
+        return "double"
+    if (a + b) % r == 0:
+        return "cancel"
+    return "generic"
+
+
+def centred(v, r):
+    v %= r
+    return v if v <= r // 2 else v - r
+
+
+class Tier:
+    """The library, a context, and how bytes reach "device" memory."""
+
+    def __init__(self, lib, ctx, to_dev):
+        self.lib, self.ctx, self.to_dev = lib, ctx, to_dev
+
+
+def group_of(C, group):
+    """(oracle group, raw encoder, raw point size)"""
+    if group == 1:
+        return g1(C), Z.g1_raw, 2 * C.fq_bytes
+    return g2(C), Z.g2_raw, 4 * C.fq_bytes
+
+
+def dlog(C, group):
+    """s of P = s G: one seeded value per curve and group."""
+    return random.Random("grouplaw/%s/%d" % (C.name, group)).randrange(2, C.r)
+
+
+_PTS = {}
+
+
+def point(C, group, m):
+    """m P as the oracle's affine point (None: infinity), cached; m is taken modulo r."""
+    key = (C.name, group, m % C.r)
+    if key not in _PTS:
+        G_ = group_of(C, group)[0]
+        _PTS[key] = G_.mul(G_.gen, m * dlog(C, group) % C.r)
+        assert (_PTS[key] is None) == (m % C.r == 0)
+    return _PTS[key]
+
+
+def point_raw(C, group, m):
+    return group_of(C, group)[1](C, point(C, group, m))
+
+
+def scalar_bytes(ks):
+    return b"".join(k.to_bytes(32, "little") for k in ks)
+
+
+def split(b, size):
+    assert len(b) % size == 0
+    return [b[i:i + size] for i in range(0, len(b), size)]
+
+
+# ---- 1. ark355_xyzz_sum ----------------------------------------------------------------------------------------------------------------
+SUM_COUNTS = (1, 2, 63, 64, 65, 127, 128, 129, 200)
+SUM_DESIGNS = (("constant", "alternating", "sign-bit-1", "sign-bit-2", "sign-bit-3", "sign-bit-4", "halves", "rows", "single-first",
+                "single-last", "single-middle", "zero") + tuple("fuzz-%d" % s for s in (1, 2, 3)))
+SIGN_BIT = {"alternating": 0, "sign-bit-1": 1, "sign-bit-2": 2, "sign-bit-3": 3, "sign-bit-4": 4, "halves": 5, "rows": 6}
+LEVELS = (32, 16, 8, 4, 2, 1)
+
+
+def sum_multipliers(design, count):
+    """m_i of the `count` entries.  `alternating`: the sign is bit 0 of the index, `halves` bit 5 (half-waves), `rows` bit 6 (the trip
+    of the lane loop), sign-bit-k bit k: lanes l and l ^ 2^k hold opposite sums when they meet."""
+    if design == "constant":
+        return [1] * count
+    if design in SIGN_BIT:
+        return [-1 if i >> SIGN_BIT[design] & 1 else 1 for i in range(count)]
+    if design.startswith("single-"):
+        at = {"first": 0, "last": count - 1, "middle": count // 2}[design.split("-")[1]]
+        return [1 if i == at else 0 for i in range(count)]
+    if design == "zero":
+        return [0] * count
+    if design.startswith("fuzz-"):
+        rnd = random.Random("grouplaw-sum/%s/%d" % (design, count))
+        return [rnd.randrange(-3, 4) for _ in range(count)]
+    raise KeyError(design)
+
+
+def sum_model(ms, r):
+    """The dealing of xyzz_sum_kernel (msm_impl.cuh) on integers: lane l adds entries l, l + 64, ... in order, starting from empty;
+    then levels mask = 32 .. 1 of wave_reduce_sum compute v = v + v[lane ^ mask] in every lane.
+    -> (classes of the serial additions, in order; six lists of the 64 classes of a level; the integer lane 0 ends with)"""
+    v, serial = [0] * 64, []
+    for lane in range(64):
+        for i in range(lane, len(ms), 64):
+            serial.append(classify(v[lane], ms[i], r))
+            v[lane] = (v[lane] + ms[i]) % r
+    levels = []
+    for mask in LEVELS:
+        levels.append([classify(v[lane], v[lane ^ mask], r) for lane in range(64)])
+        v = [(v[lane] + v[lane ^ mask]) % r for lane in range(64)]
+    assert len(set(v)) == 1
+    return serial, levels, v[0]
+
+
+def assert_sum_design(design, count, ms, r):
+    """The property a design is named for, on the model."""
+    serial, levels, total = sum_model(ms, r)
+    assert total == sum(ms) % r and len(serial) == count
+    assert serial[0] in ("left-empty", "both-empty")           # the first addition of a lane starts from empty
+    full = count % 64 == 0
+    if design == "constant":
+        assert set(ms) == {1}
+        if full:                                               # every lane holds the same point at every level
+            assert all(set(lv) == {"double"} for lv in levels)
+        if count > 64:
+            assert serial[1] == "double"                       # lane 0: P + P in the second trip
+        if count > 128:
+            assert serial[2] == "generic"                      # 2 P + P in the third
+    elif design in SIGN_BIT:
+        k = SIGN_BIT[design]
+        if full and k < 6:                                     # equal sums above the sign bit, opposite ones at it, nothing below
+            for mask, lv in zip(LEVELS, levels):
+                assert set(lv) == {"double" if mask > 1 << k else "cancel" if mask == 1 << k else "both-empty"}, (design, count, mask)
+            assert total == 0
+        if design == "rows" and count > 64:
+            assert serial[1] == "cancel"
+    elif design.startswith("single-"):
+        assert sorted(ms)[-2:] == ([0, 1] if count > 1 else [1]) and sum(ms) == 1
+        for i, lv in enumerate(levels):                        # the point spreads: 2^i lanes hold it before level i
+            c = Counter(lv)
+            assert c["right-empty"] == c["left-empty"] == 1 << i and c["both-empty"] == 64 - (2 << i), (design, count, i)
+    elif design == "zero":
+        assert set(serial) == {"both-empty"} and all(set(lv) == {"both-empty"} for lv in levels) and total == 0
+    elif design.startswith("fuzz-"):
+        if count >= 63:
+            assert max(len(set(lv)) for lv in levels) >= 3
+    else:
+        raise KeyError(design)
+    return serial, levels, total
+
+
+def assert_sum_coverage(r):
+    """Over all designs and counts: each of the six classes occurs in the serial phase and at every butterfly level, and at least
+    one design puts three or more classes into one level of the wave (the divergent call of xyzz_add)."""
+    serial_seen, level_seen, divergent = set(), [set() for _ in LEVELS], []
+    for design in SUM_DESIGNS:
+        for count in SUM_COUNTS:
+            serial, levels, _ = sum_model(sum_multipliers(design, count), r)
+            serial_seen |= set(serial)
+            for seen, lv in zip(level_seen, levels):
+                seen |= set(lv)
+            if max(len(set(lv)) for lv in levels) >= 3:
+                divergent.append((design, count))
+    assert serial_seen == set(CLASSES), set(CLASSES) - serial_seen
+    for mask, seen in zip(LEVELS, level_seen):
+        assert seen == set(CLASSES), (mask, set(CLASSES) - seen)
+    assert divergent
+    return divergent
+
+
+def _fe(C, group, v):
+    """Montgomery image of one coordinate, in the limb order of Z.g1_raw / Z.g2_raw."""
+    nb, q = C.fq_bytes, C.q
+    R = 1 << (8 * nb)
+    return b"".join((c * R % q).to_bytes(nb, "little") for c in ((v,) if group == 1 else v))
+
+
+def _fq_nonzero(C, group, rnd):
+    """A seeded coordinate; G2: both components non-zero."""
+    return rnd.randrange(1, C.q) if group == 1 else (rnd.randrange(1, C.q), rnd.randrange(1, C.q))
+
+
+def xyzz_bytes(C, group, P, lam):
+    """(x lam^2, y lam^3, lam^2, lam^3): the XYZZ image of the affine point P with ZZ = lam^2."""
+    F = group_of(C, group)[0].F
+    l2 = F.sqr(lam)
+    l3 = F.mul(l2, lam)
+    return _fe(C, group, F.mul(P[0], l2)) + _fe(C, group, F.mul(P[1], l3)) + _fe(C, group, l2) + _fe(C, group, l3)
+
+
+def xyzz_infinity(C, group, form, rnd):
+    """form 0: all-zero bytes; form 1: ZZ = 0 with non-zero x, y, zzz ("XYZZ infinity is ZZ == 0", curve.cuh)."""
+    psz = group_of(C, group)[2]
+    if form == 0:
+        return bytes(2 * psz)
+    F = group_of(C, group)[0].F
+    x, y, zzz = (_fq_nonzero(C, group, rnd) for _ in range(3))
+    return _fe(C, group, x) + _fe(C, group, y) + _fe(C, group, F.zero) + _fe(C, group, zzz)
+
+
+def sum_case(tier, C, group, design, counts=SUM_COUNTS, lam_modes=("seeded", "one")):
+    G_, raw, psz = group_of(C, group)
+    F = G_.F
+    assert xyzz_bytes(C, group, point(C, group, 1), F.one)[:psz] == raw(C, point(C, group, 1))       # the limb order
+    for count in counts:
+        ms = sum_multipliers(design, count)
+        _, _, total = assert_sum_design(design, count, ms, C.r)
+        want = raw(C, point(C, group, total))
+        for mode in lam_modes:
+            rnd = random.Random("grouplaw-lam/%s/%d/%s/%d" % (C.name, group, design, count))
+            parts = []
+            for i, m in enumerate(ms):
+                lam = _fq_nonzero(C, group, rnd)               # (drawn in both modes: the infinity forms stay where they are)
+                if m == 0:
+                    parts.append(xyzz_infinity(C, group, (i + count) & 1, rnd))
+                else:
+                    parts.append(xyzz_bytes(C, group, point(C, group, m), lam if mode == "seeded" else F.one))
+            got = tier.lib.xyzz_sum(tier.ctx, C.curve_id, group, b"".join(parts), count, psz)
+            assert got == want, (C.name, group, design, count, mode, total)
+
+
+# ---- 2. ark355_fixed_base_mul ----------------------------------------------------------------------------------------------------------
+FB_TABLE_MIN = 512                       # api_impl.cuh: the window table from this many scalars on
+FB_NS = (511, 512, 530)
+FB_BASES = ("P", "G", "O")
+
+
+def fb_collider(r):
+    """(k, d): k = 2 d 2^248 - r with d = ceil(r / 2^248).  Its top byte is d and its low 248 bits are d 2^248 - r = d 2^248 (mod r):
+    the table route reaches window 31 with acc == T[31][d] and doubles.  (k = r and k = 2 r reach it with acc == -T[31][d].)"""
+    d = -(-r >> 248)
+    return 2 * d * (1 << 248) - r, d
+
+
+def fb_walk(k, r):
+    """fixed_base_mul_kernel's walk on integers (units of the base, which has order r): windows 0 .. 31, digit d adds
+    T[w][d] = d 2^(8 w) base.  -> (class of every addition, the result)."""
+    acc, classes = 0, []
+    for w in range(32):
+        d = k >> (8 * w) & 0xFF
+        if d:
+            t = (d << (8 * w)) % r
+            classes.append(classify(acc, t, r))
+            acc = (acc + t) % r
+    return classes, acc
+
+
+def fb_windows():
+    """d 2^(8 w) for every window w and d in {1, 255}."""
+    return [d << (8 * w) for w in range(32) for d in (1, 255)]
+
+
+def fb_specials(r):
+    return [(1 << 256) - 1, 0, 1, r - 1, r, r + 1, 2 * r, fb_collider(r)[0]]
+
+
+def fb_scalars(C, n, below_r=False):
+    """The scalars of one call.  Edge values at 0, 127, 128 and n - 1; results at infinity (k = 0 mod r) at 0, 15 and 16 -- the
+    first and the last point of a batch of batch_to_affine_kernel and the first of the next --, in the whole batch 64 .. 79, at
+    127 (the last lane of a wave, the last point of its batch) and at n - 1; the doubling collider at 128 and at 1.
+    below_r: every value >= r replaced by a seeded one below r (what a Montgomery image can hold)."""
+    r = C.r
+    coll, _ = fb_collider(r)
+    rnd = random.Random("grouplaw-fb/%s/%d" % (C.name, n))
+    edges = fb_windows() + fb_specials(r)
+    assert max(edges) < 1 << 256
+    ks = [None] * n
+    ks[0], ks[1], ks[15], ks[16], ks[127], ks[128], ks[n - 1] = 0, coll, r, 2 * r, r, coll, 2 * r
+    ks[64:80] = [(0, r, 2 * r)[i % 3] for i in range(16)]
+    free = [i for i in range(n) if ks[i] is None]
+    for i, k in zip(free, edges):
+        ks[i] = k
+    for j, i in enumerate(free[len(edges):]):
+        ks[i] = rnd.randrange(1, r) if j & 1 else rnd.randrange(1 << 255, 1 << 256)
+    if below_r:
+        ks = [k if k < r else rnd.randrange(1, r) for k in ks]
+    return ks
+
+
+def assert_fb_design(C, n, ks):
+    """On integers: the route, the placement, and that the colliders meet acc == +-T[31][d] in the window walk."""
+    r = C.r
+    coll, d = fb_collider(r)
+    assert (d - 1) << 248 < r <= d << 248 and r <= coll < 1 << 256 and coll >> 248 == d
+    assert (coll & ((1 << 248) - 1)) % r == (d << 248) % r
+    walk = fb_walk(coll, r)
+    assert walk[0][-1] == "double" and walk[1] == coll % r != 0
+    for k in (r, 2 * r):
+        assert k < 1 << 256
+        walk = fb_walk(k, r)
+        assert walk[0][-1] == "cancel" and walk[1] == 0 and "cancel" not in walk[0][:-1]
+    for k in ks:                                   # every walk ends at k mod r; below r no addition doubles or cancels
+        classes, end = fb_walk(k, r)
+        assert end == k % r
+        assert k >= r or set(classes) <= {"left-empty", "generic"}, hex(k)
+    assert (n >= FB_TABLE_MIN) == (n != 511)
+    if n == 530:
+        assert n % 128 and n % 16
+    assert len(ks) == n and ks[0] == 0 and ks[15] == ks[127] == r and ks[16] == ks[n - 1] == 2 * r and ks[1] == ks[128] == coll
+    assert all(k % r == 0 for k in ks[64:80])
+    assert set(fb_windows() + fb_specials(r)) <= set(ks)
+    assert any(k < r for k in ks[130:]) and any(k >> 255 for k in ks[130:])
+    return [i for i, k in enumerate(ks) if k % r == 0]
+
+
+_FB_EXPECTED = {}
+_FB_CROSS = set()
+
+
+def fb_base(C, group, name):
+    G_ = group_of(C, group)[0]
+    return {"P": point(C, group, 1), "G": G_.gen, "O": None}[name]
+
+
+def fb_expected(C, group, name, n, below_r=False):
+    """(scalars, [(k mod r) base] as raw points): oracle.c for all outputs, Group.mul for the edge scalars (once per base)."""
+    key = (C.name, group, name, n, below_r)
+    if key not in _FB_EXPECTED:
+        G_, raw, psz = group_of(C, group)
+        ks = fb_scalars(C, n, below_r)
+        base = fb_base(C, group, name)
+        want = split(cbase.fixed_base(C, group, raw(C, base), scalar_bytes([k % C.r for k in ks]), n), psz)
+        if name == "O":
+            assert want == [bytes(psz)] * n
+        else:
+            inf = assert_fb_design(C, n, ks) if not below_r else [i for i, k in enumerate(ks) if k == 0]
+            assert [i for i, w in enumerate(want) if w == bytes(psz)] == inf
+            if not below_r and (C.name, group, name) not in _FB_CROSS:
+                _FB_CROSS.add((C.name, group, name))
+                # the 72 edge values for the seeded base, the eight special ones for the generator
+                for k in fb_specials(C.r) + (fb_windows() if name == "P" else []):
+                    assert want[ks.index(k)] == raw(C, G_.mul(base, k % C.r)), (C.name, group, name, hex(k))
+        _FB_EXPECTED[key] = (ks, want)
+    return _FB_EXPECTED[key]
+
+
+def fixed_base_case(tier, C, group, n, name, entry="host"):
+    """entry: "host" (ark355_fixed_base_mul), "dev" (canonical scalars in device memory), "dev-mont" (Montgomery images: the
+    values below r only).  Every output is compared."""
+    _, raw, psz = group_of(C, group)
+    lib, ctx = tier.lib, tier.ctx
+    ks, want = fb_expected(C, group, name, n, below_r=entry == "dev-mont")
+    base = raw(C, fb_base(C, group, name))
+    if entry == "host":
+        got = lib.fixed_base_mul(ctx, C.curve_id, group, base, scalar_bytes(ks), n, psz)
+    elif entry == "dev":
+        ptr, keep = tier.to_dev(scalar_bytes(ks))
+        got = lib.fixed_base_mul_dev(ctx, C.curve_id, group, base, ptr, n, 0, psz)
+    else:
+        assert max(ks) < C.r
+        ptr, keep = tier.to_dev(b"".join(Z.fr_mont(C, k) for k in ks))
+        got = lib.fixed_base_mul_dev(ctx, C.curve_id, group, base, ptr, n, 1, psz)
+    got = split(got, psz)
+    bad = [(i, hex(ks[i])) for i in range(n) if got[i] != want[i]]
+    assert not bad, (C.name, group, n, name, entry, bad[:8])
+
+
+# ---- 3. ark355_hbasis_transform --------------------------------------------------------------------------------------------------------
+HB_DESIGNS = ("constant", "alternating", "w^k", "g^k", "w^k-closed", "g^k-closed", "single", "zero")
+
+
+def hb_inputs(C, log_n, design):
+    """s_k of H_k = s_k G for k < N - 1 (H_{N-1} is the point at infinity: the h query has N - 1 points)."""
+    r, N = C.r, 1 << log_n
+    d = Domain(C, log_n)
+    s = random.Random("grouplaw-hb/%s" % C.name).randrange(2, r)
+    wi = d.omega_inv
+    f = {"constant": lambda k: s,
+         "alternating": lambda k: -s if k & 1 else s,
+         "w^k": lambda k: s * pow(d.omega, k, r),
+         "g^k": lambda k: s * pow(d.g, k, r),
+         # ... minus the multiple of the constant that makes s_{N-1} vanish: what an h query can hold of a pure w^k
+         "w^k-closed": lambda k: s * (pow(d.omega, k, r) - wi),
+         "g^k-closed": lambda k: s * pow(d.g, k, r) * (pow(d.omega, k, r) - wi),
+         "single": lambda k: s if k == (N - 1) // 2 else 0,
+         "zero": lambda k: 0}[design]
+    return [f(k) % r for k in range(N - 1)]
+
+
+def hb_model(C, log_n, ss, shift):
+    """hbasis_impl.cuh in the exponent: Q_k = c0 s_k (g^-k with `shift`) at the bit-reversed index, then the stages
+    (a, b) <- (a + t b, a - t b) of hb_stage_kernel.  -> (the N outputs, a Counter of addition classes per stage)."""
+    r, N = C.r, 1 << log_n
+    d = Domain(C, log_n)
+    c0 = pow(N * (pow(d.g, N, r) - 1) % r, -1, r)
+    x = [0] * N
+    for k, s in enumerate(ss):
+        x[int(format(k, "0%db" % log_n)[::-1], 2)] = c0 * s * (pow(d.g_inv, k, r) if shift else 1) % r
+    stages = []
+    for st in range(log_n):
+        half, w_stage, seen = 1 << st, pow(d.omega_inv, 1 << (log_n - st - 1), r), Counter()
+        for t in range(N // 2):
+            j = t & (half - 1)
+            i0 = ((t >> st) << (st + 1)) + j
+            a, b = x[i0], x[i0 + half] * pow(w_stage, j, r) % r
+            seen[classify(a, b, r)] += 1
+            seen[classify(a, -b, r)] += 1
+            x[i0], x[i0 + half] = (a + b) % r, (a - b) % r
+        stages.append(seen)
+    # the model against the direct sums E'_j = sum_k c0 g^-k w^-jk s_k, U'_j = sum_k c0 w^-jk s_k
+    for j in range(N):
+        direct = sum(c0 * (pow(d.g_inv, k, r) if shift else 1) * pow(d.omega_inv, j * k, r) * s for k, s in enumerate(ss)) % r
+        assert x[j] == direct, (C.name, log_n, j, shift)
+    return x, stages
+
+
+def assert_hb_design(C, log_n, design, ss):
+    """The outputs at infinity and the classes of the butterflies, on integers.  A pure w^k (g^k) would leave U' (E') with ONE
+    non-empty output; the h query has no H_{N-1}, so the missing term w^(j-1) (w^j) stands in every output, and none is at
+    infinity -- but every first-stage butterfly except the one of H_{N-1} still cancels in one half and doubles in the other.
+    The -closed designs vanish at k = N - 1 themselves: exactly the outputs 0 and 1 are non-empty."""
+    N = 1 << log_n
+    (e, se), (u, su) = hb_model(C, log_n, ss, True), hb_model(C, log_n, ss, False)
+    inf_e, inf_u = [j for j in range(N) if not e[j]], [j for j in range(N) if not u[j]]
+    if design == "zero":
+        assert inf_e == inf_u == list(range(N))
+        assert all(set(c) == {"both-empty"} for c in se + su)
+    elif design in ("w^k-closed", "g^k-closed"):
+        inf, stages = (inf_u, su) if design[0] == "w" else (inf_e, se)
+        assert inf == list(range(2, N)), (design, log_n, inf)
+        assert log_n < 2 or any(c["cancel"] for c in stages)
+    elif design in ("w^k", "g^k"):
+        assert inf_e == inf_u == []
+        stages = su if design[0] == "w" else se
+        if design == "w^k" and log_n >= 2:
+            assert stages[0]["cancel"] == stages[0]["double"] == N // 2 - 1           # H_k + H_{k+N/2} = O, H_k - H_{k+N/2} = 2 H_k
+        if design == "g^k" and log_n >= 2:
+            assert stages[0]["double"] == stages[0]["cancel"] == N // 2 - 1           # g^-k s_k is constant
+    elif design == "constant":
+        assert inf_e == inf_u == []
+        assert log_n < 2 or su[0]["double"] == su[0]["cancel"] == N // 2 - 1
+    elif design == "alternating":
+        assert inf_e == inf_u == []
+        assert log_n < 2 or su[0]["double"] == su[0]["cancel"] == N // 2 - 1
+    elif design == "single":
+        assert inf_e == inf_u == [] and sum(1 for s in ss if s) == 1
+        assert all(set(c) <= {"left-empty", "right-empty", "both-empty", "double", "cancel"} for c in se + su)
+    else:
+        raise KeyError(design)
+    return e, u
+
+
+_HB_EXPECTED = {}
+
+
+def hb_expected(C, log_n, design):
+    key = (C.name, log_n, design)
+    if key not in _HB_EXPECTED:
+        G_, raw, psz = group_of(C, 1)
+        ss = hb_inputs(C, log_n, design)
+        e, u = assert_hb_design(C, log_n, design, ss)
+        N = 1 << log_n
+        pts = cbase.fixed_base(C, 1, raw(C, G_.gen), scalar_bytes(ss + e + u), 3 * N - 1)
+        assert split(pts, psz)[0] == raw(C, G_.mul(G_.gen, ss[0]))
+        _HB_EXPECTED[key] = (pts[:(N - 1) * psz], pts[(N - 1) * psz:(2 * N - 1) * psz], pts[(2 * N - 1) * psz:],
+                             [j for j in range(N) if not e[j]], [j for j in range(N) if not u[j]])
+    return _HB_EXPECTED[key]
+
+
+def transform_case(tier, C, log_n, design):
+    psz = group_of(C, 1)[2]
+    h, want_e, want_u, inf_e, inf_u = hb_expected(C, log_n, design)
+    e, u = tier.lib.hbasis_transform(tier.ctx, C.curve_id, h, log_n)
+    for name, got, want, inf in (("E'", e, want_e, inf_e), ("U'", u, want_u, inf_u)):
+        got, want = split(got, psz), split(want, psz)
+        assert [j for j, p in enumerate(got) if p == bytes(psz)] == inf, (C.name, log_n, design, name)
+        assert got == want, (C.name, log_n, design, name, [j for j in range(len(want)) if got[j] != want[j]])
+    # each output alone (the entry skips the copy of the scaled points then)
+    assert tier.lib.hbasis_transform(tier.ctx, C.curve_id, h, log_n, want_u=False)[0] == want_e
+    assert tier.lib.hbasis_transform(tier.ctx, C.curve_id, h, log_n, want_e=False)[1] == want_u
+
+
+# ---- 4. ark355_hbasis_gather -----------------------------------------------------------------------------------------------------------
+GATHER_DESIGNS = ("constant", "alternating", "mixed")
+SETUP_LANE_COL, SETUP_CHUNK = 64, 2048                      # setup_impl.cuh
+HEAVY_LENGTHS = (200, 4100)                                 # above one lane's column and below one chunk; three chunks
+
+
+def gather_multipliers(design, N):
+    if design == "constant":
+        return [1] * N
+    if design == "alternating":
+        return [-1 if j & 1 else 1 for j in range(N)]
+    if design == "mixed":
+        return [(2, 0, 1, 0, -1, 0, -2, 1)[j % 8] for j in range(N)]
+    raise KeyError(design)
+
+
+def gather_columns(C, Cm, m, ms):
+    """Per column: the terms C[j][i] m_j (centred, in row order) and their sum, on integers."""
+    cols = [[] for _ in range(m)]
+    for j, row in enumerate(Cm):
+        for c, i in row:
+            cols[i].append(centred(c * ms[j], C.r))
+    return cols, [sum(col) % C.r for col in cols]
+
+
+def gather_hand_built_case(tier, C, design):
+    """hbasis_cases.hand_built_c: column 0 a non-unit coefficient, 1 two unit entries, 2 a unit entry and a -1, 3 two non-unit
+    coefficients, 4 one unit entry, 5 empty.  Which columns double, cancel and end at infinity is asserted on the terms (the
+    order in which a column's entries are added is the scatter's; with two terms both orders take the same branch)."""
+    lib, ctx = tier.lib, tier.ctx
+    _, raw, psz = group_of(C, 1)
+    A, B, Cm, ell, w = hc.hand_built_c(C)
+    m = ell + w
+    ms = gather_multipliers(design, 8)
+    cols, sums = gather_columns(C, Cm, m, ms)
+    kinds = [classify(col[0], col[1], C.r) if len(col) == 2 else None for col in cols]
+    inf = [i for i in range(m) if not sums[i]]
+    if design == "constant":            # U_2 + U_4 = 2 P: xyzz_madd_ni's P == acc; U_0 - U_1 = O
+        assert cols[1] == [1, 1] and kinds[1] == "double" and kinds[2] == "cancel" and kinds[3] == "generic" and inf == [2, 5]
+    elif design == "alternating":       # U_0 + (r - 1) U_1 = P + P, the second operand a product of hb_mul: xyzz_add doubles, ZZ != ZZ'
+        assert cols[2] == [1, 1] and kinds[1] == "double" and kinds[2] == "double" and kinds[3] == "generic" and inf == [5]
+    else:                               # U_2 + U_4 = P - P: xyzz_madd_ni cancels; columns 0 and 2 meet empty operands
+        assert cols[1] == [1, -1] and kinds[1] == "cancel" and kinds[2] == "right-empty" and kinds[3] == "left-empty"
+        assert cols[0] == [0] and inf == [0, 1, 5]
+    r1 = r1cs_load_from_rows(lib, ctx, C, A, B, Cm, ell, w)
+    try:
+        assert lib.dll.ark355_r1cs_domain_size(r1) == 8
+        u = b"".join(point_raw(C, 1, v) for v in ms)
+        got = split(lib.hbasis_gather(ctx, r1, C.curve_id, u, m), psz)
+        assert [i for i in range(m) if got[i] == bytes(psz)] == inf, (C.name, design)
+        assert got == [point_raw(C, 1, v) for v in sums], (C.name, design)
+    finally:
+        lib.dll.ark355_r1cs_free(r1)
+
+
+def gather_heavy_case(tier, C, n, design):
+    """The heavy column of synthetic.dummy_csr: n - 1 unit entries in column 1, every other column empty.  `constant`: every lane of
+    hb_heavy_kernel with equally many entries holds the same point, so the butterflies, the sums of the four waves and (three
+    chunks) the chunk sums add equal operands; `alternating`: as many P as -P (n - 1 even), the column ends at infinity and every
+    way of dealing it must cancel somewhere; `mixed`: zeros, doublings and cancellations in any dealing, the sum is not."""
+    lib, ctx = tier.lib, tier.ctx
+    _, raw, psz = group_of(C, 1)
+    length = n - 1
+    assert length in HEAVY_LENGTHS and length > SETUP_LANE_COL
+    assert (length < SETUP_CHUNK) == (length == HEAVY_LENGTHS[0]) and -(-HEAVY_LENGTHS[1] // SETUP_CHUNK) == 3
+    n_, ell, w, mats, _ = S.dummy_csr(C.r, n)
+    r1 = lib.r1cs_load(ctx, C.curve_id, n_, ell, w, mats)
+    try:
+        N = lib.dll.ark355_r1cs_domain_size(r1)
+        ms = gather_multipliers(design, N)
+        total = sum(ms[:length]) % C.r
+        if design == "constant":
+            assert total == length
+        elif design == "alternating":
+            assert length % 2 == 0 and total == 0
+        else:
+            assert total == centred(total, C.r) != 0 and {0, 1, -1, 2, -2} == set(ms[:length])
+        rows = {v: point_raw(C, 1, v) for v in set(ms)}
+        m = ell + w
+        got = split(lib.hbasis_gather(ctx, r1, C.curve_id, b"".join(rows[v] for v in ms), m), psz)
+        assert got[1] == point_raw(C, 1, total), (C.name, n, design)
+        assert all(p == bytes(psz) for i, p in enumerate(got) if i != 1)
+    finally:
+        lib.dll.ark355_r1cs_free(r1)
+
+
+# ---- 5. ark355_verify_each / ark355_verify_each_pvk ------------------------------------------------------------------------------------
+# (m_0 .. m_3): gamma_abc_i = m_i s G1.  The second key starts every prepared input from a gamma_abc_0 at infinity.
+VERIFY_KEYS = {"abc0": (2, 1, -1, 3), "abc0-infinity": (0, 1, -1, 3)}
+
+
+def verify_lanes(C, key):
+    """[(x_1, x_2, x_3), accepted] per proof: small public inputs chosen for the running sum acc = m_0 + sum x_i m_i, and ordinary
+    ones (seeded, full size)."""
+    rnd = random.Random("grouplaw-verify/%s/%s" % (C.name, key))
+    big = lambda: tuple(rnd.randrange(1, C.r) for _ in range(3))            # noqa: E731
+    if key == "abc0":
+        xs = [((2, 0, 0), True),          # 2 + 2: doubles (acc affine, the term a product of xyzz_mul_scalar); then two empty terms
+              (big(), True),
+              ((-2, 0, 0), True),         # 2 - 2: cancels; O + O twice; ends at infinity, accepted
+              ((-2, 0, 0), False),        # ... rejected
+              ((-2, 5, 0), True),         # cancels, then O + (-5)
+              (big(), False),
+              ((1, 3, 0), True),          # 3, then 3 - 3: ends at infinity at the second term
+              ((1, 3, 0), False),
+              ((1, 0, 1), True),          # 3 + O, then 3 + 3: doubles at the last term
+              ((1, 0, 1), False),
+              ((-1, -1, 0), True),        # 2 - 1 = 1, then 1 + 1: doubles
+              (big(), True)]
+    else:
+        xs = [((1, 1, 0), True),          # O + 1, 1 - 1: ends at infinity
+              ((1, 1, 0), False),
+              (big(), True),
+              ((0, 0, 0), True),          # nothing but empty operands: the prepared input is gamma_abc_0 = O
+              ((0, 0, 0), False),
+              ((3, 0, 1), True),          # O + 3, 3 + O, 3 + 3
+              ((3, 0, -1), True),         # ... 3 - 3
+              ((3, 0, -1), False),
+              (big(), False),
+              ((0, -3, 1), False)]        # O + O, O + 3, 3 + 3
+    return xs
+
+
+def verify_model(C, ms, xs):
+    """The running sum of verify_each_pairs_kernel / each_host in units of s G1: (classes of the additions, the end)."""
+    acc, classes = ms[0] % C.r, []
+    for x, m in zip(xs, ms[1:]):
+        classes.append(classify(acc, x * m, C.r))
+        acc = (acc + x * m) % C.r
+    return classes, acc
+
+
+_VERIFY = {}
+
+
+def verify_batch(C, key):
+    """(vk parts, proofs, public inputs as Montgomery bytes, the verdicts): everything in the exponent.  With alpha = a G1,
+    (beta, gamma, delta) = (b, g, d) G2, the prepared input p G1 and a proof (x G1, y G2, z G1) the check
+    e(A, B) = e(alpha, beta) e(acc, gamma) e(C, delta) holds iff x y = a b + p g + z d (mod r): z is solved for in an accepted
+    proof and is one more in a rejected one."""
+    if (C.name, key) in _VERIFY:
+        return _VERIFY[(C.name, key)]
+    r = C.r
+    ms = VERIFY_KEYS[key]
+    lanes = verify_lanes(C, key)
+    rnd = random.Random("grouplaw-vk/%s/%s" % (C.name, key))
+    s = dlog(C, 1)
+    a, b, g, d = (rnd.randrange(1, r) for _ in range(4))
+    seen, ends = Counter(), []
+    g1s, g2s, inputs, want = [a] + [m * s % r for m in ms], [b, g, d], [], []
+    for xs, ok in lanes:
+        classes, end = verify_model(C, ms, xs)
+        seen.update(classes)
+        ends.append((end == 0, ok))
+        p = end * s % r
+        x, y = rnd.randrange(1, r), rnd.randrange(1, r)
+        z = (x * y - a * b - p * g) * pow(d, -1, r) % r
+        if not ok:
+            z = (z + 1) % r
+        assert ((x * y - a * b - p * g - z * d) % r == 0) == ok
+        g1s += [x, z]
+        g2s.append(y)
+        inputs.append(b"".join(Z.fr_mont(C, v) for v in xs))
+        want.append(ok)
+    # on integers: the lanes of this batch double, cancel, meet empty operands on either side and add ordinary points; prepared
+    # inputs at infinity belong to accepted and to rejected proofs; the same batch holds ordinary proofs of both kinds
+    assert set(seen) == set(CLASSES), (key, seen)
+    assert (True, True) in ends and (True, False) in ends and (False, True) in ends and (False, False) in ends
+    assert (ms[0] == 0) == (key == "abc0-infinity")
+    n1, n2 = group_of(C, 1)[2], group_of(C, 2)[2]
+    P = split(cbase.fixed_base(C, 1, Z.g1_raw(C, C.g1_gen), scalar_bytes(g1s), len(g1s)), n1)
+    Q = split(cbase.fixed_base(C, 2, Z.g2_raw(C, C.g2_gen), scalar_bytes(g2s), len(g2s)), n2)
+    assert P[0] == Z.g1_raw(C, g1(C).mul(C.g1_gen, a)) and Q[0] == Z.g2_raw(C, g2(C).mul(C.g2_gen, b))
+    assert P[1] == point_raw(C, 1, ms[0]) and P[2] == point_raw(C, 1, ms[1])
+    vk = (P[0], Q[0], Q[1], Q[2], b"".join(P[1:5]))
+    proofs = [(P[5 + 2 * j], Q[3 + j], P[6 + 2 * j]) for j in range(len(lanes))]
+    _VERIFY[(C.name, key)] = (vk, proofs, inputs, want)
+    return _VERIFY[(C.name, key)]
+
+
+def verify_case(tier, policy, C, key, route):
+    """Both entries on one route (PAIRING_DEVICE = 1: the device kernels, 0: the host's), against the integer verdicts."""
+    lib, ctx = tier.lib, tier.ctx
+    vk, proofs, inputs, want = verify_batch(C, key)
+    policy.setenv("ARK355_PAIRING_DEVICE", route)
+    got = lib.verify_each(ctx, C.curve_id, vk, proofs, b"".join(inputs))
+    assert got == want, (C.name, key, route, "verify_each", [j for j in range(len(want)) if got[j] != want[j]])
+    h = lib.vk_process(ctx, C.curve_id, vk)
+    try:
+        got = lib.verify_each_pvk(ctx, h, proofs, b"".join(inputs))
+        assert got == want, (C.name, key, route, "verify_each_pvk", [j for j in range(len(want)) if got[j] != want[j]])
+    finally:
+        lib.pvk_free(h)

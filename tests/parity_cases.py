@@ -293,8 +293,9 @@ def prove_batch_case(lib, ctx, C, count=5, n=9, inflight=3):
 
 
 def fixed_base_case(lib, ctx, C, group, n=70, seed=21):
-    """ark355_fixed_base_mul (windowed table, batched normalisation) against the oracle's C fixed-base routine: random
-    scalars, 0 (infinity), 1, r - 1, single-window values, a 256-bit value beyond r, and a base at infinity."""
+    """ark355_fixed_base_mul (n = 70 is below FB_TABLE_MIN = 512: one double-and-add per lane, batched normalisation; the window
+    table is driven by tests/grouplaw_cases.py) against the oracle's C fixed-base routine: random scalars, 0 (infinity), 1, r - 1,
+    single-window values, a 256-bit value beyond r, and a base at infinity."""
     from oracle.c import cbase
     rnd = random.Random(seed + group)
     raw = Z.g1_raw if group == 1 else Z.g2_raw
