@@ -43,6 +43,7 @@
 #include <vector>
 #include "common.h"
 #include "field.cuh"
+#include "fr_wave.cuh"
 #include "ntt_impl.cuh"
 #include "setup_impl.cuh"
 
@@ -152,21 +153,6 @@ static void evals_tables(EvalsScratch& es, const EvalsPlan& plan, const EvalsPoi
   }
 }
 
-template <class Fr>
-ARK_D Fr evals_shfl_xor(const Fr& v, uint32_t mask) {
-  Fr o;
-#pragma unroll
-  for (int i = 0; i < Fr::N; i++) o.l[i] = (uint32_t)__shfl_xor((int)v.l[i], (int)mask, 64);
-  return o;
-}
-template <class Fr>
-ARK_D Fr evals_shfl_down(const Fr& v, uint32_t delta) {
-  Fr o;
-#pragma unroll
-  for (int i = 0; i < Fr::N; i++) o.l[i] = (uint32_t)__shfl_down((int)v.l[i], delta, 64);
-  return o;
-}
-
 // One element as two 16-byte loads (the vectors of the C ABI are 32-byte aligned like every Fr array of the library, and Fr itself
 // carries only the alignment of its limbs, which leaves the compiler eight single loads wherever the pointer may alias a store)
 template <class Fr>
@@ -244,7 +230,7 @@ ARK_D void evals_lane_inverses(const Fr* __restrict__ tab, uint32_t tab_digits, 
   Fr o[6];
 #pragma unroll
   for (int s = 0; s < 6; s++) {                           // acc = the product of the 2^(s+1) lanes around this one
-    o[s] = evals_shfl_xor(acc, 1u << s);
+    o[s] = fr_shfl_xor(acc, 1u << s);
     acc = Fr::mul(acc, o[s]);
   }
   // acc = the wave's product, in all 64 lanes.  ONE inversion a workgroup: wave 0 inverts the product of the four wave products while
@@ -292,28 +278,6 @@ ARK_D void evals_lane_inverses(const Fr* __restrict__ tab, uint32_t tab_digits, 
   iv[0] = inv;
 }
 
-// lane value -> workgroup sum in out[0] by thread 0; buf: the LDS of this polynomial's turn
-template <class Fr>
-ARK_D void evals_group_sum(Fr v, uint32_t (*buf)[Fr::N], Fr* out) {
-  const uint32_t tid = threadIdx.x;
-#pragma unroll
-  for (uint32_t s = 0; s < 6; s++) v = Fr::add(v, evals_shfl_down(v, 1u << s));
-  if ((tid & 63u) == 0) {
-#pragma unroll
-    for (int i = 0; i < Fr::N; i++) buf[tid >> 6][i] = v.l[i];
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (uint32_t w = 1; w < EVALS_THREADS / 64; w++) {
-      Fr o;
-#pragma unroll
-      for (int i = 0; i < Fr::N; i++) o.l[i] = buf[w][i];
-      v = Fr::add(v, o);
-    }
-    *out = v;
-  }
-}
-
 // E1: workgroup g -> part[k gridDim.x + g] = sum_{i in g} e[k][i] (1 + x / D_i) for every k < count
 template <class Fr, int E>
 __global__ void __launch_bounds__(EVALS_THREADS)
@@ -337,7 +301,7 @@ evals_eval_kernel(const Fr* __restrict__ in, uint64_t N, uint32_t count, const F
       s1 = Fr::add(s1, d[e]);
       s2 = Fr::add(s2, Fr::mul(d[e], iv[e]));
     }
-    evals_group_sum<Fr>(Fr::add(s1, Fr::mul(s2, x)), wave_val[k & 1], part + (uint64_t)k * gridDim.x + blockIdx.x);
+    fr_group_sum<Fr>(Fr::add(s1, Fr::mul(s2, x)), wave_val[k & 1], EVALS_THREADS / 64, part + (uint64_t)k * gridDim.x + blockIdx.x);
   }
 }
 
@@ -368,7 +332,7 @@ evals_quot_kernel(const Fr* in, uint64_t N, uint32_t count, const Fr* __restrict
       if (first + e < N) evals_store(o + first + e, t);
       if (SUM) acc = Fr::add(acc, Fr::mul(t, Fr::add(d[e], x)));   // a_i = D_i + x; where D was replaced, t is zero
     }
-    if (SUM) evals_group_sum<Fr>(acc, wave_val[k & 1], part + (uint64_t)k * gridDim.x + blockIdx.x);
+    if (SUM) fr_group_sum<Fr>(acc, wave_val[k & 1], EVALS_THREADS / 64, part + (uint64_t)k * gridDim.x + blockIdx.x);
   }
 }
 
@@ -388,7 +352,7 @@ evals_sum_kernel(const Fr* __restrict__ in, uint64_t len, Fr factor, uint32_t fi
     if (i < len) acc = Fr::add(acc, p[i]);
   }
   Fr total;
-  evals_group_sum<Fr>(acc, wave_val, &total);
+  fr_group_sum<Fr>(acc, wave_val, EVALS_THREADS / 64, &total);
   if (threadIdx.x == 0) {
     if (fin) total = Fr::mul(total, factor);
     if (fin == 2) {
@@ -427,18 +391,6 @@ static void evals_reserve(EvalsScratch& es, const EvalsPlan& plan, uint64_t coun
   if (own_rem) es.rem.ensure((size_t)count * sizeof(Fr));
 }
 
-#define ARK_EVALS_BY_E(E_, CALL)                   \
-  switch (E_) {                                    \
-    case 1: { constexpr int PE = 1; CALL; } break; \
-    case 2: { constexpr int PE = 2; CALL; } break; \
-    case 3: { constexpr int PE = 3; CALL; } break; \
-    case 4: { constexpr int PE = 4; CALL; } break; \
-    case 5: { constexpr int PE = 5; CALL; } break; \
-    case 6: { constexpr int PE = 6; CALL; } break; \
-    case 7: { constexpr int PE = 7; CALL; } break; \
-    default: { constexpr int PE = 8; CALL; } break; \
-  }
-
 // E2 on the partials of level 0 down to one value a polynomial, the last launch with (factor, fin) into d_out
 template <class Fr>
 static void evals_sum_levels(const EvalsPlan& plan, uint64_t count, EvalsScratch& es, const Fr& factor, uint32_t fin, Fr* d_out,
@@ -474,9 +426,9 @@ static void evals_eval_run(const void* d_evals, uint64_t count, const EvalsPlan&
     ARK_CHECK_LAUNCH();
     return;
   }
-  ARK_EVALS_BY_E(plan.E, ARK_LAUNCH((evals_eval_kernel<Fr, PE>), dim3((uint32_t)plan.len[0]), dim3(EVALS_THREADS), 0, st,
-                                    (const Fr*)d_evals, plan.N, (uint32_t)count, (const Fr*)es.tab.as<Fr>(), plan.tab_digits, pt.x,
-                                    pt.omega, es.part.as<Fr>()));
+  ARK_BY_E(plan.E, ARK_LAUNCH((evals_eval_kernel<Fr, PE>), dim3((uint32_t)plan.len[0]), dim3(EVALS_THREADS), 0, st,
+                              (const Fr*)d_evals, plan.N, (uint32_t)count, (const Fr*)es.tab.as<Fr>(), plan.tab_digits, pt.x,
+                              pt.omega, es.part.as<Fr>()));
   ARK_CHECK_LAUNCH();
   evals_sum_levels<Fr>(plan, count, es, pt.fac_eval, 1u, (Fr*)d_out, st);
 }
@@ -491,15 +443,15 @@ static void evals_div_run(const void* d_evals, uint64_t count, const EvalsPlan& 
   evals_eval_run<Curve>(d_evals, count, plan, pt, d_rem, es, st);
   const dim3 grid((uint32_t)plan.len[0]);
   if (pt.inside) {
-    ARK_EVALS_BY_E(plan.E, ARK_LAUNCH((evals_quot_kernel<Fr, PE, true>), grid, dim3(EVALS_THREADS), 0, st, (const Fr*)d_evals, plan.N,
-                                      (uint32_t)count, (const Fr*)es.tab.as<Fr>(), plan.tab_digits, pt.x, pt.omega, (const Fr*)d_rem,
-                                      (Fr*)d_q, es.part.as<Fr>()));
+    ARK_BY_E(plan.E, ARK_LAUNCH((evals_quot_kernel<Fr, PE, true>), grid, dim3(EVALS_THREADS), 0, st, (const Fr*)d_evals, plan.N,
+                                (uint32_t)count, (const Fr*)es.tab.as<Fr>(), plan.tab_digits, pt.x, pt.omega, (const Fr*)d_rem,
+                                (Fr*)d_q, es.part.as<Fr>()));
     ARK_CHECK_LAUNCH();
     evals_sum_levels<Fr>(plan, count, es, pt.fac_fix, 2u, (Fr*)d_q, st);
   } else {
-    ARK_EVALS_BY_E(plan.E, ARK_LAUNCH((evals_quot_kernel<Fr, PE, false>), grid, dim3(EVALS_THREADS), 0, st, (const Fr*)d_evals, plan.N,
-                                      (uint32_t)count, (const Fr*)es.tab.as<Fr>(), plan.tab_digits, pt.x, pt.omega, (const Fr*)d_rem,
-                                      (Fr*)d_q, es.part.as<Fr>()));
+    ARK_BY_E(plan.E, ARK_LAUNCH((evals_quot_kernel<Fr, PE, false>), grid, dim3(EVALS_THREADS), 0, st, (const Fr*)d_evals, plan.N,
+                                (uint32_t)count, (const Fr*)es.tab.as<Fr>(), plan.tab_digits, pt.x, pt.omega, (const Fr*)d_rem,
+                                (Fr*)d_q, es.part.as<Fr>()));
     ARK_CHECK_LAUNCH();
   }
 }

@@ -29,12 +29,6 @@
 
 namespace ark355 {
 
-struct Gr1csMat {
-  const uint32_t* rp;
-  const uint32_t* col;
-  const uint32_t* ci;
-};
-
 struct Gr1csPred {
   std::string label;
   uint32_t arity = 0;
@@ -401,6 +395,7 @@ static R1csDev* gr1cs_to_r1cs(const Gr1csDev& g, hipStream_t stream) {
   }
   r->pool.alloc(g.pool_count * sizeof(Fr));
   ARK_CHECK_HIP(hipMemcpyAsync(r->pool.p, g.pool.p, g.pool_count * sizeof(Fr), hipMemcpyDeviceToDevice, stream));
+  r1cs_upload_mats(r.get());
   r1cs_upload_zinv<Curve>(r.get());
   ARK_CHECK_HIP(hipStreamSynchronize(stream));
   return r.release();

@@ -14,14 +14,15 @@
 //   T3  hb_stage_kernel       one decimation-in-time stage in place: (a, b) <- (a + t b, a - t b), t the stage twiddle; one launch per
 //                             stage, log2 N of them; natural order out
 //   T4  batch_to_affine_kernel (msm_impl.cuh)
-//   G1  column-major order of C (setup_col_count_kernel / scan_exclusive / setup_col_scatter_kernel of setup_impl.cuh)
-//   G2  hb_gather_kernel      one lane per column of at most SETUP_LANE_COL entries; unit coefficients are plain additions
-//   G3  hb_heavy_kernel / hb_heavy_sum_kernel   a workgroup per chunk of SETUP_CHUNK entries of a longer column, a wave per column
+//   G1-G3  column gather of C (colgather_impl.cuh over G1Terms): column-major order, one lane per column of at most
+//       COLGATHER_LANE_MAX entries, a workgroup per chunk of a longer column and a wave per such column; unit coefficients are
+//       plain (mixed) additions
 //   G4  hb_fold_kernel        slot i of the folded L' vector: l_ext[i] - D'_i (instance slots hold infinity: -D'_i)
 #pragma once
 #include "common.h"
 #include "msm_impl.cuh"
 #include "witness_impl.cuh"
+#include "colgather_impl.cuh"
 #include "setup_impl.cuh"
 
 namespace ark355 {
@@ -136,82 +137,23 @@ static void hbasis_transforms(const void* d_h, uint32_t log_n, hipStream_t st, v
 }
 
 // ---- column gather ----------------------------------------------------------------------------------------------------------
-// one term of a column sum added to acc: coefficient * U_row (cidx 0 = the coefficient one)
-template <class F, class Fr>
-ARK_D void hb_term(XYZZ<F>& acc, const uint2 e, const Affine<F>* __restrict__ U, const Fr* __restrict__ pool) {
-  const Affine<F> u = U[e.x];
-  if (e.y == 0) xyzz_madd_ni(acc, u);
-  else acc = xyzz_add(acc, hb_mul_fr(XYZZ<F>::from_affine(u), pool[e.y]));
-}
-
-// G2.  Heavy columns only enter the list (as in setup_gather_kernel).
-template <class F, class Fr>
-__global__ void __launch_bounds__(HB_THREADS)
-hb_gather_kernel(const uint32_t* __restrict__ off, const uint2* __restrict__ ent, const Affine<F>* __restrict__ U,
-                 const Fr* __restrict__ pool, uint32_t cols, XYZZ<F>* __restrict__ D, unsigned long long* __restrict__ heavy_ctr,
-                 uint32_t* __restrict__ heavy_col, uint32_t* __restrict__ heavy_base) {
-  const uint64_t j64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j64 >= cols) return;
-  const uint32_t j = (uint32_t)j64;
-  const uint32_t lo = off[j], hi = off[j + 1], len = hi - lo;
-  if (len > SETUP_LANE_COL) {
-    const uint32_t chunks = (len + SETUP_CHUNK - 1) / SETUP_CHUNK;
-    const unsigned long long old = atomicAdd(heavy_ctr, (1ull << 32) | (unsigned long long)chunks);
-    const uint32_t slot = (uint32_t)(old >> 32);
-    heavy_col[slot] = j;
-    heavy_base[slot] = (uint32_t)old;
-    return;
+// the terms of colgather_impl.cuh over G1: coefficient * U_row added to an XYZZ sum (cidx 0 = the coefficient one: a mixed addition)
+template <class Curve>
+struct G1Terms {
+  using Fr = typename Curve::Fr;
+  using F = typename Curve::Fq;
+  using Value = XYZZ<F>;
+  using Src = Affine<F>;
+  static constexpr uint32_t GATHER_THREADS = HB_THREADS;
+  static ARK_D Value zero() { return Value::inf(); }
+  static ARK_D Value add(const Value& a, const Value& b) { return xyzz_add(a, b); }
+  static ARK_D void term(Value& acc, const uint2 e, const Src* __restrict__ U, const Fr* __restrict__ pool) {
+    const Src u = U[e.x];
+    if (e.y == 0) xyzz_madd_ni(acc, u);
+    else acc = xyzz_add(acc, hb_mul_fr(Value::from_affine(u), pool[e.y]));
   }
-  XYZZ<F> acc = XYZZ<F>::inf();
-  for (uint32_t t = lo; t < hi; t++) hb_term(acc, ent[t], U, pool);
-  D[j] = acc;
-}
-
-// G3: one workgroup per chunk of a heavy column.  item -> slot: the last slot with heavy_base[slot] <= item.
-template <class F, class Fr>
-__global__ void __launch_bounds__(SETUP_THREADS)
-hb_heavy_kernel(const uint32_t* __restrict__ off, const uint2* __restrict__ ent, const Affine<F>* __restrict__ U,
-                const Fr* __restrict__ pool, const uint32_t* __restrict__ heavy_col, const uint32_t* __restrict__ heavy_base,
-                uint32_t n_heavy, XYZZ<F>* __restrict__ partial) {
-  constexpr uint32_t WORDS = sizeof(XYZZ<F>) / 4;
-  __shared__ uint32_t wave_sum[SETUP_THREADS / 64][WORDS];
-  const uint32_t item = blockIdx.x, tid = threadIdx.x;
-  uint32_t s = 0, e = n_heavy;
-  while (e - s > 1) {
-    const uint32_t mid = s + ((e - s) >> 1);
-    if (heavy_base[mid] <= item) s = mid;
-    else e = mid;
-  }
-  const uint32_t j = heavy_col[s], c = item - heavy_base[s];
-  const uint32_t lo = off[j] + c * SETUP_CHUNK;
-  const uint32_t end = off[j + 1], hi = (end - lo > SETUP_CHUNK) ? lo + SETUP_CHUNK : end;
-  XYZZ<F> acc = XYZZ<F>::inf();
-  for (uint32_t t = lo + tid; t < hi; t += SETUP_THREADS) hb_term(acc, ent[t], U, pool);
-  acc = wave_reduce_sum(acc);
-  if ((tid & 63u) == 0) memcpy(wave_sum[tid >> 6], &acc, sizeof(acc));
-  __syncthreads();
-  if (tid == 0) {
-    for (uint32_t w = 1; w < SETUP_THREADS / 64; w++) {
-      XYZZ<F> o;
-      memcpy(&o, wave_sum[w], sizeof(o));
-      acc = xyzz_add(acc, o);
-    }
-    partial[item] = acc;
-  }
-}
-
-// G3: one wave per heavy column adds its chunk sums
-template <class F>
-__global__ void __launch_bounds__(64)
-hb_heavy_sum_kernel(const uint32_t* __restrict__ heavy_col, const uint32_t* __restrict__ heavy_base, uint32_t n_heavy,
-                    uint32_t n_items, const XYZZ<F>* __restrict__ partial, XYZZ<F>* __restrict__ D) {
-  const uint32_t s = blockIdx.x, lane = threadIdx.x;
-  const uint32_t b0 = heavy_base[s], b1 = (s + 1 < n_heavy) ? heavy_base[s + 1] : n_items;
-  XYZZ<F> acc = XYZZ<F>::inf();
-  for (uint32_t i = b0 + lane; i < b1; i += 64) acc = xyzz_add(acc, partial[i]);
-  acc = wave_reduce_sum(acc);
-  if (lane == 0) D[heavy_col[s]] = acc;
-}
+  static ARK_D Value wave_sum(const Value& x) { return wave_reduce_sum(x); }
+};
 
 // G4: out[i] = l[i] - D[i] for i < cols, l[i] beyond (the four tail slots of l_ext)
 template <class F>
@@ -226,52 +168,23 @@ hb_fold_kernel(const Affine<F>* __restrict__ l, const XYZZ<F>* __restrict__ D, u
 }
 
 // D_i = sum_j C[j][i] U_j for the m columns of the resident C (XYZZ, device).  d_U: N affine points.  One host wait reads the
-// heavy-column counter (8 bytes); all scratch of the transposition is gone on return.
+// heavy-column counter (8 bytes); all scratch of the gather is gone on return.
 template <class Curve>
 static void hbasis_gather(const R1csDev& r1, const void* d_U, hipStream_t st, void* d_D) {
   using Fr = typename Curve::Fr;
   using Fq = typename Curve::Fq;
   const uint64_t n = r1.n, m = r1.m, nnz = r1.nnz[2];
   ARK_REQUIRE(m + 1 < (1ull << 32) && nnz < (1ull << 32) && n < (1ull << 32), ARK355_EINVAL, "instance too large for the column gather");
-  const uint32_t cols = (uint32_t)m;
-  const Affine<Fq>* U = (const Affine<Fq>*)d_U;
-  XYZZ<Fq>* D = (XYZZ<Fq>*)d_D;
-  DevBuf d_cnt(((size_t)cols + 1) * 4), d_off(((size_t)cols + 1) * 4), d_cur(((size_t)cols + 1) * 4), d_ent((size_t)nnz * sizeof(uint2)), aux;
-  ARK_CHECK_HIP(hipMemsetAsync(d_cnt.p, 0, ((size_t)cols + 1) * 4, st));
-  if (nnz) {
-    ARK_LAUNCH(setup_col_count_kernel, dim3(setup_grid(nnz)), dim3(SETUP_THREADS), 0, st, r1.col[2].as<const uint32_t>(), (uint32_t)nnz, 0u,
-               d_cnt.as<uint32_t>());
-    ARK_CHECK_LAUNCH();
-  }
-  scan_exclusive(st, d_cnt.as<const uint32_t>(), d_off.as<uint32_t>(), cols, d_off.as<uint32_t>() + cols, aux);
-  ARK_CHECK_HIP(hipMemcpyAsync(d_cur.p, d_off.p, (size_t)cols * 4, hipMemcpyDeviceToDevice, st));
-  if (nnz) {
-    ARK_LAUNCH(setup_col_scatter_kernel, dim3(setup_grid(nnz)), dim3(SETUP_THREADS), 0, st, r1.row_ptr[2].as<const uint32_t>(),
-               r1.col[2].as<const uint32_t>(), r1.cidx[2].as<const uint32_t>(), (uint32_t)n, (uint32_t)nnz, 0u, d_cur.as<uint32_t>(),
-               d_ent.as<uint2>());
-    ARK_CHECK_LAUNCH();
-  }
-  const size_t heavy_cap = (size_t)(nnz / SETUP_LANE_COL) + 1;
-  DevBuf d_ctr(8), d_hcol(heavy_cap * 4), d_hbase(heavy_cap * 4);
-  ARK_CHECK_HIP(hipMemsetAsync(d_ctr.p, 0, 8, st));
-  ARK_LAUNCH((hb_gather_kernel<Fq, Fr>), dim3(hb_grid(cols)), dim3(HB_THREADS), 0, st, d_off.as<const uint32_t>(), d_ent.as<const uint2>(), U,
-             r1.pool.as<const Fr>(), cols, D, d_ctr.as<unsigned long long>(), d_hcol.as<uint32_t>(), d_hbase.as<uint32_t>());
-  ARK_CHECK_LAUNCH();
-  unsigned long long ctr = 0;
-  ARK_CHECK_HIP(hipMemcpyAsync(&ctr, d_ctr.p, 8, hipMemcpyDeviceToHost, st));
-  ARK_CHECK_HIP(hipStreamSynchronize(st));
-  const uint32_t n_heavy = (uint32_t)(ctr >> 32), n_items = (uint32_t)ctr;
-  if (n_heavy) {
-    DevBuf d_part((size_t)n_items * sizeof(XYZZ<Fq>));
-    ARK_LAUNCH((hb_heavy_kernel<Fq, Fr>), dim3(n_items), dim3(SETUP_THREADS), 0, st, d_off.as<const uint32_t>(), d_ent.as<const uint2>(), U,
-               r1.pool.as<const Fr>(), d_hcol.as<const uint32_t>(), d_hbase.as<const uint32_t>(), n_heavy, d_part.as<XYZZ<Fq>>());
-    ARK_CHECK_LAUNCH();
-    ARK_LAUNCH((hb_heavy_sum_kernel<Fq>), dim3(n_heavy), dim3(64), 0, st, d_hcol.as<const uint32_t>(), d_hbase.as<const uint32_t>(), n_heavy,
-               n_items, d_part.as<const XYZZ<Fq>>(), D);
-    ARK_CHECK_LAUNCH();
-    ARK_CHECK_HIP(hipStreamSynchronize(st));          // d_part is freed here
-  }
-  ARK_CHECK_HIP(hipStreamSynchronize(st));            // so is the column-major scratch
+  ColGatherIn in;
+  in.mats = r1.mats.as<Gr1csMat>() + 2;                 // C alone
+  in.t = 1;
+  in.n = (uint32_t)n;
+  in.m = (uint32_t)m;
+  in.nnz = in.max_nnz = nnz;
+  ColGatherScratch cs;
+  colgather_reserve(cs, m, nnz, COLGATHER_LANE_MAX, sizeof(XYZZ<Fq>));
+  colgather_run<G1Terms<Curve>>(in, (const Affine<Fq>*)d_U, r1.pool.as<const Fr>(), (XYZZ<Fq>*)d_D, cs, COLGATHER_LANE_MAX, st);
+  ARK_CHECK_HIP(hipStreamSynchronize(st));              // the scratch is freed on return
 }
 
 // The two base vectors of a bound key (affine, device): E' (N points) and the folded L' vector (m + 4 points, aligned with zx).

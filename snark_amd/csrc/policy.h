@@ -95,8 +95,8 @@ struct TunePolicy {
                                   // LDS of a 64-lane workgroup, a longer one by the any-length path on keys in global memory; clamped to 1 ..
                                   // LCS_LDS_KEYS = 1024, the keys 8 KiB hold.  Tests lower it to reach the long path at small shapes.
   int32_t cols_lane_max = 64;     // ark355_gr1cs_mat_vec_t / ark355_gr1cs_columns_at (columns_impl.cuh): a column of at most this many stored
-                                  // entries is summed by one lane, a longer one in chunks of COLS_CHUNK = 2048 entries, one workgroup each.  64 is
-                                  // the generator's SETUP_LANE_COL: a lane's serial chain stays at 64 multiply-adds while the waves of a
+                                  // entries is summed by one lane, a longer one in chunks of COLGATHER_CHUNK = 2048 entries, one workgroup each.  64 is
+                                  // the generator's COLGATHER_LANE_MAX: a lane's serial chain stays at 64 multiply-adds while the waves of a
                                   // 2^20-row circuit's few hot columns spread over the device.  <= 0: the default; clamped to 2^20.  Tests lower
                                   // it to reach the chunked path at small shapes.
   int32_t poly_lane_coeffs = 8;   // ark355_poly_eval_fr / ark355_poly_div_linear_fr (poly_impl.cuh): the consecutive coefficients a lane owns, and

@@ -42,6 +42,8 @@
 #include <vector>
 #include "common.h"
 #include "field.cuh"
+#include "fr_wave.cuh"
+#include "ntt_impl.cuh"
 
 namespace ark355 {
 
@@ -96,14 +98,6 @@ static inline PolyPlan poly_plan(uint64_t len, uint64_t count, uint32_t E) {
   return p;
 }
 
-template <class Fr>
-ARK_D Fr poly_shfl_down(const Fr& v, uint32_t delta) {
-  Fr o;
-#pragma unroll
-  for (int i = 0; i < Fr::N; i++) o.l[i] = (uint32_t)__shfl_down((int)v.l[i], delta, 64);
-  return o;
-}
-
 // the lane's E coefficients (zero behind the end) and their value sum_e a[e] X^e
 template <class Fr, int E>
 ARK_D Fr poly_lane_load(const Fr* p, uint64_t base, uint64_t len, const Fr& X, Fr (&a)[E]) {
@@ -126,7 +120,7 @@ poly_chunk_kernel(const Fr* __restrict__ in, uint64_t len, const Fr* __restrict_
   Fr a[E];
   Fr v = poly_lane_load<Fr, E>(p, base, len, tab[0], a);
   for (uint32_t s = 0; s < 6; s++) {                     // lane 0 ends with sum_t v_t (X^E)^t over its wave
-    const Fr o = poly_shfl_down(v, 1u << s);
+    const Fr o = fr_shfl_down(v, 1u << s);
     v = Fr::add(v, Fr::mul(o, tab[1 + (1u << s)]));
   }
   if ((tid & 63u) == 0) {
@@ -161,7 +155,7 @@ poly_apply_kernel(const Fr* in, uint64_t len, const Fr* __restrict__ carry, cons
   Fr a[E];
   Fr t = poly_lane_load<Fr, E>(p, base, len, X, a);
   for (uint32_t s = 0; s < 6; s++) {                     // t = sum_{u >= lane, same wave} v_u (X^E)^(u - lane)
-    const Fr o = poly_shfl_down(t, 1u << s);
+    const Fr o = fr_shfl_down(t, 1u << s);
     const Fr n = Fr::add(t, Fr::mul(o, tab[1 + (1u << s)]));
     if (lane + (1u << s) < 64u) t = n;
   }
@@ -178,7 +172,7 @@ poly_apply_kernel(const Fr* in, uint64_t len, const Fr* __restrict__ carry, cons
     for (int i = 0; i < Fr::N; i++) o.l[i] = wave_val[w][i];
     r = Fr::add(Fr::mul(r, XW), o);
   }
-  const Fr nxt = poly_shfl_down(t, 1);                   // every lane takes part; lane 63 gets its own value back and drops it
+  const Fr nxt = fr_shfl_down(t, 1);                   // every lane takes part; lane 63 gets its own value back and drops it
   Fr s = Fr::mul(r, tab[1 + 63 - lane]);                 // S at the end of this lane's coefficients
   if (lane < 63u) s = Fr::add(s, nxt);
 #pragma unroll
@@ -206,16 +200,6 @@ poly_lincomb_kernel(const Fr* polys, uint64_t len, uint32_t count, const Fr* __r
   out[j] = acc;
 }
 
-template <class Fr>
-static Fr poly_pow(Fr b, uint64_t e) {
-  Fr r = Fr::one();
-  for (; e; e >>= 1) {
-    if (e & 1) r = Fr::mul(r, b);
-    b = Fr::mul(b, b);
-  }
-  return r;
-}
-
 // the tables of every level into ps.host: level l at l * POLY_TAB_STRIDE; x in Montgomery form
 template <class Fr>
 static void poly_tables(PolyScratch& ps, const PolyPlan& plan, const Fr& x) {
@@ -223,11 +207,11 @@ static void poly_tables(PolyScratch& ps, const PolyPlan& plan, const Fr& x) {
   Fr* t = reinterpret_cast<Fr*>(ps.host.data());
   Fr X = x;
   for (uint32_t l = 0; l < plan.levels; l++, t += POLY_TAB_STRIDE) {
-    const Fr XE = poly_pow(X, plan.E);
+    const Fr XE = fr_pow_u64(X, plan.E);
     t[0] = X;
     t[1] = Fr::one();
     for (uint32_t i = 1; i <= 64; i++) t[1 + i] = Fr::mul(t[i], XE);
-    X = poly_pow(t[1 + 64], POLY_THREADS / 64);          // (X^(64 E))^4 = X^K: the next level's point
+    X = fr_pow_u64(t[1 + 64], POLY_THREADS / 64);          // (X^(64 E))^4 = X^K: the next level's point
   }
 }
 
@@ -238,18 +222,6 @@ static void poly_reserve(PolyScratch& ps, const PolyPlan& plan, uint64_t count, 
   ps.tab.ensure((size_t)POLY_MAX_LEVELS * POLY_TAB_STRIDE * sizeof(Fr));
   if (own_rem) ps.rem.ensure((size_t)count * sizeof(Fr));
 }
-
-#define ARK_POLY_BY_E(E_, CALL)                \
-  switch (E_) {                                \
-    case 1: { constexpr int PE = 1; CALL; } break; \
-    case 2: { constexpr int PE = 2; CALL; } break; \
-    case 3: { constexpr int PE = 3; CALL; } break; \
-    case 4: { constexpr int PE = 4; CALL; } break; \
-    case 5: { constexpr int PE = 5; CALL; } break; \
-    case 6: { constexpr int PE = 6; CALL; } break; \
-    case 7: { constexpr int PE = 7; CALL; } break; \
-    default: { constexpr int PE = 8; CALL; } break; \
-  }
 
 // d_out[k] = p_k(x) for k < count on `st` (queued, not waited for); ps was reserved by poly_reserve with the same plan
 template <class Curve>
@@ -268,8 +240,8 @@ static void poly_eval_run(const void* d_coeffs, uint64_t count, const PolyPlan& 
     const Fr* in = l ? ps.levels.as<Fr>() + plan.off[l] : (const Fr*)d_coeffs;
     Fr* out = l + 1 < plan.levels ? ps.levels.as<Fr>() + plan.off[l + 1] : (Fr*)d_out;
     const dim3 grid((uint32_t)plan.len[l + 1], (uint32_t)count);
-    ARK_POLY_BY_E(plan.E, ARK_LAUNCH((poly_chunk_kernel<Fr, PE>), grid, dim3(POLY_THREADS), 0, st, in, plan.len[l],
-                                     tab + (size_t)l * POLY_TAB_STRIDE, out));
+    ARK_BY_E(plan.E, ARK_LAUNCH((poly_chunk_kernel<Fr, PE>), grid, dim3(POLY_THREADS), 0, st, in, plan.len[l],
+                                tab + (size_t)l * POLY_TAB_STRIDE, out));
     ARK_CHECK_LAUNCH();
   }
 }
@@ -288,8 +260,8 @@ static void poly_div_run(const void* d_coeffs, uint64_t count, const PolyPlan& p
     Fr* out = l ? ps.levels.as<Fr>() + plan.off[l] : (Fr*)d_q;
     const Fr* carry = l + 1 < plan.levels ? ps.levels.as<Fr>() + plan.off[l + 1] : nullptr;
     const dim3 grid((uint32_t)plan.len[l + 1], (uint32_t)count);
-    ARK_POLY_BY_E(plan.E, ARK_LAUNCH((poly_apply_kernel<Fr, PE>), grid, dim3(POLY_THREADS), 0, st, in, plan.len[l], carry,
-                                     tab + (size_t)l * POLY_TAB_STRIDE, out));
+    ARK_BY_E(plan.E, ARK_LAUNCH((poly_apply_kernel<Fr, PE>), grid, dim3(POLY_THREADS), 0, st, in, plan.len[l], carry,
+                                tab + (size_t)l * POLY_TAB_STRIDE, out));
     ARK_CHECK_LAUNCH();
   }
 }

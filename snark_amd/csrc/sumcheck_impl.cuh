@@ -30,6 +30,7 @@
 #pragma once
 #include <string>
 #include "common.h"
+#include "fr_wave.cuh"
 #include "gr1cs_impl.cuh"
 #include "evals_impl.cuh"
 #include "mle_impl.cuh"
@@ -208,23 +209,7 @@ sumcheck_round_kernel(const Fr* __restrict__ src, uint64_t src_stride, const Fr*
 #pragma unroll
       for (int l = 0; l < Fr::N; l++) v.l[l] = lds[((acc0 + X) * Fr::N + l) * lanes + tid];
     }
-#pragma unroll
-    for (uint32_t s = 0; s < 6; s++) v = Fr::add(v, evals_shfl_down(v, 1u << s));
-    uint32_t (*buf)[Fr::N] = wave_val[X & 1u];
-    if ((tid & 63u) == 0) {
-#pragma unroll
-      for (int l = 0; l < Fr::N; l++) buf[tid >> 6][l] = v.l[l];
-    }
-    __syncthreads();
-    if (tid == 0) {
-      for (uint32_t w = 1; w < waves; w++) {
-        Fr o;
-#pragma unroll
-        for (int l = 0; l < Fr::N; l++) o.l[l] = buf[w][l];
-        v = Fr::add(v, o);
-      }
-      part[(uint64_t)X * gridDim.x + blockIdx.x] = v;
-    }
+    fr_group_sum<Fr>(v, wave_val[X & 1u], waves, part + (uint64_t)X * gridDim.x + blockIdx.x);
   }
 }
 

@@ -24,6 +24,13 @@ static inline uint64_t r1cs_next_uid() {
   return next.fetch_add(1);
 }
 
+// one resident CSR matrix as a kernel reads it: a table of these (device) lets grid.y select the matrix
+struct Gr1csMat {
+  const uint32_t* rp;
+  const uint32_t* col;
+  const uint32_t* ci;
+};
+
 struct R1csDev {
   uint64_t uid = r1cs_next_uid();      // identity of this handle for the life of the process (a key bound to it: groth16_impl.cuh)
   int curve = 0;
@@ -32,6 +39,7 @@ struct R1csDev {
   uint32_t log_n = 0;
   uint64_t nnz[3] = {0, 0, 0};
   DevBuf row_ptr[3], col[3], cidx[3];
+  DevBuf mats;          // 3 x Gr1csMat: A, B, C for the column gathers (colgather_impl.cuh)
   DevBuf pool;          // interned coefficients; pool[0] == 1
   DevBuf zinv;          // (g^N - 1)^-1
 };
@@ -162,6 +170,13 @@ static void r1cs_set_dims(R1csDev* r, uint64_t n, uint64_t ell, uint64_t w) {
   r->log_n = lg;
   r->N = 1ull << lg;
 }
+// the matrix table, once the CSR arrays are allocated
+static inline void r1cs_upload_mats(R1csDev* r) {
+  Gr1csMat mats[3];
+  for (int k = 0; k < 3; k++) mats[k] = Gr1csMat{r->row_ptr[k].as<uint32_t>(), r->col[k].as<uint32_t>(), r->cidx[k].as<uint32_t>()};
+  r->mats.alloc(sizeof(mats));
+  ARK_CHECK_HIP(hipMemcpy(r->mats.p, mats, sizeof(mats), hipMemcpyHostToDevice));
+}
 // (g^N - 1)^-1
 template <class Curve>
 static void r1cs_upload_zinv(R1csDev* r) {
@@ -207,6 +222,7 @@ static R1csDev* r1cs_upload(uint64_t n, uint64_t ell, uint64_t w, const uint64_t
     }
     r->pool.alloc(pool.elems.size() * sizeof(Fr));
     ARK_CHECK_HIP(hipMemcpy(r->pool.p, pool.elems.data(), pool.elems.size() * sizeof(Fr), hipMemcpyHostToDevice));
+    r1cs_upload_mats(r);
     r1cs_upload_zinv<Curve>(r);
   } catch (...) {
     delete r;

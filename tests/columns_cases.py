@@ -31,7 +31,7 @@ from snark_amd import GR1CS, LcSystem, _binding as B
 from snark_amd.gr1cs import Predicate
 from snark_amd.params import CURVES as PRODUCT_CURVES
 
-LANE_MAX, CHUNK = 64, 2048                  # COLS_LANE_MAX's default and COLS_CHUNK (snark_amd/csrc/columns_impl.cuh)
+LANE_MAX, CHUNK = 64, 2048                  # COLS_LANE_MAX's default and COLGATHER_CHUNK (snark_amd/csrc/colgather_impl.cuh)
 LINEAR = [(1, [(0, 1)])]                    # a polynomial for systems whose polynomial does not matter: x0
 
 

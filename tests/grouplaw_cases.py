@@ -497,7 +497,7 @@ def transform_case(tier, C, log_n, design):
 
 # ---- 4. ark355_hbasis_gather -----------------------------------------------------------------------------------------------------------
 GATHER_DESIGNS = ("constant", "alternating", "mixed")
-SETUP_LANE_COL, SETUP_CHUNK = 64, 2048                      # setup_impl.cuh
+SETUP_LANE_COL, SETUP_CHUNK = 64, 2048                      # COLGATHER_LANE_MAX, COLGATHER_CHUNK of colgather_impl.cuh
 HEAVY_LENGTHS = (200, 4100)                                 # above one lane's column and below one chunk; three chunks
 
 
@@ -552,7 +552,7 @@ def gather_hand_built_case(tier, C, design):
 
 def gather_heavy_case(tier, C, n, design):
     """The heavy column of synthetic.dummy_csr: n - 1 unit entries in column 1, every other column empty.  `constant`: every lane of
-    hb_heavy_kernel with equally many entries holds the same point, so the butterflies, the sums of the four waves and (three
+    colgather_heavy_kernel with equally many entries holds the same point, so the butterflies, the sums of the four waves and (three
     chunks) the chunk sums add equal operands; `alternating`: as many P as -P (n - 1 even), the column ends at infinity and every
     way of dealing it must cancel somewhere; `mixed`: zeros, doublings and cancellations in any dealing, the sum is not."""
     lib, ctx = tier.lib, tier.ctx

@@ -139,6 +139,48 @@ def gather_heavy_case(lib, ctx, C, n):
         lib.dll.ark355_r1cs_free(r1)
 
 
+GATHER_LENGTHS = (2049, 63, 64, 65, 2048, 0)          # entries of columns 0 .. 5 of lengths_c: around the lane limit (64) and the chunk (2048)
+
+
+def lengths_c(C):
+    """(A, B, C, ell, w): 2049 rows, One and five witness variables.  Column i of C holds GATHER_LENGTHS[i] entries in distinct
+    rows: 63 and 64 are summed by one lane, 65 is the shortest heavy column, 2048 fills one chunk, 2049 spills ONE entry into a
+    second, column 5 is empty.  Unit coefficients but for seven: three in the 65-entry column (a lane of the chunk kernel
+    multiplies) and four in the 2049-entry one, rows 0, 2047 and 2048 among them."""
+    r = C.r
+    n = max(GATHER_LENGTHS)
+    rows_of = [[(7 * i + 5 * k) % n for k in range(ln)] for i, ln in enumerate(GATHER_LENGTHS)]     # 5 is prime to 2049 = 3 * 683
+    assert all(len(set(rows)) == len(rows) for rows in rows_of)
+    coeff = {(3, rows_of[3][0]): 5, (3, rows_of[3][31]): r - 1, (3, rows_of[3][64]): 7,
+             (0, 0): 2, (0, 1000): r - 1, (0, 2047): 3, (0, 2048): 12345678901234567}
+    Cm = [[] for _ in range(n)]
+    for i, rows in enumerate(rows_of):
+        for j in rows:
+            Cm[j].append((coeff.get((i, j), 1), i))
+    assert sum(c != 1 for row in Cm for c, _ in row) == len(coeff) <= 8
+    A = [[(1, 1)]] * n
+    B = [[(1, 0)]] * n
+    return A, B, Cm, 1, 5
+
+
+def gather_lengths_case(lib, ctx, C):
+    A, B, Cm, ell, w = lengths_c(C)
+    m = ell + w
+    r1 = r1cs_load_from_rows(lib, ctx, C, A, B, Cm, ell, w)
+    try:
+        N = lib.dll.ark355_r1cs_domain_size(r1)
+        assert N == 4096
+        base = _points(C, 64, 5)[1]
+        U = [base[(j * 7 + j // 64) % 64] for j in range(N)]
+        U[9] = None                                  # a point at infinity among the inputs
+        got = _g1_list(C, lib.hbasis_gather(ctx, r1, C.curve_id, g1_vec_raw(C, U), m))
+        exp = gather_expected(C, Cm, m, U)
+        assert exp[5] is None and all(p is not None for p in exp[:5])
+        assert got == exp
+    finally:
+        lib.dll.ark355_r1cs_free(r1)
+
+
 # ---- proofs ---------------------------------------------------------------------------------------------------------------------
 TD = G.Trapdoor(tau=987654321, alpha=5, beta=7, gamma=11, delta=13)
 RS = ((0x1234567890abcdef, 0xfedcba0987654321aabbccdd), (0, 0))          # and r = s = 0

@@ -30,6 +30,12 @@ def test_gather_heavy_column(emul_lib, emul_ctx, n):
     H.gather_heavy_case(emul_lib, emul_ctx, BLS12_381, n)
 
 
+@CURVES
+def test_gather_column_lengths(emul_lib, emul_ctx, C):
+    """columns of 63, 64, 65, 2048, 2049 and 0 entries: both sides of the lane limit and of the chunk, with scalar multiplications"""
+    H.gather_lengths_case(emul_lib, emul_ctx, C)
+
+
 @pytest.mark.parametrize("h_eval", [1, 0], ids=["H_EVAL=1", "H_EVAL=0"])
 @pytest.mark.parametrize("name", ["mulchain-6", "mulchain-32", "golden", "ell1"])
 def test_proofs_match_the_oracle_on_both_paths(emul_lib, emul_ctx, emul_policy, name, h_eval):

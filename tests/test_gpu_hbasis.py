@@ -34,6 +34,12 @@ def test_gather_heavy_column(gpu_lib, gpu_ctx, C, n):
     H.gather_heavy_case(gpu_lib, gpu_ctx, C, n)
 
 
+@CURVES
+def test_gather_column_lengths(gpu_lib, gpu_ctx, C):
+    """columns of 63, 64, 65, 2048, 2049 and 0 entries: both sides of the lane limit and of the chunk, with scalar multiplications"""
+    H.gather_lengths_case(gpu_lib, gpu_ctx, C)
+
+
 @PATHS
 @pytest.mark.parametrize("name", ["mulchain-6", "mulchain-32", "golden", "ell1"])
 def test_proofs_match_the_oracle_on_both_paths(gpu_lib, gpu_ctx, gpu_policy, name, h_eval):

@@ -3,8 +3,9 @@
   (a) ark355_gr1cs_columns_at_dev on the R1CS shape of the 2^20-row mul-chain bench circuit plus its ell instance rows (A row
       n + i = e_i, B and C empty), the output in device memory;
   (b) ark355_setup asked for u, v, w only, on the same instance in the same process: the same three stages (Lagrange vector,
-      column-major order, gather) from its own kernels, plus the combination kernel, the canonical conversion, per-call
-      allocations and three copies back -- unchanged code, the yardstick;
+      column-major order, gather) from the SAME kernels (colgather_impl.cuh serves both), plus the combination kernel, the
+      canonical conversion, per-call allocations and three copies back -- what the resident scratch of (a) saves, not a
+      yardstick for the kernels;
   (c) the SR1CS system of that circuit (2 n + P rows, t = 2);
   (d) a degree-3 predicate of arity 4 at 2^18 rows.
 (c) and (d) are first measurements with nothing to compare against.  The readings are interleaved after a warm-up of every call;
