@@ -101,6 +101,9 @@ int32_t ark355_sizes(int32_t curve, uint32_t what[4]);
  *                 SUMCHECK_LANE_PAIRS (ark355_sumcheck_round: the consecutive output pairs a lane owns; ark355_mle_fix_fr /
  *                 ark355_mle_eval_fr: the consecutive outputs a lane owns [default 1; <= 0 selects it; clamped to 1 .. 8]; the
  *                 outputs do not depend on it).
+ *                 MLE_OPEN_LANE_ENTRIES (ark355_mle_quotients_fr / ark355_mle_open_dev: the consecutive table entries a lane owns
+ *                 [default 8; <= 0 selects it; clamped to 1 .. 8 and rounded down to a power of two]; the outputs do not depend
+ *                 on it).
  * ARK355_EINVAL for an unknown name.  ark355_prove_batch runs its worker contexts under the caller's policy.
  * (No counterpart in the reference: ark-groth16 has no runtime knobs; rayon's thread count is its only one.) */
 int32_t ark355_ctx_set_policy(ark355_ctx* ctx, const char* name, int64_t value);
@@ -760,6 +763,41 @@ int32_t ark355_mle_eval_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* evals,
                            uint8_t* out);
 int32_t ark355_mle_eval_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_evals, uint32_t num_vars, uint64_t count,
                                const uint8_t* point, void* d_out);
+
+/* ---- Multilinear openings: quotient tables and PST proofs (snark_amd/csrc/mle_open_impl.cuh) ---------------------------------------
+ * The multilinear counterpart of ark355_poly_div_linear_fr: what ark-poly-commit's MultilinearPC::open (PST13) computes for a
+ * committed table f at the point p a sum-check ends at.  Conventions of the block above: Montgomery Fr, variable 0 the lowest index
+ * bit, the point `num_vars` canonical 32-byte integers below r in HOST memory, `count` tables back to back, v = num_vars, N = 2^v.
+ * With f^(0) = f and f^(j+1)[i] = f^(j)[2i] + p_j (f^(j)[2i+1] - f^(j)[2i]), the rule of ark355_mle_fix_fr, the quotient tables are
+ *     q_j[i] = f^(j)[2i+1] - f^(j)[2i],   i < 2^(v-1-j),   j = 0 .. v-1
+ * and satisfy f~(X) - f~(p) = sum_j (X_j - p_j) q_j~(X_{j+1}, .., X_{v-1}) for every X.
+ * quotients: q_out holds count x N Fr, every element written.  Table c starts at element c N; inside it level j occupies the
+ *   elements N - 2^(v-j) .. N - 2^(v-j) + 2^(v-1-j) - 1 -- the levels back to back, largest first -- and element N - 1 is f~_c(p),
+ *   byte for byte what ark355_mle_eval_fr returns.  rem_out (count Fr) receives the same values and may be NULL.  v = 0 writes only
+ *   the value.  Every output is fully reduced: the bytes do not depend on the decomposition.  A level's row feeds ark355_msm_dev
+ *   (scalars_mont = 1) directly; its offset is a multiple of 32 bytes.  In place is not offered: any overlap of q_out with evals,
+ *   or of rem_out with either, is ARK355_EINVAL.  count = 0 returns ARK355_OK and writes nothing.
+ * open_dev: one table in DEVICE memory.  The quotients go to the context's own scratch; for level j the entry runs the MSM of q_j
+ *   against level_bases[j], a resident handle of at least 2^(v-1-j) points (the route of ark355_msm_dev with Montgomery scalars).
+ *   proofs_out (host): v affine points of the handles' group, G1 or G2, an all-zero quotient level giving the point at infinity
+ *   (all-zero bytes); value_out (host): f~(p), one Fr.  v = 0 writes only the value and reads no handle.  With the key
+ *   level_bases[j][i] = eq((t_{j+1} .. t_{v-1}), i) g the verifier checks e(C - [y] g, h) = prod_j e(pi_j, [t_j - p_j] h).
+ * Refusals, all made before any allocation or launch, each with a message in ark355_last_error; the context works after every one
+ * of them: ARK355_EINVAL for a NULL pointer where something is read or written, an unknown curve, a point coordinate >= r,
+ * count > ARK355_POLY_MAX_COUNT, num_vars > 40, count * N >= 2^40 and the overlaps above; for open_dev also level_bases NULL with
+ * v > 0, a NULL handle, a handle of another curve, handles of mixed groups and a handle with too few bases (the message names the
+ * level).  ARK355_ENOMEM when the scratch does not fit: it is grow-only, owned by the context and reserved before the first launch
+ * -- 32 * count * (N / 2048 + N / 2048^2) bytes of pass rows, for the host variant the staging of the tables and of the output, for
+ * open_dev N Fr of quotients; none of it is shared with the scratch of the MSMs.
+ * Policy MLE_OPEN_LANE_ENTRIES (per call; default 8; <= 0 selects it; clamped to 1 .. 8 and rounded down to a power of two): the
+ * consecutive entries one lane owns, 256 times as many a workgroup, log2 of that many halvings a pass.  It moves every border of the
+ * decomposition and never a byte of any output. */
+int32_t ark355_mle_quotients_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* evals, uint32_t num_vars, uint64_t count,
+                                const uint8_t* point, uint8_t* q_out, uint8_t* rem_out);
+int32_t ark355_mle_quotients_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_evals, uint32_t num_vars, uint64_t count,
+                                    const uint8_t* point, void* d_q_out, void* d_rem_out);
+int32_t ark355_mle_open_dev(ark355_ctx* ctx, int32_t curve, const ark355_bases* const* level_bases, const void* d_evals,
+                            uint32_t num_vars, const uint8_t* point, uint8_t* proofs_out, uint8_t* value_out);
 
 /* ---- Sum-check of a GR1CS predicate over resident tables (snark_amd/csrc/sumcheck_impl.cuh) ------------------------------------
  * The prover's side of ark-linear-sumcheck's IPForMLSumcheck::prove_round for the claim

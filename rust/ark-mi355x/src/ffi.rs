@@ -716,6 +716,37 @@ extern "C" {
         d_out: *mut c_void,
     ) -> i32;
 
+    pub fn ark355_mle_quotients_fr(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        evals: *const u8,
+        num_vars: u32,
+        count: u64,
+        point: *const u8,
+        q_out: *mut u8,
+        rem_out: *mut u8,
+    ) -> i32;
+    pub fn ark355_mle_quotients_fr_dev(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        d_evals: *const c_void,
+        num_vars: u32,
+        count: u64,
+        point: *const u8,
+        d_q_out: *mut c_void,
+        d_rem_out: *mut c_void,
+    ) -> i32;
+    pub fn ark355_mle_open_dev(
+        ctx: *mut ark355_ctx,
+        curve: i32,
+        level_bases: *const *const ark355_bases,
+        d_evals: *const c_void,
+        num_vars: u32,
+        point: *const u8,
+        proofs_out: *mut u8,
+        value_out: *mut u8,
+    ) -> i32;
+
     pub fn ark355_gr1cs_sumcheck_begin_dev(
         ctx: *mut ark355_ctx,
         g: *const ark355_gr1cs,

@@ -67,6 +67,7 @@ SYMBOLS = [
     "ark355_evals_eval_fr", "ark355_evals_eval_fr_dev", "ark355_evals_div_linear_fr", "ark355_evals_div_linear_fr_dev",
     "ark355_gr1cs_mat_vec_dev",
     "ark355_mle_eq_fr", "ark355_mle_eq_fr_dev", "ark355_mle_fix_fr", "ark355_mle_fix_fr_dev", "ark355_mle_eval_fr", "ark355_mle_eval_fr_dev",
+    "ark355_mle_quotients_fr", "ark355_mle_quotients_fr_dev", "ark355_mle_open_dev",
     "ark355_gr1cs_sumcheck_begin_dev", "ark355_sumcheck_info", "ark355_sumcheck_round", "ark355_sumcheck_finish", "ark355_sumcheck_free",
     "ark355_ntt_fr", "ark355_ntt_fr_dev",
     "ark355_msm_g1", "ark355_msm_g2", "ark355_bases_load", "ark355_bases_free", "ark355_msm_dev",
@@ -249,6 +250,9 @@ class Lib:
         d.ark355_mle_fix_fr_dev.argtypes = [vp, i32, vp, u32, u64, vp, u32, vp]
         d.ark355_mle_eval_fr.argtypes = [vp, i32, vp, u32, u64, vp, vp]
         d.ark355_mle_eval_fr_dev.argtypes = [vp, i32, vp, u32, u64, vp, vp]
+        d.ark355_mle_quotients_fr.argtypes = [vp, i32, vp, u32, u64, vp, vp, vp]
+        d.ark355_mle_quotients_fr_dev.argtypes = [vp, i32, vp, u32, u64, vp, vp, vp]
+        d.ark355_mle_open_dev.argtypes = [vp, i32, vp, vp, u32, vp, vp, vp]
         d.ark355_gr1cs_sumcheck_begin_dev.argtypes = [vp, vp, u32, vp, vp, u32, P(vp)]
         d.ark355_sumcheck_info.argtypes = [vp, P(u32), P(u32), P(u32), P(u32)]
         d.ark355_sumcheck_round.argtypes = [vp, vp, vp, vp]
@@ -908,6 +912,37 @@ class Lib:
     def mle_eval_fr_dev(self, ctx, curve, d_evals, num_vars, count, point: bytes, d_out):
         pb, kp = _buf(point if len(point) else b"\0")
         self.check(ctx, self.dll.ark355_mle_eval_fr_dev(ctx, curve, C.c_void_p(d_evals), num_vars, count, pb, C.c_void_p(d_out)))
+
+    # ---- multilinear openings (csrc/mle_open_impl.cuh) ----------------------------------------------------------------------
+    def mle_quotients_fr(self, ctx, curve, evals, num_vars, count, point: bytes, want_rem=True, fr_size=32):
+        """(q, rem): the quotient tables of `count` tables of 2^num_vars Montgomery Fr at `point`, count x 2^num_vars Fr -- level j of
+        table c at element (c << num_vars) + mle_level(num_vars, j)[0], the value f~_c(point) in the table's last element -- and the
+        count values again (None when want_rem is false)"""
+        size = (count << num_vars) * fr_size
+        q = np.zeros(max(1, size), dtype=np.uint8)
+        rem = np.zeros(max(1, count * fr_size), dtype=np.uint8)
+        eb, ke = _buf(evals if len(evals) else b"\0")
+        pb, kp = _buf(point if len(point) else b"\0")
+        self.check(ctx, self.dll.ark355_mle_quotients_fr(ctx, curve, eb, num_vars, count, pb, q.ctypes.data_as(C.c_void_p),
+                                                         rem.ctypes.data_as(C.c_void_p) if want_rem else None))
+        return q.tobytes()[:size], (rem.tobytes()[:count * fr_size] if want_rem else None)
+
+    def mle_quotients_fr_dev(self, ctx, curve, d_evals, num_vars, count, point: bytes, d_q_out, d_rem_out=None):
+        """the same on device pointers (ints); d_rem_out may be None; no overlap of the three ranges is legal"""
+        pb, kp = _buf(point if len(point) else b"\0")
+        self.check(ctx, self.dll.ark355_mle_quotients_fr_dev(ctx, curve, C.c_void_p(d_evals), num_vars, count, pb, C.c_void_p(d_q_out),
+                                                             C.c_void_p(d_rem_out) if d_rem_out else None))
+
+    def mle_open_dev(self, ctx, curve, level_bases, d_evals, num_vars, point: bytes, point_size, fr_size=32):
+        """(proofs, value): the PST opening of one table in device memory against num_vars resident base handles (level j: at least
+        2^(num_vars-1-j) points): num_vars affine points of point_size bytes, and f~(point) as one Montgomery Fr"""
+        proofs = np.zeros(max(1, num_vars * point_size), dtype=np.uint8)
+        value = np.zeros(fr_size, dtype=np.uint8)
+        arr = (C.c_void_p * max(1, num_vars))(*[h if isinstance(h, C.c_void_p) else C.c_void_p(h) for h in level_bases])
+        pb, kp = _buf(point if len(point) else b"\0")
+        self.check(ctx, self.dll.ark355_mle_open_dev(ctx, curve, arr, C.c_void_p(d_evals), num_vars, pb, proofs.ctypes.data_as(C.c_void_p),
+                                                     value.ctypes.data_as(C.c_void_p)))
+        return proofs.tobytes()[:num_vars * point_size], value.tobytes()
 
     # ---- sum-check of a predicate (csrc/sumcheck_impl.cuh) ------------------------------------------------------------------
     def gr1cs_sumcheck_begin_dev(self, ctx, g, predicate, d_tables, d_weight, num_vars):

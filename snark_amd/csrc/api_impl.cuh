@@ -12,6 +12,7 @@
 #include "poly_impl.cuh"
 #include "evals_impl.cuh"
 #include "mle_impl.cuh"
+#include "mle_open_impl.cuh"
 #include "sumcheck_impl.cuh"
 #include "lcmap_impl.cuh"
 #include "setup_impl.cuh"
@@ -485,6 +486,16 @@ struct Api {
     if (!on_dev) ARK_CHECK_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     ARK_CHECK_HIP(hipStreamSynchronize(st));
   }
+
+  // ---- multilinear openings (mle_open_impl.cuh).  Declared here and defined behind the struct: a member defined in the class is
+  // inline, and capi.hip -- which only declares the explicit instantiations -- would compile its kernels a second time
+  // the quotient tables of `count` tables of 2^v at pt: count x 2^v Fr at q, the count values at rem (may be nullptr)
+  static void mle_quotients(ark355_ctx* ctx, MleScratch& ms, const void* evals, uint32_t v, uint64_t count, const Fr* pt, void* q, void* rem,
+                            bool on_dev);
+  // the PST opening of one table in device memory: the quotients into the context's scratch, then one MSM a level against
+  // bases[j] (msm_generic, Montgomery scalars); v affine points at proofs, the value at value_out
+  static void mle_open_dev(ark355_ctx* ctx, MleScratch& ms, GenericScratch& g, const BasesDev* const* bases, const void* d_evals, uint32_t v,
+                           const Fr* pt, uint8_t* proofs, uint8_t* value_out);
 
   // ---- sum-check of a predicate (sumcheck_impl.cuh): the order of the calls is checked by capi.hip
   static SumcheckDev* sumcheck_begin(ark355_ctx* ctx, const Gr1csDev& g, uint32_t p, const void* d_tables, const void* d_weight,
@@ -1256,5 +1267,51 @@ struct Api {
     return pk_upload<Curve>(ctx->policy, &d, st);
   }
 };
+
+// ---- multilinear openings (mle_open_impl.cuh): the two members Api declares without a body
+// the quotient tables of `count` tables of 2^v at pt: count x 2^v Fr at q, the count values at rem (may be nullptr)
+template <class Curve>
+void Api<Curve>::mle_quotients(ark355_ctx* ctx, MleScratch& ms, const void* evals, uint32_t v, uint64_t count, const Fr* pt, void* q, void* rem,
+                               bool on_dev) {
+  hipStream_t st = ctx->stream;
+  if (!count) return;
+  const uint32_t E = mle_open_lane_entries(ctx->policy.mle_open_lane_entries);
+  const size_t bytes = (size_t)(count << v) * sizeof(Fr), rem_bytes = (size_t)count * sizeof(Fr);
+  mle_open_reserve<Fr>(ms, v, count, E);
+  if (!on_dev) {
+    ms.in.ensure(bytes);
+    ms.q.ensure(bytes);
+    if (rem) ms.rem.ensure(rem_bytes);
+    ARK_CHECK_HIP(hipMemcpyAsync(ms.in.p, evals, bytes, hipMemcpyHostToDevice, st));
+  }
+  Fr* d_q = on_dev ? (Fr*)q : ms.q.template as<Fr>();
+  Fr* d_rem = on_dev ? (Fr*)rem : (rem ? ms.rem.template as<Fr>() : nullptr);
+  mle_open_run<Fr>(on_dev ? (const Fr*)evals : (const Fr*)ms.in.template as<Fr>(), v, count, pt, d_q, d_rem, ms, E, st);
+  if (!on_dev) {
+    ARK_CHECK_HIP(hipMemcpyAsync(q, d_q, bytes, hipMemcpyDeviceToHost, st));
+    if (rem) ARK_CHECK_HIP(hipMemcpyAsync(rem, d_rem, rem_bytes, hipMemcpyDeviceToHost, st));
+  }
+  ARK_CHECK_HIP(hipStreamSynchronize(st));
+}
+// the PST opening of one table in device memory: the quotients into the context's scratch, then one MSM a level against
+// bases[j] (msm_generic, Montgomery scalars); v affine points at proofs, the value at value_out
+template <class Curve>
+void Api<Curve>::mle_open_dev(ark355_ctx* ctx, MleScratch& ms, GenericScratch& g, const BasesDev* const* bases, const void* d_evals, uint32_t v,
+                         const Fr* pt, uint8_t* proofs, uint8_t* value_out) {
+  hipStream_t st = ctx->stream;
+  const uint32_t E = mle_open_lane_entries(ctx->policy.mle_open_lane_entries);
+  const uint64_t N = 1ull << v;
+  mle_open_reserve<Fr>(ms, v, 1, E);
+  ms.q.ensure((size_t)N * sizeof(Fr));
+  ms.rem.ensure(sizeof(Fr));
+  mle_open_run<Fr>((const Fr*)d_evals, v, 1, pt, ms.q.template as<Fr>(), ms.rem.template as<Fr>(), ms, E, st);
+  ARK_CHECK_HIP(hipMemcpyAsync(value_out, ms.rem.p, sizeof(Fr), hipMemcpyDeviceToHost, st));
+  ARK_CHECK_HIP(hipStreamSynchronize(st));
+  for (uint32_t j = 0; j < v; j++) {
+    const BasesDev& b = *bases[j];
+    const size_t psz = b.group == 1 ? sizeof(Affine<Fq>) : sizeof(Affine<Fq2>);
+    msm_dev(ctx, g, b, ms.q.template as<Fr>() + mle_open_level_offset(N, j), N >> (j + 1), 1, proofs + (size_t)j * psz, true);
+  }
+}
 
 }  // namespace ark355

@@ -1245,6 +1245,68 @@ int32_t ark355_mle_eval_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_eva
   return mle_fix_common(ctx, "ark355_mle_eval_fr", curve, d_evals, num_vars, count, point, -1, d_out, true);
 }
 
+// ---- multilinear openings (mle_open_impl.cuh) -------------------------------------------------------------------------------------
+
+static int32_t mle_quotients_common(ark355_ctx* ctx, int32_t curve, const void* evals, uint32_t num_vars, uint64_t count,
+                                    const uint8_t* point, void* q, void* rem, bool on_dev) {
+  if (!ctx) return ARK355_EINVAL;
+  const std::string pre = "ark355_mle_quotients_fr: ";
+  std::string why;
+  if (const int32_t rc = mle_shape(curve, num_vars, count, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if ((num_vars && !point) || (count && (!evals || !q))) return refuse(ctx, (pre + "evals / point / q_out is NULL").c_str());
+  std::vector<BlsCurve::Fr> p_bls;
+  std::vector<BnCurve::Fr> p_bn;
+  if (const int32_t rc = mle_point(curve, point, num_vars, &p_bls, &p_bn, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  const uint64_t bytes = (count << num_vars) * 32;
+  if (poly_overlap(evals, bytes, q, bytes)) return refuse(ctx, (pre + "q_out overlaps evals").c_str());
+  if (rem && (poly_overlap(evals, bytes, rem, count * 32) || poly_overlap(q, bytes, rem, count * 32)))
+    return refuse(ctx, (pre + "rem_out overlaps evals or q_out").c_str());
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    if (curve == ARK355_BLS12_381) Api<BlsCurve>::mle_quotients(ctx, ex.mle, evals, num_vars, count, p_bls.data(), q, rem, on_dev);
+    else Api<BnCurve>::mle_quotients(ctx, ex.mle, evals, num_vars, count, p_bn.data(), q, rem, on_dev);
+  });
+}
+int32_t ark355_mle_quotients_fr(ark355_ctx* ctx, int32_t curve, const uint8_t* evals, uint32_t num_vars, uint64_t count,
+                                const uint8_t* point, uint8_t* q_out, uint8_t* rem_out) {
+  return mle_quotients_common(ctx, curve, evals, num_vars, count, point, q_out, rem_out, false);
+}
+int32_t ark355_mle_quotients_fr_dev(ark355_ctx* ctx, int32_t curve, const void* d_evals, uint32_t num_vars, uint64_t count,
+                                    const uint8_t* point, void* d_q_out, void* d_rem_out) {
+  return mle_quotients_common(ctx, curve, d_evals, num_vars, count, point, d_q_out, d_rem_out, true);
+}
+
+int32_t ark355_mle_open_dev(ark355_ctx* ctx, int32_t curve, const ark355_bases* const* level_bases, const void* d_evals,
+                            uint32_t num_vars, const uint8_t* point, uint8_t* proofs_out, uint8_t* value_out) {
+  if (!ctx) return ARK355_EINVAL;
+  const std::string pre = "ark355_mle_open_dev: ";
+  std::string why;
+  if (const int32_t rc = mle_shape(curve, num_vars, 1, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  if (!d_evals || !value_out || (num_vars && (!point || !proofs_out)))
+    return refuse(ctx, (pre + "d_evals / point / proofs_out / value_out is NULL").c_str());
+  if (num_vars && !level_bases) return refuse(ctx, (pre + "level_bases is NULL").c_str());
+  std::vector<const BasesDev*> bases(num_vars);
+  for (uint32_t j = 0; j < num_vars; j++) {
+    const std::string lvl = "the handle of level " + std::to_string(j);
+    if (!level_bases[j] || !level_bases[j]->d) return refuse(ctx, (pre + lvl + " is NULL").c_str());
+    const BasesDev* b = level_bases[j]->d;
+    if (b->curve != curve) return refuse(ctx, (pre + lvl + " belongs to another curve").c_str());
+    if (b->group != level_bases[0]->d->group) return refuse(ctx, (pre + lvl + " is of another group than level 0: the handles mix G1 and G2").c_str());
+    if (b->n < (1ull << (num_vars - 1 - j)))
+      return refuse(ctx, (pre + lvl + " holds " + std::to_string(b->n) + " bases, fewer than the 2^" + std::to_string(num_vars - 1 - j) + " of its quotient").c_str());
+    bases[j] = b;
+  }
+  std::vector<BlsCurve::Fr> p_bls;
+  std::vector<BnCurve::Fr> p_bn;
+  if (const int32_t rc = mle_point(curve, point, num_vars, &p_bls, &p_bn, &why)) return refuse(ctx, (pre + why).c_str(), rc);
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    if (curve == ARK355_BLS12_381)
+      Api<BlsCurve>::mle_open_dev(ctx, ex.mle, ex.generic, bases.data(), d_evals, num_vars, p_bls.data(), proofs_out, value_out);
+    else Api<BnCurve>::mle_open_dev(ctx, ex.mle, ex.generic, bases.data(), d_evals, num_vars, p_bn.data(), proofs_out, value_out);
+  });
+}
+
 // ---- sum-check of a predicate (sumcheck_impl.cuh) -------------------------------------------------------------------------------
 
 int32_t ark355_gr1cs_sumcheck_begin_dev(ark355_ctx* ctx, const ark355_gr1cs* g, uint32_t predicate, const void* d_tables,

@@ -21,6 +21,7 @@
 // Scratch of one call (MleScratch, grow-only, owned by the context, reserved before the first launch):
 //     32 * 2 v           the factors of eq                 32 count (N / 2 + N / 4)   ping-pong of fix / eval
 //     32 count N (+ out) staging of the host variants
+// The quotient tables of an opening (mle_open_impl.cuh) keep their own fields of MleScratch.
 #pragma once
 #include <vector>
 #include "common.h"
@@ -38,6 +39,8 @@ struct MleScratch {
   DevBuf pt;                         // eq: p_j, 1 - p_j for j < v
   DevBuf a, b;                       // ping-pong of the halvings
   DevBuf in, out;                    // staging of the host variants
+  DevBuf row_a, row_b;               // mle_open_impl.cuh: the surviving values of a pass, the input of the next
+  DevBuf q, rem;                     // mle_open_impl.cuh: quotients and values of the host variant and of ark355_mle_open_dev
   std::vector<unsigned char> host;   // host image of `pt`: alive until the call's last wait
 };
 

@@ -101,7 +101,8 @@ class Mle:
     ``2^num_vars`` Montgomery Fr over the Boolean hypercube, variable 0 the lowest index bit (ark-poly's
     ``DenseMultilinearExtension``).  Points are sequences of Python integers below r and stay on the host; the ``_dev`` forms take
     device pointers (ints) for the tables and the outputs: ``GR1CS.mat_vec_dev`` -> ``Mle.eq_dev`` -> ``GR1CS.sumcheck_dev`` ->
-    ``Mle.eval_dev`` never visits the host with a table."""
+    ``Mle.eval_dev`` never visits the host with a table, and ``Mle.open_dev`` opens a committed table at the point the sum-check
+    ends at (PST13, ark-poly-commit's ``MultilinearPC::open``) against a key from ``Mle.commit_key``."""
 
     def __init__(self, curve="bls12_381", lib=None, ctx=None, device: int = 0):
         self.curve: Curve = CURVES[curve] if not isinstance(curve, Curve) else curve
@@ -143,6 +144,69 @@ class Mle:
     def eval_dev(self, d_evals: int, num_vars: int, point: Sequence[int], d_out: int, count: int = 1) -> None:
         assert len(point) == num_vars
         self.lib.mle_eval_fr_dev(self.ctx, self.curve.curve_id, d_evals, num_vars, count, self._point(point), d_out)
+
+
+    # ---- openings (csrc/mle_open_impl.cuh) ---------------------------------------------------------------------------
+    @staticmethod
+    def level(num_vars: int, j: int) -> Tuple[int, int]:
+        """(offset, length) in elements of quotient level ``j`` inside one table's ``2^num_vars`` output elements"""
+        assert 0 <= j < num_vars
+        n = 1 << num_vars
+        return n - (n >> j), n >> (j + 1)
+
+    def quotients(self, evals: bytes, num_vars: int, point: Sequence[int], count: int = 1, want_rem: bool = True) -> Tuple[bytes, Optional[bytes]]:
+        """(q, rem): the PST quotient tables ``q_j[i] = f^(j)[2i+1] - f^(j)[2i]`` of ``count`` tables at ``point``, count x 2^num_vars
+        Montgomery Fr -- level j of a table at ``level(num_vars, j)``, ``f~(point)`` in the table's last element -- and the values"""
+        assert len(point) == num_vars
+        return self.lib.mle_quotients_fr(self.ctx, self.curve.curve_id, evals, num_vars, count, self._point(point), want_rem)
+
+    def quotients_dev(self, d_evals: int, num_vars: int, point: Sequence[int], d_q_out: int, d_rem_out: Optional[int] = None,
+                      count: int = 1) -> None:
+        """no two of the three ranges may overlap; ``d_rem_out`` may be None"""
+        assert len(point) == num_vars
+        self.lib.mle_quotients_fr_dev(self.ctx, self.curve.curve_id, d_evals, num_vars, count, self._point(point), d_q_out, d_rem_out)
+
+    def open_dev(self, level_bases, d_evals: int, num_vars: int, point: Sequence[int], group: int = 1) -> Tuple[bytes, bytes]:
+        """(proofs, value): ``num_vars`` affine points ``pi_j = <q_j, level_bases[j]>`` of group ``group`` and ``f~(point)``; the
+        handles are what ``commit_key`` returns, the quotients never leave the context's scratch"""
+        assert len(point) == num_vars and len(level_bases) >= num_vars
+        size = self.lib.sizes(self.curve.curve_id)["g1" if group == 1 else "g2"]
+        return self.lib.mle_open_dev(self.ctx, self.curve.curve_id, list(level_bases[:num_vars]), d_evals, num_vars, self._point(point), size)
+
+    def commit_key(self, group: int, base: bytes, t: Sequence[int], alloc=None):
+        """The PST key of ``len(t)`` variables over the trapdoor ``t``: ``(commit, levels)``, resident base handles
+        (``ark355_bases_free`` each).  ``commit`` holds the 2^v points ``eq(t, i) base``, so that ``ark355_msm_dev`` of a table
+        against it is the commitment ``[f~(t)] base``; ``levels[j]`` holds the 2^(v-1-j) points ``eq((t_{j+1} .. t_{v-1}), i) base``
+        that ``open_dev`` pairs with quotient level j.  Built from ``eq_dev``, ``fixed_base_mul_dev`` and ``bases_load``; the points
+        pass through host memory, which key generation can afford.  ``alloc(nbytes) -> (device pointer, keepalive)`` supplies the
+        device memory of the eq tables; by default a torch tensor."""
+        if alloc is None:
+            def alloc(nbytes):
+                import torch
+                buf = torch.empty((max(1, nbytes),), dtype=torch.uint8, device="cuda")
+                return buf.data_ptr(), buf
+        cid = self.curve.curve_id
+        size = self.lib.sizes(cid)["g1" if group == 1 else "g2"]
+        v = len(t)
+        d_eq, keep = alloc(32 << v)
+
+        def handle(suffix):
+            n = 1 << len(suffix)
+            self.eq_dev(suffix, d_eq)
+            points = self.lib.fixed_base_mul_dev(self.ctx, cid, group, base, d_eq, n, True, size)
+            return self.lib.bases_load(self.ctx, cid, group, points, n)
+
+        handles = []
+        try:
+            handles.append(handle(list(t)))
+            for j in range(v):
+                handles.append(handle(list(t[j + 1:])))
+        except Exception:
+            for h in handles:
+                self.lib.dll.ark355_bases_free(h)
+            raise
+        del keep
+        return handles[0], handles[1:]
 
 
 class Sumcheck:

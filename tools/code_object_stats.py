@@ -70,6 +70,10 @@ KERNELS = [
     (r"mle_fold_kernelINS_2FpINS_10BnFrParams", "bn254.mle_fold"),
     (r"mle_eq_kernelINS_2FpINS_11BlsFrParamsEEELi3E", "bls12_381.mle_eq"),
     (r"mle_eq_kernelINS_2FpINS_10BnFrParamsEEELi3E", "bn254.mle_eq"),
+    (r"mle_open_kernelINS_2FpINS_11BlsFrParamsEEELi8E", "bls12_381.mle_open"),
+    (r"mle_open_kernelINS_2FpINS_10BnFrParamsEEELi8E", "bn254.mle_open"),
+    (r"mle_open_kernelINS_2FpINS_11BlsFrParamsEEELi1E", "bls12_381.mle_open_e1"),
+    (r"mle_open_kernelINS_2FpINS_10BnFrParamsEEELi1E", "bn254.mle_open_e1"),
     # the test kernels of ark355_diag_field_ops: their long branch-free runs are the INLINED multipliers (no scratch access there,
     # none at all in the Fp28 kernels); the 16 - 58 accesses of the Fp / Fp2 kernels are the by-reference operands (and, for the
     # 24-word BLS12-381 Fq2, the returned value) of the out-of-line `_ni` bodies they call as the production kernels do
