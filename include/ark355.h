@@ -104,6 +104,9 @@ int32_t ark355_sizes(int32_t curve, uint32_t what[4]);
  *                 MLE_OPEN_LANE_ENTRIES (ark355_mle_quotients_fr / ark355_mle_open_dev: the consecutive table entries a lane owns
  *                 [default 8; <= 0 selects it; clamped to 1 .. 8 and rounded down to a power of two]; the outputs do not depend
  *                 on it).
+ *                 MSM_BATCH_SMALL_MAX (ark355_msm_batch_dev / ark355_mle_open_dev: the longest segment that takes the short route
+ *                 [default: see that block; negative selects it; 0 switches the route off; clamped to 2^14]; the outputs do not
+ *                 depend on it).
  * ARK355_EINVAL for an unknown name.  ark355_prove_batch runs its worker contexts under the caller's policy.
  * (No counterpart in the reference: ark-groth16 has no runtime knobs; rayon's thread count is its only one.) */
 int32_t ark355_ctx_set_policy(ark355_ctx* ctx, const char* name, int64_t value);
@@ -798,6 +801,33 @@ int32_t ark355_mle_quotients_fr_dev(ark355_ctx* ctx, int32_t curve, const void* 
                                     const uint8_t* point, void* d_q_out, void* d_rem_out);
 int32_t ark355_mle_open_dev(ark355_ctx* ctx, int32_t curve, const ark355_bases* const* level_bases, const void* d_evals,
                             uint32_t num_vars, const uint8_t* point, uint8_t* proofs_out, uint8_t* value_out);
+
+/* ---- Batched short MSMs: many independent inner products in one launch sequence (snark_amd/csrc/msm_batch_impl.cuh) ---------------
+ * `count` independent MSMs, out[s] = sum_{i < n[s]} scalars_s[i] * bases[s][i]: ark-ec's VariableBaseMSM::msm_bigint once per
+ * segment -- the levels of a multilinear opening (ark355_mle_open_dev hands all its levels to this driver), the commitments to many
+ * small tables.
+ * bases[s]: a resident handle (ark355_bases_load); the same handle may appear many times.  d_scalars[s]: n[s] Fr in DEVICE memory,
+ *   canonical, or Montgomery images when scalars_mont != 0, as for ark355_msm_dev.  n[s] = 0 reads neither.
+ * out_affine (host): count affine points of the handles' group back to back; infinity is all-zero bytes, and so is n[s] = 0.
+ * Contract: for every segment the bytes are exactly what ark355_msm_dev(ctx, bases[s], d_scalars[s], n[s], scalars_mont, ..) writes
+ *   -- the result is a canonical affine point, whichever route computes it.
+ * Refusals, all made before any allocation, copy or launch, each with a message in ark355_last_error that names the segment where
+ * there is one; the context works after every one of them: ARK355_EINVAL for a NULL ctx; with count > 0 for a NULL bases, d_scalars,
+ * n or out_affine; for count > ARK355_MSM_BATCH_MAX; for a NULL handle (required even where n[s] = 0: the handles fix the group and
+ * so the output stride); for a handle of another device than the context's, handles of mixed curves or of mixed groups; for n[s]
+ * above the handle's point count; for a NULL d_scalars[s] with n[s] > 0.  ARK355_ENOMEM when the scratch does not fit.  count = 0
+ * returns ARK355_OK and writes nothing.
+ * Policy MSM_BATCH_SMALL_MAX (per call; int32; default 512, the measured crossover; negative selects it; 0 switches the short route off; clamped to 2^14):
+ * a segment with 1 <= n[s] <= MSM_BATCH_SMALL_MAX takes the short route -- the signed window digits of the handle's own plan, then
+ * plain sums of the handle's table rows (about 128 mixed additions a scalar at every window size, no sort, no bucket), all such
+ * segments of a call in ONE launch sequence with one host wait, the last 2 c group operations a bucket set and one batched inversion
+ * on the host.  Every other non-empty segment runs through the pipeline of ark355_msm_dev, one after another.  The policy moves
+ * segments between the routes and never a byte of any output.
+ * Scratch: grow-only, owned by the context, reserved before the first launch, shared with neither the MSM pipeline's scratch nor the
+ * openings' -- one descriptor a short segment, 4 bytes per (scalar, window) and c XYZZ sums per bucket set of every short segment. */
+#define ARK355_MSM_BATCH_MAX 4096
+int32_t ark355_msm_batch_dev(ark355_ctx* ctx, const ark355_bases* const* bases, const void* const* d_scalars, const uint64_t* n,
+                             uint64_t count, int32_t scalars_mont, uint8_t* out_affine);
 
 /* ---- Sum-check of a GR1CS predicate over resident tables (snark_amd/csrc/sumcheck_impl.cuh) ------------------------------------
  * The prover's side of ark-linear-sumcheck's IPForMLSumcheck::prove_round for the claim

@@ -77,6 +77,8 @@ pub const ARK355_VAR_LC: u64 = 4;
 pub const ARK355_PAIRING_GROUP_MAX: u32 = 64;
 /// most polynomials one call of the `ark355_poly_*` entries takes
 pub const ARK355_POLY_MAX_COUNT: u32 = 1024;
+/// most segments one call of `ark355_msm_batch_dev` takes
+pub const ARK355_MSM_BATCH_MAX: u64 = 4096;
 /// most evaluation points of one sum-check round: the predicate's degree as written, plus one with a weight, plus one
 pub const ARK355_SUMCHECK_MAX_POINTS: u32 = 32;
 /// words of the `plan` array of `ark355_diag_msm_sort`
@@ -745,6 +747,16 @@ extern "C" {
         point: *const u8,
         proofs_out: *mut u8,
         value_out: *mut u8,
+    ) -> i32;
+
+    pub fn ark355_msm_batch_dev(
+        ctx: *mut ark355_ctx,
+        bases: *const *const ark355_bases,
+        d_scalars: *const *const c_void,
+        n: *const u64,
+        count: u64,
+        scalars_mont: i32,
+        out_affine: *mut u8,
     ) -> i32;
 
     pub fn ark355_gr1cs_sumcheck_begin_dev(

@@ -70,7 +70,7 @@ SYMBOLS = [
     "ark355_mle_quotients_fr", "ark355_mle_quotients_fr_dev", "ark355_mle_open_dev",
     "ark355_gr1cs_sumcheck_begin_dev", "ark355_sumcheck_info", "ark355_sumcheck_round", "ark355_sumcheck_finish", "ark355_sumcheck_free",
     "ark355_ntt_fr", "ark355_ntt_fr_dev",
-    "ark355_msm_g1", "ark355_msm_g2", "ark355_bases_load", "ark355_bases_free", "ark355_msm_dev",
+    "ark355_msm_g1", "ark355_msm_g2", "ark355_bases_load", "ark355_bases_free", "ark355_msm_dev", "ark355_msm_batch_dev",
     "ark355_msm_dev_partial", "ark355_xyzz_sum", "ark355_fixed_base_mul", "ark355_fixed_base_mul_dev", "ark355_get_timings",
     "ark355_get_kernel_stats", "ark355_pk_load_shard", "ark355_partial_size", "ark355_prove_shard",
     "ark355_prove_combine", "ark355_prove_batch", "ark355_comm_unique_id", "ark355_comm_init", "ark355_comm_destroy",
@@ -268,6 +268,7 @@ class Lib:
         d.ark355_bases_free.restype = None
         d.ark355_msm_dev.argtypes = [vp, vp, vp, u64, i32, vp]
         d.ark355_msm_dev_partial.argtypes = [vp, vp, vp, u64, i32, vp]
+        d.ark355_msm_batch_dev.argtypes = [vp, vp, vp, vp, u64, i32, vp]
         d.ark355_xyzz_sum.argtypes = [vp, i32, i32, vp, u64, vp]
         d.ark355_fixed_base_mul.argtypes = [vp, i32, i32, vp, vp, u64, vp]
         d.ark355_fixed_base_mul_dev.argtypes = [vp, i32, i32, vp, vp, u64, i32, vp]
@@ -1126,6 +1127,19 @@ class Lib:
         fn = self.dll.ark355_msm_dev_partial if partial else self.dll.ark355_msm_dev
         self.check(ctx, fn(ctx, bases_h, C.c_void_p(d_scalars_ptr), n, int(mont), out.ctypes.data_as(C.c_void_p)))
         return out.tobytes()
+
+    def msm_batch_dev(self, ctx, handles, d_ptrs, ns, mont, out_size):
+        """ark355_msm_batch_dev: len(ns) independent MSMs, segment s over ns[s] scalars at the device pointer d_ptrs[s] (None where
+        ns[s] is 0) against the resident handle handles[s]; all handles of one curve and group.  Returns the affine points, out_size
+        bytes each, back to back."""
+        count = len(ns)
+        assert len(handles) == count and len(d_ptrs) == count
+        out = np.zeros(max(1, count * out_size), dtype=np.uint8)
+        hs = (C.c_void_p * max(1, count))(*[h if isinstance(h, C.c_void_p) else C.c_void_p(h) for h in handles])
+        ps = (C.c_void_p * max(1, count))(*[C.c_void_p(p) if p else None for p in d_ptrs])
+        nn = (C.c_uint64 * max(1, count))(*[int(x) for x in ns])
+        self.check(ctx, self.dll.ark355_msm_batch_dev(ctx, hs, ps, nn, count, int(mont), out.ctypes.data_as(C.c_void_p)))
+        return out.tobytes()[:count * out_size]
 
     def xyzz_sum(self, ctx, curve, group, partials: bytes, count, out_size):
         out = np.zeros(out_size, dtype=np.uint8)

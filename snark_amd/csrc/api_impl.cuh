@@ -13,6 +13,7 @@
 #include "evals_impl.cuh"
 #include "mle_impl.cuh"
 #include "mle_open_impl.cuh"
+#include "msm_batch_impl.cuh"
 #include "sumcheck_impl.cuh"
 #include "lcmap_impl.cuh"
 #include "setup_impl.cuh"
@@ -23,6 +24,7 @@ namespace ark355 {
 
 struct BasesDev {
   int curve = 0, group = 1;
+  int device = -1;       // where the tables are resident (set by ark355_bases_load)
   uint64_t n = 0;
   PrecompTable tab;      // per-window tables of the resident bases
 };
@@ -494,8 +496,17 @@ struct Api {
                             bool on_dev);
   // the PST opening of one table in device memory: the quotients into the context's scratch, then one MSM a level against
   // bases[j] (msm_generic, Montgomery scalars); v affine points at proofs, the value at value_out
-  static void mle_open_dev(ark355_ctx* ctx, MleScratch& ms, GenericScratch& g, const BasesDev* const* bases, const void* d_evals, uint32_t v,
-                           const Fr* pt, uint8_t* proofs, uint8_t* value_out);
+  static void mle_open_dev(ark355_ctx* ctx, MleScratch& ms, MsmBatchScratch& bs, GenericScratch& g, const BasesDev* const* bases,
+                           const void* d_evals, uint32_t v, const Fr* pt, uint8_t* proofs, uint8_t* value_out);
+
+  // ---- batched short MSMs (msm_batch_impl.cuh); declared here and defined behind the struct for the same reason
+  // `count` independent MSMs over handles of ONE group: out[s] = sum_{i < n[s]} scalars_s[i] bases[s][i], affine, back to back.
+  // Segments of 1 .. MSM_BATCH_SMALL_MAX scalars leave as one batch, the others run through msm_dev one after another.
+  static void msm_batch_dev(ark355_ctx* ctx, MsmBatchScratch& bs, GenericScratch& g, const BasesDev* const* bases, const void* const* d_scalars,
+                            const uint64_t* n, uint64_t count, int mont, uint8_t* out);
+  template <class F>
+  static void msm_batch_t(ark355_ctx* ctx, MsmBatchScratch& bs, GenericScratch& g, const BasesDev* const* bases, const void* const* d_scalars,
+                          const uint64_t* n, uint64_t count, int mont, uint8_t* out);
 
   // ---- sum-check of a predicate (sumcheck_impl.cuh): the order of the calls is checked by capi.hip
   static SumcheckDev* sumcheck_begin(ark355_ctx* ctx, const Gr1csDev& g, uint32_t p, const void* d_tables, const void* d_weight,
@@ -1293,11 +1304,70 @@ void Api<Curve>::mle_quotients(ark355_ctx* ctx, MleScratch& ms, const void* eval
   }
   ARK_CHECK_HIP(hipStreamSynchronize(st));
 }
-// the PST opening of one table in device memory: the quotients into the context's scratch, then one MSM a level against
-// bases[j] (msm_generic, Montgomery scalars); v affine points at proofs, the value at value_out
+// ---- batched short MSMs (msm_batch_impl.cuh)
 template <class Curve>
-void Api<Curve>::mle_open_dev(ark355_ctx* ctx, MleScratch& ms, GenericScratch& g, const BasesDev* const* bases, const void* d_evals, uint32_t v,
-                         const Fr* pt, uint8_t* proofs, uint8_t* value_out) {
+template <class F>
+void Api<Curve>::msm_batch_t(ark355_ctx* ctx, MsmBatchScratch& bs, GenericScratch& g, const BasesDev* const* bases, const void* const* d_scalars,
+                             const uint64_t* n, uint64_t count, int mont, uint8_t* out) {
+  hipStream_t st = ctx->stream;
+  const uint64_t small_max = msm_batch_small_max(ctx->policy.msm_batch_small_max);
+  auto* res = reinterpret_cast<Affine<F>*>(out);
+  // the short route: every segment of 1 .. small_max scalars, in one launch sequence
+  std::vector<MsmBatchSeg> segs;
+  std::vector<uint64_t> who;
+  uint64_t digits_total = 0, parts_total = 0;
+  for (uint64_t s = 0; s < count; s++) {
+    if (n[s] < 1 || n[s] > small_max) continue;
+    const PrecompTable& tab = bases[s]->tab;
+    const MsmPlan& p = tab.plan;
+    MsmBatchSeg sg;
+    sg.rows = tab.table.p;
+    sg.scalars = d_scalars[s];
+    sg.dig_off = digits_total;
+    sg.out_off = (uint32_t)parts_total;
+    sg.n = (uint32_t)n[s];
+    sg.c = p.c;
+    sg.windows = p.windows;
+    sg.wstride = p.wstride;
+    sg.row_stride = (uint32_t)tab.n;
+    sg.packed = tab.packed ? 1u : 0u;
+    sg.digit_flags = msm_digit_flags(p);
+    digits_total += (uint64_t)p.windows * n[s];
+    parts_total += msm_parts_count(p);
+    segs.push_back(sg);
+    who.push_back(s);
+  }
+  ARK_REQUIRE(parts_total < (1ull << 31), ARK355_EINVAL, "batched MSM: too many partial sums");
+  if (!segs.empty()) {
+    std::vector<XYZZ<F>> h_parts;
+    msm_batch_short_run<F, Fr>(bs, segs, digits_total, (uint32_t)parts_total, mont, h_parts, st);
+    // Horner over the bit sums of each segment (msm_parts_finish, as msm_generic), then one inversion for all of them
+    std::vector<XYZZ<F>> sums(segs.size());
+    for (size_t t = 0; t < segs.size(); t++) sums[t] = msm_parts_finish<F>(h_parts.data() + segs[t].out_off, bases[who[t]]->tab.plan);
+    std::vector<Affine<F>> aff(segs.size());
+    xyzz_batch_to_affine_host<F>(sums.data(), sums.size(), aff.data());
+    for (size_t t = 0; t < segs.size(); t++) res[who[t]] = aff[t];
+  }
+  // every other segment: the empty ones are the point at infinity, the long ones run as ark355_msm_dev runs them
+  for (uint64_t s = 0; s < count; s++) {
+    if (n[s] == 0) res[s] = Affine<F>::inf();
+    else if (n[s] > small_max) msm_dev(ctx, g, *bases[s], d_scalars[s], n[s], mont, out + (size_t)s * sizeof(Affine<F>), true);
+  }
+}
+template <class Curve>
+void Api<Curve>::msm_batch_dev(ark355_ctx* ctx, MsmBatchScratch& bs, GenericScratch& g, const BasesDev* const* bases, const void* const* d_scalars,
+                               const uint64_t* n, uint64_t count, int mont, uint8_t* out) {
+  if (!count) return;
+  if (bases[0]->group == 1) msm_batch_t<Fq>(ctx, bs, g, bases, d_scalars, n, count, mont, out);
+  else msm_batch_t<Fq2>(ctx, bs, g, bases, d_scalars, n, count, mont, out);
+}
+
+// the PST opening of one table in device memory: the quotients into the context's scratch, then the MSMs of all levels against
+// bases[j] as ONE batch (msm_batch_dev, Montgomery scalars: the short levels in one launch sequence, the long ones through
+// msm_generic one after another); v affine points at proofs, the value at value_out
+template <class Curve>
+void Api<Curve>::mle_open_dev(ark355_ctx* ctx, MleScratch& ms, MsmBatchScratch& bs, GenericScratch& g, const BasesDev* const* bases,
+                              const void* d_evals, uint32_t v, const Fr* pt, uint8_t* proofs, uint8_t* value_out) {
   hipStream_t st = ctx->stream;
   const uint32_t E = mle_open_lane_entries(ctx->policy.mle_open_lane_entries);
   const uint64_t N = 1ull << v;
@@ -1307,11 +1377,13 @@ void Api<Curve>::mle_open_dev(ark355_ctx* ctx, MleScratch& ms, GenericScratch& g
   mle_open_run<Fr>((const Fr*)d_evals, v, 1, pt, ms.q.template as<Fr>(), ms.rem.template as<Fr>(), ms, E, st);
   ARK_CHECK_HIP(hipMemcpyAsync(value_out, ms.rem.p, sizeof(Fr), hipMemcpyDeviceToHost, st));
   ARK_CHECK_HIP(hipStreamSynchronize(st));
+  std::vector<const void*> scalars(v);
+  std::vector<uint64_t> lens(v);
   for (uint32_t j = 0; j < v; j++) {
-    const BasesDev& b = *bases[j];
-    const size_t psz = b.group == 1 ? sizeof(Affine<Fq>) : sizeof(Affine<Fq2>);
-    msm_dev(ctx, g, b, ms.q.template as<Fr>() + mle_open_level_offset(N, j), N >> (j + 1), 1, proofs + (size_t)j * psz, true);
+    scalars[j] = ms.q.template as<Fr>() + mle_open_level_offset(N, j);
+    lens[j] = N >> (j + 1);
   }
+  msm_batch_dev(ctx, bs, g, bases, scalars.data(), lens.data(), v, 1, proofs);
 }
 
 }  // namespace ark355

@@ -51,6 +51,7 @@ struct CtxExtra {
   PolyScratch poly;
   EvalsScratch evals;
   MleScratch mle;
+  MsmBatchScratch msm_batch;
   std::vector<ark355_ctx*> lanes;     // child contexts of ark355_prove_batch (same device, private streams/scratch)
   ~CtxExtra();
 };
@@ -1302,8 +1303,8 @@ int32_t ark355_mle_open_dev(ark355_ctx* ctx, int32_t curve, const ark355_bases* 
   return guarded(ctx, [&] {
     CtxExtra& ex = extra(ctx);
     if (curve == ARK355_BLS12_381)
-      Api<BlsCurve>::mle_open_dev(ctx, ex.mle, ex.generic, bases.data(), d_evals, num_vars, p_bls.data(), proofs_out, value_out);
-    else Api<BnCurve>::mle_open_dev(ctx, ex.mle, ex.generic, bases.data(), d_evals, num_vars, p_bn.data(), proofs_out, value_out);
+      Api<BlsCurve>::mle_open_dev(ctx, ex.mle, ex.msm_batch, ex.generic, bases.data(), d_evals, num_vars, p_bls.data(), proofs_out, value_out);
+    else Api<BnCurve>::mle_open_dev(ctx, ex.mle, ex.msm_batch, ex.generic, bases.data(), d_evals, num_vars, p_bn.data(), proofs_out, value_out);
   });
 }
 
@@ -1434,6 +1435,7 @@ int32_t ark355_bases_load(ark355_ctx* ctx, int32_t curve, int32_t group, const u
   return guarded(ctx, [&] {
     BasesDev* d = nullptr;
     CURVE_DISPATCH(curve, d = A::bases_load(ctx->policy, group, bases, n, ctx->stream));
+    d->device = ctx->device;
     *out = new ark355_bases{d};
   });
 }
@@ -1457,6 +1459,35 @@ int32_t ark355_msm_dev_partial(ark355_ctx* ctx, const ark355_bases* bases, const
   return guarded(ctx, [&] {
     CtxExtra& ex = extra(ctx);
     CURVE_DISPATCH(bases->d->curve, A::msm_dev(ctx, ex.generic, *bases->d, d_scalars, n, scalars_mont, out_xyzz, false));
+  });
+}
+
+// ---- batched short MSMs (msm_batch_impl.cuh): every refusal precedes the first allocation, copy or launch
+int32_t ark355_msm_batch_dev(ark355_ctx* ctx, const ark355_bases* const* bases, const void* const* d_scalars, const uint64_t* n,
+                             uint64_t count, int32_t scalars_mont, uint8_t* out_affine) {
+  if (!ctx) return ARK355_EINVAL;
+  if (count == 0) return ARK355_OK;
+  const std::string pre = "ark355_msm_batch_dev: ";
+  if (!bases || !d_scalars || !n || !out_affine) return refuse(ctx, (pre + "bases / d_scalars / n / out_affine is NULL").c_str());
+  if (count > ARK355_MSM_BATCH_MAX)
+    return refuse(ctx, (pre + std::to_string(count) + " segments, more than ARK355_MSM_BATCH_MAX = " + std::to_string(ARK355_MSM_BATCH_MAX)).c_str());
+  std::vector<const BasesDev*> hs(count);
+  for (uint64_t s = 0; s < count; s++) {
+    const std::string seg = "segment " + std::to_string(s) + ": ";
+    if (!bases[s] || !bases[s]->d) return refuse(ctx, (pre + seg + "the handle is NULL").c_str());
+    const BasesDev* b = bases[s]->d;
+    if (b->device != ctx->device) return refuse(ctx, (pre + seg + "the handle lives on another device than the context").c_str());
+    if (b->curve != bases[0]->d->curve) return refuse(ctx, (pre + seg + "the handle belongs to another curve than segment 0's").c_str());
+    if (b->group != bases[0]->d->group)
+      return refuse(ctx, (pre + seg + "the handle is of another group than segment 0's: the handles mix G1 and G2").c_str());
+    if (n[s] > b->n)
+      return refuse(ctx, (pre + seg + std::to_string(n[s]) + " scalars, more than the handle's " + std::to_string(b->n) + " bases").c_str());
+    if (n[s] && !d_scalars[s]) return refuse(ctx, (pre + seg + "d_scalars is NULL").c_str());
+    hs[s] = b;
+  }
+  return guarded(ctx, [&] {
+    CtxExtra& ex = extra(ctx);
+    CURVE_DISPATCH(hs[0]->curve, A::msm_batch_dev(ctx, ex.msm_batch, ex.generic, hs.data(), d_scalars, n, count, scalars_mont, out_affine));
   });
 }
 

@@ -208,6 +208,11 @@ template <class P>
 ARK_HD_NOINLINE typename Fp28<P>::Vec one28_ni() {
   return Fp28<P>::from_fp(Fp<P>::one()).to_vec();
 }
+// How the group law below and in tails28_impl.cuh reaches its cold paths: a class with classify / dbl / dbl_g2.  Cold28 (the
+// default, defined behind dbl28_g2_coord_ni) forwards to the out-of-line helpers of this file, so every existing caller compiles
+// to the calls it always made; a kernel that must not touch scratch memory even there passes its own (msm_batch_impl.cuh).
+template <class P>
+struct Cold28;
 
 // Where zz / zzz of the pair's accumulator live between their uses.  ZzRegs: in the accumulator's own registers.  ZzLds
 // (round 6): in LDS.  The lane-pair addition over BLS12-381 does not fit 256 registers -- the code object of the first
@@ -344,7 +349,7 @@ struct ZzLds {
 //   X3 = norm(R^2 + 5p - (PPP + 2Q))             (< 6.1 p)
 //   Y3 = R (Q + 8p - X3) + (3p - Y1) PPP         (one fused pass; operand limbs < 2^29.6 each)
 // Largest column: 14 * 2^59.2 + 14 * 2^57.6 + 14 * 2^56 < 2^63.5.
-template <class P, class Z>
+template <class P, class Z, class C = Cold28<P>>
 ARK_D void madd28z(Acc28<P>& acc, const Z& z, bool& empty, const Fp28<P>& px, const Fp28<P>& py, bool negate) {
   using F = Fp28<P>;
   F pys;
@@ -367,14 +372,14 @@ ARK_D void madd28z(Acc28<P>& acc, const Z& z, bool& empty, const Fp28<P>& px, co
   const F Pd = F::template sub<8, 1>(U2, z.x());
   const F R = F::template sub<3, 1>(S2, z.y());
   if (Pd.multiple_hint() < 10u) {
-    const int cls = madd28_classify<P>(Pd, R);
+    const int cls = C::classify(Pd, R);
     if (cls == 1) {
       const F yn = F::norm(pys);
-      z.set_x(F::from_vec(dbl28_coord_ni<P>(px, yn, 0)));
-      z.set_y(F::from_vec(dbl28_coord_ni<P>(px, yn, 1)));
-      const F nzz = F::from_vec(dbl28_coord_ni<P>(px, yn, 2));
+      z.set_x(F::from_vec(C::dbl(px, yn, 0)));
+      z.set_y(F::from_vec(C::dbl(px, yn, 1)));
+      const F nzz = F::from_vec(C::dbl(px, yn, 2));
       z.set_zz(nzz);
-      z.set_zzz(F::from_vec(dbl28_coord_ni<P>(px, yn, 3)));
+      z.set_zzz(F::from_vec(C::dbl(px, yn, 3)));
       if (nzz.limbs_all_zero()) empty = true;       // 2P = infinity (no such point on these curves)
       return;
     }
@@ -395,10 +400,10 @@ ARK_D void madd28z(Acc28<P>& acc, const Z& z, bool& empty, const Fp28<P>& px, co
   z.set_x(X3);
   z.set_y(F::mul2sum(R, T, NY, PPP));
 }
-template <class P>
+template <class P, class C = Cold28<P>>
 ARK_D void madd28(Acc28<P>& acc, bool& empty, const Fp28<P>& px, const Fp28<P>& py, bool negate) {
   const ZzRegs<P> z{acc};
-  madd28z<P, ZzRegs<P>>(acc, z, empty, px, py, negate);
+  madd28z<P, ZzRegs<P>, C>(acc, z, empty, px, py, negate);
 }
 
 // (Round 6, run O: this walk at THREE waves per SIMD -- 168 registers, x / zz / zzz of the accumulator in LDS through ZzLds, no
@@ -794,6 +799,13 @@ ARK_HD_NOINLINE typename Fp28<P>::Vec dbl28_g2_coord_ni(Fp28<P> x, Fp28<P> y, in
   const F NW = F::template neg<3, 1>(W);
   return L::template mul2<5, 1, 4, 3>(M, T, NW, y).to_vec();
 }
+template <class P>
+struct Cold28 {
+  using F = Fp28<P>;
+  ARK_D static int classify(const F& pd, const F& r) { return madd28_classify<P>(pd, r); }
+  ARK_D static typename F::Vec dbl(const F& x, const F& y, int which) { return dbl28_coord_ni<P>(x, y, which); }
+  ARK_D static typename F::Vec dbl_g2(const F& x, const F& y, int which) { return dbl28_g2_coord_ni<P>(x, y, which); }
+};
 
 // acc += (px, +-py) over Fq2, one component per lane.  Same formula and value classes as madd28; Pd, R and
 // T = Q - X3 are normalised before they enter a multi-product pass, which keeps every column below
@@ -801,7 +813,7 @@ ARK_HD_NOINLINE typename Fp28<P>::Vec dbl28_g2_coord_ni(Fp28<P> x, Fp28<P> y, in
 // The addition comes in two halves so that the accumulation loop can issue the gather of the NEXT table row between
 // them: after the first half px / py are dead, and the row's latency hides under the eight products of the second.
 // madd28_g2_head returns false when the entry is already dealt with (bucket opened, doubling, cancellation).
-template <class P, class Z>
+template <class P, class Z, class C = Cold28<P>>
 ARK_D bool madd28_g2_head(Acc28<P>& acc, const Z& z, bool& empty, const Fp28<P>& px, const Fp28<P>& py, bool negate,
                           Fp28<P>& Pd, Fp28<P>& R) {
   using F = Fp28<P>;
@@ -827,11 +839,11 @@ ARK_D bool madd28_g2_head(Acc28<P>& acc, const Z& z, bool& empty, const Fp28<P>&
     if (L::both(F::is_zero_mod_p_inl(Pd))) {
       if (L::both(F::is_zero_mod_p_inl(R))) {
         const F yn = F::norm(pys);
-        z.set_x(F::from_vec(dbl28_g2_coord_ni<P>(px, yn, 0)));
-        z.set_y(F::from_vec(dbl28_g2_coord_ni<P>(px, yn, 1)));
-        const F nzz = F::from_vec(dbl28_g2_coord_ni<P>(px, yn, 2));
+        z.set_x(F::from_vec(C::dbl_g2(px, yn, 0)));
+        z.set_y(F::from_vec(C::dbl_g2(px, yn, 1)));
+        const F nzz = F::from_vec(C::dbl_g2(px, yn, 2));
         z.set_zz(nzz);
-        z.set_zzz(F::from_vec(dbl28_g2_coord_ni<P>(px, yn, 3)));
+        z.set_zzz(F::from_vec(C::dbl_g2(px, yn, 3)));
         if (L::both(nzz.limbs_all_zero())) empty = true;
       } else {
         empty = true;
@@ -876,16 +888,16 @@ ARK_D void madd28_g2_tail(Acc28<P>& acc, const Z& z, const Fp28<P>& Pd, const Fp
   else
     z.set_y(L::mul2b(L::template both_with<6, 1>(R, pR), T, L::xchg(T), bPPP, NY, L::xchg(NY)));
 }
-template <class P, class Z>
+template <class P, class Z, class C = Cold28<P>>
 ARK_D void madd28_g2z(Acc28<P>& acc, const Z& z, bool& empty, const Fp28<P>& px, const Fp28<P>& py, bool negate) {
   Fp28<P> Pd, R;
-  if (madd28_g2_head<P, Z>(acc, z, empty, px, py, negate, Pd, R)) madd28_g2_tail<P, Z>(acc, z, Pd, R);
+  if (madd28_g2_head<P, Z, C>(acc, z, empty, px, py, negate, Pd, R)) madd28_g2_tail<P, Z>(acc, z, Pd, R);
 }
 // (zz / zzz in the accumulator's registers: the packed-row kernel, BN254, tests)
-template <class P>
+template <class P, class C = Cold28<P>>
 ARK_D void madd28_g2(Acc28<P>& acc, bool& empty, const Fp28<P>& px, const Fp28<P>& py, bool negate) {
   const ZzRegs<P> z{acc};
-  madd28_g2z<P, ZzRegs<P>>(acc, z, empty, px, py, negate);
+  madd28_g2z<P, ZzRegs<P>, C>(acc, z, empty, px, py, negate);
 }
 
 #ifndef ARK_G2L28_WAVES

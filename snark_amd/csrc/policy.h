@@ -22,7 +22,8 @@
 //                  ark355_poly_eval_fr / ark355_poly_div_linear_fr owns), EVALS_LANE_POINTS (the domain points one lane of
 //                  ark355_evals_eval_fr / ark355_evals_div_linear_fr owns), SUMCHECK_LANE_PAIRS (the output pairs one lane of
 //                  ark355_sumcheck_round owns, and the outputs one lane of ark355_mle_fix_fr / ark355_mle_eval_fr owns),
-//                  MLE_OPEN_LANE_ENTRIES (the table entries one lane of ark355_mle_quotients_fr / ark355_mle_open_dev owns)
+//                  MLE_OPEN_LANE_ENTRIES (the table entries one lane of ark355_mle_quotients_fr / ark355_mle_open_dev owns),
+//                  MSM_BATCH_SMALL_MAX (the longest segment ark355_msm_batch_dev / ark355_mle_open_dev hand to the short route)
 //   process-wide   POISON_ALLOC: a TEST knob, not a tuning switch.  Device and pinned host buffers are allocated by objects that know no
 //                  context (DevBuf, common.h), so the value is mirrored into ONE atomic of the process (poison_alloc_byte): setting it
 //                  through any context, or through the environment of a context created later, changes it for every context.
@@ -115,6 +116,11 @@ struct TunePolicy {
                                   // a workgroup owns 256 times as many and runs log2 of that many halvings a pass.  <= 0: the default; clamped
                                   // to 1 .. 8 and rounded down to a power of two.  Tests lower it to reach the wave and workgroup borders
                                   // and a second and third pass at small tables; it moves every border and never a byte of any output.
+  int32_t msm_batch_small_max = -1;// ark355_msm_batch_dev / ark355_mle_open_dev (msm_batch_impl.cuh): a segment of 1 .. this many scalars takes the
+                                  // short route (digits and plain sums of table rows, all such segments of a call in one launch sequence),
+                                  // every other one runs through the MSM pipeline on its own.  0 switches the short route off; negative
+                                  // (default) selects MSM_BATCH_SMALL_MAX_DEFAULT; clamped to 2^14.  It moves segments between the routes and
+                                  // never changes a byte of any output.
   // ---- process-wide (test knob)
   int32_t poison_alloc = -1;     // 0 .. 255: every device buffer (DevBuf::alloc) and pinned host buffer is filled with this byte, synchronously,
                                   // before the allocator returns, so that no test passes because fresh memory happened to hold zeros; -1 (default)
@@ -176,6 +182,7 @@ inline const TunePolicy::Field* TunePolicy::fields(int* count) {
       ARK_POLICY_FIELD32("EVALS_LANE_POINTS", evals_lane_points),
       ARK_POLICY_FIELD32("SUMCHECK_LANE_PAIRS", sumcheck_lane_pairs),
       ARK_POLICY_FIELD32("MLE_OPEN_LANE_ENTRIES", mle_open_lane_entries),
+      ARK_POLICY_FIELD32("MSM_BATCH_SMALL_MAX", msm_batch_small_max),
       ARK_POLICY_FIELD32("POISON_ALLOC", poison_alloc),
   };
   *count = (int)(sizeof(tab) / sizeof(tab[0]));

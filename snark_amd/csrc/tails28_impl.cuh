@@ -29,14 +29,14 @@ namespace ark355 {
 // ---- cold path of the general addition: 2 (x, y, zz, zzz) ---------------------------------------------------------
 // dbl-2008-s-1 with a = 0 never reads zz / zzz for X3, Y3: they are the coordinates of mdbl on (x, y), and
 // ZZ3 = V zz, ZZZ3 = W zzz with V, W the "zz, zzz" that mdbl returns.  So the cold helpers of the mixed addition serve.
-template <class P>
+template <class P, class C = Cold28<P>>
 ARK_D void dbl28(Acc28<P>& a, bool& empty) {
   using F = Fp28<P>;
   const F x = a.x, y = a.y;
-  const F X3 = F::from_vec(dbl28_coord_ni<P>(x, y, 0));
-  const F Y3 = F::from_vec(dbl28_coord_ni<P>(x, y, 1));
-  const F V = F::from_vec(dbl28_coord_ni<P>(x, y, 2));
-  const F W = F::from_vec(dbl28_coord_ni<P>(x, y, 3));
+  const F X3 = F::from_vec(C::dbl(x, y, 0));
+  const F Y3 = F::from_vec(C::dbl(x, y, 1));
+  const F V = F::from_vec(C::dbl(x, y, 2));
+  const F W = F::from_vec(C::dbl(x, y, 3));
   if (V.limbs_all_zero()) {      // y == 0: a point of order two (neither curve has one)
     empty = true;
     return;
@@ -53,7 +53,7 @@ ARK_D void dbl28(Acc28<P>& a, bool& empty) {
 //   PP = Pd^2, PPP = Pd PP, Q = U1 PP, ZZ3 = ZZ1 ZZ2 PP, ZZZ3 = ZZZ1 ZZZ2 PPP
 //   X3 = norm(R^2 + 5p - (PPP + 2Q))                                         (< 6.05 p)
 //   Y3 = R (Q + 8p - X3) + (3p - S1) PPP                                     (one fused pass, columns as in madd28)
-template <class P>
+template <class P, class C = Cold28<P>>
 ARK_D void add28(Acc28<P>& a, bool& a_empty, const Acc28<P>& b, bool b_empty) {
   using F = Fp28<P>;
   if (b_empty) return;
@@ -69,9 +69,9 @@ ARK_D void add28(Acc28<P>& a, bool& a_empty, const Acc28<P>& b, bool b_empty) {
   const F Pd = F::template sub<3, 1>(U2, U1);
   const F R = F::template sub<3, 1>(S2, S1);
   if (Pd.multiple_hint() < 10u) {
-    const int cls = madd28_classify<P>(Pd, R);
+    const int cls = C::classify(Pd, R);
     if (cls == 1) {
-      dbl28<P>(a, a_empty);
+      dbl28<P, C>(a, a_empty);
       return;
     }
     if (cls == 2) {
@@ -94,15 +94,15 @@ ARK_D void add28(Acc28<P>& a, bool& a_empty, const Acc28<P>& b, bool b_empty) {
 
 // The same over Fq2 on a lane pair (one component of every coordinate per lane; Pair28 of msm28_impl.cuh).  `empty` flags
 // are pair-wide (both lanes hold the same value).
-template <class P>
+template <class P, class C = Cold28<P>>
 ARK_D void dbl28_g2(Acc28<P>& a, bool& empty) {
   using F = Fp28<P>;
   using L = Pair28<P>;
   const F x = F::canon(a.x), y = a.y;           // dbl28_g2_coord_ni wants x canonical, y normalised and < 2p
-  const F X3 = F::from_vec(dbl28_g2_coord_ni<P>(x, y, 0));
-  const F Y3 = F::from_vec(dbl28_g2_coord_ni<P>(x, y, 1));
-  const F V = F::from_vec(dbl28_g2_coord_ni<P>(x, y, 2));
-  const F W = F::from_vec(dbl28_g2_coord_ni<P>(x, y, 3));
+  const F X3 = F::from_vec(C::dbl_g2(x, y, 0));
+  const F Y3 = F::from_vec(C::dbl_g2(x, y, 1));
+  const F V = F::from_vec(C::dbl_g2(x, y, 2));
+  const F W = F::from_vec(C::dbl_g2(x, y, 3));
   if (L::both(F::is_zero_mod_p(V))) {
     empty = true;
     return;
@@ -112,7 +112,7 @@ ARK_D void dbl28_g2(Acc28<P>& a, bool& empty) {
   a.zz = L::template mul<3, 1>(a.zz, V);
   a.zzz = L::template mul<3, 1>(a.zzz, W);
 }
-template <class P>
+template <class P, class C = Cold28<P>>
 ARK_D void add28_g2(Acc28<P>& a, bool& a_empty, const Acc28<P>& b, bool b_empty) {
   using F = Fp28<P>;
   using L = Pair28<P>;
@@ -130,7 +130,7 @@ ARK_D void add28_g2(Acc28<P>& a, bool& a_empty, const Acc28<P>& b, bool b_empty)
   const F R = F::norm(F::template sub<3, 1>(S2, S1));
   if (L::both(Pd.multiple_hint() < 10u)) {
     if (L::both(F::is_zero_mod_p_inl(Pd))) {
-      if (L::both(F::is_zero_mod_p_inl(R))) dbl28_g2<P>(a, a_empty);
+      if (L::both(F::is_zero_mod_p_inl(R))) dbl28_g2<P, C>(a, a_empty);
       else a_empty = true;
       return;
     }
@@ -149,7 +149,7 @@ ARK_D void add28_g2(Acc28<P>& a, bool& a_empty, const Acc28<P>& b, bool b_empty)
 }
 
 // ---- one item (bucket / partial sum) per lane (G1) or per lane pair (G2) --------------------------------------------
-template <class P, bool G2>
+template <class P, bool G2, class C = Cold28<P>>
 struct Tail28 {
   using F = Fp28<P>;
   using Fq = Fp<P>;
@@ -173,8 +173,8 @@ struct Tail28 {
   }
   ARK_D static void store(Slot* s, const Acc28<P>& a, bool empty) { slot28_put<P>(half(s), a, empty); }
   ARK_D static void add(Acc28<P>& a, bool& ae, const Acc28<P>& b, bool be) {
-    if constexpr (G2) add28_g2<P>(a, ae, b, be);
-    else add28<P>(a, ae, b, be);
+    if constexpr (G2) add28_g2<P, C>(a, ae, b, be);
+    else add28<P, C>(a, ae, b, be);
   }
   // a += (the value of lane ^ mask); mask >= LPI keeps the lane parity of a pair
   ARK_D static void add_xor(Acc28<P>& a, bool& ae, int mask) {

@@ -173,6 +173,14 @@ class Mle:
         size = self.lib.sizes(self.curve.curve_id)["g1" if group == 1 else "g2"]
         return self.lib.mle_open_dev(self.ctx, self.curve.curve_id, list(level_bases[:num_vars]), d_evals, num_vars, self._point(point), size)
 
+    def commit_dev(self, handle, d_tables: int, num_vars: int, count: int = 1, group: int = 1) -> bytes:
+        """The commitments ``<f_k, handle>`` to ``count`` resident tables of ``2^num_vars`` Montgomery Fr, back to back at
+        ``d_tables``, with one key (``commit`` of ``commit_key``): ``count`` affine points of group ``group`` from ONE call of
+        ``ark355_msm_batch_dev`` -- byte for byte what ``ark355_msm_dev`` returns table by table"""
+        size = self.lib.sizes(self.curve.curve_id)["g1" if group == 1 else "g2"]
+        n = 1 << num_vars
+        return self.lib.msm_batch_dev(self.ctx, [handle] * count, [d_tables + 32 * n * k for k in range(count)], [n] * count, 1, size)
+
     def commit_key(self, group: int, base: bytes, t: Sequence[int], alloc=None):
         """The PST key of ``len(t)`` variables over the trapdoor ``t``: ``(commit, levels)``, resident base handles
         (``ark355_bases_free`` each).  ``commit`` holds the 2^v points ``eq(t, i) base``, so that ``ark355_msm_dev`` of a table

@@ -74,6 +74,17 @@ KERNELS = [
     (r"mle_open_kernelINS_2FpINS_10BnFrParamsEEELi8E", "bn254.mle_open"),
     (r"mle_open_kernelINS_2FpINS_11BlsFrParamsEEELi1E", "bls12_381.mle_open_e1"),
     (r"mle_open_kernelINS_2FpINS_10BnFrParamsEEELi1E", "bn254.mle_open_e1"),
+    # the batched short MSMs: the digit kernel, then the sum kernel <G2, PACKED>
+    (r"msm_batch_digits_kernelINS_2FpINS_11BlsFrParams", "bls12_381.msm_batch_digits"),
+    (r"msm_batch_digits_kernelINS_2FpINS_10BnFrParams", "bn254.msm_batch_digits"),
+    (r"msm_batch_sum_kernelINS_11BlsFqParamsELb0ELb0E", "bls12_381.msm_batch_sum_g1"),
+    (r"msm_batch_sum_kernelINS_11BlsFqParamsELb0ELb1E", "bls12_381.msm_batch_sum_g1_packed"),
+    (r"msm_batch_sum_kernelINS_11BlsFqParamsELb1ELb0E", "bls12_381.msm_batch_sum_g2"),
+    (r"msm_batch_sum_kernelINS_11BlsFqParamsELb1ELb1E", "bls12_381.msm_batch_sum_g2_packed"),
+    (r"msm_batch_sum_kernelINS_10BnFqParamsELb0ELb0E", "bn254.msm_batch_sum_g1"),
+    (r"msm_batch_sum_kernelINS_10BnFqParamsELb0ELb1E", "bn254.msm_batch_sum_g1_packed"),
+    (r"msm_batch_sum_kernelINS_10BnFqParamsELb1ELb0E", "bn254.msm_batch_sum_g2"),
+    (r"msm_batch_sum_kernelINS_10BnFqParamsELb1ELb1E", "bn254.msm_batch_sum_g2_packed"),
     # the test kernels of ark355_diag_field_ops: their long branch-free runs are the INLINED multipliers (no scratch access there,
     # none at all in the Fp28 kernels); the 16 - 58 accesses of the Fp / Fp2 kernels are the by-reference operands (and, for the
     # 24-word BLS12-381 Fq2, the returned value) of the out-of-line `_ni` bodies they call as the production kernels do
